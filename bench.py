@@ -176,29 +176,35 @@ def cpu_baseline_flow(H, W, budget_s=10.0):
 CNN_GFLOP_PER_FRAME = {(720, 1280): 154.5, (288, 512): 24.6}
 
 
-def latency_mode(net, dev, sizes=((720, 1280), (288, 512)), n_frames=48, precision="f32"):
+def latency_mode(net, dev, sizes=((720, 1280), (288, 512)), n_frames=48, precision="f32", n_clips=5):
     """The reference's actual operating point (eval.py:93-124, config.py:12-13,123): ONE clip, batch 1, every frame's
     window reading the stabilised frames before it -- a lag-1 recurrence, nothing to batch.  `clip.stabilize_clip` on a
     synthetic float32 clip resident in HBM (one dvsg_stabilize_ring_f32 call per frame), steady state after a 4-frame
-    warm-up clip; 720p and the reference's own 512x288.  Outside the timed region of the line of record."""
+    warm-up clip; 720p and the reference's own 512x288.  One clip is ~0.1 s of work, short enough for a host or clock
+    hiccup to move it, so `n_clips` clips are timed one by one and the median is reported beside all of them.  Outside
+    the timed region of the line of record."""
     from coupe.dvsg_amd.clip import stabilize_clip
     from coupe.dvsg_amd.model import StabNet
     out = {"mode": "eval.py clip loop: batch 1, exact autoregressive history, clip resident in HBM, %s"
                    % ("float32" if precision == "f32" else precision),
-           "frames_per_clip": n_frames}
+           "frames_per_clip": n_frames, "clips": n_clips}
     for H, W in sizes:
         model = StabNet(H, W)
         model.locnet = net
         model.precision = precision
         frames = gpu_windows(n_frames, H, W, 4321, dev, S=1)
         stabilize_clip(model, None, frames[:4])
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        stab = stabilize_clip(model, None, frames)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / n_frames
-        assert stab.shape == frames.shape
-        out["%dx%d" % (W, H)] = {"ms_per_frame": 1e3 * dt, "frames_per_s": 1.0 / dt,
+        per_clip = []
+        for _ in range(n_clips):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            stab = stabilize_clip(model, None, frames)
+            torch.cuda.synchronize()
+            per_clip.append((time.perf_counter() - t0) / n_frames)
+            assert stab.shape == frames.shape
+        dt = float(np.median(per_clip))
+        out["%dx%d" % (W, H)] = {"ms_per_frame": 1e3 * dt, "ms_per_frame_per_clip": [1e3 * t for t in per_clip],
+                                 "frames_per_s": 1.0 / dt,
                                  "achieved_tflops": CNN_GFLOP_PER_FRAME[(H, W)] / dt / 1e3,
                                  "frac_of_f32_mfma_peak": CNN_GFLOP_PER_FRAME[(H, W)] / dt / 1e3 / PEAK_F32_MFMA_TFLOPS}
         del frames, stab
@@ -245,6 +251,29 @@ def prof_region(cls, fn, steps):
     ms, n, fl, by = ctypes.c_double(), ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
     _lib.call("dvsg_prof_end", ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl), ctypes.byref(by))
     return dt, (ms.value, n.value, fl.value, by.value)
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all ranks' files together stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays, budget, suffix=""):
+    """--dump-outputs: write each device tensor of `arrays` (name -> tensor) as out_dir/<name><suffix>.npy in float32.
+    Tensors are taken smallest first, each with an even share of what is left of `budget`; one that does not fit its
+    share is written as <name>_sample<suffix>.npy instead, the flattened tensor's elements at sorted flat indices drawn
+    from numpy's default_rng(0) -- the same indices for the same shape in every run, so two builds compare value for value."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        share = budget // (len(items) - i)
+        flat = t.detach().reshape(-1)
+        if flat.numel() * 4 <= share:
+            host = flat.reshape(t.shape).float().cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), size=share // 4))
+            host = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), host.astype(np.float32, copy=False))
+        budget -= host.nbytes
 
 
 def free_gib(dev):
@@ -438,7 +467,13 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the batch of one step is split over (LocNet.stabilize); 2 is <1 %% faster "
                          "but concurrent launches make the per-kernel hipEvent durations of `roofline` meaningless")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): F_t whole, the "
+                         "stabilised (or tf_warp) frames whole or, over 48 MiB, as a fixed seeded sample; with N > 1 GPUs every rank writes its "
+                         "shard's files with a _rank<r> suffix.  The inputs are seeded, the same in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args.gpus)
@@ -594,6 +629,11 @@ def main():
         rank_ms = {"min": 1e3 * float(tmin.item()) / args.steps, "max": 1e3 * float(t.item()) / args.steps,
                    "this_rank": 1e3 * elapsed / args.steps}
         elapsed = float(t.item())
+    if args.dump_outputs:
+        # outside the timed region, before anything below reuses `outs` / `F_t`
+        last = outs[(args.steps - 1) & 1]
+        dumped = {"tf_warp_out": last} if flow_mode else {"s_t_pred": last, "F_t": F_t}
+        dump_outputs(args.dump_outputs, dumped, DUMP_BUDGET_BYTES // world, "_rank%d" % rank if world > 1 else "")
 
     if rank == 0:
         frames = world * B * args.steps

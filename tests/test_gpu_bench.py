@@ -47,6 +47,9 @@ def test_bench_line_has_the_contract_fields():
     assert "error" not in lat, lat
     assert 0 < lat["1280x720"]["ms_per_frame"] < 2.7 and 0 < lat["512x288"]["ms_per_frame"] < 1.39
     assert abs(lat["1280x720"]["achieved_tflops"] - 154.5 / lat["1280x720"]["ms_per_frame"]) < 1e-6
+    for size in ("1280x720", "512x288"):     # the median of the clips timed one by one, every clip listed
+        clips = lat[size]["ms_per_frame_per_clip"]
+        assert len(clips) == lat["clips"] >= 3 and lat[size]["ms_per_frame"] == pytest.approx(sorted(clips)[len(clips) // 2])
 
 
 def test_bench_default_line_carries_the_other_single_gpu_configs():
@@ -89,6 +92,57 @@ def test_bench_tf_warp_workload():
     d = _run("--workload", "tf_warp", "--steps", "2", "--warmup", "1", "--batch", "3", "--height", "96", "--width", "160")
     assert d["metric"].startswith("tf_warp") and d["dtype"] == "f32" and d["roofline"]["bound"] == "hbm"
     assert "stn_kernel" in d["roofline"]["kernel"] and d["roofline"]["launches"] == 2 and d["cpu_baseline"]["cores"] == 1
+
+
+def _bench_module():
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    return bench
+
+
+def test_bench_dump_outputs_are_the_timed_paths_last_step(tmp_path):
+    """--dump-outputs writes the last timed step's s_t_pred and F_t (whole at this size), the same in two runs and the
+    same as one dvsg_stabilize_f32 call on the seeded inputs the benchmark builds."""
+    import numpy as np
+    import torch
+    from coupe.dvsg_amd.networks import LocNet
+    from coupe.dvsg_amd.weights import make_synthetic_weights
+    flags = ("--steps", "3", "--warmup", "1", "--batch", "2", "--height", "96", "--width", "160", "--no-cpu-baseline",
+             "--no-secondary", "--no-latency")
+    for run in ("a", "b"):
+        d = _run(*flags, "--dump-outputs", str(tmp_path / run))
+        assert d["steps"] == 3
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("s_t_pred", "F_t")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["F_t.npy", "s_t_pred.npy"]
+    for n, v in got.items():
+        assert v.dtype == np.float32 and np.array_equal(v, np.load(tmp_path / "b" / (n + ".npy"))), n
+    bench = _bench_module()
+    dev = torch.device("cuda:0")
+    patches = bench.gpu_windows(2, 96, 160, 1234, dev)
+    out, F = torch.empty((2, 96, 160, 3), device=dev), torch.empty((2, 25, 2), device=dev)
+    LocNet(make_synthetic_weights(seed=0)).stabilize(patches, patches[..., 18:].contiguous(), out, F)
+    assert np.array_equal(got["s_t_pred"], out.cpu().numpy()) and np.array_equal(got["F_t"], F.cpu().numpy())
+
+
+def test_bench_dump_outputs_sample_a_large_output(tmp_path):
+    """An output over the budget (16 720p tf_warp frames, 177 MB) is written as the fixed seeded sample, under 64 MB."""
+    import numpy as np
+    import torch
+    from coupe.dvsg_amd import _lib
+    B, H, W = 16, 720, 1280
+    _run("--workload", "tf_warp", "--steps", "2", "--warmup", "1", "--batch", str(B), "--no-cpu-baseline",
+         "--dump-outputs", str(tmp_path))
+    assert os.listdir(tmp_path) == ["tf_warp_out_sample.npy"] and os.path.getsize(tmp_path / "tf_warp_out_sample.npy") < 64e6
+    got = np.load(tmp_path / "tf_warp_out_sample.npy")
+    bench = _bench_module()
+    dev = torch.device("cuda:0")
+    u_t, flow = bench.make_flow_inputs(B, H, W, 0, dev)
+    out = torch.empty((B, H, W, 3), device=dev)
+    _lib.call("dvsg_flow_warp_f32", u_t.data_ptr(), flow.data_ptr(), B, H, W, 3, out.data_ptr(),
+              torch.cuda.current_stream().cuda_stream)
+    idx = np.unique(np.random.default_rng(0).integers(0, out.numel(), size=bench.DUMP_BUDGET_BYTES // 4))
+    assert got.dtype == np.float32 and np.array_equal(got, out.reshape(-1).cpu().numpy()[idx])
 
 
 def test_bench_rccl_calls_of_the_sharded_path_run_on_one_rank():

@@ -1,5 +1,7 @@
 """GPU parity: localizationNet (HIP, exact-f32 MFMA) against the NumPy oracle, stage by
 stage and end to end, then the fused evaluation graph behind the StabNet facade."""
+import gc
+
 import numpy as np
 import pytest
 
@@ -254,9 +256,16 @@ def test_a_step_replays_from_a_captured_hip_graph(net, precision):
     with torch.cuda.stream(side):
         net.stabilize(x, u, out, F, precision=precision)   # workspace sized before the capture
     side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        net.stabilize(x, u, out, F, precision=precision)
+    # a dead network held by a reference cycle (StabNet's graph) frees device memory when the collector
+    # finds it, which would invalidate the capture: collect now and not during it
+    gc.collect()
+    gc.disable()
+    try:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            net.stabilize(x, u, out, F, precision=precision)
+    finally:
+        gc.enable()
     for _ in range(3):
         out.zero_()
         F.zero_()

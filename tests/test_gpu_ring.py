@@ -2,6 +2,8 @@
 window of eval.py:103-104 in its load stage from a pool of RGB frames and -- for a uint8 pool -- applies the
 `/ 255.` of eval.py:80 there.  Index and byte work: the bar is BIT equality with the path it replaces
 (dvsg_window_gather_f32 + dvsg_stabilize_*, dvsg_frames_u8_to_f32 for uint8), in every precision."""
+import gc
+
 import numpy as np
 import pytest
 
@@ -208,9 +210,16 @@ def test_a_ring_step_replays_from_a_captured_hip_graph(net, precision, variant):
         with torch.cuda.stream(side):
             net.stabilize_ring(pool, table, out, F, precision=precision)
         side.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            net.stabilize_ring(pool, table, out, F, precision=precision)
+        # a dead network held by a reference cycle (StabNet's graph) frees device memory when the collector
+        # finds it, which would invalidate the capture: collect now and not during it
+        gc.collect()
+        gc.disable()
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                net.stabilize_ring(pool, table, out, F, precision=precision)
+        finally:
+            gc.enable()
         for _ in range(3):
             out.zero_()
             F.zero_()
