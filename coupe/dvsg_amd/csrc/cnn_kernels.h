@@ -57,6 +57,11 @@ struct ConvGemm {
 constexpr int kSplitKMaxTiles = 512;                                   // tickets one launch may use
 constexpr size_t kSplitKSlabBytes = (size_t)512 * 2 * 128 * 128 * 4;   // 64 MiB: 512 workgroups x 2 partial 128x128 f32 tiles (stream-K tail)
 int launch_conv_gemm(const ConvGemm &p, hipStream_t s);
+// diagnostic record of the last conv_gemm_kernel launch (dvsg_debug_last_conv_config): T (0 float32 tensors, 1 float16),
+// BN, WM, WN, KS, RELU, RES, MODE, SPLIT, X3, ksplit, streamk_tail, mt_fast; T = -1 when the last launch_conv_gemm call did
+// not end in conv_gemm_kernel (the float16 mode's 256 x 128 geometry) or there was none.  Host-only; written by launch_cfg
+constexpr int kConvConfigFields = 13;
+extern int g_last_conv_config[kConvConfigFields];
 // f32x3 weights: float32 wt [rows][K] (rows % 64 == 0, K % 32 == 0) -> per group of 64 rows and 32-k stage three 4 KB planes
 // of bfloat16 pieces [64 rows][32 k] (p1 = bf16(w), p2 = bf16(w - p1), p3 = bf16(w - p1 - p2)), row R's 16-byte chunk c at
 // position c ^ ((R >> 2) & 3): 6 bytes per weight, [rows / 64][K / 32][3][64][32]

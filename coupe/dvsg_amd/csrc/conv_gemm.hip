@@ -12,6 +12,8 @@ long g_wide16_min_tiles = 128;   // float16 mode: 256 x 128 tiles from this many
                                  // weight stages, 128-byte activation rows and the 3x3 row reuse 128 is -0.5 % at batch 16, -4.5 %
                                  // at batch 4 (720p), equal at batch 1; 64 and 32 lose 4-27 % at batch 1-4
 
+int g_last_conv_config[kConvConfigFields] = {-1};
+
 void set_conv_variant(int v) { g_conv_variant = v; }
 void set_wide16_min_tiles(int v) { g_wide16_min_tiles = v; }
 
@@ -51,6 +53,7 @@ int launch_zero_tickets(int *tickets, size_t n, hipStream_t s) {
 }
 
 int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
+  g_last_conv_config[0] = -1;   // until launch_cfg records this call's launch
   DVSG_REQUIRE(p.prec == kF32 || p.prec == kF16, "conv_gemm: unknown precision %d", p.prec);
   DVSG_REQUIRE(p.ksize == 1 || p.ksize == 3, "conv_gemm: kernel size %d unsupported", p.ksize);
   const int bke = ROWB / (int)elem_size(p.prec);

@@ -709,6 +709,10 @@ int launch_cfg(const ConvGemmDev &d, int blocks, bool relu, int res, hipStream_t
     else DVSG_LAUNCH(false, 2);
   }
 #undef DVSG_LAUNCH
+  // the launch record (dvsg_debug_last_conv_config); MODE 2 has returned above unless res == 0
+  const int rec[kConvConfigFields] = {sizeof(T) == 4 ? 0 : 1, BN, WM, WN, KS, relu ? 1 : 0, res, MODE, SPLIT, X3,
+                                      d.ksplit, MODE == 2 ? d.tile_count : 0, d.mt_fast};
+  std::copy(rec, rec + kConvConfigFields, g_last_conv_config);
   return check_launch("conv_gemm_kernel");
 }
 

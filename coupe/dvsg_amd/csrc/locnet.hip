@@ -1019,6 +1019,12 @@ int dvsg_conv3x3_1x1_f32x3(const float *x, const void *wt2_packed, const float *
   return launch_conv3x3_1x1(f, as_stream(stream));
 }
 
+int dvsg_debug_last_conv_config(int *fields, int n) {
+  DVSG_REQUIRE(fields && n >= kConvConfigFields, "dvsg_debug_last_conv_config: need room for %d fields", kConvConfigFields);
+  std::copy(g_last_conv_config, g_last_conv_config + kConvConfigFields, fields);
+  return DVSG_OK;
+}
+
 int dvsg_debug_set_option(const char *name, int value) {
   DVSG_REQUIRE(name, "dvsg_debug_set_option: NULL name");
   if (std::strcmp(name, "conv_variant") == 0) {

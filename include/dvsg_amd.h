@@ -419,6 +419,12 @@ int dvsg_conv3x3_1x1_f32(const float *x, const float *wt2, const float *bias2, c
  * fused kernel; 0 selects the kernel each replaced), "warp_xcd" (0: the sampler kernels' workgroups in plain dispatch order).
  * Results do not depend on them beyond float32 re-association. */
 int dvsg_debug_set_option(const char *name, int value);
+/* What the last dvsg_conv_gemm_* call (or conv launch of a network call) ran, recorded on the host when it was launched; no
+ * synchronisation.  fields (n >= 13): T (0: float32 tensors, 1: float16), BN (tile width 64 / 128), WM, WN (wave layout), KS
+ * (1 / 3), RELU, RES (0 none, 1 full-size, 2 subsampled), MODE (0 plain, 1 split-K, 2 stream-K), SPLIT (f32s pieces / float16
+ * hi-lo rows), X3 (f32x3), ksplit (slices per tile), streamk_tail (tiles shared as stream-K units), mt_fast (tile order).
+ * T = -1: that call ran no conv_gemm_kernel (the float16 mode's 256 x 128 geometry), or none was made. */
+int dvsg_debug_last_conv_config(int *fields, int n);
 /* The A/B form of dvsg_locnet_calibrate_f16 (tools/f16_ef_sweep.py): re-rounds the plain float16 weight copies and leaves
  * the pair policy to "f16_pair_mask".  mode 0: round to nearest (what dvsg_locnet_create makes); 1: error feedback with
  * mu = 1 (measured: useless -- channel means are far from uniform); 2: calibrated channel means. */

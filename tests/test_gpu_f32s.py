@@ -132,6 +132,10 @@ def test_layers_against_float64(net):
         es = float((ys.double() - ref).abs().max())
         scale = float(ref.abs().max())
         assert es <= max(4.0 * e32, 2e-6 * scale), (k, stride, cin, cout, Bs, es, e32, scale)
+        # the yardstick itself: the exact kernel within its per-element float64 bound (tests/test_conv_gemm_f64.py)
+        from test_conv_gemm_f64 import bound, reference
+        _, S = reference(x.double(), wt.double(), bias.double(), res.double(), k, stride, 1, True)
+        assert bool(((y32.double() - ref).abs() <= bound("f32", K, S)).all()), (k, stride, cin, cout, Bs, e32)
 
 
 def test_stabilize_720p_end_to_end(synthetic_weights):
