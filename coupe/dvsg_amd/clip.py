@@ -102,6 +102,14 @@ def stabilize_windows_sharded(run_fn, patches_t, u_t, batch=16, group=None, dst=
                        (u_t.shape[1], u_t.shape[2], 3), torch.as_tensor(u_t[:0]), group, dst)
 
 
+def check_skip_length(skip_length):
+    """skip_length (config.py:48) as int64: it must start at 0 and increase strictly."""
+    skip = np.asarray(skip_length, dtype=np.int64)
+    if skip.ndim != 1 or skip.size < 1 or skip[0] != 0 or np.any(np.diff(skip) <= 0):
+        raise ValueError("skip_length must start at 0 and increase strictly (config.py:48)")
+    return skip
+
+
 def window_index_table(n_frames, skip_length=SKIP_LENGTH):
     """The frame loop of eval.py:93-124 as an index table.  With the clip kept in a pool of
     2 N frames -- [0, N) the unstable inputs, [N, 2 N) the stabilised outputs -- entry [k, s] is
@@ -112,9 +120,7 @@ def window_index_table(n_frames, skip_length=SKIP_LENGTH):
       * one of the 32 prepended copies of frame 0 (eval.py:93-94) otherwise -- the unstable
         frame 0 at step 0, the stabilised frame 0 afterwards (eval.py:118-120).
     Returns int32 [N, S]."""
-    skip = np.asarray(skip_length, dtype=np.int64)
-    if skip.ndim != 1 or skip.size < 1 or skip[0] != 0 or np.any(np.diff(skip) <= 0):
-        raise ValueError("skip_length must start at 0 and increase strictly (config.py:48)")
+    skip = check_skip_length(skip_length)
     N = int(n_frames)
     span = int(skip[-1])
     k = np.arange(N, dtype=np.int64)[:, None]
@@ -221,9 +227,7 @@ def teacher_forced_index_table(n_frames, skip_length=SKIP_LENGTH):
     (frame k + 32) sees stable frames in every slot but the last.  With a pool of 2 N frames --
     [0, N) unstable, [N, 2N) stable -- entry [k, s] = N + k + skip[s], and [k, -1] = k + 32.
     The windows do not depend on each other: they shard over GPUs.  Returns int32 [N-32, S]."""
-    skip = np.asarray(skip_length, dtype=np.int64)
-    if skip.ndim != 1 or skip.size < 1 or skip[0] != 0 or np.any(np.diff(skip) <= 0):
-        raise ValueError("skip_length must start at 0 and increase strictly (config.py:48)")
+    skip = check_skip_length(skip_length)
     N, span = int(n_frames), int(skip[-1])
     if N <= span:
         raise ValueError("eval_train.py needs more than %d frames, got %d" % (span, N))

@@ -48,7 +48,7 @@ int tps_warp_impl(const float *U, const float *coord, long coord_bstride, const 
 
 int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *table, int tstride, const float *coord,
                        long coord_bstride, const float *T, int B, int H, int W, int P, float *out, float *x_s, float *y_s,
-                       void *stream);
+                       void *stream, const int *out_index = nullptr);
 
 void set_flow_tiled(int v); // diagnostic (dvsg_debug_set_option "flow_tiled"): 0 = tf_warp by global gathers (stn_kernel<kFlow>)
 void set_flow_rounds(int v);

@@ -9,6 +9,8 @@
 //                                      into a column band of a wider image (side-by-side layout)
 //   resize_bilinear    eval.py:80      cv2.resize(frame / 255., (w, h)), INTER_LINEAR on float64
 //
+// The conversions also run on frame SLOTS of a pool (dvsg_frames_ingest_u8, dvsg_frames_f32_to_u8_slots: the rings of
+// coupe.dvsg_amd.online): the same kernels with frame i read from / written to pool frame slots[i], same values.
 // All of them move each byte once: the roofline is HBM bandwidth.
 #include <cstdint>
 
@@ -24,14 +26,26 @@ inline int grid_for(size_t items, int cap = 1 << 16) {
   return (int)(b < (size_t)cap ? (b ? b : 1) : (size_t)cap);
 }
 
-// One thread converts 4 consecutive pixels (12 bytes in, 48 bytes out).
+// A pool slot is a frame index in [0, n_pool); a kernel given slots skips (ingest) or zero-fills (egress) a frame whose
+// slot lies outside, so a bad slot never addresses memory outside the pool.
+__device__ __forceinline__ bool slot_ok(int s, int n_pool) { return s >= 0 && s < n_pool; }
+
+// One thread converts 4 consecutive pixels (12 bytes in, 48 bytes out).  With `slots`, blockIdx.y is the frame: npix
+// pixels of src frame blockIdx.y go to pool frame slots[blockIdx.y] of dst.
 __global__ __launch_bounds__(kThreads) void frames_u8_to_f32_kernel(const uint8_t *__restrict__ src,
                                                                    float *__restrict__ dst, size_t npix,
-                                                                   int flip) {
+                                                                   int flip, const int *__restrict__ slots = nullptr,
+                                                                   int n_pool = 0) {
+  if (slots) {
+    const int s = slots[blockIdx.y];
+    if (!slot_ok(s, n_pool)) return;
+    src += (size_t)blockIdx.y * npix * 3;
+    dst += (size_t)s * npix * 3;
+  }
   const size_t ngroups = (npix + 3) / 4;
   for (size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * kThreads) {
     const size_t p0 = 4 * g;
-    if (p0 + 4 <= npix && (reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+    if (p0 + 4 <= npix && (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
       const uint32_t *s4 = reinterpret_cast<const uint32_t *>(src + 3 * p0);
       const uint32_t w[3] = {s4[0], s4[1], s4[2]};
       float v[12];
@@ -104,23 +118,34 @@ __device__ __forceinline__ uint8_t to_u8(double x) {
 }
 
 // One thread converts 4 consecutive values of a row (row = W*3 values); rows land at
-// dst + (n*H + y) * dst_row_bytes + dst_col_bytes.
+// dst + (n*H + y) * dst_row_bytes + dst_col_bytes.  With `slots`, row n*H + y is read from pool frame slots[n]
+// (H rows per frame); a slot outside [0, n_pool) reads as a frame of zeros.
 template <typename T>
 __global__ __launch_bounds__(kThreads) void frames_to_u8_kernel(const T *__restrict__ src, uint8_t *__restrict__ dst,
                                                                size_t rows, int row_vals, size_t dst_row_bytes,
-                                                               size_t dst_col_bytes, int flip) {
+                                                               size_t dst_col_bytes, int flip,
+                                                               const int *__restrict__ slots = nullptr, int H = 1,
+                                                               int n_pool = 0) {
   const int groups_per_row = (row_vals + 3) / 4;
   const size_t ngroups = rows * groups_per_row;
   for (size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * kThreads) {
     const size_t row = g / groups_per_row;
     const int v0 = 4 * (int)(g - row * groups_per_row);
-    const T *s = src + row * row_vals;
+    bool src_ok = true;
+    size_t src_row = row;
+    if (slots) {
+      const size_t n = row / H;
+      const int sl = slots[n];
+      src_ok = slot_ok(sl, n_pool);
+      src_row = src_ok ? (size_t)sl * H + (row - n * H) : 0;
+    }
+    const T *s = src + src_row * row_vals;
     uint8_t *d = dst + row * dst_row_bytes + dst_col_bytes;
     uint8_t o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int v = v0 + i;
-      if (v < row_vals) {
+      if (v < row_vals && src_ok) {
         const int px = v / 3, c = v - 3 * px;
         o[i] = to_u8((double)s[flip ? 3 * px + 2 - c : v]);
       } else {
@@ -164,9 +189,11 @@ __device__ __forceinline__ ResizeTap resize_tap(int d, double scale, int n_src) 
   return t;
 }
 
+// With `slots`, resized frame f goes to pool frame slots[f] of dst (skipped, u8 half included, if outside [0, n_pool)).
 __global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t *__restrict__ src, int n, int sh, int sw,
                                                             float *__restrict__ dst, int dh, int dw, int flip,
-                                                            uint8_t *__restrict__ u8_dst, int u8_w, int u8_x0) {
+                                                            uint8_t *__restrict__ u8_dst, int u8_w, int u8_x0,
+                                                            const int *__restrict__ slots = nullptr, int n_pool = 0) {
   const double scale_x = (double)sw / dw, scale_y = (double)sh / dh;
   const size_t total = (size_t)n * dh * dw;
   for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
@@ -174,6 +201,12 @@ __global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t *__re
     const size_t t = e / dw;
     const int dy = (int)(t % dh);
     const size_t f = t / dh;
+    size_t de = e;   // destination pixel in dst
+    if (slots) {
+      const int sl = slots[f];
+      if (!slot_ok(sl, n_pool)) continue;
+      de = ((size_t)sl * dh + dy) * dw + dx;
+    }
     const ResizeTap tx = resize_tap(dx, scale_x, sw), ty = resize_tap(dy, scale_y, sh);
     const uint8_t *r0 = src + ((f * sh + ty.s0) * sw) * 3;
     const uint8_t *r1 = src + ((f * sh + ty.s1) * sw) * 3;
@@ -187,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t *__re
       const double h0 = __dadd_rn(__dmul_rn(p00, a0), __dmul_rn(p01, a1));
       const double h1 = __dadd_rn(__dmul_rn(p10, a0), __dmul_rn(p11, a1));
       const double v = __dadd_rn(__dmul_rn(h0, b0), __dmul_rn(h1, b1));
-      dst[e * 3 + c] = (float)v;
+      dst[de * 3 + c] = (float)v;
       // the unstable half of the output video (eval.py:112-113) is rendered from the float64 value
       if (u8_dst) u8_dst[((t * u8_w) + u8_x0 + dx) * 3 + cs] = to_u8(v);
     }
@@ -196,7 +229,7 @@ __global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t *__re
 
 template <typename T>
 int frames_to_u8(const char *what, const T *src, int n, int H, int W, int channel_flip, uint8_t *dst, int dst_W, int dst_x0,
-                 void *stream) {
+                 void *stream, const int32_t *slots = nullptr, int n_pool = 0) {
   DVSG_REQUIRE(src && dst, "%s: NULL pointer", what);
   DVSG_REQUIRE(n > 0 && H > 0 && W > 0, "%s: bad shape n=%d H=%d W=%d", what, n, H, W);
   DVSG_REQUIRE(dst_x0 >= 0 && dst_W >= dst_x0 + W, "%s: columns [%d, %d) do not fit a row of %d pixels", what, dst_x0,
@@ -204,7 +237,7 @@ int frames_to_u8(const char *what, const T *src, int n, int H, int W, int channe
   const size_t rows = (size_t)n * H;
   const size_t groups = rows * ((3 * (size_t)W + 3) / 4);
   hipLaunchKernelGGL(frames_to_u8_kernel<T>, dim3(grid_for(groups)), dim3(kThreads), 0, as_stream(stream), src, dst, rows,
-                     3 * W, (size_t)3 * dst_W, (size_t)3 * dst_x0, channel_flip);
+                     3 * W, (size_t)3 * dst_W, (size_t)3 * dst_x0, channel_flip, slots, H, n_pool);
   return check_launch("frames_to_u8_kernel");
 }
 
@@ -257,6 +290,33 @@ int dvsg_frames_resize_u8_f32(const uint8_t *src, int n, int src_H, int src_W, i
   hipLaunchKernelGGL(resize_u8_kernel, dim3(grid_for((size_t)n * dst_H * dst_W)), dim3(kThreads), 0, as_stream(stream), src,
                      n, src_H, src_W, dst, dst_H, dst_W, channel_flip, u8_dst, u8_W, u8_x0);
   return check_launch("resize_u8_kernel");
+}
+
+int dvsg_frames_ingest_u8(const uint8_t *src, int n, int src_H, int src_W, int channel_flip, float *pool, int n_pool,
+                          const int32_t *slots, int dst_H, int dst_W, uint8_t *u8_dst, int u8_W, int u8_x0, void *stream) {
+  DVSG_REQUIRE(src && pool && slots, "dvsg_frames_ingest_u8: NULL pointer");
+  DVSG_REQUIRE(n > 0 && n <= 65535 && n_pool > 0 && src_H > 0 && src_W > 0 && dst_H > 0 && dst_W > 0,
+               "dvsg_frames_ingest_u8: bad shape n=%d n_pool=%d src=%dx%d dst=%dx%d", n, n_pool, src_H, src_W, dst_H, dst_W);
+  if (src_H == dst_H && src_W == dst_W) {
+    DVSG_REQUIRE(!u8_dst, "dvsg_frames_ingest_u8: no size change, so no uint8 half: render it from the pool "
+                          "(dvsg_frames_f32_to_u8_slots)");
+    const size_t hw = (size_t)dst_H * dst_W;
+    hipLaunchKernelGGL(frames_u8_to_f32_kernel, dim3(grid_for((hw + 3) / 4), n), dim3(kThreads), 0, as_stream(stream), src,
+                       pool, hw, channel_flip, slots, n_pool);
+    return check_launch("frames_u8_to_f32_kernel");
+  }
+  DVSG_REQUIRE(!u8_dst || (u8_x0 >= 0 && u8_W >= u8_x0 + dst_W),
+               "dvsg_frames_ingest_u8: columns [%d, %d) do not fit a row of %d pixels", u8_x0, u8_x0 + dst_W, u8_W);
+  hipLaunchKernelGGL(resize_u8_kernel, dim3(grid_for((size_t)n * dst_H * dst_W)), dim3(kThreads), 0, as_stream(stream), src,
+                     n, src_H, src_W, pool, dst_H, dst_W, channel_flip, u8_dst, u8_W, u8_x0, slots, n_pool);
+  return check_launch("resize_u8_kernel");
+}
+
+int dvsg_frames_f32_to_u8_slots(const float *pool, int n_pool, const int32_t *slots, int n, int H, int W, int channel_flip,
+                                uint8_t *dst, int dst_W, int dst_x0, void *stream) {
+  DVSG_REQUIRE(slots, "dvsg_frames_f32_to_u8_slots: NULL pointer");
+  DVSG_REQUIRE(n_pool > 0, "dvsg_frames_f32_to_u8_slots: bad shape n_pool=%d", n_pool);
+  return frames_to_u8("dvsg_frames_f32_to_u8_slots", pool, n, H, W, channel_flip, dst, dst_W, dst_x0, stream, slots, n_pool);
 }
 
 }  // extern "C"

@@ -667,10 +667,11 @@ int stabilize(const dvsg_locnet *net, int prec, const float *patches_t, const fl
 
 // The evaluation graph fed from a frame ring: window b = pool frames table[b][0..6], u_t = its newest
 // frame table[b][6]; conv1 assembles the window in its load stage (eval.py:103-104) and, for a uint8 pool, applies the
-// / 255. of eval.py:80 there; the warp reads u_t from the pool through the same table.
+// / 255. of eval.py:80 there; the warp reads u_t from the pool through the same table.  With out_slots, s_t_pred is the
+// float32 pool and sample b's frame lands in its frame out_slots[b] (the history slot of an online stream).
 int stabilize_ring(const dvsg_locnet *net, int prec, const void *pool, int pool_is_u8, int n_pool, const int32_t *table,
                    const float *mask, int B, int H, int W, float *s_t_pred, float *F_t, float *x_s, float *y_s, void *workspace,
-                   size_t workspace_bytes, void *stream) {
+                   size_t workspace_bytes, void *stream, const int32_t *out_slots = nullptr) {
   DVSG_REQUIRE(net && pool && table && s_t_pred && workspace, "dvsg_stabilize_ring: NULL pointer");
   DVSG_REQUIRE(B > 0 && B <= 65535 && n_pool > 0, "dvsg_stabilize_ring: B=%d n_pool=%d out of range", B, n_pool);
   DVSG_REQUIRE(prec == kF32 || prec == kF16 || prec == kF32S || prec == kF32X, "dvsg_stabilize_ring: unknown precision %d", prec);
@@ -687,7 +688,7 @@ int stabilize_ring(const dvsg_locnet *net, int prec, const void *pool, int pool_
   MarkerRange mr("dvsg/tps");
   if (int rc = tps_apply_impl(net->winv, net->v_src, F, 1, B, 25, ws.T, stream)) return rc;
   return tps_warp_ring_impl(pool, pool_is_u8, n_pool, table + 6, 7, net->v_src, 0, ws.T, B, H, W, 25, s_t_pred, x_s, y_s,
-                            stream);
+                            stream, out_slots);
 }
 
 int conv_gemm_op(int prec, int wsplit, const void *x, const void *wt, const float *bias, const void *res, void *y, int B,
@@ -1245,6 +1246,17 @@ int dvsg_stabilize_ring_u8(const dvsg_locnet_t *net, int precision, const uint8_
                            size_t workspace_bytes, void *stream) {
   return stabilize_ring(net, ring_precision(precision), pool, 1, n_pool, table, nullptr, B, H, W, s_t_pred, F_t, x_s, y_s,
                         workspace, workspace_bytes, stream);
+}
+
+// dvsg_stabilize_ring_f32 with the result of window b written into pool frame out_slots[b]: the write-back of eval.py:116
+// for streams whose history lives in the pool (coupe.dvsg_amd.online).  The contract of the header (distinct out slots,
+// none of them read by `table`) is the caller's; it is not checked on the device.
+int dvsg_stabilize_ring_inplace_f32(const dvsg_locnet_t *net, int precision, float *pool, int n_pool, const int32_t *table,
+                                    const int32_t *out_slots, int B, int H, int W, float *F_t, float *x_s, float *y_s,
+                                    void *workspace, size_t workspace_bytes, void *stream) {
+  DVSG_REQUIRE(out_slots, "dvsg_stabilize_ring_inplace_f32: NULL out_slots");
+  return stabilize_ring(net, ring_precision(precision), pool, 0, n_pool, table, nullptr, B, H, W, pool, F_t, x_s, y_s,
+                        workspace, workspace_bytes, stream, out_slots);
 }
 
 // eval_train.py's evaluation graph (:25-51): F_t = localizationNet(patches_t * mask), the warp on the unmasked u_t.

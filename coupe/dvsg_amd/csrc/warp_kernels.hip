@@ -405,13 +405,16 @@ constexpr float kLn2 = 0x1.62e43p-1f;
 // U is [B,H,W,C], or -- u_index given -- a pool of frames [n_pool,H,W,C] of which sample b reads frame
 // u_index[b * u_stride] (the frame ring of dvsg_stabilize_ring_*: u_t is the newest frame of the window; an index
 // outside the pool reads as a zero frame, like dvsg_window_gather_f32).  TU = uint8_t: raw frames, / 255. fused.
+// out_index given (dvsg_stabilize_ring_inplace_f32): `out` is that pool too, and sample b stores its frame into pool frame
+// out_index[b] instead of out + b; an index outside [0, n_pool) stores no frame (x_s / y_s are still written).  Only the
+// store address changes: the samples' arithmetic is the contiguous form's.
 template <int C, typename TU = float>
 __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     const TU *__restrict__ U, const float *__restrict__ coord, long coord_bstride,
     const float *__restrict__ T, int H, int W, int Cn, int P, int out_h, int out_w, float step_x,
     float step_y, float *__restrict__ out,
     float *__restrict__ xs_out, float *__restrict__ ys_out, const int *__restrict__ u_index = nullptr, int u_stride = 0,
-    int n_pool = 0) {
+    int n_pool = 0, const int *__restrict__ out_index = nullptr) {
   __shared__ float4 sp[64];      // {px, py, T[0][3+k], T[1][3+k]}
   __shared__ float4 sdy[64];     // (y_t[r] - py)^2 for the 4 rows of this workgroup
   __shared__ float sa[6];        // T[0][0..2], T[1][0..2]
@@ -445,6 +448,12 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     if (!frame_ok) frame = 0;
   }
   const TU *img = U ? U + (size_t)frame * H * W * Cn : nullptr;
+  size_t out_frame = b;
+  if (out_index) {
+    const int o = out_index[b];
+    if (o < 0 || o >= n_pool) out = nullptr;
+    out_frame = (size_t)o;
+  }
 
   floatx2 xs2[2], ys2[2];
 #pragma unroll
@@ -484,7 +493,7 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     if (ys_out) ys_out[pix] = ys[r];
     if (img) sample_a_load<C, TU>(img, H, W, Cn, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
   }
-  if (!img) return;
+  if (!img || !out) return;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = i0 + r;
@@ -497,7 +506,7 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
         for (int c = 0; c < C; ++c) v[c] = 0.f;
       }
     }
-    store_pix<C>(out, ((size_t)b * out_h + i) * out_w + j, Cn, v);
+    store_pix<C>(out, (out_frame * out_h + i) * out_w + j, Cn, v);
   }
 }
 
@@ -1001,11 +1010,13 @@ int tps_warp_impl(const float *U, const float *coord, long coord_bstride, const 
   return check_launch("tps_warp_kernel");
 }
 
-// u_t = frame table[b * tstride] of a pool [n_pool,H,W,3] (float32, or uint8 with / 255. fused), same-size output
+// u_t = frame table[b * tstride] of a pool [n_pool,H,W,3] (float32, or uint8 with / 255. fused), same-size output;
+// with out_index, sample b's frame goes to frame out_index[b] of `out` = the float32 pool itself
 int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *table, int tstride, const float *coord,
                        long coord_bstride, const float *T, int B, int H, int W, int P, float *out, float *x_s, float *y_s,
-                       void *stream) {
+                       void *stream, const int *out_index) {
   DVSG_REQUIRE(pool && table && coord && T && out, "tps_warp_ring: NULL pointer");
+  DVSG_REQUIRE(!out_index || (!pool_is_u8 && out == pool), "tps_warp_ring: out_index needs out == the float32 pool");
   DVSG_REQUIRE(n_pool > 0 && tstride > 0 && P >= 1 && P <= kMaxPts, "tps_warp_ring: bad arguments");
   if (int rc = check_image_args("tps_warp_ring", B, H, W, 3, H, W)) return rc;
   dim3 grid(ceil_div(W, kThreads), ceil_div(H, kTpsRows), B);
@@ -1018,7 +1029,7 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
                        coord_bstride, T, H, W, 3, P, H, W, sx, sy, out, x_s, y_s, table, tstride, n_pool);
   else
     hipLaunchKernelGGL((tps_warp_kernel<3, float>), grid, dim3(kThreads), 0, s, static_cast<const float *>(pool), coord,
-                       coord_bstride, T, H, W, 3, P, H, W, sx, sy, out, x_s, y_s, table, tstride, n_pool);
+                       coord_bstride, T, H, W, 3, P, H, W, sx, sy, out, x_s, y_s, table, tstride, n_pool, out_index);
   return check_launch("tps_warp_kernel");
 }
 

@@ -195,6 +195,34 @@ class LocNet(object):
         _lib.call(fn, self.handle, self._PRECISION_CODE[precision], ptr(pool), int(pool.shape[0]), ptr(table), B, H, W,
                   ptr(out), ptr(F), ptr(xs), ptr(ys), ptr(ws), nbytes, stream())
 
+    def stabilize_ring_inplace(self, pool, table, out_slots, F, xs=None, ys=None, precision="f32"):
+        """`dvsg_stabilize_ring_inplace_f32`: `stabilize_ring` on a float32 pool whose result for window b is written
+        into pool frame out_slots[b] (int32 [B] on the device) -- the history write-back of eval.py:116 for online
+        streams (coupe.dvsg_amd.online).  The out slots must be distinct and no entry of `table` may name one of them
+        (not checked on the device)."""
+        import torch
+        B, H, W = self._check_ring(pool, table)
+        if pool.dtype != torch.float32:
+            raise ValueError("an in-place ring holds the stabilised history: pool must be float32")
+        if precision not in self._PRECISION_CODE:
+            raise ValueError("precision must be 'f32', 'f32s', 'f32x3' or 'f16', got %r" % (precision,))
+        if out_slots.dtype != torch.int32 or out_slots.dim() != 1 or out_slots.shape[0] != B or not out_slots.is_cuda \
+                or not out_slots.is_contiguous():
+            raise ValueError("out_slots must be a contiguous int32 device tensor [%d]" % B)
+        if F.numel() != B * 50:
+            raise ValueError("F_t must be [B,25,2]")
+        for name, t, n in (("F_t", F, None), ("x_s", xs, B * H * W), ("y_s", ys, B * H * W)):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("%s must be a contiguous float32 device tensor" % name)
+            if n is not None and t.numel() != n:
+                raise ValueError("%s must hold B*H*W = %d values" % (name, n))
+        ws, nbytes = self.workspace(B, H, W)
+        _lib.call("dvsg_stabilize_ring_inplace_f32", self.handle, self._PRECISION_CODE[precision], ptr(pool),
+                  int(pool.shape[0]), ptr(table), ptr(out_slots), B, H, W, ptr(F), ptr(xs), ptr(ys), ptr(ws), nbytes,
+                  stream())
+
     def forward_masked(self, src, mask, table=None, precision="f32", stage=-1):
         """`dvsg_locnet_forward_masked`: F_t [B,25,2] (stage -1) or the parity tap of `stage` (0 conv1, 1 pool1) with
         the mask plane [B,H,W] multiplied into the history channels in conv1's load stage.  `src` is a window tensor

@@ -1,0 +1,260 @@
+"""eval.py:93-124 online: one frame in, its stabilised frame out, for several streams that share one GPU.
+
+The reference's driver is causal -- the output for frame k depends on frames up to k and on earlier outputs only -- so
+it does not need the whole clip.  `clip.stabilize_clip` keeps a clip of N frames in a pool of 2 N; here every stream
+owns a RING of span + 2 pool frames (span = skip_length[-1] = 32) from `base`:
+
+  * span + 1 history slots: stabilised frame j lives in base + j % (span + 1);
+  * one input slot base + span + 1: the unstable frame of the current step.
+
+The window of step k (`stream_window_row`) names the input slot in its last entry and, for k >= 1, the history slot of
+stabilised frame max(k + skip[s] - span, 0) in entry s: eval.py's padded history list, whose 32 prepended copies of
+frame 0 are the unstable frame 0 at step 0 (every entry the input slot, eval.py:93-94) and the stabilised frame 0
+afterwards (the write-back of :118-120).  Step k writes its result into the history slot of frame k; that slot held
+frame k - span - 1, which no window of step k reads (they read frames k - span .. k - 1).
+
+`OnlineStabilizer.step` runs every stream that has a frame in ONE `dvsg_stabilize_ring_inplace_f32` call (B = number
+of those streams), whose warp stores each result straight into its stream's history slot: independent streams keep
+their own lag-1 recurrence and still share batched CNN launches.  The pool never grows with the length of a stream.
+"""
+import numpy as np
+import torch
+
+from .clip import SKIP_LENGTH, _check_window, check_skip_length
+
+
+def stream_window_row(k, base, skip_length=SKIP_LENGTH):
+    """Window of step k of a stream whose ring starts at pool frame `base`: (row int32 [S], out_slot), where row[s] is
+    the pool frame window slot s reads (eval.py:103's `sample_idx` on the ring) and out_slot the history slot that
+    receives stabilised frame k (eval.py:116)."""
+    skip = check_skip_length(skip_length)
+    k, base = int(k), int(base)
+    if k < 0 or base < 0:
+        raise ValueError("step k and base must be >= 0, got k=%d base=%d" % (k, base))
+    span = int(skip[-1])
+    hist = span + 1
+    if k == 0:
+        row = np.full(skip.size, base + hist, dtype=np.int32)          # 32 copies of unstable frame 0 (eval.py:93-94)
+    else:
+        row = (base + np.maximum(k + skip - span, 0) % hist).astype(np.int32)
+        row[-1] = base + hist                                           # the unstable frame k (eval.py:103)
+    return row, base + k % hist
+
+
+class OnlineStabilizer(object):
+    """eval.py:93-124 for up to `max_streams` live streams, one step at a time.
+
+    stab = OnlineStabilizer(model, max_streams=4)
+    sid = stab.open()
+    out = stab.push(sid, frame)                    # or stab.step({sid: frame, sid2: frame2, ...}) -> {sid: out}
+    stab.close(sid)                                # its ring is handed to the next open()
+
+    Frames are [h0,w0,3] and take the formats of `clip.stabilize_clip`: uint8 (resized to the model's (w, h) and
+    BGR-flipped with channel_order="bgr" as eval.py:79-80 does), or float RGB in [0,1] of the model's size (float64
+    renders the unstable half of side_by_side from float64).  The output of a stream is its stabilised frame [h,w,3]
+    float32, or uint8 with as_uint8, and with side_by_side the pair (out, side [h,2w,3] uint8).  NumPy in -> NumPy out
+    after a synchronise; device tensors in -> device tensors out with nothing synchronised.  model.precision selects
+    the precision.
+
+    One step: one `dvsg_frames_ingest_u8` launch per distinct uint8 source size (a float frame is copied into its
+    input slot), ONE `dvsg_stabilize_ring_inplace_f32` call for all streams in the step, then the uint8 egress
+    (`dvsg_frames_f32_to_u8_slots`) when asked for.  Streams may open and close at any step and a step may leave
+    a stream out; each stream's step count advances only with its own frames."""
+
+    def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
+                 as_uint8=False):
+        from . import _lib
+        from ._tensor import device
+        if channel_order not in ("rgb", "bgr"):
+            raise ValueError("channel_order must be 'rgb' or 'bgr'")
+        if model.locnet is None:
+            raise _lib.DvsgError("StabNet has no weights: call load_weights()/load_ckpt() first")
+        skip = check_skip_length(skip_length)
+        _check_window(model, skip.size)
+        if int(max_streams) < 1:
+            raise ValueError("max_streams must be >= 1, got %r" % (max_streams,))
+        self.model = model
+        self.skip_length = tuple(int(s) for s in skip)
+        self.max_streams = int(max_streams)
+        self.span = int(skip[-1])
+        self.frames_per_stream = self.span + 2
+        self.h, self.w = model.h, model.w
+        self.flip = 1 if channel_order == "bgr" else 0
+        self.side_by_side, self.as_uint8 = bool(side_by_side), bool(as_uint8)
+        dev = device()
+        self.pool = torch.empty((self.max_streams * self.frames_per_stream, self.h, self.w, 3), dtype=torch.float32,
+                                device=dev)
+        self._F = torch.empty((self.max_streams, model.param_dim, 2), dtype=torch.float32, device=dev)
+        self._free = list(range(self.max_streams))   # rings no open stream owns
+        self._streams = {}                           # sid -> [ring, frames pushed]
+        self._next_sid = 0
+
+    @property
+    def open_streams(self):
+        return sorted(self._streams)
+
+    def open(self):
+        """Start a stream (its first frame is step 0 of eval.py) and return its id."""
+        if not self._free:
+            raise RuntimeError("all %d streams of this OnlineStabilizer are open: close one first" % self.max_streams)
+        ring = self._free.pop(0)
+        sid = self._next_sid
+        self._next_sid += 1
+        self._streams[sid] = [ring, 0]
+        return sid
+
+    def close(self, sid):
+        ring, _ = self._stream(sid)
+        del self._streams[sid]
+        self._free.append(ring)
+        self._free.sort()
+
+    def _stream(self, sid):
+        st = self._streams.get(sid)
+        if st is not None:
+            return st
+        if isinstance(sid, (int, np.integer)) and 0 <= sid < self._next_sid:
+            raise ValueError("stream %d is closed" % sid)
+        raise ValueError("stream %r was never opened" % (sid,))
+
+    def push(self, sid, frame):
+        """`step` for a single stream: its output for `frame`."""
+        return self.step({sid: frame})[sid]
+
+    def step(self, frames):
+        """One step of every stream in `frames` ({sid: frame}); returns {sid: output}."""
+        from . import _lib
+        from ._tensor import device, ptr, stream
+        if not frames:
+            return {}
+        dev = device()
+        h, w, flip = self.h, self.w, self.flip
+        # ---- check everything before the first launch: a bad frame leaves every stream as it was
+        entries = []
+        for sid, fr in frames.items():
+            ring, k = self._stream(sid)
+            host = not isinstance(fr, torch.Tensor)
+            t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
+            if t.dim() != 3 or t.shape[2] != 3:
+                raise ValueError("stream %r: a frame must be [h,w,3], got %s" % (sid, tuple(t.shape)))
+            if t.dtype == torch.uint8:
+                kind = (0, int(t.shape[0]), int(t.shape[1])) if tuple(t.shape[:2]) != (h, w) else (1,)
+            elif t.dtype.is_floating_point:
+                if tuple(t.shape[:2]) != (h, w):
+                    raise ValueError("stream %r: float frames must already be [%d,%d,3] (StabNet(h, w) fixes the STN "
+                                     "out_size), got %s" % (sid, h, w, tuple(t.shape)))
+                kind = (3,) if t.dtype == torch.float64 else (2,)
+            else:
+                raise TypeError("stream %r: frames must be uint8 or floating point, got %s" % (sid, t.dtype))
+            entries.append((kind, sid, host, t, ring, k))
+        # batch order: resized uint8 by source size, same-size uint8, float, float64 -- each group is a contiguous
+        # range of the step's slot rows
+        entries.sort(key=lambda e: e[0])
+        B, S = len(entries), len(self.skip_length)
+        rows = np.empty(B * S + 2 * B, dtype=np.int32)     # [table B*S | out slots B | input slots B]
+        for i, (_, _, _, _, ring, k) in enumerate(entries):
+            base = ring * self.frames_per_stream
+            rows[i * S:(i + 1) * S], rows[B * S + i] = stream_window_row(k, base, self.skip_length)
+            rows[B * S + B + i] = base + self.span + 1
+        # a fresh pinned buffer per step: the caching host allocator does not hand it out again before this copy is done
+        idx = torch.from_numpy(rows).pin_memory().to(dev, non_blocking=True)
+        table, out_slots, in_slots = idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:]
+        n_pool = int(self.pool.shape[0])
+        side = torch.empty((B, h, 2 * w, 3), dtype=torch.uint8, device=dev) if self.side_by_side else None
+        # ---- ingest: the unstable frames into their input slots (eval.py:79-80)
+        left_from_pool = []   # batch positions whose unstable half is rendered from the float32 input slot
+        i = 0
+        while i < B:
+            kind = entries[i][0]
+            j = i
+            while j < B and entries[j][0] == kind:
+                j += 1
+            if kind[0] <= 1:
+                ts = [e[3].to(dev) for e in entries[i:j]]
+                src = ts[0].contiguous() if j - i == 1 else torch.stack(ts)
+                u8 = side[i:j] if side is not None and kind[0] == 0 else None
+                _lib.call("dvsg_frames_ingest_u8", ptr(src), j - i, int(src.shape[-3]), int(src.shape[-2]), flip,
+                          ptr(self.pool), n_pool, ptr(in_slots[i:j]), h, w, ptr(u8), 2 * w, 0, stream())
+                if kind[0] == 1:
+                    left_from_pool.extend(range(i, j))
+            else:
+                for b in range(i, j):
+                    t = entries[b][3].to(dev)
+                    self.pool[int(rows[B * S + B + b])].copy_(t)   # one rounding to float32 (the feed cast)
+                    if side is not None and kind[0] == 3:
+                        t = t.contiguous()
+                        _lib.call("dvsg_frames_f64_to_u8", ptr(t), 1, h, w, flip, ptr(side[b]), 2 * w, 0, stream())
+                    elif kind[0] == 2:
+                        left_from_pool.append(b)
+            i = j
+        if side is not None and left_from_pool:   # one contiguous range: same-size uint8 and float32 frames
+            a, b = left_from_pool[0], left_from_pool[-1] + 1
+            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(in_slots[a:b]), b - a, h, w, flip,
+                      ptr(side[a:b]), 2 * w, 0, stream())
+        # ---- the step: every stream's window from its ring, every result into its history slot (eval.py:101-120)
+        self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
+        for e in entries:
+            self._streams[e[1]][1] += 1
+        # ---- egress (eval.py:112-113)
+        if side is not None:
+            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(out_slots), B, h, w, flip, ptr(side),
+                      2 * w, w, stream())
+        if self.as_uint8:
+            out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev)
+            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(out_slots), B, h, w, flip, ptr(out),
+                      w, 0, stream())
+        else:
+            out = self.pool.index_select(0, out_slots)   # the ring slot is overwritten span + 1 steps later
+        if any(e[2] for e in entries):
+            out_h = out.cpu().numpy()
+            side_h = side.cpu().numpy() if side is not None else None
+        res = {}
+        for b, e in enumerate(entries):
+            o, sd = (out_h[b], side_h[b] if side is not None else None) if e[2] else (out[b], side[b] if side is not None else None)
+            res[e[1]] = (o, sd) if self.side_by_side else o
+        return {sid: res[sid] for sid in frames}
+
+
+def stabilize_clips(model, clips, batch=None, **kw):
+    """eval.py:76-124 for K whole clips at once: the clips run through one `OnlineStabilizer` of `batch` streams
+    (default K) in lockstep, so each step is one batched call and every clip keeps its own recurrence exactly.  Clips
+    may differ in length (a finished clip's ring goes to the next waiting clip).  `kw` are OnlineStabilizer's options.
+    Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips)."""
+    from ._tensor import device
+    K = len(clips)
+    if K == 0:
+        return []
+    batch = K if batch is None else max(1, min(int(batch), K))
+    dev = device()
+    host = [not isinstance(c, torch.Tensor) for c in clips]
+    dclips = []
+    for c, hst in zip(clips, host):
+        t = (torch.as_tensor(np.ascontiguousarray(c)) if hst else c).to(dev).contiguous()
+        if t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+            raise ValueError("every clip must be [N,h,w,3] with N >= 1, got %s" % (tuple(t.shape),))
+        dclips.append(t)
+    on = OnlineStabilizer(model, max_streams=batch, **kw)
+    outs = [[] for _ in range(K)]
+    waiting = list(range(K))
+    active = {}   # sid -> [clip, next frame]
+    while waiting or active:
+        while waiting and len(active) < batch:
+            active[on.open()] = [waiting.pop(0), 0]
+        res = on.step({sid: dclips[c][k] for sid, (c, k) in active.items()})
+        for sid, r in res.items():
+            c = active[sid][0]
+            outs[c].append(r)
+            active[sid][1] += 1
+            if active[sid][1] == dclips[c].shape[0]:
+                on.close(sid)
+                del active[sid]
+    result = []
+    for c in range(K):
+        if on.side_by_side:
+            o = (torch.stack([r[0] for r in outs[c]]), torch.stack([r[1] for r in outs[c]]))
+            o = tuple(x.cpu().numpy() for x in o) if host[c] else o
+        else:
+            o = torch.stack(outs[c])
+            o = o.cpu().numpy() if host[c] else o
+        result.append(o)
+    return result

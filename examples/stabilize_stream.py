@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""Live use of the drop-in: frames arrive one at a time (a camera or a decoder) for one or several streams, and each
+step returns every stream's stabilised frame (eval.py:93-124, online).  Decoding is host I/O and not part of this
+example: a seeded synthetic uint8 source stands in for it, BGR and larger than the model's size as cv2 would hand
+it over (eval.py:76-81 resizes it).
+
+    python examples/stabilize_stream.py [--streams 2] [--frames 48] [--height 288] [--width 512] [--precision f32|f32x3]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from coupe.dvsg_amd.model import StabNet                    # noqa: E402
+from coupe.dvsg_amd.online import OnlineStabilizer          # noqa: E402
+from coupe.dvsg_amd.weights import make_synthetic_weights   # noqa: E402
+
+
+def synthetic_source(seed, n, h, w):
+    """Yields n BGR uint8 frames [h,w,3], one at a time."""
+    import inputs
+    bank = (inputs.smooth_frames(seed, 8, h, w) * 255).astype(np.uint8)[..., ::-1]
+    for k in range(n):
+        yield np.ascontiguousarray(bank[k % 8])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=2)
+    ap.add_argument("--frames", type=int, default=48)
+    ap.add_argument("--height", type=int, default=288)    # config.py:12-13
+    ap.add_argument("--width", type=int, default=512)
+    ap.add_argument("--precision", default="f32", choices=["f32", "f32x3", "f32s", "f16"])
+    args = ap.parse_args()
+    net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0))
+    net.precision = args.precision
+    stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True)
+    sources = {stab.open(): synthetic_source(s + 1, args.frames, args.height * 3 // 2, args.width * 3 // 2)
+               for s in range(args.streams)}
+    lat = []
+    for k in range(args.frames):
+        frames = {sid: next(src) for sid, src in sources.items()}
+        t0 = time.perf_counter()
+        outs = stab.step(frames)            # NumPy in -> NumPy out: the step has finished when it returns
+        lat.append(time.perf_counter() - t0)
+        if k == 0:
+            out, side = next(iter(outs.values()))
+            print("per stream and step: stabilised", out.shape, out.dtype, "| side-by-side", side.shape, side.dtype)
+    for sid in list(sources):
+        stab.close(sid)
+    lat = np.array(lat[1:] if len(lat) > 1 else lat) * 1e3
+    print("%d stream(s) of %dx%d, %s: median %.2f ms per step (%.2f ms per frame), %.1f frames/s in all"
+          % (args.streams, args.width, args.height, args.precision, np.median(lat), np.median(lat) / args.streams,
+             args.streams * 1e3 / np.median(lat)))
+
+
+if __name__ == "__main__":
+    main()

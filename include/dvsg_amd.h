@@ -365,6 +365,34 @@ int dvsg_locnet_forward_ring(const dvsg_locnet_t *net, int precision, const void
                              const int32_t *table, int B, int H, int W, int stage, float *out, size_t out_bytes,
                              int *act_dims_host, void *workspace, size_t workspace_bytes, void *stream);
 /* ---------------------------------------------------------------------------------------
+ * ONLINE streams (eval.py:93-124 one frame at a time; coupe.dvsg_amd.online): each stream owns span + 2 consecutive
+ * frames of a float32 pool from `base` (span = skip_length[-1] = 32): span + 1 HISTORY slots, stabilised frame j in
+ * base + j % (span + 1), and one INPUT slot base + span + 1 holding the unstable frame of the current step.  The window
+ * of step k:  k == 0: every entry the input slot (eval.py:93-94);  k >= 1: entry s < 6 the history slot of frame
+ * max(k + skip[s] - span, 0) (frame 0 stands for the prepended copies after the write-back of eval.py:118-120), entry 6
+ * the input slot.  Step k writes its result into the history slot of frame k, which no window of step k reads (it
+ * held frame k - span - 1).  Several streams share one call: one table row and one out slot per stream.
+ *   dvsg_stabilize_ring_inplace_f32  dvsg_stabilize_ring_f32 whose s_t_pred of window b is written into pool frame
+ *          out_slots[b] (int32 [B] ON THE DEVICE) -- bit-identical to the contiguous s_t_pred of that call, in every
+ *          DVSG_PRECISION_*.  An out slot outside [0, n_pool) stores no frame (F_t, x_s, y_s are still written).
+ *          Contract, NOT checked on the device: the out slots of one call are distinct, and no entry of this call's
+ *          `table` names any of them.
+ *   dvsg_frames_ingest_u8  frame i of src [n,src_H,src_W,3] uint8 into pool frame slots[i] (int32 [n] on the device):
+ *          dvsg_frames_u8_to_f32's conversion when the size is (dst_H, dst_W) -- u8_dst must then be NULL, the uint8
+ *          half is rendered from the float32 slot by dvsg_frames_f32_to_u8_slots --, dvsg_frames_resize_u8_f32's resize
+ *          (and optional u8_dst [n,dst_H,u8_W,3]) otherwise.  Same values as those two, bit for bit.  A slot outside
+ *          [0, n_pool) is skipped.  n <= 65535.
+ *   dvsg_frames_f32_to_u8_slots  dvsg_frames_f32_to_u8 of frame i = pool frame slots[i] (int32 [n] on the device) into
+ *          row band i of dst; a slot outside [0, n_pool) reads as a frame of zeros.
+ * ------------------------------------------------------------------------------------- */
+int dvsg_stabilize_ring_inplace_f32(const dvsg_locnet_t *net, int precision, float *pool, int n_pool,
+                                    const int32_t *table, const int32_t *out_slots, int B, int H, int W, float *F_t,
+                                    float *x_s, float *y_s, void *workspace, size_t workspace_bytes, void *stream);
+int dvsg_frames_ingest_u8(const uint8_t *src, int n, int src_H, int src_W, int channel_flip, float *pool, int n_pool,
+                          const int32_t *slots, int dst_H, int dst_W, uint8_t *u8_dst, int u8_W, int u8_x0, void *stream);
+int dvsg_frames_f32_to_u8_slots(const float *pool, int n_pool, const int32_t *slots, int n, int H, int W, int channel_flip,
+                                uint8_t *dst, int dst_W, int dst_x0, void *stream);
+/* ---------------------------------------------------------------------------------------
  * eval_train.py's evaluation graph (eval_train.py:25-51): unlike model.py's, its CNN input is
  * `patches_masked_t = patches_t * mask` (:43-45), where `random_mask` (:53-64, = model.py:156-167) warps an all-ones
  * image of the 18 history channels with ProjectiveTransformer and a near-identity homography H and leaves the newest

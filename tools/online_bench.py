@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Throughput of online streams (coupe.dvsg_amd.online) against the one-clip loop (clip.stabilize_clip).
+
+For each size (720p and the reference's 512x288) and precision (f32, f32x3): K = 1, 4, 16 streams of same-size uint8
+frames already on the device go through one OnlineStabilizer in lockstep -- one batched
+dvsg_stabilize_ring_inplace_f32 call per step -- and the aggregate frames/s (K x steps over the host clock around
+the timed steps, which end in a synchronise) and the median step time (device events around each step) are reported.
+stabilize_clip on one clip of the same frames is the K = 1 reference.  One JSON line per measurement.
+
+    python tools/online_bench.py [--steps 40] [--warmup 6] [--sizes 720x1280,288x512] [--precisions f32,f32x3] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=6)
+    ap.add_argument("--sizes", default="720x1280,288x512")
+    ap.add_argument("--precisions", default="f32,f32x3")
+    ap.add_argument("--streams", default="1,4,16")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 1:
+        raise SystemExit("--steps and --warmup must be >= 1")
+    import numpy as np
+    import torch
+    import inputs
+    from coupe.dvsg_amd.clip import stabilize_clip
+    from coupe.dvsg_amd.model import Session, StabNet
+    from coupe.dvsg_amd.online import OnlineStabilizer
+    from coupe.dvsg_amd.weights import make_synthetic_weights
+    if not torch.cuda.is_available():
+        raise SystemExit("online_bench needs the GPU")
+    weights = make_synthetic_weights(seed=0)
+    lines = []
+
+    def emit(rec):
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+
+    for size in args.sizes.split(","):
+        H, W = (int(v) for v in size.split("x"))
+        model = StabNet(H, W).load_weights(weights)
+        model.get_evaluation_model(7)
+        # 8 distinct uint8 frames on the device; stream s at step k reads frame (k + 3 s) % 8
+        bank = torch.from_numpy((inputs.smooth_frames(11, 8, H, W) * 255).astype(np.uint8)).cuda()
+        for prec in args.precisions.split(","):
+            model.precision = prec
+            # the one-clip loop: batch 1, a clip of warmup + steps frames on the device, timed after a warm-up clip
+            n = args.warmup + args.steps
+            clip = bank[torch.arange(n) % 8].contiguous()
+            stabilize_clip(model, Session(), clip[:args.warmup])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            stabilize_clip(model, Session(), clip)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            emit({"what": "stabilize_clip", "H": H, "W": W, "precision": prec, "K": 1, "frames": n,
+                  "frames_per_s": n / dt, "ms_per_frame": 1e3 * dt / n})
+            for K in (int(v) for v in args.streams.split(",")):
+                on = OnlineStabilizer(model, max_streams=K)
+                sids = [on.open() for _ in range(K)]
+
+                def feed(k):
+                    return {sid: bank[(k + 3 * s) % 8] for s, sid in enumerate(sids)}
+                for k in range(args.warmup):
+                    on.step(feed(k))
+                torch.cuda.synchronize()
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                t0 = time.perf_counter()
+                for k in range(args.steps):
+                    ev[k][0].record()
+                    on.step(feed(args.warmup + k))
+                    ev[k][1].record()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                step_ms = sorted(a.elapsed_time(b) for a, b in ev)
+                emit({"what": "online", "H": H, "W": W, "precision": prec, "K": K, "steps": args.steps,
+                      "frames_per_s": K * args.steps / dt, "median_step_ms": step_ms[len(step_ms) // 2],
+                      "min_step_ms": step_ms[0], "max_step_ms": step_ms[-1], "ms_per_frame": 1e3 * dt / (K * args.steps),
+                      "pool_frames": int(on.pool.shape[0])})
+                del on
+                torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "a") as f:
+            for rec in lines:
+                f.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()
