@@ -78,6 +78,7 @@ SIGNATURES = {
     "dvsg_stabilize_ring_inplace_f32": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "dvsg_frames_ingest_u8": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp],
     "dvsg_frames_f32_to_u8_slots": [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
+    "dvsg_tps_render_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "dvsg_debug_set_option": [ctypes.c_char_p, _i],
     "dvsg_debug_last_conv_config": [ctypes.POINTER(_i), _i],
     "dvsg_debug_calibrate_f16_weights": [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp],

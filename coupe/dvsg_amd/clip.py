@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 SKIP_LENGTH = (0, 16, 24, 28, 30, 31, 32)   # config.py:48
+RENDER_BATCH_BYTES = 1 << 28                # output bytes per source-size render launch (stabilize_clip(source_res=True))
 
 
 def shard_range(n, world, rank):
@@ -138,7 +139,7 @@ def _check_window(model, S):
 
 
 def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side=False, channel_order="rgb",
-                   as_uint8=False):
+                   as_uint8=False, source_res=False):
     """eval.py:76-124 for one clip, entirely on the device.
 
     frames: [N,h0,w0,3], NumPy or torch.
@@ -159,6 +160,10 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     eval.py:112) with as_uint8 -- and, with side_by_side, also the reference's output video
     frames uint8 [N,h,2w,3] (unstable | stabilised, eval.py:112; BGR if channel_order="bgr",
     eval.py:113).  NumPy in -> NumPy out.
+
+    source_res=True (uint8 frames only): the outputs are at the frames' own size [N,h0,w0,3] (side [N,h0,2 w0,3], the
+    unstable half the source bytes): after the loop, each frame's F_t warps its source frame (`dvsg_tps_render_u8`, in
+    launches of at most RENDER_BATCH_BYTES of output).  The loop itself is unchanged.
     """
     from . import _lib
     from ._tensor import device, ptr, stream
@@ -178,9 +183,11 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     table = torch.from_numpy(window_index_table(N, skip_length)).to(dev)
     pool = torch.empty((2 * N, h, w, 3), dtype=torch.float32, device=dev)
     fr = fr.to(dev).contiguous()
+    if source_res and fr.dtype != torch.uint8:
+        raise ValueError("source_res renders the uint8 source frames; float frames have no source beyond the model's size")
     # the unstable half of the output video is np.uint8(float64 frame * 255.) (eval.py:112): rendered
     # from float64 wherever the float32 pool would not hold the same value
-    side = torch.empty((N, h, 2 * w, 3), dtype=torch.uint8, device=dev) if side_by_side else None
+    side = torch.empty((N, h, 2 * w, 3), dtype=torch.uint8, device=dev) if side_by_side and not source_res else None
     left_done = False
     if fr.dtype == torch.uint8:
         if tuple(fr.shape[1:3]) == (h, w):
@@ -188,7 +195,7 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
         else:
             _lib.call("dvsg_frames_resize_u8_f32", ptr(fr), N, int(fr.shape[1]), int(fr.shape[2]), flip, ptr(pool),
                       h, w, ptr(side), 2 * w, 0, stream())
-            left_done = side_by_side
+            left_done = side is not None
     elif fr.dtype.is_floating_point:
         if tuple(fr.shape[1:3]) != (h, w):
             raise ValueError("float frames must already be [N,%d,%d,3] (StabNet(h, w) fixes the STN out_size)" % (h, w))
@@ -198,12 +205,26 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
             left_done = True
     else:
         raise TypeError("frames must be uint8 or floating point, got %s" % fr.dtype)
-    F = torch.empty((1, model.param_dim, 2), dtype=torch.float32, device=dev)
+    F = torch.empty((N, model.param_dim, 2), dtype=torch.float32, device=dev)   # F_t of every frame
     # one call per frame: conv1 picks the 7 window frames out of the pool through table[k] (eval.py:103-104 fused
     # into its load stage: no window tensor, no gather launch), the warp reads u_t = pool[table[k, 6]] = pool[k],
     # and the result lands in its history slot pool[N + k] (:116), which no slot of window k reads
     for k in range(N):                                                             # eval.py:101
-        model.locnet.stabilize_ring(pool, table[k:k + 1], pool[N + k:N + k + 1], F, precision=model.precision)  # :106-110
+        model.locnet.stabilize_ring(pool, table[k:k + 1], pool[N + k:N + k + 1], F[k:k + 1],
+                                    precision=model.precision)                    # :106-110
+    if source_res:   # eval.py:112-113 at the frames' own size, in launches of at most RENDER_BATCH_BYTES of output
+        H0, W0 = int(fr.shape[1]), int(fr.shape[2])
+        out = torch.empty((N, H0, W0, 3), dtype=torch.uint8 if as_uint8 else torch.float32, device=dev)
+        side = torch.empty((N, H0, 2 * W0, 3), dtype=torch.uint8, device=dev) if side_by_side else None
+        batch = max(1, min(N, 65535, RENDER_BATCH_BYTES // (H0 * W0 * 3 * (out.element_size() + int(side_by_side)))))
+        T = torch.empty((batch, 2, model.param_dim + 3), dtype=torch.float32, device=dev)
+        for b0 in range(0, N, batch):
+            b1 = min(N, b0 + batch)
+            render_source_into(model, fr[b0:b1], F[b0:b1], T, flip, out[b0:b1], side[b0:b1] if side is not None else None)
+        if host:
+            out = out.cpu().numpy()
+            side = side.cpu().numpy() if side is not None else None
+        return (out, side) if side_by_side else out
     stab = pool[N:]
     if side_by_side:                                                               # eval.py:112-113
         if not left_done:   # uint8 / float32 input: the float32 pool holds the frame exactly
@@ -218,6 +239,26 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
         out = out.cpu().numpy()
         side = side.cpu().numpy() if side is not None else None
     return (out, side) if side_by_side else out
+
+
+def render_source_into(model, src, F, T, flip, out, side=None):
+    """`dvsg_tps_render_u8` for the uint8 frames src [n,H0,W0,3] (device) and their F_t rows F [n,25,2]: the stabilised
+    frames at source size into `out` [n,H0,W0,3] (float32, or uint8: np.uint8(x * 255.) in the channel order of src)
+    and, if given, `side` [n,H0,2 W0,3] uint8 = (source bytes | uint8 render).  T [n,2,28] receives the TPS
+    coefficients.  One render launch; a uint8 `out` is copied into the right half of `side`."""
+    from . import _lib
+    from ._tensor import ptr, stream
+    n, H0, W0 = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    if side is not None:
+        side[:, :, :W0] = src   # np.uint8(v / 255. * 255.) == v for every byte: the unstable half is the source
+    if out.dtype == torch.uint8:
+        f32, u8, u8_W, u8_x0 = None, out, W0, 0
+    else:                       # one launch writes the float32 render and the right half of side
+        f32, u8, u8_W, u8_x0 = out, side, 2 * W0, W0
+    _lib.call("dvsg_tps_render_u8", model.locnet.handle, ptr(F), ptr(src), n, H0, W0, flip, ptr(T), ptr(f32), ptr(u8),
+              u8_W, u8_x0, stream())
+    if side is not None and out.dtype == torch.uint8:
+        side[:, :, W0:] = out
 
 
 def teacher_forced_index_table(n_frames, skip_length=SKIP_LENGTH):

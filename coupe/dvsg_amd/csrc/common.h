@@ -50,11 +50,23 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
                        long coord_bstride, const float *T, int B, int H, int W, int P, float *out, float *x_s, float *y_s,
                        void *stream, const int *out_index = nullptr);
 
+// dvsg_tps_render_u8 (winv_cols / coord: the handle's W^-1 columns and V_src)
+int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
+                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream);
+
 void set_flow_tiled(int v); // diagnostic (dvsg_debug_set_option "flow_tiled"): 0 = tf_warp by global gathers (stn_kernel<kFlow>)
 void set_flow_rounds(int v);
 void set_warp_xcd(int v);   // diagnostic (dvsg_debug_set_option "warp_xcd"): XCD-aware workgroup order of the sampler kernels
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// np.uint8(x * 255.) of eval.py:112: the product is float64 and the cast truncates toward zero.
+// (NumPy leaves out-of-range casts undefined; here they saturate to 0 / 255, NaN gives 0.)
+// Shared by the frame egress (frames.hip) and the uint8 form of the TPS warp (warp_kernels.hip).
+__device__ __forceinline__ uint8_t to_u8(double x) {
+  const double d = x * 255.0;
+  return d >= 255.0 ? (uint8_t)255 : (d > 0.0 ? (uint8_t)(int)d : (uint8_t)0);
+}
 
 }  // namespace dvsg
 

@@ -110,13 +110,6 @@ __global__ __launch_bounds__(kThreads) void window_gather_kernel(const float *__
   }
 }
 
-// np.uint8(x * 255.) of eval.py:112: the product is float64 and the cast truncates toward zero.
-// (NumPy leaves out-of-range casts undefined; here they saturate to 0 / 255, NaN gives 0.)
-__device__ __forceinline__ uint8_t to_u8(double x) {
-  const double d = x * 255.0;
-  return d >= 255.0 ? (uint8_t)255 : (d > 0.0 ? (uint8_t)(int)d : (uint8_t)0);
-}
-
 // One thread converts 4 consecutive values of a row (row = W*3 values); rows land at
 // dst + (n*H + y) * dst_row_bytes + dst_col_bytes.  With `slots`, row n*H + y is read from pool frame slots[n]
 // (H rows per frame); a slot outside [0, n_pool) reads as a frame of zeros.

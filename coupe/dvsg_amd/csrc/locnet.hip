@@ -1259,6 +1259,15 @@ int dvsg_stabilize_ring_inplace_f32(const dvsg_locnet_t *net, int precision, flo
                         workspace, workspace_bytes, stream, out_slots);
 }
 
+// Source-resolution render of an online step: the T of dvsg_stabilize_* for F_t (tps_apply_kernel on the handle's W^-1
+// columns and V_src, bit for bit), then the uint8 source frames warped by it at their own size.
+int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
+                       int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
+  DVSG_REQUIRE(net, "dvsg_tps_render_u8: NULL net");
+  return tps_render_impl(net->winv, net->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8, u8_W,
+                         u8_x0, stream);
+}
+
 // eval_train.py's evaluation graph (:25-51): F_t = localizationNet(patches_t * mask), the warp on the unmasked u_t.
 int dvsg_stabilize_masked_f32(const dvsg_locnet_t *net, int precision, const float *patches_t, const float *u_t,
                               const float *mask, int B, int H, int W, float *s_t_pred, float *F_t, float *x_s, float *y_s,

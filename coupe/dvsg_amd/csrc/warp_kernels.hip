@@ -12,6 +12,7 @@
 // This translation unit is compiled with -ffp-contract=off: the reference graph is a chain
 // of separately rounded float32 mul / add ops, and keeping the same roundings lets the
 // parity tests compare source coordinates to the oracle within 1-2 ulp (only logf differs).
+#include <type_traits>
 #include <vector>
 
 #include <cstdint>
@@ -408,13 +409,22 @@ constexpr float kLn2 = 0x1.62e43p-1f;
 // out_index given (dvsg_stabilize_ring_inplace_f32): `out` is that pool too, and sample b stores its frame into pool frame
 // out_index[b] instead of out + b; an index outside [0, n_pool) stores no frame (x_s / y_s are still written).  Only the
 // store address changes: the samples' arithmetic is the contiguous form's.
-template <int C, typename TU = float>
+// TO = uint8_t (dvsg_tps_render_u8, C = 3, TU = uint8_t): `out` is a uint8 image [B,out_h,out_row,3] that receives
+// np.uint8(v * 255.) (to_u8) of each blended value in columns [out_x0, out_x0 + out_w), in the channel order of U; and
+// out_rgb, if given, the float32 values [B,out_h,out_w,3] -- channel-flipped when `flip` is set, i.e. exactly what
+// dvsg_tps_warp_f32 gives on dvsg_frames_u8_to_f32(U, flip).  Sampler A blends every channel on its own, so flipping
+// the channels on the way in and back on the way out of the uint8 image is no flip at all: only out_rgb swaps them.
+// Either output may be NULL.  The trailing arguments are read by this form only.
+template <int C, typename TU = float, typename TO = float>
 __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     const TU *__restrict__ U, const float *__restrict__ coord, long coord_bstride,
     const float *__restrict__ T, int H, int W, int Cn, int P, int out_h, int out_w, float step_x,
-    float step_y, float *__restrict__ out,
+    float step_y, TO *__restrict__ out,
     float *__restrict__ xs_out, float *__restrict__ ys_out, const int *__restrict__ u_index = nullptr, int u_stride = 0,
-    int n_pool = 0, const int *__restrict__ out_index = nullptr) {
+    int n_pool = 0, const int *__restrict__ out_index = nullptr, int out_row = 0, int out_x0 = 0, int flip = 0,
+    float *__restrict__ out_rgb = nullptr) {
+  constexpr bool kU8Out = std::is_same<TO, uint8_t>::value;
+  static_assert(!kU8Out || (C == 3 && std::is_same<TU, uint8_t>::value), "the uint8 output form reads uint8 RGB frames");
   __shared__ float4 sp[64];      // {px, py, T[0][3+k], T[1][3+k]}
   __shared__ float4 sdy[64];     // (y_t[r] - py)^2 for the 4 rows of this workgroup
   __shared__ float sa[6];        // T[0][0..2], T[1][0..2]
@@ -493,7 +503,11 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     if (ys_out) ys_out[pix] = ys[r];
     if (img) sample_a_load<C, TU>(img, H, W, Cn, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
   }
-  if (!img || !out) return;
+  if constexpr (kU8Out) {
+    if (!img || (!out && !out_rgb)) return;
+  } else {
+    if (!img || !out) return;
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = i0 + r;
@@ -506,7 +520,19 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
         for (int c = 0; c < C; ++c) v[c] = 0.f;
       }
     }
-    store_pix<C>(out, (out_frame * out_h + i) * out_w + j, Cn, v);
+    if constexpr (kU8Out) {
+      if (out_rgb) {
+        const float rgb[3] = {v[flip ? 2 : 0], v[1], v[flip ? 0 : 2]};
+        store_pix<3>(out_rgb, (out_frame * out_h + i) * out_w + j, 3, rgb);
+      }
+      if (out) {
+        uint8_t *d = out + ((out_frame * out_h + i) * out_row + out_x0 + j) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = to_u8((double)v[c]);
+      }
+    } else {
+      store_pix<C>(out, (out_frame * out_h + i) * out_w + j, Cn, v);
+    }
   }
 }
 
@@ -1030,6 +1056,30 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
   else
     hipLaunchKernelGGL((tps_warp_kernel<3, float>), grid, dim3(kThreads), 0, s, static_cast<const float *>(pool), coord,
                        coord_bstride, T, H, W, 3, P, H, W, sx, sy, out, x_s, y_s, table, tstride, n_pool, out_index);
+  return check_launch("tps_warp_kernel");
+}
+
+// T = the TPS coefficients of dvsg_stabilize_* for F_t (tps_apply_kernel on winv_cols / coord), then frame b of the uint8
+// frames src [B,H,W,3] warped at its own size (tps_warp_kernel<3, uint8_t, uint8_t>): float32 RGB out_f32 [B,H,W,3]
+// and / or uint8 out_u8 [B,H,u8_W,3] in columns [u8_x0, u8_x0 + W).  Every argument is checked before the first launch.
+int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
+                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
+  DVSG_REQUIRE(winv_cols && coord && F_t && src && T, "dvsg_tps_render_u8: NULL pointer");
+  DVSG_REQUIRE(out_f32 || out_u8, "dvsg_tps_render_u8: neither out_f32 nor out_u8 given");
+  DVSG_REQUIRE(B >= 1 && B <= 65535, "dvsg_tps_render_u8: n=%d outside [1, 65535]", B);
+  if (int rc = check_image_args("dvsg_tps_render_u8", B, H, W, 3, H, W)) return rc;
+  DVSG_REQUIRE(!out_u8 || (u8_x0 >= 0 && (long)u8_W >= (long)u8_x0 + W),
+               "dvsg_tps_render_u8: columns [%d, %ld) do not fit a row of %d pixels", u8_x0, (long)u8_x0 + W, u8_W);
+  DVSG_REQUIRE(!out_u8 || (long)H * u8_W < (1L << 31), "dvsg_tps_render_u8: uint8 image too large");
+  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream)) return rc;
+  dim3 grid(ceil_div(W, kThreads), ceil_div(H, kTpsRows), B);
+  const float sx = lin_step(W), sy = lin_step(H);
+  hipStream_t s = as_stream(stream);
+  // algorithmic bytes: the uint8 frame once, then 3 B (uint8) and / or 12 B (float32) per output pixel
+  ProfScope prof(kClsTpsWarp, s, 0.0, (double)B * H * W * (3.0 + (out_u8 ? 3.0 : 0.0) + (out_f32 ? 12.0 : 0.0)));
+  hipLaunchKernelGGL((tps_warp_kernel<3, uint8_t, uint8_t>), grid, dim3(kThreads), 0, s, src, coord, 0L, T, H, W, 3, P, H,
+                     W, sx, sy, out_u8, (float *)nullptr, (float *)nullptr, (const int *)nullptr, 0, 0, (const int *)nullptr,
+                     u8_W, u8_x0, channel_flip ? 1 : 0, out_f32);
   return check_launch("tps_warp_kernel");
 }
 

@@ -20,7 +20,7 @@ their own lag-1 recurrence and still share batched CNN launches.  The pool never
 import numpy as np
 import torch
 
-from .clip import SKIP_LENGTH, _check_window, check_skip_length
+from .clip import SKIP_LENGTH, _check_window, check_skip_length, render_source_into
 
 
 def stream_window_row(k, base, skip_length=SKIP_LENGTH):
@@ -59,10 +59,16 @@ class OnlineStabilizer(object):
     One step: one `dvsg_frames_ingest_u8` launch per distinct uint8 source size (a float frame is copied into its
     input slot), ONE `dvsg_stabilize_ring_inplace_f32` call for all streams in the step, then the uint8 egress
     (`dvsg_frames_f32_to_u8_slots`) when asked for.  Streams may open and close at any step and a step may leave
-    a stream out; each stream's step count advances only with its own frames."""
+    a stream out; each stream's step count advances only with its own frames.
+
+    source_res=True: the output of a stream is rendered at the size of its uint8 frame [H0,W0,3] instead of the model's:
+    the step's F_t warps the source frame itself (`dvsg_tps_render_u8`, one launch per distinct source size, reading the
+    device copy ingest made), float32 [H0,W0,3] or uint8 with as_uint8, and side [H0,2 W0,3] = (source bytes | render)
+    with side_by_side.  The recurrence is unchanged: the pool, F_t and the model-size history are those of a run
+    without it.  Float frames carry no source beyond the model's size and raise ValueError."""
 
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
-                 as_uint8=False):
+                 as_uint8=False, source_res=False):
         from . import _lib
         from ._tensor import device
         if channel_order not in ("rgb", "bgr"):
@@ -80,11 +86,14 @@ class OnlineStabilizer(object):
         self.frames_per_stream = self.span + 2
         self.h, self.w = model.h, model.w
         self.flip = 1 if channel_order == "bgr" else 0
-        self.side_by_side, self.as_uint8 = bool(side_by_side), bool(as_uint8)
+        self.side_by_side, self.as_uint8, self.source_res = bool(side_by_side), bool(as_uint8), bool(source_res)
         dev = device()
         self.pool = torch.empty((self.max_streams * self.frames_per_stream, self.h, self.w, 3), dtype=torch.float32,
                                 device=dev)
         self._F = torch.empty((self.max_streams, model.param_dim, 2), dtype=torch.float32, device=dev)
+        # the TPS coefficients of a source-size render ([n,2,P+3], written by dvsg_tps_render_u8)
+        self._T = torch.empty((self.max_streams, 2, model.param_dim + 3), dtype=torch.float32, device=dev) \
+            if self.source_res else None
         self._free = list(range(self.max_streams))   # rings no open stream owns
         self._streams = {}                           # sid -> [ring, frames pushed]
         self._next_sid = 0
@@ -140,6 +149,9 @@ class OnlineStabilizer(object):
             if t.dtype == torch.uint8:
                 kind = (0, int(t.shape[0]), int(t.shape[1])) if tuple(t.shape[:2]) != (h, w) else (1,)
             elif t.dtype.is_floating_point:
+                if self.source_res:
+                    raise ValueError("stream %r: source_res renders the uint8 source frame; a float frame has no source "
+                                     "beyond the model's size" % (sid,))
                 if tuple(t.shape[:2]) != (h, w):
                     raise ValueError("stream %r: float frames must already be [%d,%d,3] (StabNet(h, w) fixes the STN "
                                      "out_size), got %s" % (sid, h, w, tuple(t.shape)))
@@ -160,7 +172,9 @@ class OnlineStabilizer(object):
         idx = torch.from_numpy(rows).pin_memory().to(dev, non_blocking=True)
         table, out_slots, in_slots = idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:]
         n_pool = int(self.pool.shape[0])
-        side = torch.empty((B, h, 2 * w, 3), dtype=torch.uint8, device=dev) if self.side_by_side else None
+        side = torch.empty((B, h, 2 * w, 3), dtype=torch.uint8, device=dev) \
+            if self.side_by_side and not self.source_res else None
+        groups = []           # uint8 batch ranges (i, j, device frames [j-i,H0,W0,3]): one source size each
         # ---- ingest: the unstable frames into their input slots (eval.py:79-80)
         left_from_pool = []   # batch positions whose unstable half is rendered from the float32 input slot
         i = 0
@@ -175,6 +189,7 @@ class OnlineStabilizer(object):
                 u8 = side[i:j] if side is not None and kind[0] == 0 else None
                 _lib.call("dvsg_frames_ingest_u8", ptr(src), j - i, int(src.shape[-3]), int(src.shape[-2]), flip,
                           ptr(self.pool), n_pool, ptr(in_slots[i:j]), h, w, ptr(u8), 2 * w, 0, stream())
+                groups.append((i, j, src.view(j - i, *src.shape[-3:])))
                 if kind[0] == 1:
                     left_from_pool.extend(range(i, j))
             else:
@@ -195,6 +210,9 @@ class OnlineStabilizer(object):
         self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
         for e in entries:
             self._streams[e[1]][1] += 1
+        if self.source_res:
+            res = self._render_source(entries, groups)
+            return {sid: res[sid] for sid in frames}
         # ---- egress (eval.py:112-113)
         if side is not None:
             _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(out_slots), B, h, w, flip, ptr(side),
@@ -213,6 +231,25 @@ class OnlineStabilizer(object):
             o, sd = (out_h[b], side_h[b] if side is not None else None) if e[2] else (out[b], side[b] if side is not None else None)
             res[e[1]] = (o, sd) if self.side_by_side else o
         return {sid: res[sid] for sid in frames}
+
+    def _render_source(self, entries, groups):
+        """Egress of a source_res step: per source size, one `dvsg_tps_render_u8` launch that warps the uint8 frames by
+        this step's F_t rows (contiguous: a group is a contiguous batch range) at their own size."""
+        res = {}
+        for i, j, src in groups:
+            n, H0, W0 = j - i, int(src.shape[1]), int(src.shape[2])
+            out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
+            side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
+            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side)
+            if any(entries[b][2] for b in range(i, j)):
+                out_h = out.cpu().numpy()
+                side_h = side.cpu().numpy() if side is not None else None
+            for b in range(i, j):
+                e = entries[b]
+                o, sd = (out_h[b - i], side_h[b - i] if side is not None else None) if e[2] else \
+                    (out[b - i], side[b - i] if side is not None else None)
+                res[e[1]] = (o, sd) if self.side_by_side else o
+        return res
 
 
 def stabilize_clips(model, clips, batch=None, **kw):

@@ -384,6 +384,13 @@ int dvsg_locnet_forward_ring(const dvsg_locnet_t *net, int precision, const void
  *          [0, n_pool) is skipped.  n <= 65535.
  *   dvsg_frames_f32_to_u8_slots  dvsg_frames_f32_to_u8 of frame i = pool frame slots[i] (int32 [n] on the device) into
  *          row band i of dst; a slot outside [0, n_pool) reads as a frame of zeros.
+ *   dvsg_tps_render_u8  the stabilised frame at SOURCE resolution: F_t [n,25,2] (the F_t of a dvsg_stabilize_* call,
+ *          e.g. dvsg_stabilize_ring_inplace_f32 on the same stream) -> T [n,2,28] (written: the T of dvsg_stabilize_*
+ *          for that F_t, bit for bit), then frame i of src [n,src_H,src_W,3] uint8 warped at its own size: out_f32
+ *          [n,src_H,src_W,3] and/or out_u8 [n,src_H,u8_W,3] in columns [u8_x0, u8_x0 + src_W).  out_f32 is
+ *          dvsg_tps_warp_f32(dvsg_frames_u8_to_f32(src, channel_flip), V_src, T, out = (src_H, src_W)) bit for bit
+ *          (RGB), out_u8 is dvsg_frames_f32_to_u8(out_f32, channel_flip) (the channel order of src).  Either output may
+ *          be NULL, not both.  n <= 65535.
  * ------------------------------------------------------------------------------------- */
 int dvsg_stabilize_ring_inplace_f32(const dvsg_locnet_t *net, int precision, float *pool, int n_pool,
                                     const int32_t *table, const int32_t *out_slots, int B, int H, int W, float *F_t,
@@ -392,6 +399,8 @@ int dvsg_frames_ingest_u8(const uint8_t *src, int n, int src_H, int src_W, int c
                           const int32_t *slots, int dst_H, int dst_W, uint8_t *u8_dst, int u8_W, int u8_x0, void *stream);
 int dvsg_frames_f32_to_u8_slots(const float *pool, int n_pool, const int32_t *slots, int n, int H, int W, int channel_flip,
                                 uint8_t *dst, int dst_W, int dst_x0, void *stream);
+int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
+                       int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream);
 /* ---------------------------------------------------------------------------------------
  * eval_train.py's evaluation graph (eval_train.py:25-51): unlike model.py's, its CNN input is
  * `patches_masked_t = patches_t * mask` (:43-45), where `random_mask` (:53-64, = model.py:156-167) warps an all-ones
