@@ -59,9 +59,23 @@ constexpr size_t kSplitKSlabBytes = (size_t)512 * 2 * 128 * 128 * 4;   // 64 MiB
 int launch_conv_gemm(const ConvGemm &p, hipStream_t s);
 // diagnostic record of the last conv_gemm_kernel launch (dvsg_debug_last_conv_config): T (0 float32 tensors, 1 float16),
 // BN, WM, WN, KS, RELU, RES, MODE, SPLIT, X3, ksplit, streamk_tail, mt_fast; T = -1 when the last launch_conv_gemm call did
-// not end in conv_gemm_kernel (the float16 mode's 256 x 128 geometry) or there was none.  Host-only; written by launch_cfg
+// not end in conv_gemm_kernel (g_last_conv_kernel then names the kernel that ran) or there was none.  Host-only; written by
+// launch_cfg
 constexpr int kConvConfigFields = 13;
 extern int g_last_conv_config[kConvConfigFields];
+// diagnostic record of the last conv kernel launch of any family (dvsg_debug_last_conv_kernel): family (0 conv_gemm_kernel,
+// 1 conv_wide16_kernel, 2 conv_wide16a_kernel, 3 conv_wide16h_kernel, 4 conv3x3_1x1_kernel, 5 conv3x3_1x1_x3_kernel,
+// 6 conv3x3_1x1_f16_kernel, 7 conv3x3_1x1_f16h_kernel), the family's template arguments in declaration order padded with -1
+// (family 0: all -1, its details are g_last_conv_config), and for families 1-3 where the weight stages came from (0 the
+// [rows][K] layout, 1 the packed copy), else -1.  Reset by launch_conv_gemm, launch_conv_wide16 and the launch_conv3x3_1x1*
+// calls, written where they issue the launch.  Host-only
+constexpr int kConvKernelFields = 6;
+extern int g_last_conv_kernel[kConvKernelFields];
+inline void record_conv_kernel(int family, int a0 = -1, int a1 = -1, int a2 = -1, int a3 = -1, int wsrc = -1) {
+  const int rec[kConvKernelFields] = {family, a0, a1, a2, a3, wsrc};
+  for (int i = 0; i < kConvKernelFields; ++i) g_last_conv_kernel[i] = rec[i];
+}
+inline void reset_conv_kernel() { record_conv_kernel(-1); }
 // f32x3 weights: float32 wt [rows][K] (rows % 64 == 0, K % 32 == 0) -> per group of 64 rows and 32-k stage three 4 KB planes
 // of bfloat16 pieces [64 rows][32 k] (p1 = bf16(w), p2 = bf16(w - p1), p3 = bf16(w - p1 - p2)), row R's 16-byte chunk c at
 // position c ^ ((R >> 2) & 3): 6 bytes per weight, [rows / 64][K / 32][3][64][32]

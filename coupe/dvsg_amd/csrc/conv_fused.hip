@@ -911,6 +911,7 @@ bool conv_fusable(int prec, int Cin, int Cmid, int Cout, int ksize) {
 }
 
 static int launch_conv3x3_1x1_f16(const ConvFused &p, hipStream_t s) {
+  reset_conv_kernel();
   DVSG_REQUIRE(p.Cin % 64 == 0 && p.Cin >= 64 && p.Cout % 64 == 0, "conv3x3_1x1 (float16): Cin=%d and Cout=%d must be multiples of 64",
                p.Cin, p.Cout);
   const bool sc = p.sc_x != nullptr;
@@ -941,16 +942,19 @@ static int launch_conv3x3_1x1_f16(const ConvFused &p, hipStream_t s) {
     const dim3 gridh(d.mtiles), blockh(512);
     if (res == 1) hipLaunchKernelGGL((conv3x3_1x1_f16h_kernel<1>), gridh, blockh, 0, s, d);
     else hipLaunchKernelGGL((conv3x3_1x1_f16h_kernel<3>), gridh, blockh, 0, s, d);
+    record_conv_kernel(7, res);
     return check_launch("conv3x3_1x1_f16h_kernel");
   }
   const dim3 grid(d.mtiles), block(512);
   if (res == 1) hipLaunchKernelGGL((conv3x3_1x1_f16_kernel<1>), grid, block, 0, s, d);
   else if (res == 2) hipLaunchKernelGGL((conv3x3_1x1_f16_kernel<2>), grid, block, 0, s, d);
   else hipLaunchKernelGGL((conv3x3_1x1_f16_kernel<3>), grid, block, 0, s, d);
+  record_conv_kernel(6, res);
   return check_launch("conv3x3_1x1_f16_kernel");
 }
 
 int launch_conv3x3_1x1(const ConvFused &p, hipStream_t s) {
+  reset_conv_kernel();
   if (p.f16) return launch_conv3x3_1x1_f16(p, s);
   if (p.x3) return launch_conv3x3_1x1_x3(p, s);
   DVSG_REQUIRE(p.Cin % 32 == 0 && p.Cin >= 64 && p.Cout % 128 == 0, "conv3x3_1x1: Cin=%d must be a multiple of 32 (>= 64), Cout=%d of 128",
@@ -986,6 +990,7 @@ int launch_conv3x3_1x1(const ConvFused &p, hipStream_t s) {
     else if (res == 2) hipLaunchKernelGGL((conv3x3_1x1_kernel<2>), grid, block, 0, s, d);
     else hipLaunchKernelGGL((conv3x3_1x1_kernel<3>), grid, block, 0, s, d);
   }
+  record_conv_kernel(4, res, p.pieces ? 1 : 0);
   return check_launch("conv3x3_1x1_kernel");
 }
 

@@ -319,6 +319,7 @@ void conv3x3_1x1_x3_kernel(FusedX3Dev p) {
 }  // namespace
 
 int launch_conv3x3_1x1_x3(const ConvFused &p, hipStream_t s) {
+  reset_conv_kernel();
   DVSG_REQUIRE(p.Cin % 32 == 0 && p.Cin >= 64 && p.Cout % 64 == 0, "conv3x3_1x1 (f32x3): Cin=%d must be a multiple of 32 (>= 64), Cout=%d of 64",
                p.Cin, p.Cout);
   DVSG_REQUIRE(p.res && !p.sc_x, "conv3x3_1x1 (f32x3): the residual is a tensor (the opening unit's shortcut conv runs as its own launch)");
@@ -340,6 +341,7 @@ int launch_conv3x3_1x1_x3(const ConvFused &p, hipStream_t s) {
   const dim3 grid(d.mtiles), block(64 * NW);
   if (res == 1) hipLaunchKernelGGL((conv3x3_1x1_x3_kernel<1>), grid, block, 0, s, d);
   else hipLaunchKernelGGL((conv3x3_1x1_x3_kernel<2>), grid, block, 0, s, d);
+  record_conv_kernel(5, res);
   return check_launch("conv3x3_1x1_x3_kernel");
 }
 

@@ -13,6 +13,7 @@ long g_wide16_min_tiles = 128;   // float16 mode: 256 x 128 tiles from this many
                                  // at batch 4 (720p), equal at batch 1; 64 and 32 lose 4-27 % at batch 1-4
 
 int g_last_conv_config[kConvConfigFields] = {-1};
+int g_last_conv_kernel[kConvKernelFields] = {-1, -1, -1, -1, -1, -1};
 
 void set_conv_variant(int v) { g_conv_variant = v; }
 void set_wide16_min_tiles(int v) { g_wide16_min_tiles = v; }
@@ -54,6 +55,7 @@ int launch_zero_tickets(int *tickets, size_t n, hipStream_t s) {
 
 int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   g_last_conv_config[0] = -1;   // until launch_cfg records this call's launch
+  reset_conv_kernel();
   DVSG_REQUIRE(p.prec == kF32 || p.prec == kF16, "conv_gemm: unknown precision %d", p.prec);
   DVSG_REQUIRE(p.ksize == 1 || p.ksize == 3, "conv_gemm: kernel size %d unsupported", p.ksize);
   const int bke = ROWB / (int)elem_size(p.prec);

@@ -713,6 +713,7 @@ int launch_cfg(const ConvGemmDev &d, int blocks, bool relu, int res, hipStream_t
   const int rec[kConvConfigFields] = {sizeof(T) == 4 ? 0 : 1, BN, WM, WN, KS, relu ? 1 : 0, res, MODE, SPLIT, X3,
                                       d.ksplit, MODE == 2 ? d.tile_count : 0, d.mt_fast};
   std::copy(rec, rec + kConvConfigFields, g_last_conv_config);
+  record_conv_kernel(0);
   return check_launch("conv_gemm_kernel");
 }
 

@@ -714,6 +714,7 @@ int launch_h(const ConvWide16Dev &d, bool relu, int res, hipStream_t s) {
     else DVSG_LAUNCH(false, 2);
   }
 #undef DVSG_LAUNCH
+  record_conv_kernel(3, relu ? 1 : 0, res, SPLIT ? 1 : 0, -1, d.wtp ? 1 : 0);
   return check_launch("conv_wide16h_kernel");
 }
 
@@ -735,6 +736,7 @@ int launch_ks(const ConvWide16Dev &d, bool relu, int res, hipStream_t s) {
     else DVSG_LAUNCH(false, 2);
   }
 #undef DVSG_LAUNCH
+  record_conv_kernel(d.arows ? 2 : 1, KS, relu ? 1 : 0, res, SPLIT ? 1 : 0, d.wtp ? 1 : 0);
   return check_launch("conv_wide16_kernel");
 }
 
@@ -806,6 +808,7 @@ extern "C" int dvsg_debug_read_wide16_stamps(void *host, size_t bytes) {
 // p: a float16 layer -- stacked [hi | lo] weights (p.wsplit, Cout % 64 == 0) or plain ones (Cout % 128 == 0) -- with
 // Cin % 64 == 0; the caller has opened the ProfScope
 int launch_conv_wide16(const ConvGemm &p, hipStream_t s) {
+  reset_conv_kernel();
   const long M = (long)p.B * p.Ho * p.Wo;
   ConvWide16Dev d;
   d.x = static_cast<const _Float16 *>(p.x); d.wt = static_cast<const _Float16 *>(p.wt);

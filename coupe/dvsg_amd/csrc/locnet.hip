@@ -1020,6 +1020,39 @@ int dvsg_conv3x3_1x1_f32x3(const float *x, const void *wt2_packed, const float *
   return launch_conv3x3_1x1(f, as_stream(stream));
 }
 
+int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float *bias2, const void *wt3, const float *bias3,
+                           const void *res, const void *sc_x, const void *sc_wt, const float *sc_bias, int sc_cin, void *y, int B,
+                           int H, int W, int Cin, int Cout, int stride, int res_stride, void *stream) {
+  DVSG_REQUIRE(prec >= kF32 && prec <= kF32X, "dvsg_debug_conv3x3_1x1: unknown precision %d", prec);
+  DVSG_REQUIRE(x && wt2 && bias2 && wt3 && bias3 && y, "dvsg_debug_conv3x3_1x1: NULL pointer");
+  DVSG_REQUIRE(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && res_stride >= 1,
+               "dvsg_debug_conv3x3_1x1: bad shape B=%d H=%d W=%d stride=%d res_stride=%d", B, H, W, stride, res_stride);
+  // as forward() fills it for block 1's units
+  ConvFused f;
+  f.pieces = prec == kF32S;
+  f.f16 = prec == kF16;
+  f.x3 = prec == kF32X;
+  f.x = static_cast<const float *>(x); f.wt2 = static_cast<const float *>(wt2); f.bias2 = bias2;
+  f.wt3 = static_cast<const float *>(wt3); f.bias3 = bias3;
+  f.res = static_cast<const float *>(res); f.y = static_cast<float *>(y);
+  f.B = B; f.H = H; f.W = W; f.Cin = Cin; f.Cout = Cout;
+  f.Ho = (H - 1) / stride + 1; f.Wo = (W - 1) / stride + 1;
+  f.stride = stride;
+  f.res_H = (f.Ho - 1) * res_stride + 1; f.res_W = (f.Wo - 1) * res_stride + 1; f.res_stride = res_stride;
+  if (sc_x) {
+    f.res = nullptr;
+    f.sc_x = static_cast<const float *>(sc_x); f.sc_wt = static_cast<const float *>(sc_wt); f.sc_bias = sc_bias;
+    f.sc_cin = sc_cin;
+  }
+  return launch_conv3x3_1x1(f, as_stream(stream));
+}
+
+int dvsg_debug_last_conv_kernel(int *fields, int n) {
+  DVSG_REQUIRE(fields && n >= kConvKernelFields, "dvsg_debug_last_conv_kernel: need room for %d fields", kConvKernelFields);
+  std::copy(g_last_conv_kernel, g_last_conv_kernel + kConvKernelFields, fields);
+  return DVSG_OK;
+}
+
 int dvsg_debug_last_conv_config(int *fields, int n) {
   DVSG_REQUIRE(fields && n >= kConvConfigFields, "dvsg_debug_last_conv_config: need room for %d fields", kConvConfigFields);
   std::copy(g_last_conv_config, g_last_conv_config + kConvConfigFields, fields);

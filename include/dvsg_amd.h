@@ -460,8 +460,24 @@ int dvsg_debug_set_option(const char *name, int value);
  * synchronisation.  fields (n >= 13): T (0: float32 tensors, 1: float16), BN (tile width 64 / 128), WM, WN (wave layout), KS
  * (1 / 3), RELU, RES (0 none, 1 full-size, 2 subsampled), MODE (0 plain, 1 split-K, 2 stream-K), SPLIT (f32s pieces / float16
  * hi-lo rows), X3 (f32x3), ksplit (slices per tile), streamk_tail (tiles shared as stream-K units), mt_fast (tile order).
- * T = -1: that call ran no conv_gemm_kernel (the float16 mode's 256 x 128 geometry), or none was made. */
+ * T = -1: that call ran no conv_gemm_kernel (dvsg_debug_last_conv_kernel then names the kernel that ran), or none was made. */
 int dvsg_debug_last_conv_config(int *fields, int n);
+/* Which conv kernel the last dvsg_conv_gemm_* / fused call (or conv launch of a network call) ran, recorded on the host when
+ * it was launched; no synchronisation.  fields (n >= 6): family (0 conv_gemm_kernel, 1 conv_wide16_kernel, 2
+ * conv_wide16a_kernel, 3 conv_wide16h_kernel, 4 conv3x3_1x1_kernel, 5 conv3x3_1x1_x3_kernel, 6 conv3x3_1x1_f16_kernel, 7
+ * conv3x3_1x1_f16h_kernel; -1 none), then the family's template arguments in declaration order padded with -1 to four
+ * fields (family 0: all -1, see dvsg_debug_last_conv_config), then for families 1-3 where the weight stages came from (0 the
+ * [rows][K] layout, 1 the packed copy), else -1. */
+int dvsg_debug_last_conv_kernel(int *fields, int n);
+/* Block 1's fused conv2 + conv3 (dvsg_conv3x3_1x1_f32) in any precision, as the network runs it.  prec: 0 float32 (weights
+ * [rows][K]), 1 float16 (x, res, sc_x, y float16; weights the stacked [rows/64][128][K] hi / lo rows of dvsg_conv_gemm_f16s),
+ * 2 f32s (x, res, sc_x, y in pieces; weights [rows][K/32][32 hi | 32 lo]), 3 f32x3 (float32 tensors; weights
+ * dvsg_pack_weights_f32x3).  With sc_x non-NULL the residual is the 1x1 shortcut conv sc_x [B,Ho,Wo,sc_cin] x sc_wt
+ * [Cout][sc_cin] + sc_bias, computed in the kernel, and res is ignored.  The option "fused_hreuse" selects the float16
+ * kernel as in the network. */
+int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float *bias2, const void *wt3, const float *bias3,
+                           const void *res, const void *sc_x, const void *sc_wt, const float *sc_bias, int sc_cin, void *y,
+                           int B, int H, int W, int Cin, int Cout, int stride, int res_stride, void *stream);
 /* The A/B form of dvsg_locnet_calibrate_f16 (tools/f16_ef_sweep.py): re-rounds the plain float16 weight copies and leaves
  * the pair policy to "f16_pair_mask".  mode 0: round to nearest (what dvsg_locnet_create makes); 1: error feedback with
  * mu = 1 (measured: useless -- channel means are far from uniform); 2: calibrated channel means. */
