@@ -82,6 +82,7 @@ SIGNATURES = {
     "dvsg_debug_set_option": [ctypes.c_char_p, _i],
     "dvsg_debug_last_conv_config": [ctypes.POINTER(_i), _i],
     "dvsg_debug_last_conv_kernel": [ctypes.POINTER(_i), _i],
+    "dvsg_debug_last_root_kernel": [ctypes.POINTER(_i), _i],
     "dvsg_debug_conv3x3_1x1": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dvsg_debug_calibrate_f16_weights": [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp],
     "dvsg_locnet_calibrate_f16": [_vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp],

@@ -152,6 +152,24 @@ constexpr int kConv1LdH = 168;
 // p1 = bf16(w), p2 = bf16(w - p1), p3 = bf16(w - p1 - p2); rows zero-padded from 80 to 88.
 constexpr int kConv1X3Ld = 88;
 constexpr int kConv1X3StageElems = 3 * 64 * kConv1X3Ld;   // 16 896 bfloat16 per half kernel row
+// diagnostic record of the root and the head of the last network call (dvsg_debug_last_root_kernel): conv1 family (0
+// conv1_kernel, 1 conv1_f16_kernel, 2 conv1_f16_pair_kernel, 3 conv1_f16_march_kernel, 4 conv1_split_kernel, 5
+// conv1_x3_kernel), its template arguments NW, TO (0 float, 1 _Float16), SRC (-1 where the family has none), the marching
+// kernel's bands and quads_per_band (else -1), the max pool kernel (0 maxpool_kernel<float>, 1 maxpool_kernel<_Float16>, 2
+// maxpool_h8_kernel, 3 maxpool_p_kernel), the average pool kernel (0 avgpool_partial_kernel<float>, 1 <_Float16>, 2
+// avgpool_partial_p_kernel) and the number of dense batch chunks.  Reset to -1 by forward(), written where launch_conv1,
+// launch_maxpool, launch_avgpool_partial and forward() issue the launches.  Host-only
+constexpr int kRootKernelFields = 9;
+enum RootKernelField { kRootConv1 = 0, kRootNW, kRootTO, kRootSRC, kRootBands, kRootQuads, kRootMaxpool, kRootAvgpool,
+                       kRootDenseChunks };
+extern int g_last_root_kernel[kRootKernelFields];
+inline void reset_root_kernel() {
+  for (int i = 0; i < kRootKernelFields; ++i) g_last_root_kernel[i] = -1;
+}
+inline void record_conv1_kernel(int family, int nw, int to, int src, int bands = -1, int quads = -1) {
+  const int rec[6] = {family, nw, to, src, bands, quads};
+  for (int i = 0; i < 6; ++i) g_last_root_kernel[i] = rec[i];
+}
 enum Conv1SrcKind { kSrcWindow = 0, kSrcRingF32 = 1, kSrcRingU8 = 2 };
 struct Conv1Src {
   const void *base;   // window tensor, or frame pool

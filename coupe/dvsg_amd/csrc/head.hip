@@ -182,6 +182,7 @@ int launch_f32_to_p(const float *x, void *y, size_t n, hipStream_t s) {
 int launch_avgpool_partial(int prec, const void *x, float *part, int B, int HW, int C, hipStream_t s) {
   ProfScope prof(kClsHead, s, 0.0, (double)elem_size(prec) * B * HW * C);
   const dim3 grid(ceil_div(C, 256), B, kPoolSplits);
+  g_last_root_kernel[kRootAvgpool] = prec == kF32S ? 2 : (prec == kF16 ? 1 : 0);
   if (prec == kF32S) {
     hipLaunchKernelGGL(avgpool_partial_p_kernel, grid, dim3(256), 0, s, x, part, B, HW, C);
     return check_launch("avgpool_partial_p_kernel");

@@ -511,6 +511,7 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
   // split-K tickets of every conv launch of this pass (each launch owns its own segment)
   DVSG_RUN(launch_zero_tickets(ws.splitk_counters, (size_t)kMaxConvLaunches * kSplitKMaxTiles, s));
   int launch_idx = 0;
+  reset_root_kernel();
   // root: conv1 (+ fused scale_RGB; f32 multiply, output in `prec`) -> bufA, max pool -> bufB
   {
   MarkerRange mr("dvsg/conv1");
@@ -620,6 +621,7 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
     act_dims[0] = 1; act_dims[1] = 1; act_dims[2] = 2048;
     return DVSG_OK;
   }
+  g_last_root_kernel[kRootDenseChunks] = (B + 15) / 16;
   for (int b0 = 0; b0 < B; b0 += 16) {
     const int bc = std::min(16, B - b0);
     float *pa = ws.dpart0, *pb = ws.dpart1;
@@ -1050,6 +1052,12 @@ int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float
 int dvsg_debug_last_conv_kernel(int *fields, int n) {
   DVSG_REQUIRE(fields && n >= kConvKernelFields, "dvsg_debug_last_conv_kernel: need room for %d fields", kConvKernelFields);
   std::copy(g_last_conv_kernel, g_last_conv_kernel + kConvKernelFields, fields);
+  return DVSG_OK;
+}
+
+int dvsg_debug_last_root_kernel(int *fields, int n) {
+  DVSG_REQUIRE(fields && n >= kRootKernelFields, "dvsg_debug_last_root_kernel: need room for %d fields", kRootKernelFields);
+  std::copy(g_last_root_kernel, g_last_root_kernel + kRootKernelFields, fields);
   return DVSG_OK;
 }
 

@@ -469,6 +469,15 @@ int dvsg_debug_last_conv_config(int *fields, int n);
  * fields (family 0: all -1, see dvsg_debug_last_conv_config), then for families 1-3 where the weight stages came from (0 the
  * [rows][K] layout, 1 the packed copy), else -1. */
 int dvsg_debug_last_conv_kernel(int *fields, int n);
+/* Which root and head kernels the last network call (dvsg_locnet_forward_*, dvsg_stabilize_*, their ring / masked / tap
+ * forms) ran, recorded on the host when they were launched; no synchronisation.  fields (n >= 9): conv1 family (0 conv1_kernel,
+ * 1 conv1_f16_kernel, 2 conv1_f16_pair_kernel, 3 conv1_f16_march_kernel, 4 conv1_split_kernel, 5 conv1_x3_kernel), its template
+ * arguments NW, TO (0 float, 1 _Float16) and SRC (2 x source kind + rows on the 16-byte grid + 8 x masked), -1 where the family
+ * has none; the marching kernel's bands and quads_per_band (else -1); the max pool kernel (0 maxpool_kernel<float>, 1
+ * maxpool_kernel<_Float16>, 2 maxpool_h8_kernel, 3 maxpool_p_kernel); the average pool kernel (0 avgpool_partial_kernel<float>,
+ * 1 avgpool_partial_kernel<_Float16>, 2 avgpool_partial_p_kernel); the number of dense batch chunks of <= 16 samples.  A
+ * field is -1 when the call stopped (parity tap) before that launch, or none was made. */
+int dvsg_debug_last_root_kernel(int *fields, int n);
 /* Block 1's fused conv2 + conv3 (dvsg_conv3x3_1x1_f32) in any precision, as the network runs it.  prec: 0 float32 (weights
  * [rows][K]), 1 float16 (x, res, sc_x, y float16; weights the stacked [rows/64][128][K] hi / lo rows of dvsg_conv_gemm_f16s),
  * 2 f32s (x, res, sc_x, y in pieces; weights [rows][K/32][32 hi | 32 lo]), 3 f32x3 (float32 tensors; weights
