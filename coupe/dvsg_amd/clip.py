@@ -382,3 +382,105 @@ def stabilize_clip_teacher_forced(model, unstable, stable, batch=16, skip_length
     if res is not None and host:
         res = res.cpu().numpy()
     return res
+
+
+def score_clip_teacher_forced(model, unstable, stable, flows, surfs=None, surfs_dim=None, batch=16, mask_H="random",
+                              precision=None, loss_applied=None, coefs=None, group=None, skip_length=SKIP_LENGTH,
+                              channel_order="rgb"):
+    """The checkpoint score of main.py:198-221 on one pair of clips: `trainer.build_loss_train` on the two-frame graph of
+    model.py:59-96, averaged over the steps of the clip.  The windows are those of `teacher_forced_index_table` (n = N - 32 of
+    them); step k = 1 .. n-1 takes window k-1 as frame t-1 and window k as frame t, the stable clip's frames k+31 and k+32
+    as s_t_1_gt / s_t_gt, and
+      flows[k]     [h,w,2] float32 in pixels (data_loader.py:239), `flows` being [n,h,w,2] (entry 0 is not read);
+      surfs[k-1], surfs[k]          int32 [2,Ns,2] matched points of the two frames, `surfs` being [n,2,Ns,2], and
+      surfs_dim[k-1], surfs_dim[k]  their counts [n] -- without `surfs` the `surf` term is not applied.
+    mask_H: the two `random_mask` draws of each step (model.py:71-72): "random", a torch.Generator, or an array [n-1,2,8]
+    (t-1 first) after the scale / offset of :162-163.  precision: `model.precision` unless given.  loss_applied / coefs as in
+    `build_loss_train` (default: every term the data allows, `cor` never).
+
+    A step's value is the loss of that step alone (batch 1 of the reference's loop); `batch` steps run through the kernels
+    together and their per-sample values are taken, so the score does not depend on `batch` beyond the network's own
+    batching.  With torch.distributed initialised the steps shard over the ranks of `group` like the windows of
+    `stabilize_clip_teacher_forced`; each rank adds its steps up in float64, in step order, and ONE all-reduce of those
+    sums follows.  Returns an OrderedDict of Python floats on every rank: the per-term means over the steps, and `total`
+    (errs_total_test of main.py:198-215)."""
+    import collections
+    import torch.distributed as dist
+    from . import _lib, trainer
+    from ._tensor import device
+    from .model import V_SRC
+    from .networks import random_mask_plane
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError("channel_order must be 'rgb' or 'bgr'")
+    if model.locnet is None:
+        raise _lib.DvsgError("StabNet has no weights: call load_weights()/load_ckpt() first")
+    if loss_applied is None:
+        loss_applied = [k for k in ('image', 'identity', 'temporal', 'surf', 'distortion') if k != 'surf' or surfs is not None]
+    applied = trainer.applied_keys(loss_applied)
+    if 'surf' in applied and (surfs is None or surfs_dim is None):
+        raise ValueError("the surf term needs surfs [n,2,Ns,2] and surfs_dim [n]")
+    flip = 1 if channel_order == "bgr" else 0
+    dev = device()
+    to_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))).to(dev).contiguous()
+    un, st = to_dev(unstable), to_dev(stable)
+    if un.dim() != 4 or un.shape[3] != 3 or st.shape != un.shape:
+        raise ValueError("unstable and stable clips must both be [N,h,w,3]")
+    N, h, w, S = int(un.shape[0]), model.h, model.w, len(skip_length)
+    _check_window(model, S)
+    span = int(skip_length[-1])
+    table = torch.from_numpy(teacher_forced_index_table(N, skip_length)).to(dev)
+    n = N - span
+    steps = n - 1
+    if steps < 1:
+        raise ValueError("a score needs two windows: more than %d frames, got %d" % (span + 1, N))
+    fl = to_dev(flows).to(torch.float32)
+    if tuple(fl.shape) != (n, h, w, 2):
+        raise ValueError("flows must be [%d,%d,%d,2] (one per window, entry 0 unused), got %s" % (n, h, w, tuple(fl.shape)))
+    if 'surf' in applied:
+        sf, sd = to_dev(surfs).to(torch.float32), to_dev(surfs_dim).to(torch.float32).reshape(-1)
+        if sf.dim() != 4 or sf.shape[0] != n or sf.shape[1] != 2 or sf.shape[3] != 2 or sd.numel() != n:
+            raise ValueError("surfs must be [%d,2,Ns,2] and surfs_dim [%d]" % (n, n))
+    if mask_H is None:
+        Ht = None
+    elif isinstance(mask_H, (str, torch.Generator)):
+        Ht = _mask_homographies(mask_H, 2 * steps, dev).reshape(steps, 2, 8)
+    else:
+        Ht = torch.as_tensor(np.asarray(mask_H, dtype=np.float32) if not isinstance(mask_H, torch.Tensor) else mask_H)
+        if tuple(Ht.shape) != (steps, 2, 8):
+            raise ValueError("mask_H must be [%d,2,8] (the t-1 and the t draw of each step), got %s" % (steps, tuple(Ht.shape)))
+        Ht = Ht.to(dev, torch.float32).contiguous()
+    pool = torch.empty((2 * N, h, w, 3), dtype=torch.float32, device=dev)
+    _frames_to_pool(un, pool[:N], h, w, flip, "unstable")
+    _frames_to_pool(st, pool[N:], h, w, flip, "stable")
+    V = torch.from_numpy(V_SRC).to(dev).unsqueeze(0)
+    prec = model.precision if precision is None else precision
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    lo, hi = shard_range(steps, world, rank)
+    keys = applied + ['total']
+    sums = torch.zeros(len(keys), dtype=torch.float64)
+    for b0 in range(lo, hi, batch):             # steps b0 .. b1-1, i.e. k = b0+1 .. b1: window k-1 = row b0 .. of the table
+        b1 = min(hi, b0 + batch)
+        b = b1 - b0
+        if Ht is None:
+            plane = torch.ones((2 * b, h, w), dtype=torch.float32, device=dev)
+        else:
+            plane = random_mask_plane(torch.cat([Ht[b0:b1, 0], Ht[b0:b1, 1]], 0).contiguous(), h, w)
+        table2 = torch.cat([table[b0:b1], table[b0 + 1:b1 + 1]], 0).contiguous()      # ONE batch of 2 b: t-1 first
+        F2 = model.locnet.forward_masked(pool, plane, table=table2, precision=prec).reshape(2 * b, model.param_dim, 2)
+        values = dict(u_t_1=pool[span + b0:span + b1], u_t=pool[span + b0 + 1:span + b1 + 1],
+                      s_t_1_gt=pool[N + span + b0:N + span + b1], s_t_gt=pool[N + span + b0 + 1:N + span + b1 + 1],
+                      of_t=fl[b0 + 1:b1 + 1])
+        if 'surf' in applied:
+            values.update(surfs_t_1=sf[b0:b1], surfs_t=sf[b0 + 1:b1 + 1], surfs_dim_t_1=sd[b0:b1], surfs_dim_t=sd[b0 + 1:b1 + 1])
+        loss = trainer.loss_terms(values, dict(F_t_1=F2[:b].contiguous(), F_t=F2[b:].contiguous(), V_src=V,
+                                               num_control_points=model.num_control_points), applied, per_sample=True)
+        trainer.add_total(loss, coefs)
+        rows = torch.stack([loss[k].reshape(b) for k in keys], 1).to(torch.float64).cpu()   # [b, K+1], float32 values
+        for r in range(b):                      # fixed order: step by step, as main.py:210 accumulates
+            sums += rows[r]
+    if world > 1:
+        red = sums.to(dev) if dist.get_backend(group) == "nccl" else sums
+        dist.all_reduce(red, op=dist.ReduceOp.SUM, group=group)
+        sums = red.cpu()
+    return collections.OrderedDict((k, float(sums[i]) / steps) for i, k in enumerate(keys))     # main.py:215

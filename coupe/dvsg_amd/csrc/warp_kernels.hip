@@ -19,12 +19,10 @@
 
 #include "common.h"
 #include "cnn_device.h"
+#include "warp_device.h"
 
 namespace dvsg {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxPts = 61;  // P + 3 <= 64
 
 // ----------------------------------------------------------------------------------------
 // TPS system solve: ThinPlateSpline.py:143-166.  One wave per batch sample, thread = row of
@@ -175,215 +173,12 @@ __global__ __launch_bounds__(64) void tps_apply_kernel(const double *__restrict_
   }
 }
 
-// ----------------------------------------------------------------------------------------
-// Samplers.
-// ----------------------------------------------------------------------------------------
-template <int C>
-struct Pix {
-  float v[C];
-};
-
-template <int C>
-__device__ __forceinline__ Pix<C> load_pix(const float *__restrict__ p) {
-  Pix<C> r;
-#pragma unroll
-  for (int c = 0; c < C; ++c) r.v[c] = p[c];
-  return r;
-}
-// a uint8 frame: the pixel as eval.py:80 hands it to the graph, float32(v / 255.) -- the float64 quotient rounded
-// once.  A correctly rounded float32 division gives the same value for all 256 bytes (exhaustive:
-// tests/test_frames_cpu.py); hipcc's `/` is correctly rounded (no -ffast-math in this build).
-template <int C>
-__device__ __forceinline__ Pix<C> load_pix(const uint8_t *__restrict__ p) {
-  Pix<C> r;
-#pragma unroll
-  for (int c = 0; c < C; ++c) r.v[c] = (float)p[c] / 255.0f;
-  return r;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// Guarded float -> int conversion (floor already applied): out-of-range source coordinates
-// are garbage in the reference too (tf.cast saturates to INT_MIN on x86); keep it defined.
-__device__ __forceinline__ int f2i(float f) {
-  f = f < -1073741824.f ? -1073741824.f : (f > 1073741824.f ? 1073741824.f : f);
-  return (int)f;
-}
-
-// Sampler A (ThinPlateSpline.py:30-90): normalised (xs, ys) -> (x+1)*W/2, indices clipped to
-// the image BEFORE the weights are formed, so out-of-range taps coincide and cancel.
-template <int C>
-struct TapsA {  // loaded taps (x0,y0) (x0,y1) (x1,y0) (x1,y1) and their weights
-  Pix<C> a, b, c, d;
-  float wa, wb, wc, wd;
-};
-template <>
-struct TapsA<0> {  // generic channel count: the blend reads through the tap pointers
-  const float *pa, *pb, *pc, *pd;
-  float wa, wb, wc, wd;
-};
-
-// Address + weight computation and the four tap loads; the loads are only ISSUED here, so the
-// caller can do other work before sample_a_blend() needs them.
-template <int C, typename TU = float>
-__device__ __forceinline__ void sample_a_load(const TU *__restrict__ img /* [H,W,C] of this sample */,
-                                              int H, int W, int Cn, float xs, float ys, TapsA<C> &t) {
-  const float x = ((xs + 1.0f) * (float)W) / 2.0f;  // :48
-  const float y = ((ys + 1.0f) * (float)H) / 2.0f;  // :49
-  int x0 = f2i(floorf(x));
-  int y0 = f2i(floorf(y));
-  int x1 = x0 + 1;
-  int y1 = y0 + 1;
-  x0 = clampi(x0, 0, W - 1);  // :57-60
-  x1 = clampi(x1, 0, W - 1);
-  y0 = clampi(y0, 0, H - 1);
-  y1 = clampi(y1, 0, H - 1);
-  const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-  t.wa = (x1f - x) * (y1f - y);  // :85-88
-  t.wb = (x1f - x) * (y - y0f);
-  t.wc = (x - x0f) * (y1f - y);
-  t.wd = (x - x0f) * (y - y0f);
-  const TU *pa = img + ((size_t)y0 * W + x0) * Cn;  // (x0,y0)
-  const TU *pb = img + ((size_t)y1 * W + x0) * Cn;  // (x0,y1)
-  const TU *pc = img + ((size_t)y0 * W + x1) * Cn;  // (x1,y0)
-  const TU *pd = img + ((size_t)y1 * W + x1) * Cn;  // (x1,y1)
-  if constexpr (C > 0) {
-    t.a = load_pix<C>(pa);
-    t.b = load_pix<C>(pb);
-    t.c = load_pix<C>(pc);
-    t.d = load_pix<C>(pd);
-  } else {
-    t.pa = pa; t.pb = pb; t.pc = pc; t.pd = pd;
-  }
-}
-
-template <int C>
-__device__ __forceinline__ void sample_a_blend(const TapsA<C> &t, int Cn, float *__restrict__ dst) {
-  if constexpr (C > 0) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) dst[c] = ((t.wa * t.a.v[c] + t.wb * t.b.v[c]) + t.wc * t.c.v[c]) + t.wd * t.d.v[c];  // :89
-  } else {
-    for (int c = 0; c < Cn; ++c) dst[c] = ((t.wa * t.pa[c] + t.wb * t.pb[c]) + t.wc * t.pc[c]) + t.wd * t.pd[c];
-  }
-}
-
-// Samplers B and C share this tail (spatial_transformer.py:517-562,
-// warp_with_optical_flow.py:128-173): (x, y) in unpadded pixel units, clamped to [-1,W] /
-// [-1,H], +1 into the zero-ringed image, floor, upper index min()-ed, weights from the
-// UNclamped x0+1.  The ring is never materialised: a tap on it reads as 0.
-template <int C>
-struct TapsB {  // loaded taps (x0,y0) (x1,y0) (x0,y1) (x1,y1), weights, and which taps are on the ring
-  Pix<C> a, b, c, d;
-  float w00, w01, w10, w11;
-  bool v00, v01, v10, v11;
-};
-template <>
-struct TapsB<0> {  // generic channel count: the blend reads through the tap pointers
-  const float *p00, *p01, *p10, *p11;
-  float w00, w01, w10, w11;
-  bool v00, v01, v10, v11;
-};
-
-// Address / weight computation and the four tap loads (only ISSUED here, so a thread can put the taps
-// of several pixels in flight before it blends the first one).  A tap on the ring reads as 0: the
-// loads are unconditional, from indices clamped into the image, and the ring is applied in the blend
-// as a select -- a predicated load that feeds arithmetic makes the compiler wait for each load in turn.
-// weights, ring flags and the (clamped) tap coordinates of one sample; shared by the image samplers and the mask plane
-struct PadGeom {
-  float w00, w01, w10, w11;
-  bool v00, v01, v10, v11;
-  int xa, xb, ya, yb;   // tap coordinates clamped into the image (what an unconditional global load may touch)
-  int x0, y0;           // the lower tap in the zero-ringed image's coordinates (image pixel x0 - 1, y0 - 1), in [0, W + 1] / [0, H + 1]
-};
-__device__ __forceinline__ PadGeom padded_geom(int H, int W, float x, float y) {
-  PadGeom g;
-  const float wf = (float)W, hf = (float)H;
-  x = fminf(fmaxf(x, -1.0f), wf);  // (W-1)+1
-  y = fminf(fmaxf(y, -1.0f), hf);
-  x = x + 1.0f;
-  y = y + 1.0f;
-  const float x0f = floorf(x), y0f = floorf(y);
-  const float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
-  const int x0 = (int)x0f, y0 = (int)y0f;
-  const int x1 = (int)fminf(x1f, wf + 1.0f);
-  const int y1 = (int)fminf(y1f, hf + 1.0f);
-  g.w00 = (x1f - x) * (y1f - y);
-  g.w01 = (x - x0f) * (y1f - y);
-  g.w10 = (x1f - x) * (y - y0f);
-  g.w11 = (x - x0f) * (y - y0f);
-  const bool vx0 = x0 >= 1 && x0 <= W, vx1 = x1 >= 1 && x1 <= W;
-  const bool vy0 = y0 >= 1 && y0 <= H, vy1 = y1 >= 1 && y1 <= H;
-  g.v00 = vx0 && vy0; g.v01 = vx1 && vy0; g.v10 = vx0 && vy1; g.v11 = vx1 && vy1;
-  g.xa = clampi(x0 - 1, 0, W - 1); g.xb = clampi(x1 - 1, 0, W - 1);
-  g.ya = clampi(y0 - 1, 0, H - 1); g.yb = clampi(y1 - 1, 0, H - 1);
-  g.x0 = x0; g.y0 = y0;
-  return g;
-}
-
-template <int C>
-__device__ __forceinline__ void sample_padded_load(const float *__restrict__ img, int H, int W, int Cn, float x,
-                                                   float y, TapsB<C> &t) {
-  const PadGeom g = padded_geom(H, W, x, y);
-  t.w00 = g.w00; t.w01 = g.w01; t.w10 = g.w10; t.w11 = g.w11;
-  t.v00 = g.v00; t.v01 = g.v01; t.v10 = g.v10; t.v11 = g.v11;
-  const float *p00 = img + ((long)g.ya * W + g.xa) * Cn;
-  const float *p01 = img + ((long)g.ya * W + g.xb) * Cn;
-  const float *p10 = img + ((long)g.yb * W + g.xa) * Cn;
-  const float *p11 = img + ((long)g.yb * W + g.xb) * Cn;
-  if constexpr (C > 0) {
-    t.a = load_pix<C>(p00);
-    t.b = load_pix<C>(p01);
-    t.c = load_pix<C>(p10);
-    t.d = load_pix<C>(p11);
-  } else {
-    t.p00 = p00; t.p01 = p01; t.p10 = p10; t.p11 = p11;
-  }
-}
-
-template <int C>
-__device__ __forceinline__ void sample_padded_blend(const TapsB<C> &t, int Cn, float *__restrict__ dst) {
-  if constexpr (C > 0) {
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-      dst[c] = ((t.w00 * (t.v00 ? t.a.v[c] : 0.f) + t.w01 * (t.v01 ? t.b.v[c] : 0.f)) + t.w10 * (t.v10 ? t.c.v[c] : 0.f)) +
-               t.w11 * (t.v11 ? t.d.v[c] : 0.f);
-  } else {
-    for (int c = 0; c < Cn; ++c) {
-      const float a = t.v00 ? t.p00[c] : 0.f;
-      const float bq = t.v01 ? t.p01[c] : 0.f;
-      const float cq = t.v10 ? t.p10[c] : 0.f;
-      const float d = t.v11 ? t.p11[c] : 0.f;
-      dst[c] = ((t.w00 * a + t.w01 * bq) + t.w10 * cq) + t.w11 * d;
-    }
-  }
-}
-
-template <int C>
-__device__ __forceinline__ void store_pix(float *__restrict__ out, size_t pix, int Cn,
-                                          const float *__restrict__ v) {
-  if constexpr (C == 3) {
-    // one 12-byte store per lane (global_store_dwordx3 needs only 4-byte alignment): a wave writes
-    // 768 contiguous bytes with one instruction instead of three stride-12 dword stores
-    typedef float floatx3 __attribute__((ext_vector_type(3)));
-    typedef floatx3 floatx3_a4 __attribute__((aligned(4)));
-    *reinterpret_cast<floatx3_a4 *>(out + pix * 3) = floatx3{v[0], v[1], v[2]};
-  } else if constexpr (C > 0) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) out[pix * C + c] = v[c];
-  } else {
-    for (int c = 0; c < Cn; ++c) out[pix * Cn + c] = v[c];
-  }
-}
-
-constexpr int kMaxGenericC = 64;
 
 // ----------------------------------------------------------------------------------------
 // Fused TPS grid generation + sampler A (ThinPlateSpline.py:92-141).
 // Thread = one output column, PPT consecutive rows: (x_t - px)^2 is shared by the rows, and
 // each of the P control points costs one broadcast ds_read_b128 {px, py, T0, T1}.
 // ----------------------------------------------------------------------------------------
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-
 // The 25 basis terms per pixel make this kernel VALU-bound, so the inner loop is written for the
 // packed-float32 pipe -- one v_pk_* instruction per PAIR of rows -- and kept to 5 packed ops + 2
 // v_log_f32 per control point and pair:
@@ -400,8 +195,7 @@ typedef float floatx2 __attribute__((ext_vector_type(2)));
 // (3e-3 px against the oracle either way); tests/test_gpu_warps.py bounds grid and pixel error.
 // A thread owns one column and 4 rows (two pairs); a variant with 8 rows per thread that issued one
 // group's tap loads under the other group's basis loop was no faster, so the simple form stays.
-constexpr int kTpsRows = 4;
-constexpr float kLn2 = 0x1.62e43p-1f;
+// The basis term of one control point is tps_basis_point of warp_device.h, which the loss kernels' map evaluates too.
 
 // U is [B,H,W,C], or -- u_index given -- a pool of frames [n_pool,H,W,C] of which sample b reads frame
 // u_index[b * u_stride] (the frame ring of dvsg_stabilize_ring_*: u_t is the newest frame of the window; an index
@@ -474,23 +268,7 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     xs2[h] = floatx2{ax, ax} + sa[2] * yy;
     ys2[h] = floatx2{ay, ay} + sa[5] * yy;
   }
-  for (int k = 0; k < P; ++k) {
-    const float4 c = sp[k];
-    const float4 q = sdy[k];
-    const float dx = x_t - c.x;
-    const float dx2 = dx * dx;
-    const floatx2 dxx = {dx2, dx2};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const floatx2 dyy = h == 0 ? floatx2{q.x, q.y} : floatx2{q.z, q.w};
-      const floatx2 d2 = dxx + dyy;                        // :104
-      const floatx2 e = d2 + floatx2{1e-6f, 1e-6f};
-      const floatx2 l2 = {__builtin_amdgcn_logf(e.x), __builtin_amdgcn_logf(e.y)};
-      const floatx2 rk = d2 * l2;                          // :105 up to the factor ln 2 carried by c.z / c.w
-      xs2[h] = __builtin_elementwise_fma(floatx2{c.z, c.z}, rk, xs2[h]);
-      ys2[h] = __builtin_elementwise_fma(floatx2{c.w, c.w}, rk, ys2[h]);
-    }
-  }
+  for (int k = 0; k < P; ++k) tps_basis_point(sp[k], sdy[k], x_t, xs2, ys2);
   const float xs[4] = {xs2[0].x, xs2[0].y, xs2[1].x, xs2[1].y};
   const float ys[4] = {ys2[0].x, ys2[0].y, ys2[1].x, ys2[1].y};
   TapsA<C> taps[4];
@@ -911,8 +689,6 @@ __global__ __launch_bounds__(kThreads) void scale_rgb_kernel(const float *__rest
     out[e] = in[pix * C + src] * 255.0f - mean;
   }
 }
-
-inline float lin_step(int n) { return n > 1 ? (1.0f - (-1.0f)) / (float)(n - 1) : 0.0f; }
 
 int g_flow_tiled = 1;  // dvsg_debug_set_option("flow_tiled", v): 0 = stn_kernel<kFlow> (global gathers), 1 = column strips streamed
                        // through LDS, workgroups in XCD-aware order (default), 2 = the same in plain dispatch order

@@ -14,7 +14,9 @@ handles (Placeholder / Fetch) because nothing is computed until `run`.  As in TF
 the requested fetches need is executed: fetching `s_t_pred` alone never touches the
 `s_t_pred_mask` branch (model.py:121).  When `s_t_pred` (and optionally `F_t`,
 `x_offset_t`, `y_offset_t`) is requested the whole graph runs as ONE C-ABI call,
-`dvsg_stabilize_f32`.  Training graphs (`get_train_model`) are out of scope.  eval_train.py builds
+`dvsg_stabilize_f32`.  `init_train_inputs` / `get_train_model(False)` (model.py:36-96) build the two-frame graph on randomly
+masked windows that `trainer.build_loss_train` scores (forward only: `is_train=True` raises, the `CM_*` outputs of
+correlationNet are absent).  eval_train.py builds
 its OWN evaluation graph, whose CNN input is masked (eval_train.py:25-51): that one is
 `coupe.dvsg_amd.eval_train.get_evaluation_model`, a `StabNet` with `masked = True`.
 """
@@ -86,6 +88,7 @@ class StabNet:
         # eval_train.py's graph (eval_train.py:43-45): F_t = localizationNet(patches_t * random mask); False = model.py's
         self.masked = False
         self.mask_generator = None   # torch.Generator of the in-graph draw when inputs['random_H'] is not fed
+        self.train_graph = False     # get_train_model's two-frame graph (model.py:59-96) instead of an evaluation graph
         self.locnet = None
         self.inputs = None
         self.outputs = None
@@ -146,8 +149,121 @@ class StabNet:
             outputs[key] = Fetch(self, key)
         if not self.masked:
             outputs['num_control_points'] = self.num_control_points
+        self.train_graph = False
         self.inputs, self.outputs = inputs, outputs
         return inputs, outputs
+
+    # -- the test-time graph of the checkpoint score (model.py:36-96) -------------------------
+    TRAIN_KEYS = ('V_src', 'num_control_points', 'patches_masked_t_1', 'random_masks_t_1', 'patches_masked_t', 'random_masks_t',
+                  'F_t_1', 'F_t', 's_t_1_pred', 'x_offset_t_1', 'y_offset_t_1', 's_t_1_pred_mask', 's_t_pred', 'x_offset_t',
+                  'y_offset_t', 's_t_pred_mask', 's_t_1_gt_warp', 's_t_gt_warp')
+
+    def init_train_inputs(self, sample_num):
+        """model.py:36-57, plus the two graph draws of `random_mask` as OPTIONAL feeds (`random_H_t_1`, `random_H_t`: H [B,8]
+        after the scale / offset of :162-163, the `random_H` convention of eval_train.py's graph)."""
+        self.sample_num = sample_num
+        inputs = collections.OrderedDict()
+        for key, name, ch in (('patches_t_1', 'input_frames_t_1', 3 * sample_num), ('patches_t', 'input_frames_t', 3 * sample_num),
+                              ('s_t_1_gt', 'stable_frame_t_1_gt', 3), ('s_t_gt', 'stable_frame_t_gt', 3),
+                              ('u_t_1', 'unstable_frame_t_1', 3), ('u_t', 'unstable_frame_t', 3), ('of_t', 'optical_flow_t', 2),
+                              ('surfs_t_1', 'surfs_t_1', 2), ('surfs_t', 'surfs_t', 2), ('surfs_dim_t_1', 'surfs_dim_t_1', 1),
+                              ('surfs_dim_t', 'surfs_dim_t', 1), ('random_H_t_1', 'random_H_t_1', 8), ('random_H_t', 'random_H_t', 8)):
+            inputs[key] = Placeholder(name, ch)
+        self.inputs = inputs
+        return inputs
+
+    def get_train_model(self, is_train):
+        """model.py:59-96 with is_train = False: both frames' windows go through the masked localisation net as ONE batch
+        of 2 B (t-1 first).  Fetch the entries of `trainer.build_loss_train(inputs, outputs)` for the score."""
+        if is_train:
+            raise NotImplementedError("get_train_model(is_train=True): the training path (batch-norm updates, gradients) is "
+                                      "not built; only the test-time graph is")
+        if self.inputs is None or 'patches_t_1' not in self.inputs:
+            raise _lib.DvsgError("get_train_model: call init_train_inputs(sample_num) first (model.py:36)")
+        outputs = collections.OrderedDict((key, Fetch(self, key)) for key in self.TRAIN_KEYS)
+        outputs['num_control_points'] = self.num_control_points
+        self.train_graph = True
+        self.outputs = outputs
+        return outputs
+
+    def _execute_train(self, keys, feed):
+        from . import trainer
+        from .warp_with_optical_flow import tf_warp
+        inp = self.inputs
+
+        def fed(key, need=True):
+            if inp[key] not in feed:
+                if need:
+                    raise KeyError("feed_dict lacks inputs[%r]" % key)
+                return None
+            return as_dev(feed[inp[key]])
+        vals = {}
+        loss_keys = [k[5:] for k in keys if k.startswith('loss/')]
+        frames = ('s_t_1_pred', 'x_offset_t_1', 'y_offset_t_1', 's_t_pred', 'x_offset_t', 'y_offset_t')
+        masks3 = ('s_t_1_pred_mask', 's_t_pred_mask')
+        debug = ('patches_masked_t_1', 'random_masks_t_1', 'patches_masked_t', 'random_masks_t')
+        need_frames = any(k in keys for k in frames)
+        need_cnn = need_frames or loss_keys or any(k in keys for k in ('F_t', 'F_t_1') + masks3 + debug)
+        if 'V_src' in keys:
+            B = int(fed('u_t_1').shape[0])                                                              # :68
+            vals['V_src'] = torch.from_numpy(V_SRC).to(fed('u_t_1').device).unsqueeze(0).repeat(B, 1, 1)
+        if need_cnn:
+            p1, p0 = fed('patches_t_1'), fed('patches_t')
+            if p1.dim() != 4 or p1.shape != p0.shape or p1.shape[3] != 3 * self.sample_num:
+                raise ValueError("patches_t_1 and patches_t must both be [B,H,W,%d]" % (3 * self.sample_num))
+            B, H, W = int(p1.shape[0]), int(p1.shape[1]), int(p1.shape[2])
+            if (H, W) != (self.h, self.w):
+                raise ValueError("fed frames must be [B,%d,%d,*] (random_mask's out_size)" % (self.h, self.w))
+            Hs = []
+            for key in ('random_H_t_1', 'random_H_t'):                                                  # :71-72, one draw each
+                h8 = fed(key, need=False)
+                Hs.append(draw_random_H(B, p1.device, self.mask_generator) if h8 is None else h8.reshape(B, 8))
+            plane = random_mask_plane(torch.cat(Hs, 0), H, W)                                           # [2B,H,W]
+            p2 = torch.cat([p1, p0], 0)
+            if any(k in keys for k in debug):
+                m21 = torch.cat([plane.unsqueeze(3).expand(-1, -1, -1, 3 * (self.sample_num - 1)),
+                                 torch.ones_like(p2[..., :3])], dim=3)
+                pm = p2 * m21
+                vals.update(random_masks_t_1=m21[:B], random_masks_t=m21[B:], patches_masked_t_1=pm[:B], patches_masked_t=pm[B:])
+            if need_frames:                                                                             # :77-84 as one call
+                u2 = torch.cat([fed('u_t_1'), fed('u_t')], 0)
+                if tuple(u2.shape) != (2 * B, H, W, 3):
+                    raise ValueError("u_t_1 and u_t must be [B,%d,%d,3] like the windows" % (H, W))
+                out, F2 = empty((2 * B, H, W, 3), u2), empty((2 * B, self.param_dim, 2), u2)
+                xs, ys = empty((2 * B * H * W,), u2), empty((2 * B * H * W,), u2)
+                self.locnet.stabilize(p2, u2, out, F2, xs, ys, n_streams=self.n_streams, precision=self.precision, mask=plane)
+                n = B * H * W
+                vals.update(s_t_1_pred=out[:B], s_t_pred=out[B:], x_offset_t_1=xs[:n], x_offset_t=xs[n:],
+                            y_offset_t_1=ys[:n], y_offset_t=ys[n:])
+            else:
+                F2 = self.locnet.forward_masked(p2, plane, precision=self.precision)
+            F2 = F2.reshape(2 * B, self.param_dim, 2)
+            vals.update(F_t_1=F2[:B].contiguous(), F_t=F2[B:].contiguous())
+            V = torch.from_numpy(V_SRC).to(p1.device).unsqueeze(0)
+            for key, u_key, F in (('s_t_1_pred_mask', 'u_t_1', vals['F_t_1']), ('s_t_pred_mask', 'u_t', vals['F_t'])):
+                if key in keys:                                     # :82 / :85 -- three channels only when fetched by name
+                    trainer.stats['mask3'] += 1
+                    vals[key], _, _ = stn(torch.ones_like(fed(u_key)), V.repeat(B, 1, 1), F, [self.h, self.w])
+            if loss_keys:
+                applied = getattr(self, 'loss_applied', None)
+                if applied is None:
+                    raise _lib.DvsgError("loss fetches need trainer.build_loss_train(inputs, outputs) on this graph first")
+                values = {k: fed(k) for k in ('u_t', 'u_t_1', 's_t_gt', 's_t_1_gt')}
+                if 'temporal' in applied:
+                    values['of_t'] = fed('of_t')
+                if 'surf' in applied:
+                    values.update({k: fed(k) for k in ('surfs_t', 'surfs_t_1', 'surfs_dim_t', 'surfs_dim_t_1')})
+                loss = trainer.loss_terms(values, dict(F_t=vals['F_t'], F_t_1=vals['F_t_1'], V_src=V,
+                                                       num_control_points=self.num_control_points), applied)
+                for k in loss:
+                    loss[k] = loss[k].reshape(())
+                trainer.add_total(loss, self.loss_coefs)
+                for k in loss_keys:
+                    vals['loss/' + k] = loss[k]
+        for key, src in (('s_t_1_gt_warp', 's_t_1_gt'), ('s_t_gt_warp', 's_t_gt')):                     # :87-88
+            if key in keys:
+                vals[key] = tf_warp(fed(src), fed('of_t'), self.h, self.w)
+        return vals
 
     # -- eval_train.py's occlusion mask (model.py:156-167) ----------------------------------
     def random_mask(self, patches, out_size, sample_num, H=None, generator=None):
@@ -177,6 +293,8 @@ class StabNet:
         if self.locnet is None:
             raise _lib.DvsgError("StabNet has no weights: call load_weights()/load_ckpt() first (the "
                                  "reference would silently evaluate random weights, ckpt_manager.py:21-22)")
+        if self.train_graph:
+            return self._execute_train(keys, feed)
         vals = {}
         need_cnn = any(k in keys for k in ('F_t', 's_t_pred', 'x_offset_t', 'y_offset_t', 's_t_pred_mask',
                                            'patches_masked_t', 'random_masks_t'))
@@ -242,6 +360,8 @@ class Session(object):
 
     def run(self, fetches, feed_dict=None):
         feed = feed_dict or {}
+        if isinstance(fetches, dict):   # sess.run(trainer.loss_test, feed_dict) of main.py:208: a dict of the same keys
+            return type(fetches)(zip(fetches.keys(), self.run(list(fetches.values()), feed)))
         single = not isinstance(fetches, (list, tuple))
         flist = [fetches] if single else list(fetches)
         models = {f.model for f in flist if isinstance(f, Fetch)}

@@ -140,3 +140,33 @@ def load_ckpt_dir(ckpt_dir, by_score=True):
         raise ValueError("checkpoint index is empty: %s" % index)
     name = (lines[0] if by_score else lines[-1]).split(" ")[0]
     return load_npz(os.path.join(ckpt_dir, name))
+
+
+def record_score(ckpt_dir, file_name, score):
+    """Enter `file_name` with `score` into the `checkpoints` index of `ckpt_dir`, in the format `load_ckpt_dir` reads and
+    ckpt_manager.py:58-62, 66-93 writes: one `"<file> <score>"` line per checkpoint sorted by ascending score (a loss: the
+    best first), and the most recently recorded file repeated on the last line.  A file recorded before gets its new score.
+    Unlike the reference's `save_ckpt` (ckpt_manager.py:44-50, 77-81) this deletes no checkpoint files.  One difference in
+    reading an existing index: the reference always drops its last line (ckpt_manager.py:44-51); this drops it only when it
+    repeats an earlier line, so a last line naming a file the reference pruned from its top 10 stays in as a scored entry
+    (its file may still exist).  Returns the lines."""
+    score = float(score)
+    if score != score:
+        raise ValueError("record_score: the score of %s is NaN" % file_name)
+    if not file_name or " " in file_name or os.sep in file_name:
+        raise ValueError("record_score: %r is not a plain file name without blanks" % (file_name,))
+    index = os.path.join(ckpt_dir, "checkpoints")
+    lines = []
+    if os.path.isfile(index):
+        with open(index) as f:
+            lines = [ln for ln in f.read().splitlines() if ln.strip()]
+        if lines and lines[-1] in lines[:-1]:
+            lines = lines[:-1]   # the copy of the most recent one (ckpt_manager.py:46-51)
+    lines = [ln for ln in lines if ln.split(" ")[0] != file_name]
+    recent = "%s %s" % (file_name, str(score))   # ckpt_manager.py:59
+    lines.append(recent)
+    lines.sort(key=lambda ln: float(ln.split(" ")[1]))   # ckpt_manager.py:90-94 (stable: ties keep their order)
+    with open(index, "w") as f:
+        for ln in lines + [recent]:
+            f.write(ln + os.linesep)
+    return lines + [recent]

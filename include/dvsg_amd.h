@@ -494,6 +494,56 @@ int dvsg_debug_calibrate_f16_weights(dvsg_locnet_t *net, const float *patches, i
                                      size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Test-time losses: trainer.py:95-123 `build_loss_train` on get_train_model(is_train = False), the score
+ * errs_total_test['total'] that ranks checkpoints (main.py:198-221).  Forward only; the `cor` term (correlationNet) is not
+ * built.  Every per-pixel term is the TF graph's chain of separately rounded float32 ops on the bits dvsg_tps_warp_f32 /
+ * dvsg_flow_warp_f32 give for that pixel; every sum is a float64 sum of those float32 terms in a fixed order (per thread,
+ * wave shuffles, LDS across waves, one partial per workgroup in `workspace`, a second launch over the partials): no atomics,
+ * bitwise reproducible.  Each entry writes the per-sample values per_sample [B] (tf.div_no_nan of the two sums rounded to
+ * float32, trainer.py:242) and their batch mean mean [1] (trainer.py:243).  sums (optional) receives the float64 sums
+ * themselves.  workspace: 8-byte aligned, dvsg_loss_workspace_bytes(B, H, W) bytes, private to the call until it has run.
+ * ------------------------------------------------------------------------------------- */
+int dvsg_loss_workspace_bytes(int B, int H, int W, size_t *bytes);
+
+/* loss['image'] of one frame (trainer.py:100-101, 233-243; model.py:81-85): masked_MSE(pred, gt, mask) with
+ * pred = ThinPlateSpline(U) and mask = ThinPlateSpline(ones), both from ONE evaluation of the map per pixel.  U, gt
+ * [B,H,W,3]; coord [B,P,2]; T [B,2,P+3] (dvsg_tps_solve_f32).  The mask is one plane (the reference's three channels are
+ * equal): sampler A's four weights, formed after the index clip, added in the blend's order.  pred [B,H,W,3] and mask
+ * [B,H,W] are optional outputs, bit-identical to dvsg_tps_warp_f32 on U and on ones; sums [B][2] = {sum_c (pred m - gt m)^2,
+ * sum_c m}. */
+int dvsg_loss_image_f32(const float *U, const float *coord, const float *T, const float *gt, int B, int H, int W, int P,
+                        float *pred, float *mask, float *per_sample, float *mean, double *sums, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* `temporal_loss` (trainer.py:245-250): masked_MSE(tf_warp(pred), gt, tf_warp(mask_pred) * mask_gt).  pred, gt [B,H,W,3];
+ * mask_pred, mask_gt planes [B,H,W]; flow [B,H,W,2] in pixels, 8-byte aligned (a status otherwise).  Sampler C's taps and weights of a pixel are formed once and
+ * blend the three channels and the mask plane; nothing warped is written (40 algorithmic bytes per pixel).  sums [B][2]. */
+int dvsg_loss_temporal_f32(const float *pred, const float *mask_pred, const float *flow, const float *gt, const float *mask_gt,
+                           int B, int H, int W, float *per_sample, float *mean, double *sums, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
+/* `masked_MSE` (trainer.py:233-243).  pred, gt [B,H,W,C]; mask [B,H,W,C], or -- mask_is_plane != 0 -- [B,H,W] counted C
+ * times.  C <= 64.  sums [B][2]. */
+int dvsg_loss_masked_mse_f32(const float *pred, const float *gt, const float *mask, int B, int H, int W, int C,
+                             int mask_is_plane, float *per_sample, float *mean, double *sums, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
+/* The two grid terms of one frame.  identity (trainer.py:105-106): mean |F| over [P,2].  `distortion_loss`
+ * (trainer.py:252-323) exactly as written: V_src mapped to [0,1], the four get_sp_term triangles, M_rot = [[0,1],[-1,0]];
+ * two of the four pair a triangle with the other rotation sense, so the value at F = 0 on the 5 x 5 grid is 0.125, not 0.
+ * V_src, F [B,P,2], P = num_control_points^2, 2 <= num_control_points <= 7.  identity, distortion [B]; the means [1]. */
+int dvsg_loss_grid_f32(const float *V_src, const float *F, int B, int num_control_points, float *identity, float *identity_mean,
+                       float *distortion, float *distortion_mean, void *stream);
+
+/* `get_surf_loss` (trainer.py:363-386) without x_offset / y_offset: the TPS map (coord, T as above, grid H x W) is evaluated
+ * at the N flat indices idx = int(x + y W) of surf[:,1] only, to the bits dvsg_tps_warp_f32 writes to x_s / y_s there;
+ * idx == H W reads the appended -1 (:364-365), an index outside [0, H W] is clamped into it.  surf [B,2,N,2] float32 pixel
+ * positions ([:,0] unstable, [:,1] stable); surfs_dim [B] float32, the divisor (:384).  All N points count, padded ones
+ * included.  coords [B,N,2] (optional): the gathered (x, y).  sums [B]: the float64 sum of squared differences. */
+int dvsg_loss_surf_f32(const float *surf, const float *surfs_dim, const float *coord, const float *T, int B, int N, int H, int W,
+                       int P, float *coords, float *per_sample, float *mean, double *sums, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement hook (bench.py's roofline leg; not part of the reference surface).  While
  * armed for one kernel class, every launch of that class made by this library is bracketed
  * by a hipEvent pair on the launch stream.  dvsg_prof_end synchronises on those events and
