@@ -138,8 +138,119 @@ def _check_window(model, S):
                          "input channels" % (S, 3 * S, model.locnet.in_channels))
 
 
+INT32_MAX = 2 ** 31 - 1
+
+
+def _check_crop_grid(out_h, out_w):
+    """The host-side shape rules of dvsg_tps_coverage_f32, raised as ValueError before any launch; returns D."""
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h < 2 or out_w < 2:
+        raise ValueError("a crop needs an output grid of at least 2 x 2, got %d x %d" % (out_h, out_w))
+    D = (out_h - 1) * (out_w - 1)
+    if D >= INT32_MAX or out_h * out_w >= 2 ** 31:
+        raise ValueError("output grid %d x %d too large for the coverage scan: (out_h - 1)(out_w - 1) must stay below 2^31 - 1"
+                         % (out_h, out_w))
+    return D
+
+
+def _zoom_tensor(zoom, n, dev):
+    """None, a scalar or n values -> None or float32 [n] on the device"""
+    if zoom is None:
+        return None
+    if isinstance(zoom, torch.Tensor):
+        z = zoom.to(dev, torch.float32).reshape(-1)
+    else:
+        z = torch.from_numpy(np.asarray(zoom, dtype=np.float32).reshape(-1)).to(dev)
+    if z.numel() == 1:
+        z = z.expand(n)
+    if z.numel() != n:
+        raise ValueError("zoom must be a scalar or one value per frame (%d), got %d" % (n, z.numel()))
+    return z.contiguous()
+
+
+def _coverage(model, F, src_hw, out_hw, zoom, T=None):
+    """`dvsg_tps_coverage_net_f32` over all rows of F [N,25,2] (device), 65535 at a time -> int32 [2,N] on the device
+    (n_border | key_min); T [N,2,28], if given, receives the TPS coefficients."""
+    import ctypes
+    from . import _lib
+    from ._tensor import ptr, stream
+    N = int(F.shape[0])
+    (sh, sw), (oh, ow) = src_hw, out_hw
+    res = torch.empty((2, N), dtype=torch.int32, device=F.device)
+    if T is None:
+        T = torch.empty((N, 2, model.param_dim + 3), dtype=torch.float32, device=F.device)
+    need = ctypes.c_size_t()
+    _lib.call("dvsg_tps_coverage_workspace_bytes", min(N, 65535), oh, ow, ctypes.byref(need))
+    ws = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=F.device)
+    for b0 in range(0, N, 65535):
+        b1 = min(N, b0 + 65535)
+        _lib.call("dvsg_tps_coverage_net_f32", model.locnet.handle, ptr(F[b0:b1]), ptr(zoom[b0:b1]) if zoom is not None else None,
+                  b1 - b0, int(sh), int(sw), oh, ow, ptr(T[b0:b1]), ptr(res[0, b0:b1]), ptr(res[1, b0:b1]), ptr(ws),
+                  ws.numel() * 8, stream())
+    return res
+
+
+def crop_scan(model, F, src_hw, out_hw=None, zoom=None):
+    """How much of each stabilised frame is border?  F [N,25,2]: the F_t of every frame (NumPy or torch); src_hw = (H, W) of
+    the frame sampler A reads; out_hw the output grid (default src_hw); zoom: None, a scalar or [N] float32, the zoom of the
+    grid about its centre.  One fused launch pair (`dvsg_tps_coverage_net_f32`: map, validity predicate and reduction; x_s /
+    y_s never reach memory) and ONE device -> host read.  Returns a dict of NumPy arrays with one entry per frame:
+      border_pixels  int: output pixels that sampler A leaves black (two of its taps coincide and their weights cancel);
+      key_min        int: the smallest key max(|2j - (w-1)| (h-1), |2i - (h-1)| (w-1)) over them, 2^31 - 1 if there is none;
+      free           float64 min(key_min, D) / D, D = (h-1)(w-1): the centred rectangle of the frame's aspect ratio scaled
+                     by `free` is the largest one that holds no border pixel (1.0: nothing but the outermost ring, if that)."""
+    from . import _lib
+    from ._tensor import device
+    if model.locnet is None:
+        raise _lib.DvsgError("StabNet has no weights: call load_weights()/load_ckpt() first")
+    out_hw = tuple(src_hw) if out_hw is None else tuple(out_hw)
+    D = _check_crop_grid(*out_hw)
+    if int(src_hw[0]) < 1 or int(src_hw[1]) < 1:
+        raise ValueError("src_hw must be positive, got %s" % (tuple(src_hw),))
+    dev = device()
+    Ft = (F if isinstance(F, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(F, dtype=np.float32)))
+    Ft = Ft.to(dev, torch.float32).contiguous()
+    if Ft.dim() != 3 or tuple(Ft.shape[1:]) != (model.param_dim, 2) or Ft.shape[0] < 1:
+        raise ValueError("F must be [N,%d,2]" % model.param_dim)
+    res = _coverage(model, Ft, src_hw, (int(out_hw[0]), int(out_hw[1])), _zoom_tensor(zoom, int(Ft.shape[0]), dev)).cpu().numpy()
+    key = res[1].astype(np.int64)
+    return dict(free=np.minimum(key, D).astype(np.float64) / D, border_pixels=res[0].astype(np.int64), key_min=key)
+
+
+def crop_zoom(free, margin=None, crop_min=0.5, out_hw=None):
+    """The clip's ONE zoom from the per-frame `free` of `crop_scan` (a zoom per frame would put the jitter back):
+        z = max(min(free) - margin, crop_min), at most 1, rounded once to float32.
+    margin: default 2 / (min(out_h, out_w) - 1) -- one pixel of the shorter axis in the grid's units, which needs out_hw.
+    `free` is measured on the pixels of the UNZOOMED grid; the zoomed grid's pixels lie between them, and a border that is
+    not straight can reach one of them although both of its neighbours on the old grid were valid: the margin pays for that."""
+    free = np.asarray(free, dtype=np.float64).reshape(-1)
+    if free.size < 1 or not np.all(np.isfinite(free)) or free.min() < 0.0:
+        raise ValueError("free must hold at least one finite value >= 0")
+    if margin is None:
+        if out_hw is None:
+            raise ValueError("the default margin is one pixel of the shorter axis: pass out_hw or margin")
+        _check_crop_grid(*out_hw)
+        margin = 2.0 / (min(int(out_hw[0]), int(out_hw[1])) - 1)
+    margin, crop_min = float(margin), float(crop_min)
+    if not (margin >= 0.0) or not (0.0 < crop_min <= 1.0):
+        raise ValueError("margin must be >= 0 and crop_min in (0, 1]")
+    return np.float32(min(max(float(free.min()) - margin, crop_min), 1.0))
+
+
+def _check_crop(crop):
+    """crop argument of stabilize_clip -> None, "auto" or a float32 in (0, 1]"""
+    if crop is None or (isinstance(crop, str) and crop == "auto"):
+        return crop
+    if isinstance(crop, (str, bytes, bool)) or not np.isscalar(crop):
+        raise ValueError("crop must be None, 'auto' or a zoom in (0, 1], got %r" % (crop,))
+    z = np.float32(crop)
+    if not (z > 0.0 and z <= 1.0):       # NaN fails both
+        raise ValueError("crop must be None, 'auto' or a zoom in (0, 1], got %r" % (crop,))
+    return z
+
+
 def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side=False, channel_order="rgb",
-                   as_uint8=False, source_res=False):
+                   as_uint8=False, source_res=False, crop=None, crop_margin=None, crop_min=0.5, crop_info=None):
     """eval.py:76-124 for one clip, entirely on the device.
 
     frames: [N,h0,w0,3], NumPy or torch.
@@ -164,7 +275,18 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     source_res=True (uint8 frames only): the outputs are at the frames' own size [N,h0,w0,3] (side [N,h0,2 w0,3], the
     unstable half the source bytes): after the loop, each frame's F_t warps its source frame (`dvsg_tps_render_u8`, in
     launches of at most RENDER_BATCH_BYTES of output).  The loop itself is unchanged.
+
+    crop: every stabilised frame has a black border wherever sampler A's taps leave the frame (at F_t = 0 already its last
+    row and column).  None (default) returns the frames as the reference does.  "auto" or a zoom z in (0, 1] renders them
+    WITHOUT it: the loop runs unchanged -- it must keep feeding back uncropped frames --, then `crop_scan` measures every
+    frame, `crop_zoom(free, crop_margin, crop_min)` picks one z for the clip ("auto"), and every frame is rendered again
+    from its unstable frame and its F_t on the output grid scaled by z about its centre (`dvsg_tps_warp_zoom_f32` from the
+    float32 pool, `dvsg_tps_render_zoom_u8` from the uint8 source with source_res): still one interpolation per pixel.
+    crop_info, if a dict, receives zoom, cropping_ratio (= zoom), free [N], border_pixels [N] of the rendered crop (a
+    second scan at z; all 0 unless crop_min or an explicit z cut the zoom short) and limited: the frames whose
+    free - margin < crop_min.
     """
+    crop = _check_crop(crop)
     from . import _lib
     from ._tensor import device, ptr, stream
     if channel_order not in ("rgb", "bgr"):
@@ -212,6 +334,10 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     for k in range(N):                                                             # eval.py:101
         model.locnet.stabilize_ring(pool, table[k:k + 1], pool[N + k:N + k + 1], F[k:k + 1],
                                     precision=model.precision)                    # :106-110
+    zoom = None
+    if crop is not None:
+        out_hw = (int(fr.shape[1]), int(fr.shape[2])) if source_res else (h, w)
+        zoom, T_all = _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info)
     if source_res:   # eval.py:112-113 at the frames' own size, in launches of at most RENDER_BATCH_BYTES of output
         H0, W0 = int(fr.shape[1]), int(fr.shape[2])
         out = torch.empty((N, H0, W0, 3), dtype=torch.uint8 if as_uint8 else torch.float32, device=dev)
@@ -220,12 +346,21 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
         T = torch.empty((batch, 2, model.param_dim + 3), dtype=torch.float32, device=dev)
         for b0 in range(0, N, batch):
             b1 = min(N, b0 + batch)
-            render_source_into(model, fr[b0:b1], F[b0:b1], T, flip, out[b0:b1], side[b0:b1] if side is not None else None)
+            render_source_into(model, fr[b0:b1], F[b0:b1], T, flip, out[b0:b1], side[b0:b1] if side is not None else None,
+                               zoom[b0:b1] if zoom is not None else None)
         if host:
             out = out.cpu().numpy()
             side = side.cpu().numpy() if side is not None else None
         return (out, side) if side_by_side else out
     stab = pool[N:]
+    if zoom is not None:   # the cropped frames: every unstable frame warped once more, on the zoomed grid, by its own T
+        from .model import V_SRC
+        stab = torch.empty((N, h, w, 3), dtype=torch.float32, device=dev)
+        V = torch.from_numpy(V_SRC).to(dev).unsqueeze(0).repeat(min(N, 65535), 1, 1).contiguous()
+        for b0 in range(0, N, 65535):
+            b1 = min(N, b0 + 65535)
+            _lib.call("dvsg_tps_warp_zoom_f32", ptr(pool[b0:b1]), ptr(V), ptr(T_all[b0:b1]), ptr(zoom[b0:b1]), b1 - b0, h, w, 3,
+                      model.param_dim, h, w, ptr(stab[b0:b1]), None, None, stream())
     if side_by_side:                                                               # eval.py:112-113
         if not left_done:   # uint8 / float32 input: the float32 pool holds the frame exactly
             _lib.call("dvsg_frames_f32_to_u8", ptr(pool), N, h, w, flip, ptr(side), 2 * w, 0, stream())
@@ -234,18 +369,37 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
         out = torch.empty((N, h, w, 3), dtype=torch.uint8, device=dev)
         _lib.call("dvsg_frames_f32_to_u8", ptr(stab), N, h, w, flip, ptr(out), w, 0, stream())
     else:
-        out = stab.clone()
+        out = stab.clone() if zoom is None else stab
     if host:
         out = out.cpu().numpy()
         side = side.cpu().numpy() if side is not None else None
     return (out, side) if side_by_side else out
 
 
-def render_source_into(model, src, F, T, flip, out, side=None):
+def _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info):
+    """The crop of stabilize_clip: scan every frame's F_t on the plain grid, pick the clip's zoom ("auto") or take the
+    caller's, scan again at that zoom for the report.  Returns (zoom float32 [N] on the device, T [N,2,28])."""
+    N = int(F.shape[0])
+    D = _check_crop_grid(*out_hw)
+    margin = 2.0 / (min(out_hw) - 1) if crop_margin is None else float(crop_margin)
+    T = torch.empty((N, 2, model.param_dim + 3), dtype=torch.float32, device=F.device)
+    key = _coverage(model, F, out_hw, out_hw, None, T)[1].cpu().numpy().astype(np.int64)
+    free = np.minimum(key, D).astype(np.float64) / D
+    z = crop_zoom(free, margin, crop_min) if isinstance(crop, str) else crop
+    zoom = torch.full((N,), float(z), dtype=torch.float32, device=F.device)
+    if isinstance(crop_info, dict):
+        left = _coverage(model, F, out_hw, out_hw, zoom)[0].cpu().numpy().astype(np.int64)
+        crop_info.update(zoom=float(z), cropping_ratio=float(z), free=free, border_pixels=left,
+                         limited=np.nonzero(free - margin < float(crop_min))[0])
+    return zoom, T
+
+
+def render_source_into(model, src, F, T, flip, out, side=None, zoom=None):
     """`dvsg_tps_render_u8` for the uint8 frames src [n,H0,W0,3] (device) and their F_t rows F [n,25,2]: the stabilised
     frames at source size into `out` [n,H0,W0,3] (float32, or uint8: np.uint8(x * 255.) in the channel order of src)
     and, if given, `side` [n,H0,2 W0,3] uint8 = (source bytes | uint8 render).  T [n,2,28] receives the TPS
-    coefficients.  One render launch; a uint8 `out` is copied into the right half of `side`."""
+    coefficients.  One render launch; a uint8 `out` is copied into the right half of `side`.  zoom float32 [n] (device):
+    `dvsg_tps_render_zoom_u8`, the render on the grid scaled by zoom[i] about its centre."""
     from . import _lib
     from ._tensor import ptr, stream
     n, H0, W0 = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
@@ -255,8 +409,12 @@ def render_source_into(model, src, F, T, flip, out, side=None):
         f32, u8, u8_W, u8_x0 = None, out, W0, 0
     else:                       # one launch writes the float32 render and the right half of side
         f32, u8, u8_W, u8_x0 = out, side, 2 * W0, W0
-    _lib.call("dvsg_tps_render_u8", model.locnet.handle, ptr(F), ptr(src), n, H0, W0, flip, ptr(T), ptr(f32), ptr(u8),
-              u8_W, u8_x0, stream())
+    if zoom is not None:
+        _lib.call("dvsg_tps_render_zoom_u8", model.locnet.handle, ptr(F), ptr(src), n, H0, W0, flip, ptr(zoom), ptr(T), ptr(f32),
+                  ptr(u8), u8_W, u8_x0, stream())
+    else:
+        _lib.call("dvsg_tps_render_u8", model.locnet.handle, ptr(F), ptr(src), n, H0, W0, flip, ptr(T), ptr(f32), ptr(u8),
+                  u8_W, u8_x0, stream())
     if side is not None and out.dtype == torch.uint8:
         side[:, :, W0:] = out
 

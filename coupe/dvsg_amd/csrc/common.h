@@ -44,7 +44,7 @@ int tps_apply_impl(const double *winv_cols, const float *coord, const float *rhs
                    float *T, void *stream);
 int tps_warp_impl(const float *U, const float *coord, long coord_bstride, const float *T, int B, int H,
                   int W, int C, int P, int out_h, int out_w, float *out, float *x_s, float *y_s,
-                  void *stream);
+                  void *stream, const float *zoom = nullptr /* [B] device: the zoomed grid of tps_warp_zoom_kernel */);
 
 int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *table, int tstride, const float *coord,
                        long coord_bstride, const float *T, int B, int H, int W, int P, float *out, float *x_s, float *y_s,
@@ -52,7 +52,12 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 
 // dvsg_tps_render_u8 (winv_cols / coord: the handle's W^-1 columns and V_src)
 int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
-                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream);
+                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
+                    const float *zoom = nullptr);
+// crop_kernels.hip: the fused coverage scan of dvsg_tps_coverage_f32 (coord_bstride in floats; 0 = broadcast)
+int tps_coverage_impl(const char *fn, const float *coord, long coord_bstride, const float *T, const float *zoom, int B, int P,
+                      int src_H, int src_W, int out_h, int out_w, int32_t *n_border, int32_t *key_min, void *workspace,
+                      size_t workspace_bytes, void *stream);
 
 void set_flow_tiled(int v); // diagnostic (dvsg_debug_set_option "flow_tiled"): 0 = tf_warp by global gathers (stn_kernel<kFlow>)
 void set_flow_rounds(int v);

@@ -1309,6 +1309,34 @@ int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t
                          u8_x0, stream);
 }
 
+// dvsg_tps_render_u8 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_u8 itself)
+int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
+                            int channel_flip, const float *zoom, float *T, float *out_f32, uint8_t *out_u8, int u8_W,
+                            int u8_x0, void *stream) {
+  DVSG_REQUIRE(net, "dvsg_tps_render_zoom_u8: NULL net");
+  return tps_render_impl(net->winv, net->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8, u8_W,
+                         u8_x0, stream, zoom);
+}
+
+// The coverage scan of a clip's F_t rows: the T of dvsg_stabilize_* / dvsg_tps_render_u8 for F_t (written), then
+// dvsg_tps_coverage_f32 on it with V_src.  Shapes and workspace are checked before the first launch.
+int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const float *zoom, int n, int src_H, int src_W,
+                              int out_h, int out_w, float *T, int32_t *n_border, int32_t *key_min, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+  const char *fn = "dvsg_tps_coverage_net_f32";
+  DVSG_REQUIRE(net && F_t && T && n_border && key_min, "%s: NULL pointer", fn);
+  size_t need = 0;
+  if (int rc = dvsg_tps_coverage_workspace_bytes(n, out_h, out_w, &need)) return rc;
+  DVSG_REQUIRE(src_H >= 1 && src_W >= 1, "%s: source size %dx%d must be positive", fn, src_H, src_W);
+  DVSG_REQUIRE(workspace, "%s: NULL workspace", fn);
+  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || workspace_bytes < need)
+    return fail(DVSG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed, 8-byte aligned (dvsg_tps_coverage_workspace_bytes)",
+                fn, workspace_bytes, need);
+  if (int rc = tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream)) return rc;
+  return tps_coverage_impl(fn, net->v_src, 0, T, zoom, n, 25, src_H, src_W, out_h, out_w, n_border, key_min, workspace,
+                           workspace_bytes, stream);
+}
+
 // eval_train.py's evaluation graph (:25-51): F_t = localizationNet(patches_t * mask), the warp on the unmasked u_t.
 int dvsg_stabilize_masked_f32(const dvsg_locnet_t *net, int precision, const float *patches_t, const float *u_t,
                               const float *mask, int B, int H, int W, float *s_t_pred, float *F_t, float *x_s, float *y_s,

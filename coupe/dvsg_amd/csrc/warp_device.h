@@ -94,6 +94,26 @@ __device__ __forceinline__ void sample_a_load(const TU *__restrict__ img /* [H,W
   }
 }
 
+// Does sample_a_load blend four DISTINCT taps at (xs, ys)?  The same float32 coordinate and index expressions in the same
+// order; the sample is valid iff neither clip moved an index onto its neighbour, (x1 - x0) (y1 - y0) == 1 after the clip,
+// i.e. 0 <= x < W - 1 and 0 <= y < H - 1.  Everywhere else two taps coincide, their weights cancel and the blend is 0 up to
+// its own rounding: the black border of a stabilised frame.  NaN is tested on its own (no float -> int conversion decides it) and is
+// invalid.  W == 1 or H == 1: no sample is valid.
+__device__ __forceinline__ bool sample_a_valid(int H, int W, float xs, float ys) {
+  const float x = ((xs + 1.0f) * (float)W) / 2.0f;  // :48
+  const float y = ((ys + 1.0f) * (float)H) / 2.0f;  // :49
+  if (x != x || y != y) return false;
+  int x0 = f2i(floorf(x));
+  int y0 = f2i(floorf(y));
+  int x1 = x0 + 1;
+  int y1 = y0 + 1;
+  x0 = clampi(x0, 0, W - 1);  // :57-60
+  x1 = clampi(x1, 0, W - 1);
+  y0 = clampi(y0, 0, H - 1);
+  y1 = clampi(y1, 0, H - 1);
+  return (x1 - x0) * (y1 - y0) == 1;
+}
+
 template <int C>
 __device__ __forceinline__ void sample_a_blend(const TapsA<C> &t, int Cn, float *__restrict__ dst) {
   if constexpr (C > 0) {
@@ -236,9 +256,11 @@ constexpr float kLn2 = 0x1.62e43p-1f;
 
 // Thread t < P stages control point t as {px, py, T[0][3+t] ln 2, T[1][3+t] ln 2} and -- kRowTerms -- (y_t[r] - py)^2 of the
 // rows i0 .. i0 + 3; threads 64 .. 69 stage the affine part T[0][0..2], T[1][0..2].  The caller's barrier follows.
-template <bool kRowTerms>
+// kZoom: the output grid scaled about its centre, y_t' = z y_t (one more float32 multiply; z == 1.0f gives y_t's bits).
+template <bool kRowTerms, bool kZoom = false>
 __device__ __forceinline__ void tps_stage(const float *coord, long coord_bstride, const float *T,
-                                          int b, int P, int t, int i0, float step_y, float4 *sp, float4 *sdy, float *sa) {
+                                          int b, int P, int t, int i0, float step_y, float4 *sp, float4 *sdy, float *sa,
+                                          float z = 1.0f) {
   const int n = P + 3;
   if (t < P) {
     const float px = coord[b * coord_bstride + t * 2], py = coord[b * coord_bstride + t * 2 + 1];
@@ -247,7 +269,9 @@ __device__ __forceinline__ void tps_stage(const float *coord, long coord_bstride
       float dy2[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float dy = (-1.0f + step_y * (float)(i0 + r)) - py;  // :96
+        float y_t = -1.0f + step_y * (float)(i0 + r);
+        if constexpr (kZoom) y_t = z * y_t;
+        const float dy = y_t - py;  // :96
         dy2[r] = dy * dy;
       }
       sdy[t] = make_float4(dy2[0], dy2[1], dy2[2], dy2[3]);
@@ -278,14 +302,16 @@ __device__ __forceinline__ void tps_basis_point(const float4 c, const float4 q, 
 
 // (x_s, y_s) of column x_t, rows i0 .. i0 + 3.  kRowTerms: (y_t - py)^2 comes from sdy (the rows are the workgroup's);
 // otherwise it is formed here from sp[k].y by the same two operations (a thread with rows of its own: the SURF gather).
-template <bool kRowTerms>
+// kZoom: x_t is the caller's zoomed column z x_t already; the rows are scaled here, y_t' = z y_t, as tps_stage scales them.
+template <bool kRowTerms, bool kZoom = false>
 __device__ __forceinline__ void tps_map_rows(const float4 *sp, const float4 *sdy, const float *sa, int P, float x_t,
-                                             float step_y, int i0, float (&xs)[4], float (&ys)[4]) {
+                                             float step_y, int i0, float (&xs)[4], float (&ys)[4], float z = 1.0f) {
   floatx2 xs2[2], ys2[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     // T . [1, x_t, y_t, ...] accumulated in k order (:129)
-    const floatx2 yy = {-1.0f + step_y * (float)(i0 + 2 * h), -1.0f + step_y * (float)(i0 + 2 * h + 1)};
+    floatx2 yy = {-1.0f + step_y * (float)(i0 + 2 * h), -1.0f + step_y * (float)(i0 + 2 * h + 1)};
+    if constexpr (kZoom) yy = z * yy;
     const float ax = sa[0] + sa[1] * x_t, ay = sa[3] + sa[4] * x_t;
     xs2[h] = floatx2{ax, ax} + sa[2] * yy;
     ys2[h] = floatx2{ay, ay} + sa[5] * yy;
@@ -299,7 +325,9 @@ __device__ __forceinline__ void tps_map_rows(const float4 *sp, const float4 *sdy
       float dy2[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float dy = (-1.0f + step_y * (float)(i0 + r)) - c.y;  // :96
+        float y_t = -1.0f + step_y * (float)(i0 + r);
+        if constexpr (kZoom) y_t = z * y_t;
+        const float dy = y_t - c.y;  // :96
         dy2[r] = dy * dy;
       }
       q = make_float4(dy2[0], dy2[1], dy2[2], dy2[3]);

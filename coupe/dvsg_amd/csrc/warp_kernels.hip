@@ -209,6 +209,12 @@ __global__ __launch_bounds__(64) void tps_apply_kernel(const double *__restrict_
 // dvsg_tps_warp_f32 gives on dvsg_frames_u8_to_f32(U, flip).  Sampler A blends every channel on its own, so flipping
 // the channels on the way in and back on the way out of the uint8 image is no flip at all: only out_rgb swaps them.
 // Either output may be NULL.  The trailing arguments are read by this form only.
+// kZoom (tps_warp_zoom_kernel): sample b's output grid is scaled about its centre by zoom[b], x_t' = z x_t and y_t' = z y_t --
+// one float32 multiply each on the values formed in the body, nothing else moves; z == 1.0f gives tps_warp_kernel's bits.
+// The body is ONE text, tps_warp_body.inc, that both kernels include: thread layout, tap-load scheduling and output forms
+// cannot drift apart, and tps_warp_kernel -- kZoom = false drops every zoom statement -- compiles to the instructions it
+// had before the zoomed form existed (an inlined device function with the same text does not: profiles/r08_warp_isa_diff.txt).
+
 template <int C, typename TU = float, typename TO = float>
 __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     const TU *__restrict__ U, const float *__restrict__ coord, long coord_bstride,
@@ -217,101 +223,22 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     float *__restrict__ xs_out, float *__restrict__ ys_out, const int *__restrict__ u_index = nullptr, int u_stride = 0,
     int n_pool = 0, const int *__restrict__ out_index = nullptr, int out_row = 0, int out_x0 = 0, int flip = 0,
     float *__restrict__ out_rgb = nullptr) {
-  constexpr bool kU8Out = std::is_same<TO, uint8_t>::value;
-  static_assert(!kU8Out || (C == 3 && std::is_same<TU, uint8_t>::value), "the uint8 output form reads uint8 RGB frames");
-  __shared__ float4 sp[64];      // {px, py, T[0][3+k], T[1][3+k]}
-  __shared__ float4 sdy[64];     // (y_t[r] - py)^2 for the 4 rows of this workgroup
-  __shared__ float sa[6];        // T[0][0..2], T[1][0..2]
-  const int b = blockIdx.z;
-  const int n = P + 3;
-  const int t = threadIdx.x;
-  const int i0 = blockIdx.y * kTpsRows;
-  if (t < P) {
-    const float px = coord[b * coord_bstride + t * 2], py = coord[b * coord_bstride + t * 2 + 1];
-    sp[t] = make_float4(px, py, T[((size_t)b * 2) * n + 3 + t] * kLn2, T[((size_t)b * 2 + 1) * n + 3 + t] * kLn2);
-    float dy2[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float dy = (-1.0f + step_y * (float)(i0 + r)) - py;  // :96
-      dy2[r] = dy * dy;
-    }
-    sdy[t] = make_float4(dy2[0], dy2[1], dy2[2], dy2[3]);
-  } else if (t >= 64 && t < 70) {
-    const int q = t - 64;
-    sa[q] = T[((size_t)b * 2 + q / 3) * n + q % 3];
-  }
-  __syncthreads();
-  const int j = blockIdx.x * kThreads + t;
-  if (j >= out_w) return;
-  const float x_t = -1.0f + step_x * (float)j;  // tf.linspace: start + step * i (:94)
-  int frame = b;
-  bool frame_ok = true;
-  if (u_index) {
-    frame = u_index[(size_t)b * u_stride];
-    frame_ok = frame >= 0 && frame < n_pool;
-    if (!frame_ok) frame = 0;
-  }
-  const TU *img = U ? U + (size_t)frame * H * W * Cn : nullptr;
-  size_t out_frame = b;
-  if (out_index) {
-    const int o = out_index[b];
-    if (o < 0 || o >= n_pool) out = nullptr;
-    out_frame = (size_t)o;
-  }
+  constexpr bool kZoom = false;
+  const float *const zoom = nullptr;
+#include "tps_warp_body.inc"
+}
 
-  floatx2 xs2[2], ys2[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    // T . [1, x_t, y_t, ...] accumulated in k order (:129)
-    const floatx2 yy = {-1.0f + step_y * (float)(i0 + 2 * h), -1.0f + step_y * (float)(i0 + 2 * h + 1)};
-    const float ax = sa[0] + sa[1] * x_t, ay = sa[3] + sa[4] * x_t;
-    xs2[h] = floatx2{ax, ax} + sa[2] * yy;
-    ys2[h] = floatx2{ay, ay} + sa[5] * yy;
-  }
-  for (int k = 0; k < P; ++k) tps_basis_point(sp[k], sdy[k], x_t, xs2, ys2);
-  const float xs[4] = {xs2[0].x, xs2[0].y, xs2[1].x, xs2[1].y};
-  const float ys[4] = {ys2[0].x, ys2[0].y, ys2[1].x, ys2[1].y};
-  TapsA<C> taps[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = i0 + r;
-    if (i >= out_h) break;
-    const size_t pix = ((size_t)b * out_h + i) * out_w + j;
-    if (xs_out) xs_out[pix] = xs[r];
-    if (ys_out) ys_out[pix] = ys[r];
-    if (img) sample_a_load<C, TU>(img, H, W, Cn, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
-  }
-  if constexpr (kU8Out) {
-    if (!img || (!out && !out_rgb)) return;
-  } else {
-    if (!img || !out) return;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = i0 + r;
-    if (i >= out_h) break;
-    float v[C > 0 ? C : kMaxGenericC];
-    sample_a_blend<C>(taps[r], Cn, v);
-    if constexpr (C > 0) {
-      if (!frame_ok) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) v[c] = 0.f;
-      }
-    }
-    if constexpr (kU8Out) {
-      if (out_rgb) {
-        const float rgb[3] = {v[flip ? 2 : 0], v[1], v[flip ? 0 : 2]};
-        store_pix<3>(out_rgb, (out_frame * out_h + i) * out_w + j, 3, rgb);
-      }
-      if (out) {
-        uint8_t *d = out + ((out_frame * out_h + i) * out_row + out_x0 + j) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[c] = to_u8((double)v[c]);
-      }
-    } else {
-      store_pix<C>(out, (out_frame * out_h + i) * out_w + j, Cn, v);
-    }
-  }
+// the warp on the zoomed grid (dvsg_tps_warp_zoom_f32, dvsg_tps_render_zoom_u8): contiguous frames, zoom [B] on the device
+template <int C, typename TU = float, typename TO = float>
+__global__ __launch_bounds__(kThreads) void tps_warp_zoom_kernel(
+    const TU *__restrict__ U, const float *__restrict__ coord, long coord_bstride,
+    const float *__restrict__ T, const float *__restrict__ zoom, int H, int W, int Cn, int P, int out_h, int out_w,
+    float step_x, float step_y, TO *__restrict__ out, float *__restrict__ xs_out, float *__restrict__ ys_out,
+    int out_row = 0, int out_x0 = 0, int flip = 0, float *__restrict__ out_rgb = nullptr) {
+  constexpr bool kZoom = true;
+  const int *const u_index = nullptr, *const out_index = nullptr;   // contiguous frames in, contiguous frames out
+  constexpr int u_stride = 0, n_pool = 0;
+#include "tps_warp_body.inc"
 }
 
 // ----------------------------------------------------------------------------------------
@@ -786,12 +713,13 @@ int tps_apply_impl(const double *winv_cols, const float *coord, const float *rhs
 
 int tps_warp_impl(const float *U, const float *coord, long coord_bstride, const float *T, int B, int H,
                   int W, int C, int P, int out_h, int out_w, float *out, float *x_s, float *y_s,
-                  void *stream) {
-  DVSG_REQUIRE(coord && T, "dvsg_tps_warp_f32: NULL coord/T");
-  DVSG_REQUIRE((U == nullptr) == (out == nullptr), "dvsg_tps_warp_f32: U and out must both be given or both NULL");
-  DVSG_REQUIRE(U || x_s || y_s, "dvsg_tps_warp_f32: nothing to compute");
-  DVSG_REQUIRE(P >= 1 && P <= kMaxPts, "dvsg_tps_warp_f32: P=%d outside [1,%d]", P, kMaxPts);
-  if (int rc = check_image_args("dvsg_tps_warp_f32", B, U ? H : 1, U ? W : 1, U ? C : 1, out_h, out_w)) return rc;
+                  void *stream, const float *zoom) {
+  const char *fn = zoom ? "dvsg_tps_warp_zoom_f32" : "dvsg_tps_warp_f32";
+  DVSG_REQUIRE(coord && T, "%s: NULL coord/T", fn);
+  DVSG_REQUIRE((U == nullptr) == (out == nullptr), "%s: U and out must both be given or both NULL", fn);
+  DVSG_REQUIRE(U || x_s || y_s, "%s: nothing to compute", fn);
+  DVSG_REQUIRE(P >= 1 && P <= kMaxPts, "%s: P=%d outside [1,%d]", fn, P, kMaxPts);
+  if (int rc = check_image_args(fn, B, U ? H : 1, U ? W : 1, U ? C : 1, out_h, out_w)) return rc;
   dim3 grid(ceil_div(out_w, kThreads), ceil_div(out_h, kTpsRows), B);
   const float sx = lin_step(out_w), sy = lin_step(out_h);
   hipStream_t s = as_stream(stream);
@@ -800,6 +728,18 @@ int tps_warp_impl(const float *U, const float *coord, long coord_bstride, const 
                  (U ? 4.0 * C * ((double)B * H * W + (double)B * out_h * out_w) : 0.0) +
                      (double)B * out_h * out_w * ((x_s ? 4.0 : 0.0) + (y_s ? 4.0 : 0.0)));
   if (!U) C = 3;
+  if (zoom) {   // the same grid of workgroups on the zoomed output grid
+    if (C == 3)
+      hipLaunchKernelGGL((tps_warp_zoom_kernel<3, float>), grid, dim3(kThreads), 0, s, U, coord, coord_bstride, T, zoom, H, W,
+                         C, P, out_h, out_w, sx, sy, out, x_s, y_s);
+    else if (C == 1)
+      hipLaunchKernelGGL((tps_warp_zoom_kernel<1, float>), grid, dim3(kThreads), 0, s, U, coord, coord_bstride, T, zoom, H, W,
+                         C, P, out_h, out_w, sx, sy, out, x_s, y_s);
+    else
+      hipLaunchKernelGGL((tps_warp_zoom_kernel<0, float>), grid, dim3(kThreads), 0, s, U, coord, coord_bstride, T, zoom, H, W,
+                         C, P, out_h, out_w, sx, sy, out, x_s, y_s);
+    return check_launch("tps_warp_zoom_kernel");
+  }
   if (C == 3)
     hipLaunchKernelGGL((tps_warp_kernel<3, float>), grid, dim3(kThreads), 0, s, U, coord, coord_bstride, T, H, W,
                        C, P, out_h, out_w, sx, sy, out, x_s, y_s, (const int *)nullptr, 0, 0);
@@ -839,7 +779,8 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 // frames src [B,H,W,3] warped at its own size (tps_warp_kernel<3, uint8_t, uint8_t>): float32 RGB out_f32 [B,H,W,3]
 // and / or uint8 out_u8 [B,H,u8_W,3] in columns [u8_x0, u8_x0 + W).  Every argument is checked before the first launch.
 int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
-                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
+                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
+                    const float *zoom) {
   DVSG_REQUIRE(winv_cols && coord && F_t && src && T, "dvsg_tps_render_u8: NULL pointer");
   DVSG_REQUIRE(out_f32 || out_u8, "dvsg_tps_render_u8: neither out_f32 nor out_u8 given");
   DVSG_REQUIRE(B >= 1 && B <= 65535, "dvsg_tps_render_u8: n=%d outside [1, 65535]", B);
@@ -853,6 +794,12 @@ int tps_render_impl(const double *winv_cols, const float *coord, const float *F_
   hipStream_t s = as_stream(stream);
   // algorithmic bytes: the uint8 frame once, then 3 B (uint8) and / or 12 B (float32) per output pixel
   ProfScope prof(kClsTpsWarp, s, 0.0, (double)B * H * W * (3.0 + (out_u8 ? 3.0 : 0.0) + (out_f32 ? 12.0 : 0.0)));
+  if (zoom) {   // dvsg_tps_render_zoom_u8: the same launch on the zoomed grid
+    hipLaunchKernelGGL((tps_warp_zoom_kernel<3, uint8_t, uint8_t>), grid, dim3(kThreads), 0, s, src, coord, 0L, T, zoom, H, W,
+                       3, P, H, W, sx, sy, out_u8, (float *)nullptr, (float *)nullptr, u8_W, u8_x0, channel_flip ? 1 : 0,
+                       out_f32);
+    return check_launch("tps_warp_zoom_kernel");
+  }
   hipLaunchKernelGGL((tps_warp_kernel<3, uint8_t, uint8_t>), grid, dim3(kThreads), 0, s, src, coord, 0L, T, H, W, 3, P, H,
                      W, sx, sy, out_u8, (float *)nullptr, (float *)nullptr, (const int *)nullptr, 0, 0, (const int *)nullptr,
                      u8_W, u8_x0, channel_flip ? 1 : 0, out_f32);
@@ -880,6 +827,12 @@ int dvsg_tps_warp_f32(const float *U, const float *coord, const float *T, int B,
                       int C, int P, int out_h, int out_w, float *out, float *x_s, float *y_s,
                       void *stream) {
   return tps_warp_impl(U, coord, (long)P * 2, T, B, H, W, C, P, out_h, out_w, out, x_s, y_s, stream);
+}
+
+// dvsg_tps_warp_f32 on the output grid scaled about its centre by zoom[b] (NULL: the plain grid and kernel)
+int dvsg_tps_warp_zoom_f32(const float *U, const float *coord, const float *T, const float *zoom, int B, int H, int W,
+                           int C, int P, int out_h, int out_w, float *out, float *x_s, float *y_s, void *stream) {
+  return tps_warp_impl(U, coord, (long)P * 2, T, B, H, W, C, P, out_h, out_w, out, x_s, y_s, stream, zoom);
 }
 
 int dvsg_flow_warp_f32(const float *im, const float *flow, int B, int H, int W, int C, float *out,

@@ -3,7 +3,7 @@
 reference's call surface.  The reference reads an .avi with cv2 and loads an .npz checkpoint; neither
 ships here, so this example uses a seeded synthetic clip and the seeded synthetic checkpoint.
 
-    python examples/stabilize_clip.py [--frames 8] [--height 288] [--width 512] [--ckpt DIR] [--precision f32|f32x3|f32s|f16]
+    python examples/stabilize_clip.py [--frames 8] [--height 288] [--width 512] [--ckpt DIR] [--precision f32|f32x3|f32s|f16] [--crop auto|Z]
 """
 import argparse
 import os
@@ -30,7 +30,10 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "f32x3", "f32s", "f16"],
                     help="f32: float32 matrix instructions (the default); f32x3: float32 tensors and float32-level results from "
                          "three bfloat16 pieces per operand, ~1.3x faster (include/dvsg_amd.h)")
+    ap.add_argument("--crop", default=None, help="'auto' or a zoom in (0, 1]: return the frames without sampler A's black border "
+                                                 "(stabilize_clip(crop=...)); default: the reference's frames, border included")
     args = ap.parse_args()
+    crop = args.crop if args.crop in (None, "auto") else float(args.crop)
     import inputs
     # stands in for the decoded video: BGR uint8 frames of another size (eval.py:76-81 resizes them)
     frames = (inputs.smooth_frames(1, args.frames, args.height * 3 // 2, args.width * 3 // 2) * 255).astype(np.uint8)
@@ -46,8 +49,11 @@ def main():
         net.load_weights(make_synthetic_weights(seed=0))
     t0 = time.perf_counter()
     stabilised, side_by_side = stabilize_clip(net, sess, frames, side_by_side=True, channel_order="bgr",
-                                              as_uint8=True)                       # eval.py:76-124
+                                              as_uint8=True, crop=crop, crop_info=(info := {}))   # eval.py:76-124
     dt = time.perf_counter() - t0
+    if crop is not None:
+        print("cropping ratio %.4f (frames limited by crop_min: %s), border pixels left per frame: %d"
+              % (info["cropping_ratio"], info["limited"].tolist(), int(info["border_pixels"].max())))
     print("stabilised %d frames of %dx%d in %.3f s (%.1f frames/s, autoregressive, batch 1)"
           % (len(stabilised), args.width, args.height, dt, len(stabilised) / dt))
     print("output", stabilised.shape, stabilised.dtype, "side-by-side", side_by_side.shape, side_by_side.dtype)

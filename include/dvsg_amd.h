@@ -402,6 +402,43 @@ int dvsg_frames_f32_to_u8_slots(const float *pool, int n_pool, const int32_t *sl
 int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
                        int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream);
 /* ---------------------------------------------------------------------------------------
+ * CROP to the valid region (coupe.dvsg_amd.clip.stabilize_clip(crop=...)).  Sampler A clips its tap indices before it forms
+ * the weights, so an output pixel whose source sample lies outside 0 <= x < W - 1, 0 <= y < H - 1 (x = ((x_s + 1) W) / 2 in
+ * float32, as the sampler takes it) blends coincident taps with cancelling weights and is 0 (up to the rounding of that sum): the black border of a
+ * stabilised frame.  A pixel is VALID iff its four taps are distinct after the clip, (x1 - x0)(y1 - y0) == 1; NaN is invalid.
+ * The crop is a ZOOM of the output grid about its centre, x_t' = z x_t, y_t' = z y_t (one float32 multiply each on
+ * tf.linspace's values; z = 1.0f gives the plain entry points' bits), composed into the TPS map, so every output pixel is
+ * still interpolated exactly once.  zoom is float32 [B] ON THE DEVICE, one value per sample.
+ *   dvsg_tps_coverage_f32  one fused scan: the TPS map of dvsg_tps_warp_zoom_f32 (same bits for the same coord, T, zoom),
+ *          the validity test against a source of src_H x src_W, and per sample b
+ *            n_border[b]  int32: the number of invalid output pixels;
+ *            key_min[b]   int32: the minimum over the invalid pixels (i, j) of
+ *                         key = max(|2 j - (out_w - 1)| (out_h - 1), |2 i - (out_h - 1)| (out_w - 1)),
+ *                         INT32_MAX when none is invalid.  With D = (out_h - 1)(out_w - 1), key / D is the pixel's
+ *                         normalised Chebyshev distance from the centre: every pixel with key < key_min is valid, the
+ *                         largest centred rectangle of the frame's aspect ratio that holds no border.
+ *          x_s / y_s never reach memory.  Integer results: exact, the same on every run; the outputs need no zeroing.
+ *          zoom NULL = 1.  out_h, out_w >= 2, D < 2^31 - 1, B <= 65535.  workspace: dvsg_tps_coverage_workspace_bytes
+ *          bytes, 8-byte aligned (one partial per workgroup; DVSG_ERR_WORKSPACE if short, before any launch).
+ *   dvsg_tps_warp_zoom_f32  dvsg_tps_warp_f32 on the zoomed grid: same thread layout, same outputs, the grid-only form
+ *          (U == NULL && out == NULL) included.  zoom NULL: dvsg_tps_warp_f32 itself.
+ *   dvsg_tps_coverage_net_f32  F_t [n,25,2] -> T [n,2,28] (written: the T of dvsg_tps_render_u8 for that F_t, bit for
+ *          bit), then dvsg_tps_coverage_f32 on that T with the handle's V_src.
+ *   dvsg_tps_render_zoom_u8  dvsg_tps_render_u8 on the zoomed grid; zoom NULL: dvsg_tps_render_u8 itself.
+ * ------------------------------------------------------------------------------------- */
+int dvsg_tps_coverage_workspace_bytes(int B, int out_h, int out_w, size_t *bytes);
+int dvsg_tps_coverage_f32(const float *coord, const float *T, const float *zoom, int B, int P, int src_H, int src_W,
+                          int out_h, int out_w, int32_t *n_border, int32_t *key_min, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int dvsg_tps_warp_zoom_f32(const float *U, const float *coord, const float *T, const float *zoom, int B, int H, int W,
+                           int C, int P, int out_h, int out_w, float *out, float *x_s, float *y_s, void *stream);
+int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const float *zoom, int n, int src_H, int src_W,
+                              int out_h, int out_w, float *T, int32_t *n_border, int32_t *key_min, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
+                            int channel_flip, const float *zoom, float *T, float *out_f32, uint8_t *out_u8, int u8_W,
+                            int u8_x0, void *stream);
+/* ---------------------------------------------------------------------------------------
  * eval_train.py's evaluation graph (eval_train.py:25-51): unlike model.py's, its CNN input is
  * `patches_masked_t = patches_t * mask` (:43-45), where `random_mask` (:53-64, = model.py:156-167) warps an all-ones
  * image of the 18 history channels with ProjectiveTransformer and a near-identity homography H and leaves the newest
