@@ -422,7 +422,7 @@ __global__ __launch_bounds__(kThreads) void mask_plane_kernel(const float *__res
 // its four taps from global memory as before; taps on the zero ring are never read.  Geometry (`padded_geom`) and blend
 // are the functions stn_kernel uses on the same values in the same order: the output is bit-identical.
 // ----------------------------------------------------------------------------------------
-constexpr int kFsThreads = 1024;                           // 8 waves: 128 columns x 4 row pairs
+constexpr int kFsThreads = 1024;                           // 16 waves: 128 columns x 8 row pairs
 constexpr int kFsW = 128, kFsStep = 16, kFsPPT = 2;        // strip width, rows per step, rows per thread
 constexpr int kFsMX = 12, kFsMY = 12;                     // window margins, pixels
 constexpr int kFsCols = kFsW + 2 * kFsMX + 1;             // 153 pixels: taps x .. x + 1
@@ -483,13 +483,13 @@ void flow_warp_strip_kernel(FlowStripParams p) {
   // the whole ring starts finite: slots of rows / columns outside the image are read (and dropped by the blend's select)
   for (int e = t; e < kFsRing * kFsCpr; e += kFsThreads) reinterpret_cast<floatx4 *>(ring)[e] = floatx4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
-  // prologue: the 33 rows of the first step, straight into ring slots 0..32
+  // prologue: the 41 rows (kFsLive) of the first step, straight into ring slots 0..40
   for (int e = t; e < kFsLive * kFsCpr; e += kFsThreads) {
     const int r = e / kFsCpr, c = e - r * kFsCpr;
     const int y = i_begin - kFsMY + r;
     if (y >= 0 && y < H) reinterpret_cast<floatx4 *>(ring)[r * kFsCpr + c] = load_chunk(y, c);
   }
-  // Two steps of prefetch, in registers: at the head of step s the 8 new source rows and the flow of step s + 2 are
+  // Two steps of prefetch, in registers: at the head of step s the 16 new source rows and the flow of step s + 2 are
   // requested; the rows of step s + 1 (requested a step earlier) go into the ring at the end of step s.  Register sets
   // rotate by compile-time index (nw[s & 1], fl[s & 3]; the loop is unrolled by four), so no copy ever waits on a load.
   floatx4 nw[2][kFsNew];
@@ -500,7 +500,7 @@ void flow_warp_strip_kernel(FlowStripParams p) {
     for (int k = 0; k < kFsNew; ++k) {
       const int e = min(t + kFsThreads * k, kFsStep * kFsCpr - 1);   // (the lanes behind the last chunk repeat it: no branch)
       const int r = e / kFsCpr, c = e - r * kFsCpr;
-      const int y = i_of_step + kFsMY + 1 + r;             // the 8 rows that step adds to the window of the one before it
+      const int y = i_of_step + kFsMY + 1 + r;             // the 16 rows that step adds to the window of the one before it
       rows[k] = load_chunk(min(y, H - 1), c);              // rows behind the image: a copy of its last row, never committed
     }
     const int rn = i_of_step + rg * kFsPPT;
