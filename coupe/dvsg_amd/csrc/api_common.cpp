@@ -16,6 +16,8 @@ int fail(int status, const char *fmt, ...) {
   return status;
 }
 
+DebugOptions g_opt;
+
 }  // namespace dvsg
 
 extern "C" {

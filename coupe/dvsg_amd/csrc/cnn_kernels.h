@@ -83,13 +83,9 @@ inline size_t x3_packed_bytes(int rows, int K) { return (size_t)rows * K * 6; }
 int launch_pack_x3(const float *wt, void *out, int rows, int K, hipStream_t s);
 // float16 mode, big launches: 256 x 128 tiles with 64-byte K stages (conv_gemm_wide16.hip); called by launch_conv_gemm
 int launch_conv_wide16(const ConvGemm &p, hipStream_t s);
-void set_wide16_min_tiles(int v);
 // weights packed for that kernel: every 32-k stage of a 128-row tile contiguous, in the LDS image's chunk order
 size_t wide16_packed_bytes(int rows, int Cin, int ksize);
 int launch_pack_wide16(const void *wt, void *out, int rows, int Cin, int ksize, int order, hipStream_t s);
-void set_wide16_arows(int v);       // diagnostic (dvsg_debug_set_option "wide16_arows")
-void set_wide16_hreuse(int v);      // diagnostic (dvsg_debug_set_option "wide16_hreuse")
-void set_wide16_packed(int v);      // diagnostic (dvsg_debug_set_option "wide16_packed")
 // Zeroes n split-K / stream-K tickets with a KERNEL: a hipMemsetAsync captured into a HIP graph (memset node) did not
 // take effect on the second and later replays of the graph on ROCm 7.2 (tests/test_gpu_cnn.py::test_a_step_replays_...).
 int launch_zero_tickets(int *tickets, size_t n, hipStream_t s);
@@ -124,13 +120,8 @@ struct ConvFused {
   int x3 = 0;
 };
 int launch_conv3x3_1x1_x3(const ConvFused &p, hipStream_t s);
-bool conv_fusable(int prec, int Cin, int Cmid, int Cout, int ksize);
+bool conv_fusable(int prec, int Cin, int Cmid, int Cout, int ksize);   // a predicate of precision and shape alone
 int launch_conv3x3_1x1(const ConvFused &p, hipStream_t s);
-void set_fuse_conv(int v);
-int get_fuse_conv();
-void set_fused_hreuse(int v);        // diagnostic (dvsg_debug_set_option "fused_hreuse")
-void set_conv_variant(int v);   // diagnostic A/B switches (dvsg_debug_set_option)
-void set_conv1_variant(int v);
 
 // conv1: 7x7 stride 2, explicit pad 3, C_in = 21 -> 64, with scale_RGB fused into the LDS
 // load stage (networks.py:6-16 + slim conv2d_same root).  wt1 is [7][64][kConv1Ld] float32:
@@ -171,6 +162,13 @@ inline void record_conv1_kernel(int family, int nw, int to, int src, int bands =
   for (int i = 0; i < 6; ++i) g_last_root_kernel[i] = rec[i];
 }
 enum Conv1SrcKind { kSrcWindow = 0, kSrcRingF32 = 1, kSrcRingU8 = 2 };
+// SRC, the conv1 kernels' template argument and the launch record's field: where the input comes from and how it is staged
+constexpr int kSrcAligned = 1;     // bit 0: rows on the 16-byte (4-byte for uint8) grid
+constexpr int kSrcKindShift = 1;   // bits 1-2: the Conv1SrcKind
+constexpr int kSrcMasked = 8;      // bit 3: the history channels are multiplied by src.mask (eval_train.py's graph)
+constexpr int conv1_src(int kind, bool aligned, bool masked) {
+  return (kind << kSrcKindShift) | (aligned ? kSrcAligned : 0) | (masked ? kSrcMasked : 0);
+}
 struct Conv1Src {
   const void *base;   // window tensor, or frame pool
   const int *table;   // ring: [B,7] pool indices (device); an index outside [0, n_pool) stages zeros

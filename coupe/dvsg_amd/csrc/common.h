@@ -59,9 +59,41 @@ int tps_coverage_impl(const char *fn, const float *coord, long coord_bstride, co
                       int src_H, int src_W, int out_h, int out_w, int32_t *n_border, int32_t *key_min, void *workspace,
                       size_t workspace_bytes, void *stream);
 
-void set_flow_tiled(int v); // diagnostic (dvsg_debug_set_option "flow_tiled"): 0 = tf_warp by global gathers (stn_kernel<kFlow>)
-void set_flow_rounds(int v);
-void set_warp_xcd(int v);   // diagnostic (dvsg_debug_set_option "warp_xcd"): XCD-aware workgroup order of the sampler kernels
+// The diagnostic A/B switches of dvsg_debug_set_option, one member per option name, at their defaults.  One instance,
+// g_opt (api_common.cpp); the launch policies read its members.  Host-only, not synchronised: tests and tools set a
+// switch between calls, never during one.
+struct DebugOptions {
+  int conv_variant = 0;        // 0 = auto, 1 = 4 waves, 2 = 8 waves, 3 = no split-K, 4 = 64-wide tiles only,
+                               // 5 = no 256 x 128 float16 tiles, 6 = no stream-K tail (conv_gemm.hip)
+  int conv1_variant = 0;       // 0 = auto; 1 = float32 kernel with 8 waves; 2 = float16 output from the float32 multiply;
+                               // 3 = float16, one output row per workgroup; 4 = never the marching kernel; 5 = always
+  int wide16_min_tiles = 128;  // float16 mode: 256 x 128 tiles from this many of them (a quarter of a round of 512 workgroups).
+                               // Round 2 measured 256 (128 and below lost at batch 1-2 with the kernels of then); with packed
+                               // weight stages, 128-byte activation rows and the 3x3 row reuse 128 is -0.5 % at batch 16, -4.5 %
+                               // at batch 4 (720p), equal at batch 1; 64 and 32 lose 4-27 % at batch 1-4
+  int wide16_packed = 1;       // 0: weight stages fetched from the [rows][K] layout
+  int wide16_arows = 1;        // 0 = 64-byte activation rows everywhere (conv_wide16_kernel), 2 = 128-byte rows for K = 128
+                               // too (tests)
+  int wide16_hreuse = 1;       // 0: 3x3 stride-1 layers through conv_wide16a_kernel
+  int fused_hreuse = 1;        // 0: block 1's stride-1 units through conv3x3_1x1_f16_kernel
+  int fuse_conv = 1;           // 0 turns the fused block-1 path off
+  int fuse_shortcut = 1;       // block 1's shortcut conv inside the fused conv2 + conv3 kernel (0: A/B)
+  int concat_sc = 1;           // blocks 2-4's opening units: shortcut + conv1 as one launch (0: A/B)
+  int x3_conv1 = 1;            // 0: the f32x3 precision with the float32 conv1 kernel (A/B)
+  int x3_fuse = 3;             // A/B of block 1's fusion in the f32x3 precision (forward())
+  int f16_split = 1;           // float16 precision: conv weights as hi / lo float16 pairs (default) or plain float16 (A/B only:
+                               // 0; 9/10 of the plain mode's F_t error is the weights' rounding)
+  // Which layers of the float16 mode carry the lo piece: bit 4 * kind + block (kind 0 = a unit's conv1, 1 = conv2, 2 = conv3,
+  // 3 = shortcut; block 0..3).  A plain float16 weight is off by up to 2^-12 relative at every pixel alike, an error the global
+  // average pool does not average away; how much of it reaches F_t depends on the layer (tools/f16_pair_sweep.py measures
+  // every block x kind).  A layer without the lo piece runs half the MFMAs and, in the big launches, 128 channels per tile.
+  int f16_pair_mask = 0xFFFF;
+  int flow_tiled = 1;          // 0 = tf_warp by global gathers (stn_kernel<kFlow>), 1 = column strips streamed through LDS,
+                               // workgroups in XCD-aware order (default), 2 = the same in plain dispatch order
+  int flow_rounds = 4;         // rounds of resident workgroups the strip kernel's bands aim at
+  int warp_xcd = 0;            // XCD-aware workgroup order of the sampler kernels; 0: plain dispatch order (A/B)
+};
+extern DebugOptions g_opt;
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 

@@ -3,6 +3,7 @@
 // load stage.
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 
 #include "cnn_device.h"
 #include "cnn_kernels.h"
@@ -367,29 +368,17 @@ struct Conv1RingRow {
   }
 };
 
-// SRC of the conv1 kernels: bit 0 = rows on the 16-byte (4-byte for uint8) grid; 0/1 window tensor, 2/3 float32 frame
-// ring, 4/5 uint8 frame ring; + 8: the history channels are multiplied by src.mask (eval_train.py's graph).
+// The staged row of a conv1 kernel's SRC (kSrcAligned, kSrcKindShift, kSrcMasked in cnn_kernels.h): a window tensor's
+// Conv1Row, or a frame ring's Conv1RingRow over float32 / uint8 frames.
 template <int NT, int GROUPS, int SRC>
 struct Conv1RowSel {
-  static_assert((SRC & 6) == 0, "ring sources are specialised below");
-  typedef Conv1Row<NT, GROUPS, (SRC & 1) != 0, (SRC & 8) != 0> type;
+  static constexpr int kKind = SRC >> kSrcKindShift & 3;
+  static constexpr bool kAligned = (SRC & kSrcAligned) != 0, kMasked = (SRC & kSrcMasked) != 0;
+  static_assert(SRC >= 0 && SRC < 16 && kKind <= kSrcRingU8, "no such conv1 source");
+  typedef std::conditional_t<kKind == kSrcWindow, Conv1Row<NT, GROUPS, kAligned, kMasked>,
+                             Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, std::conditional_t<kKind == kSrcRingU8, uint8_t, float>,
+                                          kAligned, kMasked>> type;
 };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 10> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, float, false, true> type; };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 11> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, float, true, true> type; };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 12> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, uint8_t, false, true> type; };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 13> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, uint8_t, true, true> type; };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 2> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, float, false> type; };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 3> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, float, true> type; };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 4> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, uint8_t, false> type; };
-template <int NT, int GROUPS>
-struct Conv1RowSel<NT, GROUPS, 5> { typedef Conv1RingRow<NT, (C1_RING_GROUPS + NT - 1) / NT, uint8_t, true> type; };
 
 #ifdef DVSG_STAMPS  // diagnostic build (tools/stamp_probe_conv1.py): per-workgroup phase times of conv1_kernel
 __device__ unsigned long long g_c1_stamps[8 * 65536];
@@ -1753,12 +1742,25 @@ int march_bands(int B, int Ho, int wtiles, int *quads_per_band) {
   return 0;
 }
 
-int g_conv1_variant = 0;  // dvsg_debug_set_option("conv1_variant", v): 0 = auto; 1 = float32 kernel with 8 waves; 2 = float16 output from
-                          // the float32 multiply; 3 = float16, one output row per workgroup; 4 = never the marching kernel; 5 = always
+// Run-time SRC -> compile-time constant: calls f(std::integral_constant<int, SRC>) for the legal value equal to `src`: every
+// Conv1SrcKind, aligned or not, unmasked, and with MASKED_TOO the same six with kSrcMasked.  False, and no call, for any other.
+template <int S>
+using SrcC = std::integral_constant<int, S>;
+template <bool MASKED_TOO, typename F>
+bool with_conv1_src(int src, F &&f) {
+  auto is = [&](auto c) { return src == c && (f(c), true); };
+  if (is(SrcC<conv1_src(kSrcWindow, false, false)>{}) || is(SrcC<conv1_src(kSrcWindow, true, false)>{}) ||
+      is(SrcC<conv1_src(kSrcRingF32, false, false)>{}) || is(SrcC<conv1_src(kSrcRingF32, true, false)>{}) ||
+      is(SrcC<conv1_src(kSrcRingU8, false, false)>{}) || is(SrcC<conv1_src(kSrcRingU8, true, false)>{}))
+    return true;
+  if constexpr (MASKED_TOO)
+    return is(SrcC<conv1_src(kSrcWindow, false, true)>{}) || is(SrcC<conv1_src(kSrcWindow, true, true)>{}) ||
+           is(SrcC<conv1_src(kSrcRingF32, false, true)>{}) || is(SrcC<conv1_src(kSrcRingF32, true, true)>{}) ||
+           is(SrcC<conv1_src(kSrcRingU8, false, true)>{}) || is(SrcC<conv1_src(kSrcRingU8, true, true)>{});
+  return false;
+}
 
 }  // namespace
-
-void set_conv1_variant(int v) { g_conv1_variant = v; }
 
 int g_last_root_kernel[kRootKernelFields] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
 
@@ -1775,105 +1777,81 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *w
   const dim3 grid((unsigned)blocks);
   // rows that start on 16-byte boundaries (4-byte for uint8 frames): the staged segment then consists of whole aligned groups
   const bool aligned = W % 4 == 0 && reinterpret_cast<uintptr_t>(src.base) % (src_kind == kSrcRingU8 ? 4 : 16) == 0;
-  const int SRC = 2 * src_kind + (aligned ? 1 : 0) + (src.mask ? 8 : 0);
+  const int SRC = conv1_src(src_kind, aligned, src.mask != nullptr);
   // the f32s activations are float16 pieces (P format): only conv1_split_kernel writes them, whatever the A/B switch says
   // (the float32 kernel's output would be read back as pieces: silent garbage)
   if (out_prec == kF32S && !wt1s) return fail(DVSG_ERR_UNSUPPORTED, "conv1: the f32s precision needs the piece weights");
-#define DVSG_K_F32(SRC) conv1_kernel<4, float, SRC>
-#define DVSG_K_F16(SRC) conv1_f16_kernel<_Float16, (SRC) & 7>   /* A/B kernel: never launched with a mask */
-#define DVSG_K_SPLIT(SRC) conv1_split_kernel<float, SRC>
-#define DVSG_K_X3(SRC) conv1_x3_kernel<SRC>
-#define DVSG_C1(KERNEL, NTHREADS, WPTR, YPTR)                                                                            \
-  do {                                                                                                                   \
-    switch (SRC) {                                                                                                       \
-      case 0: hipLaunchKernelGGL((KERNEL(0)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 1: hipLaunchKernelGGL((KERNEL(1)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 2: hipLaunchKernelGGL((KERNEL(2)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 3: hipLaunchKernelGGL((KERNEL(3)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 4: hipLaunchKernelGGL((KERNEL(4)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 5: hipLaunchKernelGGL((KERNEL(5)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 8: hipLaunchKernelGGL((KERNEL(8)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 9: hipLaunchKernelGGL((KERNEL(9)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 10: hipLaunchKernelGGL((KERNEL(10)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 11: hipLaunchKernelGGL((KERNEL(11)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      case 12: hipLaunchKernelGGL((KERNEL(12)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-      default: hipLaunchKernelGGL((KERNEL(13)), grid, dim3(NTHREADS), 0, s, src, WPTR, bias, YPTR, H, W, Ho, Wo, wtiles); break; \
-    }                                                                                                                    \
-  } while (0)
   if (out_prec == kF32X && !wt1x) return fail(DVSG_ERR_UNSUPPORTED, "conv1: the f32x3 precision needs the bfloat16 piece weights");
-  // the launch record (dvsg_debug_last_root_kernel): the switch's default label launches SRC 13 (5 in the marching kernel)
-  const int rec_src = (SRC >= 0 && SRC <= 5) || (SRC >= 8 && SRC <= 12) ? SRC : 13;
+  const int variant = g_opt.conv1_variant;
+  // SRC names one of the kernels' instantiations.  Unreachable from the ABI when not: every entry point passes one of
+  // the three Conv1SrcKind values, or checks the kind it is given (dvsg_locnet_forward_masked)
+  bool legal = true;
   if (out_prec == kF32X) {
-    record_conv1_kernel(5, -1, -1, rec_src);
-    DVSG_C1(DVSG_K_X3, 256, static_cast<const unsigned short *>(wt1x), static_cast<float *>(y));
+    legal = with_conv1_src<true>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(5, -1, -1, S);
+      hipLaunchKernelGGL((conv1_x3_kernel<S>), grid, dim3(256), 0, s, src, static_cast<const unsigned short *>(wt1x), bias,
+                         static_cast<float *>(y), H, W, Ho, Wo, wtiles);
+    });
   } else if (out_prec == kF32S) {
-    record_conv1_kernel(4, -1, 0, rec_src);
-    DVSG_C1(DVSG_K_SPLIT, 256, static_cast<const _Float16 *>(wt1s), static_cast<float *>(y));
-  } else if (out_prec == kF16 && wt1h && g_conv1_variant == 3 && !src.mask) {   // A/B: one output row per workgroup
-    record_conv1_kernel(1, -1, 1, rec_src & 7);
-    DVSG_C1(DVSG_K_F16, 256, static_cast<const _Float16 *>(wt1h), static_cast<_Float16 *>(y));
-  } else if (out_prec == kF16 && wt1h && g_conv1_variant != 2 && g_conv1_variant != 4 && !src.mask &&
-             (g_conv1_variant == 5 || march_bands(B, Ho, wtiles, nullptr) > 0)) {   // (a masked window -- eval_train.py's
+    legal = with_conv1_src<true>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(4, -1, 0, S);
+      hipLaunchKernelGGL((conv1_split_kernel<float, S>), grid, dim3(256), 0, s, src, static_cast<const _Float16 *>(wt1s), bias,
+                         static_cast<float *>(y), H, W, Ho, Wo, wtiles);
+    });
+  } else if (out_prec == kF16 && wt1h && variant == 3 && !src.mask) {   // A/B: one output row per workgroup, never with a mask
+    legal = with_conv1_src<false>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(1, -1, 1, S);
+      hipLaunchKernelGGL((conv1_f16_kernel<_Float16, S>), grid, dim3(256), 0, s, src, static_cast<const _Float16 *>(wt1h), bias,
+                         static_cast<_Float16 *>(y), H, W, Ho, Wo, wtiles);
+    });
+  } else if (out_prec == kF16 && wt1h && variant != 2 && variant != 4 && !src.mask &&
+             (variant == 5 || march_bands(B, Ho, wtiles, nullptr) > 0)) {   // (a masked window -- eval_train.py's
     // graph -- takes the two-row kernel below: same products in the same order)
     // big launches: marching, wave-specialised workgroups (conv1_f16_march_kernel), one per CU
     // (conv1_variant 5 forces it at any size, bands of <= 3 quads: the parity tests run it on small frames)
     int qpb = 0;
     int bands = march_bands(B, Ho, wtiles, &qpb);
-    if (g_conv1_variant == 5) {
+    if (variant == 5) {
       qpb = 3;
       bands = ((Ho + C1M_QUAD - 1) / C1M_QUAD + qpb - 1) / qpb;
     }
     const dim3 mgrid((unsigned)((long)wtiles * bands * B));
-    record_conv1_kernel(3, -1, -1, SRC >= 0 && SRC <= 4 ? SRC : 5, bands, qpb);
-    const _Float16 *wp = static_cast<const _Float16 *>(wt1h);
-    _Float16 *yp = static_cast<_Float16 *>(y);
-    switch (SRC) {
-      case 0: hipLaunchKernelGGL((conv1_f16_march_kernel<0>), mgrid, dim3(512), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, bands, qpb); break;
-      case 1: hipLaunchKernelGGL((conv1_f16_march_kernel<1>), mgrid, dim3(512), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, bands, qpb); break;
-      case 2: hipLaunchKernelGGL((conv1_f16_march_kernel<2>), mgrid, dim3(512), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, bands, qpb); break;
-      case 3: hipLaunchKernelGGL((conv1_f16_march_kernel<3>), mgrid, dim3(512), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, bands, qpb); break;
-      case 4: hipLaunchKernelGGL((conv1_f16_march_kernel<4>), mgrid, dim3(512), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, bands, qpb); break;
-      default: hipLaunchKernelGGL((conv1_f16_march_kernel<5>), mgrid, dim3(512), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, bands, qpb); break;
-    }
-  } else if (out_prec == kF16 && wt1h && g_conv1_variant != 2) {   // two output rows per workgroup (conv1_f16_pair_kernel)
+    legal = with_conv1_src<false>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(3, -1, -1, S, bands, qpb);
+      hipLaunchKernelGGL((conv1_f16_march_kernel<S>), mgrid, dim3(512), 0, s, src, static_cast<const _Float16 *>(wt1h), bias,
+                         static_cast<_Float16 *>(y), H, W, Ho, Wo, wtiles, bands, qpb);
+    });
+  } else if (out_prec == kF16 && wt1h && variant != 2) {   // two output rows per workgroup (conv1_f16_pair_kernel)
     const int hpairs = (Ho + 1) / 2;
-    const long pblocks = (long)wtiles * hpairs * B;
-    const dim3 pgrid((unsigned)pblocks);
-    record_conv1_kernel(2, -1, 1, rec_src);
-    const _Float16 *wp = static_cast<const _Float16 *>(wt1h);
-    _Float16 *yp = static_cast<_Float16 *>(y);
-    switch (SRC) {
-      case 0: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 0>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 1: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 1>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 2: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 2>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 3: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 3>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 4: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 4>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 5: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 5>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 8: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 8>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 9: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 9>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 10: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 10>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 11: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 11>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      case 12: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 12>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-      default: hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, 13>), pgrid, dim3(256), 0, s, src, wp, bias, yp, H, W, Ho, Wo, wtiles, hpairs); break;
-    }
+    const dim3 pgrid((unsigned)((long)wtiles * hpairs * B));
+    legal = with_conv1_src<true>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(2, -1, 1, S);
+      hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, S>), pgrid, dim3(256), 0, s, src, static_cast<const _Float16 *>(wt1h), bias,
+                         static_cast<_Float16 *>(y), H, W, Ho, Wo, wtiles, hpairs);
+    });
   } else if (out_prec == kF16) {  // conv1_variant 2: f32 multiply, f16 output (window tensors only)
     DVSG_REQUIRE(src_kind == kSrcWindow && !src.mask, "conv1: conv1_variant 2 takes an unmasked window tensor");
     record_conv1_kernel(0, 4, 1, 0);
     hipLaunchKernelGGL((conv1_kernel<4, _Float16, 0>), grid, dim3(256), 0, s, src, wt1, bias, static_cast<_Float16 *>(y), H, W,
                        Ho, Wo, wtiles);
-  } else if (g_conv1_variant != 0 && src_kind == kSrcWindow && !src.mask) {
+  } else if (variant != 0 && src_kind == kSrcWindow && !src.mask) {
     record_conv1_kernel(0, 8, 0, 0);
     hipLaunchKernelGGL((conv1_kernel<8, float, 0>), grid, dim3(512), 0, s, src, wt1, bias, static_cast<float *>(y), H, W, Ho,
                        Wo, wtiles);
   } else {
-    record_conv1_kernel(0, 4, 0, rec_src);
-    DVSG_C1(DVSG_K_F32, 256, wt1, static_cast<float *>(y));
+    legal = with_conv1_src<true>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(0, 4, 0, S);
+      hipLaunchKernelGGL((conv1_kernel<4, float, S>), grid, dim3(256), 0, s, src, wt1, bias, static_cast<float *>(y), H, W, Ho, Wo,
+                         wtiles);
+    });
   }
-#undef DVSG_C1
-#undef DVSG_K_F32
-#undef DVSG_K_F16
-#undef DVSG_K_SPLIT
-#undef DVSG_K_X3
+  DVSG_REQUIRE(legal, "conv1: no kernel for source %d", SRC);
   return check_launch("conv1_kernel");
 }
 

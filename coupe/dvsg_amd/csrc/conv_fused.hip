@@ -896,18 +896,11 @@ void conv3x3_1x1_f16h_kernel(ConvFusedF16Dev p) {
   }
 }
 
-int g_fused_hreuse = 1;   // dvsg_debug_set_option("fused_hreuse", 0): block 1's stride-1 units through conv3x3_1x1_f16_kernel
-
-int g_fuse_conv = 1;  // dvsg_debug_set_option("fuse_conv", 0) turns the fused block-1 path off
-
 }  // namespace
 
-void set_fuse_conv(int v) { g_fuse_conv = v; }
-int get_fuse_conv() { return g_fuse_conv; }
-void set_fused_hreuse(int v) { g_fused_hreuse = v; }
 bool conv_fusable(int prec, int Cin, int Cmid, int Cout, int ksize) {
-  if (prec == kF16) return g_fuse_conv != 0 && ksize == 3 && Cmid == CMID && Cin % 64 == 0 && Cout % 64 == 0;
-  return g_fuse_conv != 0 && (prec == kF32 || prec == kF32S) && ksize == 3 && Cmid == CMID && Cin % 32 == 0 && Cin >= 64 && Cout % 128 == 0;
+  if (prec == kF16) return ksize == 3 && Cmid == CMID && Cin % 64 == 0 && Cout % 64 == 0;
+  return (prec == kF32 || prec == kF32S) && ksize == 3 && Cmid == CMID && Cin % 32 == 0 && Cin >= 64 && Cout % 128 == 0;
 }
 
 static int launch_conv3x3_1x1_f16(const ConvFused &p, hipStream_t s) {
@@ -937,7 +930,7 @@ static int launch_conv3x3_1x1_f16(const ConvFused &p, hipStream_t s) {
                  2.0 * (double)M * CMID * (9.0 * p.Cin) + 2.0 * (double)M * p.Cout * CMID + (sc ? 2.0 * (double)M * p.Cout * CSC : 0.0),
                  2.0 * ((double)p.B * p.H * p.W * p.Cin + 2.0 * CMID * 9 * p.Cin + 2.0 * p.Cout * CMID +
                         (sc ? (double)M * CSC + 2.0 * p.Cout * CSC + (double)M * p.Cout : 2.0 * (double)M * p.Cout)));
-  if (g_fused_hreuse && p.stride == 1 && p.Cin == 64 && p.Cout >= 128 && p.H == p.Ho && p.W == p.Wo && (res == 1 || res == 3)) {
+  if (g_opt.fused_hreuse && p.stride == 1 && p.Cin == 64 && p.Cout >= 128 && p.H == p.Ho && p.W == p.Wo && (res == 1 || res == 3)) {
     d.mtiles = (int)((M + FHM - 1) / FHM);
     const dim3 gridh(d.mtiles), blockh(512);
     if (res == 1) hipLaunchKernelGGL((conv3x3_1x1_f16h_kernel<1>), gridh, blockh, 0, s, d);

@@ -5,18 +5,8 @@
 
 namespace dvsg {
 
-int g_conv_variant = 0;  // dvsg_debug_set_option("conv_variant", v): 0 = auto, 1 = 4 waves, 2 = 8 waves,
-                         // 3 = no split-K, 4 = 64-wide tiles only, 5 = no 256 x 128 float16 tiles, 6 = no stream-K tail
-long g_wide16_min_tiles = 128;   // float16 mode: 256 x 128 tiles from this many of them (a quarter of a round of 512 workgroups).
-                                 // Round 2 measured 256 (128 and below lost at batch 1-2 with the kernels of then); with packed
-                                 // weight stages, 128-byte activation rows and the 3x3 row reuse 128 is -0.5 % at batch 16, -4.5 %
-                                 // at batch 4 (720p), equal at batch 1; 64 and 32 lose 4-27 % at batch 1-4
-
 int g_last_conv_config[kConvConfigFields] = {-1};
 int g_last_conv_kernel[kConvKernelFields] = {-1, -1, -1, -1, -1, -1};
-
-void set_conv_variant(int v) { g_conv_variant = v; }
-void set_wide16_min_tiles(int v) { g_wide16_min_tiles = v; }
 
 namespace {
 __global__ __launch_bounds__(256) void pack_x3_kernel(const float *__restrict__ wt, unsigned short *__restrict__ out, int rows, int K) {
@@ -96,11 +86,11 @@ int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   const long tiles128 = split ? (long)d.mtiles * (p.Cout / 64) : p.Cout % 128 == 0 ? (long)d.mtiles * (p.Cout / 128) : 0;
   const int kt_all = d.K / bke;
   const size_t streamk_need = (size_t)kResident * 2 * BM * 128 * sizeof(float);
-  const bool streamk_ok = g_conv_variant == 0 && p.splitk_scratch && streamk_need <= p.splitk_scratch_bytes && res == 0;
+  const bool streamk_ok = g_opt.conv_variant == 0 && p.splitk_scratch && streamk_need <= p.splitk_scratch_bytes && res == 0;
   // (f32s: only for the very long K loops -- block 4's 3x3 layers; 1024- and 2048-deep 1x1 layers of 460 tiles run
   // 52 vs 87 us and 96 vs 157 us without it)
   const bool streamk_all = streamk_ok && tiles128 >= kResident / 2 && tiles128 < kResident && kt_all >= (psplit ? 128 : 32);
-  const bool wide = split || (g_conv_variant != 4 && (tiles128 >= kResident || streamk_all));
+  const bool wide = split || (g_opt.conv_variant != 4 && (tiles128 >= kResident || streamk_all));
   d.ntiles = split ? p.Cout / 64 : p.Cout / (wide ? 128 : 64);
   // Tile order.  Each XCD runs a contiguous range of tiles.  With nt fastest that range covers every
   // weight panel, which is right while a panel (BN x K) is small; block 4's 3x3 conv has 2.4 MB
@@ -109,10 +99,10 @@ int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   // two panels and re-reads the (much smaller) activations instead.
   d.mt_fast = d.ntiles > 1 && (size_t)(wide ? 128 : 64) * d.K * elem_size(p.prec) >= ((size_t)2 << 20);
   // float16 mode: a launch of several rounds of tiles runs in the 256 x 128 / 64-byte-stage geometry (conv_gemm_wide16.hip)
-  if (split && g_conv_variant != 5 && (long)((M + 255) / 256) * (p.Cout / 64) >= g_wide16_min_tiles) return launch_conv_wide16(p, s);
+  if (split && g_opt.conv_variant != 5 && (long)((M + 255) / 256) * (p.Cout / 64) >= g_opt.wide16_min_tiles) return launch_conv_wide16(p, s);
   // ... and so does a plain-float16 layer (no lo piece: locnet.hip's pair policy) whose 128-channel tiles fill the chip
-  if (p.prec == kF16 && !split && g_conv_variant != 5 && p.Cout % 128 == 0 && p.Cin % 64 == 0 &&
-      (long)((M + 255) / 256) * (p.Cout / 128) >= g_wide16_min_tiles)
+  if (p.prec == kF16 && !split && g_opt.conv_variant != 5 && p.Cout % 128 == 0 && p.Cin % 64 == 0 &&
+      (long)((M + 255) / 256) * (p.Cout / 128) >= g_opt.wide16_min_tiles)
     return launch_conv_wide16(p, s);
   d.ksplit = 1;
   d.slabs = static_cast<float *>(p.splitk_scratch);
@@ -123,7 +113,7 @@ int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   // (measured at batch 1, 720p: pays for <= 128 tiles and K rows of >= 4 KiB, i.e. the 3x3 convs of
   // blocks 3-4 and block 4's 1x1 convs; shorter K loops lose more to the reduction than they gain;
   // round 2, up to 16 / 32 slices per tile: a 512x288 frame takes 1.21 / 1.40 ms instead of 1.09, 720p unchanged)
-  if (g_conv_variant != 3 && p.splitk_scratch && (!wide || split) && tiles <= 128 && kt_all >= 32) {
+  if (g_opt.conv_variant != 3 && p.splitk_scratch && (!wide || split) && tiles <= 128 && kt_all >= 32) {
     const int ks = (int)std::min<long>(8, std::min<long>(kResident / tiles, kt_all / 2));
     const size_t need = (size_t)tiles * ks * BM * (split ? 128 : 64) * sizeof(float);
     if (ks > 1 && need <= p.splitk_scratch_bytes && tiles <= kSplitKMaxTiles) d.ksplit = ks;

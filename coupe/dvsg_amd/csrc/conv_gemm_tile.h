@@ -80,10 +80,6 @@
 
 namespace dvsg {
 
-// launch-policy switches (conv_gemm.hip)
-extern int g_conv_variant;
-extern long g_wide16_min_tiles;
-
 struct ConvGemmDev {
   const void *x, *wt, *res;
   const float *bias;
@@ -754,8 +750,8 @@ int launch_ks(ConvGemmDev d, bool wide, int streamk_tail, bool relu, int res, hi
   // round trip, transpose, partial-tile exchange, drain -- 13-25 us where an empty kernel takes 5.)
   // f32s (SPLIT, float): a tile's matrix-core time is a fifth of the exact path's, so the 4 fat waves win at every
   // tile count -- half the fragment reads per MFMA -- (measured per layer, tools/conv_bench.py --precision f32s)
-  const bool four = g_conv_variant == 1 || (SPLIT && sizeof(T) == 4 && g_conv_variant == 0) ||
-                    ((g_conv_variant == 0 || g_conv_variant == 6) && tiles <= 512);
+  const bool four = g_opt.conv_variant == 1 || (SPLIT && sizeof(T) == 4 && g_opt.conv_variant == 0) ||
+                    ((g_opt.conv_variant == 0 || g_opt.conv_variant == 6) && tiles <= 512);
   if (four)
     return wide ? launch_cfg<T, 128, 2, 2, KS, 0, SPLIT>(d, tiles, relu, res, s)
                 : launch_cfg<T, 64, 2, 2, KS, 0, SPLIT>(d, tiles, relu, res, s);

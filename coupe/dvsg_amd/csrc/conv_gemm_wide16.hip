@@ -768,15 +768,6 @@ __global__ void pack_wide16_kernel(const _Float16 *__restrict__ wt, _Float16 *__
 
 }  // namespace
 
-int g_wide16_packed = 1;   // dvsg_debug_set_option("wide16_packed", 0): weight stages fetched from the [rows][K] layout
-void set_wide16_packed(int v) { g_wide16_packed = v; }
-int g_wide16_hreuse = 1;   // dvsg_debug_set_option("wide16_hreuse", 0): 3x3 stride-1 layers through conv_wide16a_kernel
-void set_wide16_hreuse(int v) { g_wide16_hreuse = v; }
-int g_wide16_arows = 1;    // dvsg_debug_set_option("wide16_arows", v): 0 = 64-byte activation rows everywhere (conv_wide16_kernel),
-                           // 2 = 128-byte rows for K = 128 too (tests)
-void set_wide16_arows(int v) { g_wide16_arows = v; }
-int wide16_pack_order() { return g_wide16_arows ? 1 : 0; }
-
 size_t wide16_packed_bytes(int rows, int Cin, int ksize) { return (size_t)rows * ksize * ksize * Cin * sizeof(_Float16); }
 
 // wt: `rows` weight rows of K = ksize^2 Cin float16 (stacked hi / lo rows, or plain ones), rows % 128 == 0, Cin % 64 == 0
@@ -814,8 +805,8 @@ int launch_conv_wide16(const ConvGemm &p, hipStream_t s) {
   d.x = static_cast<const _Float16 *>(p.x); d.wt = static_cast<const _Float16 *>(p.wt);
   d.res = static_cast<const _Float16 *>(p.res); d.bias = p.bias; d.y = static_cast<_Float16 *>(p.y);
   // (K = 128 -- two super-stages -- keeps the 64-byte rows: block 2's conv3 2.48 against 2.55 ms)
-  d.arows = g_wide16_arows && p.wt_packed_a != nullptr && (g_wide16_arows == 2 || p.ksize * p.ksize * p.Cin >= 256);
-  d.wtp = d.arows ? static_cast<const _Float16 *>(p.wt_packed_a) : g_wide16_packed ? static_cast<const _Float16 *>(p.wt_packed) : nullptr;
+  d.arows = g_opt.wide16_arows && p.wt_packed_a != nullptr && (g_opt.wide16_arows == 2 || p.ksize * p.ksize * p.Cin >= 256);
+  d.wtp = d.arows ? static_cast<const _Float16 *>(p.wt_packed_a) : g_opt.wide16_packed ? static_cast<const _Float16 *>(p.wt_packed) : nullptr;
   d.H = p.H; d.W = p.W; d.Cin = p.Cin; d.Ho = p.Ho; d.Wo = p.Wo; d.Cout = p.Cout;
   d.stride = p.stride; d.pad = p.pad;
   d.res_H = p.res_H; d.res_W = p.res_W; d.res_stride = p.res_stride;
@@ -823,7 +814,7 @@ int launch_conv_wide16(const ConvGemm &p, hipStream_t s) {
   d.K = p.ksize * p.ksize * p.Cin;
   d.mtiles = (int)((M + WBM - 1) / WBM);
   d.ntiles = p.wsplit ? p.Cout / 64 : p.Cout / 128;
-  const bool hreuse = g_wide16_hreuse && p.wt_packed_h != nullptr && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.H == p.Ho && p.W == p.Wo;
+  const bool hreuse = g_opt.wide16_hreuse && p.wt_packed_h != nullptr && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.H == p.Ho && p.W == p.Wo;
   if (hreuse) {
     d.wtp = static_cast<const _Float16 *>(p.wt_packed_h);
     d.mtiles = (int)((M + WHM - 1) / WHM);

@@ -79,7 +79,7 @@ struct dvsg_locnet {
   float *dense_b[4] = {nullptr, nullptr, nullptr, nullptr};
   float *v_src = nullptr;  // [25,2] model.py:105-110
   double *winv = nullptr;  // [25][28]: columns of the TPS system's inverse for v_src (see tps_apply_kernel)
-  // float16 mode: which layers multiply by hi / lo weight PAIRS (bit 4 * kind + block, see g_f16_pair_mask).  All of them
+  // float16 mode: which layers multiply by hi / lo weight PAIRS (bit 4 * kind + block, see DebugOptions::f16_pair_mask).  All of them
   // until dvsg_locnet_calibrate_f16 has re-rounded the plain copies of blocks 2-4 with error feedback: then block 1 only.
   int f16_pair_mask = 0xFFFF;
   std::vector<void *> allocs;
@@ -319,26 +319,10 @@ Dims root_dims(int H, int W) {
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-// float16 precision: conv weights as hi / lo float16 pairs (default) or plain float16 (A/B only:
-// dvsg_debug_set_option("f16_split", 0); 9/10 of the plain mode's F_t error is the weights' rounding)
-int g_f16_split = 1;
-// Which layers of the float16 mode carry the lo piece: bit 4 * kind + block (kind 0 = a unit's conv1, 1 = conv2, 2 = conv3,
-// 3 = shortcut; block 0..3).  A plain float16 weight is off by up to 2^-12 relative at every pixel alike, an error the global
-// average pool does not average away; how much of it reaches F_t depends on the layer (tools/f16_pair_sweep.py measures
-// every block x kind).  A layer without the lo piece runs half the MFMAs and, in the big launches, 128 channels per tile.
-// dvsg_debug_set_option("f16_pair_mask", m): A/B.
-int g_f16_pair_mask = 0xFFFF;
 enum LayerKind { kKindC1 = 0, kKindC2 = 1, kKindC3 = 2, kKindSc = 3 };
 inline bool f16_pairs(const dvsg_locnet *net, int block, int kind) {
-  return g_f16_split && ((g_f16_pair_mask & net->f16_pair_mask) >> (4 * kind + block)) & 1;
+  return g_opt.f16_split && ((g_opt.f16_pair_mask & net->f16_pair_mask) >> (4 * kind + block)) & 1;
 }
-// block 1's shortcut conv inside the fused conv2 + conv3 kernel (dvsg_debug_set_option("fuse_shortcut", 0): A/B)
-int g_fuse_shortcut = 1;
-int g_x3_conv1 = 1;  // dvsg_debug_set_option("x3_conv1", 0): the f32x3 precision with the float32 conv1 kernel (A/B)
-int g_x3_fuse = 3;   // dvsg_debug_set_option("x3_fuse", v): A/B of block 1's fusion in the f32x3 precision (forward())
-// blocks 2-4's opening units: shortcut + conv1 as one launch (dvsg_debug_set_option("concat_sc", 0): A/B)
-int g_concat_sc = 1;
-
 struct Workspace {
   char *bufA, *bufB, *bufS, *r1, *r2;  // activations (element type = the run's precision)
   float *pool_part, *dpart0, *dpart1, *T, *Ft;
@@ -424,14 +408,13 @@ int run_conv(int prec, const ConvLayer &L, bool pairs, const void *x, int B, int
 }
 
 // ---- calibration of the float16 mode's PLAIN weights (dvsg_debug_calibrate_f16_weights) --------------------------------
-// While armed, forward() adds up every bottleneck unit's three convolution inputs per channel: slot 3 u + {0: the unit's
+// With a recorder, forward() adds up every bottleneck unit's three convolution inputs per channel: slot 3 u + {0: the unit's
 // input (shortcut, conv1), 1: conv1's output (conv2's input), 2: conv2's output (conv3's input)}.
 struct Calib {
   double *sums = nullptr;    // device [16 * 3][2048]
   float *part = nullptr;     // device [kCalibBlocks][2048]: per-block partial sums of the tensor being recorded
   double rows[48] = {0};     // pixels summed per slot
-  bool on = false;
-} g_calib;
+};
 
 // deterministic: block b adds up rows [b chunk, (b + 1) chunk) per channel into part[b][c]; channel_sum_final adds the
 // blocks' partial sums in block order (double) onto out[c] -- the same bits from run to run, so the weights re-rounded from
@@ -454,21 +437,23 @@ __global__ __launch_bounds__(256) void channel_sum_final(const float *__restrict
   out[c] = acc;
 }
 
-int calib_record(int slot, const void *x, long M, int C, hipStream_t s) {
-  if (!g_calib.on) return DVSG_OK;
+int calib_record(Calib *calib, int slot, const void *x, long M, int C, hipStream_t s) {
+  if (!calib) return DVSG_OK;
   const long chunk = (M + kCalibBlocks - 1) / kCalibBlocks;
   const int nblk = (int)((M + chunk - 1) / chunk);
-  hipLaunchKernelGGL(channel_sum_kernel, dim3(nblk), dim3(256), 0, s, static_cast<const float *>(x), M, C, chunk, g_calib.part);
-  hipLaunchKernelGGL(channel_sum_final, dim3((C + 255) / 256), dim3(256), 0, s, g_calib.part, nblk, C,
-                     g_calib.sums + (size_t)slot * 2048);
-  g_calib.rows[slot] += (double)M;
+  hipLaunchKernelGGL(channel_sum_kernel, dim3(nblk), dim3(256), 0, s, static_cast<const float *>(x), M, C, chunk, calib->part);
+  hipLaunchKernelGGL(channel_sum_final, dim3((C + 255) / 256), dim3(256), 0, s, calib->part, nblk, C,
+                     calib->sums + (size_t)slot * 2048);
+  calib->rows[slot] += (double)M;
   return check_launch("channel_sum_kernel");
 }
 
-// Runs the network in precision `prec`; stop_stage < 0 runs everything and writes F_t [B,50].
+// Runs the network in precision `prec`; stop_stage < 0 runs everything and writes F_t [B,50].  With `calib` (a float32
+// pass) the units' convolution inputs are recorded into it, and block 1 runs unfused: its conv2 output only exists in
+// LDS when fused.
 int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind, int B, int H, int W, float *F_t, int stop_stage,
             float *act_out, size_t act_out_bytes, int *act_dims, void *workspace, size_t workspace_bytes,
-            hipStream_t s) {
+            hipStream_t s, Calib *calib) {
   DVSG_REQUIRE(net && src.base && workspace, "locnet forward: NULL pointer");
   DVSG_REQUIRE(B > 0 && H >= 1 && W >= 1, "locnet forward: bad shape B=%d H=%d W=%d", B, H, W);
   DVSG_REQUIRE(((uintptr_t)workspace & 255) == 0, "locnet forward: workspace must be 256-byte aligned");
@@ -511,11 +496,12 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
   // split-K tickets of every conv launch of this pass (each launch owns its own segment)
   DVSG_RUN(launch_zero_tickets(ws.splitk_counters, (size_t)kMaxConvLaunches * kSplitKMaxTiles, s));
   int launch_idx = 0;
+  const bool fuse_allowed = g_opt.fuse_conv != 0 && calib == nullptr;   // block 1's conv2 + conv3 in one kernel
   reset_root_kernel();
   // root: conv1 (+ fused scale_RGB; f32 multiply, output in `prec`) -> bufA, max pool -> bufB
   {
   MarkerRange mr("dvsg/conv1");
-  DVSG_RUN(launch_conv1(gprec == kF32X && g_x3_conv1 ? kF32X : prec, src, src_kind, net->conv1.wt, net->conv1.wt16, net->conv1.wt32s,
+  DVSG_RUN(launch_conv1(gprec == kF32X && g_opt.x3_conv1 ? kF32X : prec, src, src_kind, net->conv1.wt, net->conv1.wt16, net->conv1.wt32s,
                         net->conv1.wt3x, net->conv1.bias, ws.bufA, B, H, W, d.H1, d.W1, s));
   }
   DVSG_TAP(0, ws.bufA, d.H1, d.W1, 64);
@@ -539,23 +525,23 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
     const void *res = X;
     int res_h = h, res_w = w, res_stride = u.stride;
     const int calib_slot = 3 * (stage - 2);
-    DVSG_RUN(calib_record(calib_slot, X, (long)B * h * w, u.c1.cin, s));
+    DVSG_RUN(calib_record(calib, calib_slot, X, (long)B * h * w, u.c1.cin, s));
     // (float16 mode: the fused kernel multiplies against the stacked hi / lo weights only)
     // (f32x3: block 1's units run conv2 + conv3 in the f32x3 fused kernel, conv_fused_x3.hip, the opening unit's shortcut as
-    // its own f32x3 GEMM -- g_x3_fuse = 3; A/B: 0 never fused, 1 the opening unit only and in the exact float32 kernel with
+    // its own f32x3 GEMM -- x3_fuse = 3; A/B: 0 never fused, 1 the opening unit only and in the exact float32 kernel with
     // its shortcut, 2 all three in the exact float32 kernel)
-    const bool x3_fused = gprec == kF32X && g_x3_fuse == 3;
-    const bool x3_unfused = gprec == kF32X && (g_x3_fuse == 0 || (g_x3_fuse == 1 && !u.has_shortcut));
-    const bool fuse23 = !x3_unfused && conv_fusable(prec, u.c2.cin, u.c2.cout, u.c3.cout, u.c2.ksize) &&
+    const bool x3_fused = gprec == kF32X && g_opt.x3_fuse == 3;
+    const bool x3_unfused = gprec == kF32X && (g_opt.x3_fuse == 0 || (g_opt.x3_fuse == 1 && !u.has_shortcut));
+    const bool fuse23 = fuse_allowed && !x3_unfused && conv_fusable(prec, u.c2.cin, u.c2.cout, u.c3.cout, u.c2.ksize) &&
                         (prec != kF16 || (f16_pairs(net, u.block, kKindC2) && f16_pairs(net, u.block, kKindC3) &&
                                           (!u.has_shortcut || f16_pairs(net, u.block, kKindSc))));
     // block 1's opening unit: its shortcut conv (64 -> 256) runs inside the fused conv2 + conv3 kernel
     const bool fuse_sc = fuse23 && !x3_fused && u.has_shortcut && u.stride == 1 && u.shortcut.cin == 64 && u.shortcut.cout == 256 &&
-                         g_fuse_shortcut;
+                         g_opt.fuse_shortcut;
     // blocks 2-4's opening units, float32 / f32s: shortcut and conv1 as ONE launch over [shortcut | conv1] weight rows; its
     // output [M, depth + base] sits in bufS, the shortcut in columns [0, depth) (conv3's residual, row stride depth + base),
     // conv1's ReLU'd output behind it (conv2's input, same stride).  One launch and one read of the unit's input less.
-    const bool cat = u.has_shortcut && !fuse_sc && u.has_cat && prec != kF16 && g_concat_sc && !g_calib.on && u.stride == 1;
+    const bool cat = u.has_shortcut && !fuse_sc && u.has_cat && prec != kF16 && g_opt.concat_sc && !calib && u.stride == 1;
     const void *c2_in = ws.r1;
     int c2_ldx = 0, res_ld = 0;
     if (cat) {
@@ -596,10 +582,10 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
       }
       DVSG_RUN(launch_conv3x3_1x1(f, s));
     } else {
-      DVSG_RUN(calib_record(calib_slot + 1, ws.r1, (long)B * h * w, u.c2.cin, s));
+      DVSG_RUN(calib_record(calib, calib_slot + 1, ws.r1, (long)B * h * w, u.c2.cin, s));
       DVSG_RUN(run_conv(gprec, u.c2, f16_pairs(net, u.block, kKindC2), c2_in, B, h, w, ws.r2, ho, wo, nullptr, 0, 0, 1, true, ws,
                         &launch_idx, s, c2_ldx));
-      DVSG_RUN(calib_record(calib_slot + 2, ws.r2, (long)B * ho * wo, u.c3.cin, s));
+      DVSG_RUN(calib_record(calib, calib_slot + 2, ws.r2, (long)B * ho * wo, u.c3.cin, s));
       DVSG_RUN(run_conv(gprec, u.c3, f16_pairs(net, u.block, kKindC3), ws.r2, B, ho, wo, Y, ho, wo, res, res_h, res_w, res_stride, true,
                         ws, &launch_idx, s, 0, res_ld));
     }
@@ -639,10 +625,31 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
 
 int forward(const dvsg_locnet *net, int prec, const float *patches, int B, int H, int W, float *F_t, int stop_stage,
             float *act_out, size_t act_out_bytes, int *act_dims, void *workspace, size_t workspace_bytes,
-            hipStream_t s) {
+            hipStream_t s, Calib *calib) {
   const Conv1Src src{patches, nullptr, 0};
   return forward(net, prec, src, kSrcWindow, B, H, W, F_t, stop_stage, act_out, act_out_bytes, act_dims, workspace,
-                 workspace_bytes, s);
+                 workspace_bytes, s, calib);
+}
+
+// What stabilize() and stabilize_ring() share, behind their own NULL and range checks (`fn` names the caller in the
+// messages): F_t = localizationNet(src), T = the TPS of F_t on the constant V_src, then the caller's warp(T).  A source
+// that only a 7-frame window can take (a mask, a ring) passes the message for any other handle in `needs_window`.
+template <typename Warp>
+int stabilize_from(const char *fn, const dvsg_locnet *net, int prec, const char *needs_window, const Conv1Src &src, int src_kind,
+                   int B, int H, int W, float *F_t, void *workspace, size_t workspace_bytes, void *stream, Warp warp) {
+  DVSG_REQUIRE(prec == kF32 || prec == kF16 || prec == kF32S || prec == kF32X, "%s: unknown precision %d", fn, prec);
+  DVSG_REQUIRE(!needs_window || net->c_in == 21, "%s", needs_window);
+  const Workspace ws = plan(static_cast<char *>(workspace), B, H, W);
+  if (ws.total > workspace_bytes)
+    return fail(DVSG_ERR_WORKSPACE, "%s: workspace %zu bytes < required %zu", fn, workspace_bytes, ws.total);
+  float *F = F_t ? F_t : ws.Ft;
+  if (int rc = forward(net, prec, src, src_kind, B, H, W, F, -1, nullptr, 0, nullptr, workspace, workspace_bytes,
+                       as_stream(stream), nullptr))
+    return rc;
+  // model.py:120: stn(u_t, V_src, F_t, [h, w]) with V_src tiled over the batch (:111); float32
+  MarkerRange mr("dvsg/tps");
+  if (int rc = tps_apply_impl(net->winv, net->v_src, F, 1, B, 25, ws.T, stream)) return rc;
+  return warp(ws.T);
 }
 
 int stabilize(const dvsg_locnet *net, int prec, const float *patches_t, const float *u_t, const float *mask, int B, int H,
@@ -650,21 +657,13 @@ int stabilize(const dvsg_locnet *net, int prec, const float *patches_t, const fl
               void *stream) {
   DVSG_REQUIRE(net && patches_t && u_t && s_t_pred && workspace, "dvsg_stabilize: NULL pointer");
   DVSG_REQUIRE(B > 0 && B <= 65535, "dvsg_stabilize: B=%d out of range", B);
-  DVSG_REQUIRE(prec == kF32 || prec == kF16 || prec == kF32S || prec == kF32X, "dvsg_stabilize: unknown precision %d", prec);
-  DVSG_REQUIRE(!mask || net->c_in == 21, "dvsg_stabilize_masked: the mask covers the 18 history channels of a 7-frame window");
-  const Workspace ws = plan(static_cast<char *>(workspace), B, H, W);
-  if (ws.total > workspace_bytes)
-    return fail(DVSG_ERR_WORKSPACE, "dvsg_stabilize: workspace %zu bytes < required %zu", workspace_bytes, ws.total);
-  float *F = F_t ? F_t : ws.Ft;
   Conv1Src src{patches_t, nullptr, 0};
   src.mask = mask;   // eval_train.py:43-45: the CNN sees patches * mask, the warp below the unmasked u_t
-  if (int rc = forward(net, prec, src, kSrcWindow, B, H, W, F, -1, nullptr, 0, nullptr, workspace, workspace_bytes,
-                       as_stream(stream)))
-    return rc;
-  // model.py:120: stn(u_t, V_src, F_t, [h, w]) with V_src tiled over the batch (:111); float32
-  MarkerRange mr("dvsg/tps");
-  if (int rc = tps_apply_impl(net->winv, net->v_src, F, 1, B, 25, ws.T, stream)) return rc;
-  return tps_warp_impl(u_t, net->v_src, 0, ws.T, B, H, W, 3, 25, H, W, s_t_pred, x_s, y_s, stream);
+  return stabilize_from("dvsg_stabilize", net, prec,
+                        mask ? "dvsg_stabilize_masked: the mask covers the 18 history channels of a 7-frame window" : nullptr, src,
+                        kSrcWindow, B, H, W, F_t, workspace, workspace_bytes, stream, [&](const float *T) {
+                          return tps_warp_impl(u_t, net->v_src, 0, T, B, H, W, 3, 25, H, W, s_t_pred, x_s, y_s, stream);
+                        });
 }
 
 // The evaluation graph fed from a frame ring: window b = pool frames table[b][0..6], u_t = its newest
@@ -676,21 +675,14 @@ int stabilize_ring(const dvsg_locnet *net, int prec, const void *pool, int pool_
                    size_t workspace_bytes, void *stream, const int32_t *out_slots = nullptr) {
   DVSG_REQUIRE(net && pool && table && s_t_pred && workspace, "dvsg_stabilize_ring: NULL pointer");
   DVSG_REQUIRE(B > 0 && B <= 65535 && n_pool > 0, "dvsg_stabilize_ring: B=%d n_pool=%d out of range", B, n_pool);
-  DVSG_REQUIRE(prec == kF32 || prec == kF16 || prec == kF32S || prec == kF32X, "dvsg_stabilize_ring: unknown precision %d", prec);
-  DVSG_REQUIRE(net->c_in == 21, "dvsg_stabilize_ring: the ring holds RGB frames, 7 per window");
-  const Workspace ws = plan(static_cast<char *>(workspace), B, H, W);
-  if (ws.total > workspace_bytes)
-    return fail(DVSG_ERR_WORKSPACE, "dvsg_stabilize_ring: workspace %zu bytes < required %zu", workspace_bytes, ws.total);
-  float *F = F_t ? F_t : ws.Ft;
   Conv1Src src{pool, table, n_pool};
   src.mask = mask;
-  if (int rc = forward(net, prec, src, pool_is_u8 ? kSrcRingU8 : kSrcRingF32, B, H, W, F, -1, nullptr, 0, nullptr, workspace,
-                       workspace_bytes, as_stream(stream)))
-    return rc;
-  MarkerRange mr("dvsg/tps");
-  if (int rc = tps_apply_impl(net->winv, net->v_src, F, 1, B, 25, ws.T, stream)) return rc;
-  return tps_warp_ring_impl(pool, pool_is_u8, n_pool, table + 6, 7, net->v_src, 0, ws.T, B, H, W, 25, s_t_pred, x_s, y_s,
-                            stream, out_slots);
+  return stabilize_from("dvsg_stabilize_ring", net, prec, "dvsg_stabilize_ring: the ring holds RGB frames, 7 per window", src,
+                        pool_is_u8 ? kSrcRingU8 : kSrcRingF32, B, H, W, F_t, workspace, workspace_bytes, stream,
+                        [&](const float *T) {
+                          return tps_warp_ring_impl(pool, pool_is_u8, n_pool, table + 6, 7, net->v_src, 0, T, B, H, W, 25,
+                                                    s_t_pred, x_s, y_s, stream, out_slots);
+                        });
 }
 
 int conv_gemm_op(int prec, int wsplit, const void *x, const void *wt, const float *bias, const void *res, void *y, int B,
@@ -742,6 +734,79 @@ int conv_gemm_op(int prec, int wsplit, const void *x, const void *wt, const floa
   }
   return launch_conv_gemm(p, as_stream(stream));
 }
+
+// dvsg_locnet_forward_<prec> / dvsg_locnet_forward_tap_<prec> (`fn` names the entry point in the messages)
+int forward_entry(const char *fn, int prec, const dvsg_locnet *net, const float *patches, int B, int H, int W, float *F_t,
+                  void *workspace, size_t workspace_bytes, void *stream) {
+  DVSG_REQUIRE(F_t, "%s: NULL F_t", fn);
+  return forward(net, prec, patches, B, H, W, F_t, -1, nullptr, 0, nullptr, workspace, workspace_bytes, as_stream(stream),
+                 nullptr);
+}
+
+int forward_tap_entry(const char *fn, int prec, const dvsg_locnet *net, const float *patches, int B, int H, int W, int stage,
+                      float *act_out, size_t act_out_bytes, int *act_dims_host, void *workspace, size_t workspace_bytes,
+                      void *stream) {
+  DVSG_REQUIRE(act_out && act_dims_host, "%s: NULL pointer", fn);
+  DVSG_REQUIRE(stage >= 0 && stage <= 18, "%s: stage %d outside [0,18]", fn, stage);
+  return forward(net, prec, patches, B, H, W, nullptr, stage, act_out, act_out_bytes, act_dims_host, workspace,
+                 workspace_bytes, as_stream(stream), nullptr);
+}
+
+// The ConvFused of dvsg_conv3x3_1x1_f32, dvsg_conv3x3_1x1_f32x3 and dvsg_debug_conv3x3_1x1, as forward() fills it for block
+// 1's units (`fn` names the entry point in the messages).  The residual is the tensor `res`, or, with sc_x, the 1x1
+// shortcut conv of sc_x computed in the kernel.
+int fused_op(const char *fn, int prec, const void *x, const void *wt2, const float *bias2, const void *wt3, const float *bias3,
+             const void *res, const void *sc_x, const void *sc_wt, const float *sc_bias, int sc_cin, void *y, int B, int H,
+             int W, int Cin, int Cout, int stride, int res_stride, void *stream) {
+  DVSG_REQUIRE(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && res_stride >= 1,
+               "%s: bad shape B=%d H=%d W=%d stride=%d res_stride=%d", fn, B, H, W, stride, res_stride);
+  ConvFused f;
+  f.pieces = prec == kF32S;
+  f.f16 = prec == kF16;
+  f.x3 = prec == kF32X;
+  f.x = static_cast<const float *>(x); f.wt2 = static_cast<const float *>(wt2); f.bias2 = bias2;
+  f.wt3 = static_cast<const float *>(wt3); f.bias3 = bias3;
+  f.res = static_cast<const float *>(res); f.y = static_cast<float *>(y);
+  f.B = B; f.H = H; f.W = W; f.Cin = Cin; f.Cout = Cout;
+  f.Ho = (H - 1) / stride + 1; f.Wo = (W - 1) / stride + 1;
+  f.stride = stride;
+  f.res_H = (f.Ho - 1) * res_stride + 1; f.res_W = (f.Wo - 1) * res_stride + 1; f.res_stride = res_stride;
+  if (sc_x) {
+    f.res = nullptr;
+    f.sc_x = static_cast<const float *>(sc_x); f.sc_wt = static_cast<const float *>(sc_wt); f.sc_bias = sc_bias;
+    f.sc_cin = sc_cin;
+  }
+  return launch_conv3x3_1x1(f, as_stream(stream));
+}
+
+// dvsg_debug_set_option: every switch's name, its member of g_opt, and what a value is normalised to before it is stored
+int opt_any(int v) { return v; }
+int opt_flag(int v) { return v != 0; }
+int opt_positive(int v) { return v > 0 ? v : 1; }
+int opt_mask16(int v) { return v & 0xFFFF; }
+constexpr struct {
+  const char *name;
+  int DebugOptions::*member;
+  int (*normalise)(int);
+} kDebugOptions[] = {
+    {"conv_variant", &DebugOptions::conv_variant, opt_any},
+    {"conv1_variant", &DebugOptions::conv1_variant, opt_any},
+    {"wide16_min_tiles", &DebugOptions::wide16_min_tiles, opt_any},
+    {"wide16_packed", &DebugOptions::wide16_packed, opt_any},
+    {"wide16_arows", &DebugOptions::wide16_arows, opt_any},
+    {"wide16_hreuse", &DebugOptions::wide16_hreuse, opt_any},
+    {"fused_hreuse", &DebugOptions::fused_hreuse, opt_any},
+    {"fuse_conv", &DebugOptions::fuse_conv, opt_any},
+    {"fuse_shortcut", &DebugOptions::fuse_shortcut, opt_flag},
+    {"concat_sc", &DebugOptions::concat_sc, opt_flag},
+    {"x3_conv1", &DebugOptions::x3_conv1, opt_any},
+    {"x3_fuse", &DebugOptions::x3_fuse, opt_any},
+    {"f16_split", &DebugOptions::f16_split, opt_flag},
+    {"f16_pair_mask", &DebugOptions::f16_pair_mask, opt_mask16},
+    {"flow_tiled", &DebugOptions::flow_tiled, opt_any},
+    {"flow_rounds", &DebugOptions::flow_rounds, opt_positive},
+    {"warp_xcd", &DebugOptions::warp_xcd, opt_flag},
+};
 
 }  // namespace
 }  // namespace dvsg
@@ -879,66 +944,50 @@ int dvsg_locnet_workspace_bytes(const dvsg_locnet_t *net, int B, int H, int W, s
 
 int dvsg_locnet_forward_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, float *F_t,
                             void *workspace, size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(F_t, "dvsg_locnet_forward_f32: NULL F_t");
-  return forward(net, kF32, patches, B, H, W, F_t, -1, nullptr, 0, nullptr, workspace, workspace_bytes,
-                 as_stream(stream));
+  return forward_entry("dvsg_locnet_forward_f32", kF32, net, patches, B, H, W, F_t, workspace, workspace_bytes, stream);
 }
 
 int dvsg_locnet_forward_f16(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, float *F_t,
                             void *workspace, size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(F_t, "dvsg_locnet_forward_f16: NULL F_t");
-  return forward(net, kF16, patches, B, H, W, F_t, -1, nullptr, 0, nullptr, workspace, workspace_bytes,
-                 as_stream(stream));
+  return forward_entry("dvsg_locnet_forward_f16", kF16, net, patches, B, H, W, F_t, workspace, workspace_bytes, stream);
 }
 
 int dvsg_locnet_forward_f32s(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, float *F_t,
                              void *workspace, size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(F_t, "dvsg_locnet_forward_f32s: NULL F_t");
-  return forward(net, kF32S, patches, B, H, W, F_t, -1, nullptr, 0, nullptr, workspace, workspace_bytes,
-                 as_stream(stream));
+  return forward_entry("dvsg_locnet_forward_f32s", kF32S, net, patches, B, H, W, F_t, workspace, workspace_bytes, stream);
 }
 
 int dvsg_locnet_forward_f32x3(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, float *F_t,
                               void *workspace, size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(F_t, "dvsg_locnet_forward_f32x3: NULL F_t");
-  return forward(net, kF32X, patches, B, H, W, F_t, -1, nullptr, 0, nullptr, workspace, workspace_bytes,
-                 as_stream(stream));
-}
-
-int dvsg_locnet_forward_tap_f32x3(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, int stage,
-                                  float *act_out, size_t act_out_bytes, int *act_dims_host, void *workspace,
-                                  size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(act_out && act_dims_host, "dvsg_locnet_forward_tap_f32x3: NULL pointer");
-  DVSG_REQUIRE(stage >= 0 && stage <= 18, "dvsg_locnet_forward_tap_f32x3: stage %d outside [0,18]", stage);
-  return forward(net, kF32X, patches, B, H, W, nullptr, stage, act_out, act_out_bytes, act_dims_host, workspace,
-                 workspace_bytes, as_stream(stream));
-}
-
-int dvsg_locnet_forward_tap_f32s(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, int stage,
-                                 float *act_out, size_t act_out_bytes, int *act_dims_host, void *workspace,
-                                 size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(act_out && act_dims_host, "dvsg_locnet_forward_tap_f32s: NULL pointer");
-  DVSG_REQUIRE(stage >= 0 && stage <= 18, "dvsg_locnet_forward_tap_f32s: stage %d outside [0,18]", stage);
-  return forward(net, kF32S, patches, B, H, W, nullptr, stage, act_out, act_out_bytes, act_dims_host, workspace,
-                 workspace_bytes, as_stream(stream));
+  return forward_entry("dvsg_locnet_forward_f32x3", kF32X, net, patches, B, H, W, F_t, workspace, workspace_bytes, stream);
 }
 
 int dvsg_locnet_forward_tap_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, int stage,
                                 float *act_out, size_t act_out_bytes, int *act_dims_host, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(act_out && act_dims_host, "dvsg_locnet_forward_tap_f32: NULL pointer");
-  DVSG_REQUIRE(stage >= 0 && stage <= 18, "dvsg_locnet_forward_tap_f32: stage %d outside [0,18]", stage);
-  return forward(net, kF32, patches, B, H, W, nullptr, stage, act_out, act_out_bytes, act_dims_host, workspace,
-                 workspace_bytes, as_stream(stream));
+  return forward_tap_entry("dvsg_locnet_forward_tap_f32", kF32, net, patches, B, H, W, stage, act_out, act_out_bytes,
+                           act_dims_host, workspace, workspace_bytes, stream);
 }
 
 int dvsg_locnet_forward_tap_f16(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, int stage,
                                 float *act_out, size_t act_out_bytes, int *act_dims_host, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-  DVSG_REQUIRE(act_out && act_dims_host, "dvsg_locnet_forward_tap_f16: NULL pointer");
-  DVSG_REQUIRE(stage >= 0 && stage <= 18, "dvsg_locnet_forward_tap_f16: stage %d outside [0,18]", stage);
-  return forward(net, kF16, patches, B, H, W, nullptr, stage, act_out, act_out_bytes, act_dims_host, workspace,
-                 workspace_bytes, as_stream(stream));
+  return forward_tap_entry("dvsg_locnet_forward_tap_f16", kF16, net, patches, B, H, W, stage, act_out, act_out_bytes,
+                           act_dims_host, workspace, workspace_bytes, stream);
+}
+
+int dvsg_locnet_forward_tap_f32s(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, int stage,
+                                 float *act_out, size_t act_out_bytes, int *act_dims_host, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+  return forward_tap_entry("dvsg_locnet_forward_tap_f32s", kF32S, net, patches, B, H, W, stage, act_out, act_out_bytes,
+                           act_dims_host, workspace, workspace_bytes, stream);
+}
+
+int dvsg_locnet_forward_tap_f32x3(const dvsg_locnet_t *net, const float *patches, int B, int H, int W, int stage,
+                                  float *act_out, size_t act_out_bytes, int *act_dims_host, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  return forward_tap_entry("dvsg_locnet_forward_tap_f32x3", kF32X, net, patches, B, H, W, stage, act_out, act_out_bytes,
+                           act_dims_host, workspace, workspace_bytes, stream);
 }
 
 int dvsg_conv_gemm_f32(const float *x, const float *wt, const float *bias, const float *res, float *y, int B, int H,
@@ -994,32 +1043,16 @@ int dvsg_conv3x3_1x1_f32(const float *x, const float *wt2, const float *bias2, c
                          const float *res, float *y, int B, int H, int W, int Cin, int Cout, int stride, int res_stride,
                          void *stream) {
   DVSG_REQUIRE(x && wt2 && bias2 && wt3 && bias3 && res && y, "dvsg_conv3x3_1x1_f32: NULL pointer");
-  DVSG_REQUIRE(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && res_stride >= 1,
-               "dvsg_conv3x3_1x1_f32: bad shape B=%d H=%d W=%d stride=%d res_stride=%d", B, H, W, stride, res_stride);
-  ConvFused f;
-  f.x = x; f.wt2 = wt2; f.bias2 = bias2; f.wt3 = wt3; f.bias3 = bias3; f.res = res; f.y = y;
-  f.B = B; f.H = H; f.W = W; f.Cin = Cin; f.Cout = Cout;
-  f.Ho = (H - 1) / stride + 1; f.Wo = (W - 1) / stride + 1;
-  f.stride = stride;
-  f.res_H = (f.Ho - 1) * res_stride + 1; f.res_W = (f.Wo - 1) * res_stride + 1; f.res_stride = res_stride;
-  return launch_conv3x3_1x1(f, as_stream(stream));
+  return fused_op("dvsg_conv3x3_1x1_f32", kF32, x, wt2, bias2, wt3, bias3, res, nullptr, nullptr, nullptr, 0, y, B, H, W, Cin,
+                  Cout, stride, res_stride, stream);
 }
 
 int dvsg_conv3x3_1x1_f32x3(const float *x, const void *wt2_packed, const float *bias2, const void *wt3_packed, const float *bias3,
                            const float *res, float *y, int B, int H, int W, int Cin, int Cout, int stride, int res_stride,
                            void *stream) {
   DVSG_REQUIRE(x && wt2_packed && bias2 && wt3_packed && bias3 && res && y, "dvsg_conv3x3_1x1_f32x3: NULL pointer");
-  DVSG_REQUIRE(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && res_stride >= 1,
-               "dvsg_conv3x3_1x1_f32x3: bad shape B=%d H=%d W=%d stride=%d res_stride=%d", B, H, W, stride, res_stride);
-  ConvFused f;
-  f.x = x; f.wt2 = static_cast<const float *>(wt2_packed); f.bias2 = bias2; f.wt3 = static_cast<const float *>(wt3_packed);
-  f.bias3 = bias3; f.res = res; f.y = y;
-  f.B = B; f.H = H; f.W = W; f.Cin = Cin; f.Cout = Cout;
-  f.Ho = (H - 1) / stride + 1; f.Wo = (W - 1) / stride + 1;
-  f.stride = stride;
-  f.res_H = (f.Ho - 1) * res_stride + 1; f.res_W = (f.Wo - 1) * res_stride + 1; f.res_stride = res_stride;
-  f.x3 = 1;
-  return launch_conv3x3_1x1(f, as_stream(stream));
+  return fused_op("dvsg_conv3x3_1x1_f32x3", kF32X, x, wt2_packed, bias2, wt3_packed, bias3, res, nullptr, nullptr, nullptr, 0,
+                  y, B, H, W, Cin, Cout, stride, res_stride, stream);
 }
 
 int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float *bias2, const void *wt3, const float *bias3,
@@ -1027,26 +1060,8 @@ int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float
                            int H, int W, int Cin, int Cout, int stride, int res_stride, void *stream) {
   DVSG_REQUIRE(prec >= kF32 && prec <= kF32X, "dvsg_debug_conv3x3_1x1: unknown precision %d", prec);
   DVSG_REQUIRE(x && wt2 && bias2 && wt3 && bias3 && y, "dvsg_debug_conv3x3_1x1: NULL pointer");
-  DVSG_REQUIRE(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && res_stride >= 1,
-               "dvsg_debug_conv3x3_1x1: bad shape B=%d H=%d W=%d stride=%d res_stride=%d", B, H, W, stride, res_stride);
-  // as forward() fills it for block 1's units
-  ConvFused f;
-  f.pieces = prec == kF32S;
-  f.f16 = prec == kF16;
-  f.x3 = prec == kF32X;
-  f.x = static_cast<const float *>(x); f.wt2 = static_cast<const float *>(wt2); f.bias2 = bias2;
-  f.wt3 = static_cast<const float *>(wt3); f.bias3 = bias3;
-  f.res = static_cast<const float *>(res); f.y = static_cast<float *>(y);
-  f.B = B; f.H = H; f.W = W; f.Cin = Cin; f.Cout = Cout;
-  f.Ho = (H - 1) / stride + 1; f.Wo = (W - 1) / stride + 1;
-  f.stride = stride;
-  f.res_H = (f.Ho - 1) * res_stride + 1; f.res_W = (f.Wo - 1) * res_stride + 1; f.res_stride = res_stride;
-  if (sc_x) {
-    f.res = nullptr;
-    f.sc_x = static_cast<const float *>(sc_x); f.sc_wt = static_cast<const float *>(sc_wt); f.sc_bias = sc_bias;
-    f.sc_cin = sc_cin;
-  }
-  return launch_conv3x3_1x1(f, as_stream(stream));
+  return fused_op("dvsg_debug_conv3x3_1x1", prec, x, wt2, bias2, wt3, bias3, res, sc_x, sc_wt, sc_bias, sc_cin, y, B, H, W,
+                  Cin, Cout, stride, res_stride, stream);
 }
 
 int dvsg_debug_last_conv_kernel(int *fields, int n) {
@@ -1069,74 +1084,11 @@ int dvsg_debug_last_conv_config(int *fields, int n) {
 
 int dvsg_debug_set_option(const char *name, int value) {
   DVSG_REQUIRE(name, "dvsg_debug_set_option: NULL name");
-  if (std::strcmp(name, "conv_variant") == 0) {
-    set_conv_variant(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "wide16_min_tiles") == 0) {
-    set_wide16_min_tiles(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "fused_hreuse") == 0) {
-    set_fused_hreuse(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "wide16_hreuse") == 0) {
-    set_wide16_hreuse(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "wide16_arows") == 0) {
-    set_wide16_arows(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "wide16_packed") == 0) {
-    set_wide16_packed(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "flow_tiled") == 0) {
-    set_flow_tiled(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "flow_rounds") == 0) {
-    set_flow_rounds(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "warp_xcd") == 0) {
-    set_warp_xcd(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "conv1_variant") == 0) {
-    set_conv1_variant(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "fuse_conv") == 0) {
-    set_fuse_conv(value);
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "concat_sc") == 0) {
-    g_concat_sc = value != 0;
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "x3_conv1") == 0) {
-    g_x3_conv1 = value;
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "x3_fuse") == 0) {
-    g_x3_fuse = value;
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "fuse_shortcut") == 0) {
-    g_fuse_shortcut = value != 0;
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "f16_split") == 0) {
-    g_f16_split = value != 0;
-    return DVSG_OK;
-  }
-  if (std::strcmp(name, "f16_pair_mask") == 0) {
-    g_f16_pair_mask = value & 0xFFFF;
-    return DVSG_OK;
-  }
+  for (const auto &o : kDebugOptions)
+    if (std::strcmp(name, o.name) == 0) {
+      g_opt.*o.member = o.normalise(value);
+      return DVSG_OK;
+    }
   return fail(DVSG_ERR_INVALID_ARG, "dvsg_debug_set_option: unknown option %s", name);
 }
 
@@ -1154,6 +1106,7 @@ static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, i
                          size_t workspace_bytes, hipStream_t s) {
   std::vector<double> mu((size_t)48 * 2048, 1.0);
   if (mode == 2) {   // calibrated channel means
+    Calib calib;   // the recorder of this pass alone: forward() of other handles and threads never see it
     void *sums = nullptr, *part = nullptr, *F = nullptr;
     hipError_t e = hipMalloc(&sums, 48 * 2048 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&part, (size_t)kCalibBlocks * 2048 * sizeof(float));
@@ -1161,15 +1114,10 @@ static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, i
     if (e == hipSuccess) e = hipMemsetAsync(sums, 0, 48 * 2048 * sizeof(double), s);
     int rc = e == hipSuccess ? DVSG_OK : fail(DVSG_ERR_HIP, "calibration: %s", hipGetErrorString(e));
     if (rc == DVSG_OK) {
-      g_calib.sums = static_cast<double *>(sums);
-      g_calib.part = static_cast<float *>(part);
-      for (double &r : g_calib.rows) r = 0;
-      const int fuse_was = get_fuse_conv();
-      set_fuse_conv(0);       // block 1's conv2 output only exists in LDS when fused
-      g_calib.on = true;
-      rc = forward(net, kF32, patches, B, H, W, static_cast<float *>(F), -1, nullptr, 0, nullptr, workspace, workspace_bytes, s);
-      g_calib.on = false;
-      set_fuse_conv(fuse_was);
+      calib.sums = static_cast<double *>(sums);
+      calib.part = static_cast<float *>(part);
+      rc = forward(net, kF32, patches, B, H, W, static_cast<float *>(F), -1, nullptr, 0, nullptr, workspace, workspace_bytes, s,
+                   &calib);   // (with a recorder block 1 runs unfused)
       if (rc == DVSG_OK && hipMemcpyAsync(mu.data(), sums, mu.size() * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
         rc = fail(DVSG_ERR_HIP, "copy of the calibration sums failed");
       if (rc == DVSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(DVSG_ERR_HIP, "calibration pass failed");
@@ -1179,7 +1127,7 @@ static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, i
     (void)hipFree(F);
     if (rc) return rc;
     for (int slot = 0; slot < 48; ++slot)
-      for (int c = 0; c < 2048; ++c) mu[(size_t)slot * 2048 + c] = g_calib.rows[slot] > 0 ? mu[(size_t)slot * 2048 + c] / g_calib.rows[slot] : 1.0;
+      for (int c = 0; c < 2048; ++c) mu[(size_t)slot * 2048 + c] = calib.rows[slot] > 0 ? mu[(size_t)slot * 2048 + c] / calib.rows[slot] : 1.0;
   }
   auto f16_bits = [](_Float16 v) { unsigned short b; std::memcpy(&b, &v, 2); return b; };
   auto f16_from = [](unsigned short b) { _Float16 v; std::memcpy(&v, &b, 2); return v; };
@@ -1378,7 +1326,7 @@ int dvsg_locnet_forward_masked(const dvsg_locnet_t *net, int precision, const vo
   Conv1Src src{src_ptr, src_kind ? table : nullptr, src_kind ? n_pool : 0};
   src.mask = mask;
   return forward(net, prec, src, src_kind, B, H, W, stage < 0 ? out : nullptr, stage, stage < 0 ? nullptr : out, out_bytes,
-                 act_dims_host, workspace, workspace_bytes, as_stream(stream));
+                 act_dims_host, workspace, workspace_bytes, as_stream(stream), nullptr);
 }
 
 int dvsg_locnet_forward_ring(const dvsg_locnet_t *net, int precision, const void *pool, int pool_is_u8, int n_pool,
@@ -1391,7 +1339,7 @@ int dvsg_locnet_forward_ring(const dvsg_locnet_t *net, int precision, const void
   DVSG_REQUIRE(prec >= 0, "dvsg_locnet_forward_ring: unknown precision %d", precision);
   const Conv1Src src{pool, table, n_pool};
   return forward(net, prec, src, pool_is_u8 ? kSrcRingU8 : kSrcRingF32, B, H, W, stage < 0 ? out : nullptr, stage,
-                 stage < 0 ? nullptr : out, out_bytes, act_dims_host, workspace, workspace_bytes, as_stream(stream));
+                 stage < 0 ? nullptr : out, out_bytes, act_dims_host, workspace, workspace_bytes, as_stream(stream), nullptr);
 }
 
 }  // extern "C"

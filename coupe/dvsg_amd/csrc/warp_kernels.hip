@@ -617,17 +617,12 @@ __global__ __launch_bounds__(kThreads) void scale_rgb_kernel(const float *__rest
   }
 }
 
-int g_flow_tiled = 1;  // dvsg_debug_set_option("flow_tiled", v): 0 = stn_kernel<kFlow> (global gathers), 1 = column strips streamed
-                       // through LDS, workgroups in XCD-aware order (default), 2 = the same in plain dispatch order
-int g_flow_rounds = 4; // rounds of resident workgroups the strip kernel's bands aim at ("flow_rounds")
-int g_warp_xcd = 0;   // dvsg_debug_set_option("warp_xcd", 0): the samplers' workgroups in plain dispatch order (A/B)
-
 template <int SRC>
 int launch_stn(StnParams p, int B, hipStream_t s, const char *what) {
   constexpr int PPT = (SRC == kFlow || SRC == kCoords) ? 4 : 2;  // memory-fed coordinates: more loads in flight per thread
   p.nbx = ceil_div(p.out_w, kThreads);
   p.nby = ceil_div(p.out_h, PPT);
-  p.xcd = g_warp_xcd;
+  p.xcd = g_opt.warp_xcd;
   DVSG_REQUIRE((long)p.nbx * p.nby * B < (1L << 31), "%s: grid of %ld workgroups out of range", what, (long)p.nbx * p.nby * B);
   dim3 grid((unsigned)(p.nbx * p.nby * B));
   // algorithmic bytes per output pixel: read C + write C floats (+ flow 8 B / coords 8 B)
@@ -654,10 +649,6 @@ int check_image_args(const char *fn, int B, int H, int W, int C, int out_h, int 
 }
 
 }  // namespace
-
-void set_warp_xcd(int v) { g_warp_xcd = v != 0; }
-void set_flow_tiled(int v) { g_flow_tiled = v; }
-void set_flow_rounds(int v) { g_flow_rounds = v > 0 ? v : 1; }
 
 // coord_bstride = 0 broadcasts one set of control points over the batch (model.py:111 tiles
 // the constant V_src; the fused evaluation graph does not materialise the tile).
@@ -839,7 +830,7 @@ int dvsg_flow_warp_f32(const float *im, const float *flow, int B, int H, int W, 
                        void *stream) {
   DVSG_REQUIRE(im && flow && out, "dvsg_flow_warp_f32: NULL pointer");
   if (int rc = check_image_args("dvsg_flow_warp_f32", B, H, W, C, H, W)) return rc;
-  if (C == 3 && g_flow_tiled && reinterpret_cast<uintptr_t>(im) % 16 == 0) {
+  if (C == 3 && g_opt.flow_tiled && reinterpret_cast<uintptr_t>(im) % 16 == 0) {
     // RGB frames: the source rows of a column strip streamed through LDS (flow_warp_strip_kernel); same bits as stn_kernel<kFlow>
     FlowStripParams q{};
     q.im = im; q.flow = flow; q.out = out;
@@ -847,11 +838,11 @@ int dvsg_flow_warp_f32(const float *im, const float *flow, int B, int H, int W, 
     q.nstrips = ceil_div(W, kFsW);
     // bands: enough workgroups for >= 4 rounds of the 256 resident ones, bands of >= 128 rows (a band primes 41 rows)
     const int steps = ceil_div(H, kFsStep);
-    int bands = (int)std::min<long>(std::max<long>(1, ((long)g_flow_rounds * 256 + (long)q.nstrips * B - 1) / ((long)q.nstrips * B)), std::max(1, steps / 8));
+    int bands = (int)std::min<long>(std::max<long>(1, ((long)g_opt.flow_rounds * 256 + (long)q.nstrips * B - 1) / ((long)q.nstrips * B)), std::max(1, steps / 8));
     const int band_steps = ceil_div(steps, bands);
     q.band_rows = band_steps * kFsStep;
     q.nbands = ceil_div(H, q.band_rows);
-    q.xcd = g_flow_tiled != 2;
+    q.xcd = g_opt.flow_tiled != 2;
     const long wgs = (long)q.nstrips * q.nbands * B;
     DVSG_REQUIRE(wgs < (1L << 31), "dvsg_flow_warp_f32: grid of %ld workgroups out of range", wgs);
     hipStream_t s = as_stream(stream);

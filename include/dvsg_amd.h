@@ -486,11 +486,17 @@ int dvsg_conv3x3_1x1_f32(const float *x, const float *wt2, const float *bias2, c
                          const float *res, float *y, int B, int H, int W, int Cin, int Cout, int stride, int res_stride,
                          void *stream);
 
-/* Diagnostic A/B switches for kernel experiments, process-global: "conv_variant", "conv1_variant", "fuse_conv",
- * "fuse_shortcut", "f16_split", "f16_pair_mask", and for the float16 mode's big launches "wide16_min_tiles" (tiles from
- * which the 256 x 128 geometry runs: 128), "wide16_packed" / "wide16_arows" / "wide16_hreuse" / "fused_hreuse" (1: weight
- * stages from the packed copy, 128-byte activation rows, a 3x3 kernel row's taps from one staged run, the same in block 1's
- * fused kernel; 0 selects the kernel each replaced), "warp_xcd" (0: the sampler kernels' workgroups in plain dispatch order).
+/* Diagnostic A/B switches for kernel experiments, process-global; an unknown name is DVSG_ERR_INVALID_ARG.  The 17
+ * names and their defaults: "conv_variant" 0, "conv1_variant" 0 (0 = the launch policy's own choice of kernel), "fuse_conv" 1,
+ * "fuse_shortcut" 1, "concat_sc" 1 (block 1's conv2 + conv3 in one kernel, its shortcut conv in that kernel too, the
+ * shortcut + conv1 of blocks 2-4's opening units as one launch; 0 selects the separate launches), "x3_conv1" 1, "x3_fuse" 3
+ * (the f32x3 precision's own conv1 kernel and block-1 fusion; 0 the float32 kernel / never fused), "f16_split" 1,
+ * "f16_pair_mask" 0xFFFF (float16 mode: hi / lo weight pairs, and the layers that carry them), for the float16 mode's big
+ * launches "wide16_min_tiles" (tiles from which the 256 x 128 geometry runs: 128), "wide16_packed" / "wide16_arows" /
+ * "wide16_hreuse" / "fused_hreuse" (1: weight stages from the packed copy, 128-byte activation rows, a 3x3 kernel row's taps
+ * from one staged run, the same in block 1's fused kernel; 0 selects the kernel each replaced), "flow_tiled" 1, "flow_rounds"
+ * 4 (dvsg_flow_warp_f32 on RGB frames: column strips streamed through LDS, 0 = global gathers; rounds of resident workgroups
+ * its bands aim at), "warp_xcd" 0 (0: the sampler kernels' workgroups in plain dispatch order).
  * Results do not depend on them beyond float32 re-association. */
 int dvsg_debug_set_option(const char *name, int value);
 /* What the last dvsg_conv_gemm_* call (or conv launch of a network call) ran, recorded on the host when it was launched; no

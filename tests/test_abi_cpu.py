@@ -59,6 +59,27 @@ def test_bad_arguments_return_status_not_abort(lib):
         _lib.call("dvsg_locnet_workspace_bytes", None, 1, 8, 8, None)
 
 
+DEBUG_OPTION_DEFAULTS = {
+    "conv_variant": 0, "conv1_variant": 0, "wide16_min_tiles": 128, "wide16_packed": 1, "wide16_arows": 1,
+    "wide16_hreuse": 1, "fused_hreuse": 1, "fuse_conv": 1, "fuse_shortcut": 1, "concat_sc": 1, "x3_conv1": 1, "x3_fuse": 3,
+    "f16_split": 1, "f16_pair_mask": 0xFFFF, "flow_tiled": 1, "flow_rounds": 4, "warp_xcd": 0}
+
+
+def test_debug_options_are_one_table(lib):
+    """dvsg_debug_set_option knows the 17 switches and nothing else, and the header names every one of them.  The setter
+    makes no HIP call; only defaults are set, so the process is left as it was found."""
+    assert len(DEBUG_OPTION_DEFAULTS) == 17
+    for name, default in DEBUG_OPTION_DEFAULTS.items():
+        assert lib.dvsg_debug_set_option(name.encode(), default) == 0, name
+    assert lib.dvsg_debug_set_option(b"no_such_option", 1) == -1
+    assert b"no_such_option" in lib.dvsg_last_error_string()
+    assert lib.dvsg_debug_set_option(None, 1) == -1
+    text = open(HEADER).read()
+    comments = re.findall(r"/\*.*?\*/", text[:text.index("int dvsg_debug_set_option(")], flags=re.S)
+    for name in DEBUG_OPTION_DEFAULTS:
+        assert '"%s"' % name in comments[-1], "include/dvsg_amd.h does not document %s" % name
+
+
 def test_locnet_create_rejects_incomplete_checkpoint(lib):
     """Runs before any device work: a missing array is DVSG_ERR_WEIGHTS (-4)."""
     name = (ctypes.c_char_p * 1)(b"stabNet/localizationNet/df/dense1/b:0")

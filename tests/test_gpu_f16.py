@@ -338,6 +338,28 @@ def test_calibrated_float16_mode(synthetic_weights):
     assert np.abs(net.forward(xs[0], precision="f32").cpu().numpy() - refs[0]).max() <= 1e-5
 
 
+def test_calibration_leaves_the_options_alone(synthetic_weights):
+    """dvsg_locnet_calibrate_f16 leaves the "fuse_conv" switch as it found it: after a calibration the float32 opening unit of block 1 (tap stage 2: the call returns after that unit) ends in
+    conv3x3_1x1_kernel (family 4 of dvsg_debug_last_conv_kernel) with the option at 1, in conv_gemm_kernel (0) with it at 0.
+    40 x 72 frames: a pooled map of 10 x 18, every unit runs, blocks 3-4 on maps of a few pixels."""
+    import ctypes
+    from coupe.dvsg_amd import _lib
+    from coupe.dvsg_amd.networks import LocNet
+    net = LocNet(synthetic_weights)
+    x = inputs.window_frames(41, 1, 40, 72)
+    fields = (ctypes.c_int * 6)()
+    try:
+        for fuse, family in ((1, 4), (0, 0)):
+            _lib.call("dvsg_debug_set_option", b"fuse_conv", fuse)
+            net.calibrate_f16(x)
+            net.tap(x, 2, precision="f32")
+            _lib.call("dvsg_debug_last_conv_kernel", fields, 6)
+            assert fields[0] == family, "fuse_conv %d: block 1's opening unit ended in kernel family %d" % (fuse, fields[0])
+    finally:
+        _lib.call("dvsg_debug_set_option", b"fuse_conv", 1)
+        net.calibrate_f16(None)
+
+
 def test_plain_float16_layers_on_the_wide_tiles():
     """A layer WITHOUT the lo piece (`dvsg_conv_gemm_f16`; in the network: `f16_split=0` or a layer cleared in
     `f16_pair_mask`) with Cout % 128 == 0 and Cin % 64 == 0 runs, from `wide16_min_tiles` tiles on, in the SPLIT = false

@@ -737,10 +737,10 @@ def test_shapes_meet_every_row_residue_partial_column_blocks_and_the_asked_sizes
 def test_band_table_is_the_launch_formula_of_dvsg_flow_warp_f32():
     """the table against the formula restated above, the restatement against the source text, and the seams the table
     must hold: 2 bands of 8, 9, 10 and 11 steps, 3 bands of 8 with a short last one, 1-5 single-band steps, every W & 3"""
-    src = open(WARP_SRC).read()
+    src = open(WARP_SRC).read() + open(os.path.join(os.path.dirname(WARP_SRC), "common.h")).read()   # (the switches' defaults)
     for text in ("constexpr int kFsW = 128, kFsStep = 16, kFsPPT = 2;", "constexpr int kFsMX = 12, kFsMY = 12;",
-                 "int g_flow_rounds = 4;", "q.nstrips = ceil_div(W, kFsW);", "const int steps = ceil_div(H, kFsStep);",
-                 "int bands = (int)std::min<long>(std::max<long>(1, ((long)g_flow_rounds * 256 + (long)q.nstrips * B - 1) / "
+                 "int flow_rounds = 4;", "q.nstrips = ceil_div(W, kFsW);", "const int steps = ceil_div(H, kFsStep);",
+                 "int bands = (int)std::min<long>(std::max<long>(1, ((long)g_opt.flow_rounds * 256 + (long)q.nstrips * B - 1) / "
                  "((long)q.nstrips * B)), std::max(1, steps / 8));",
                  "const int band_steps = ceil_div(steps, bands);", "q.band_rows = band_steps * kFsStep;",
                  "q.nbands = ceil_div(H, q.band_rows);",
