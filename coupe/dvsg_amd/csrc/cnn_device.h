@@ -150,6 +150,26 @@ __device__ __forceinline__ void store4(_Float16 *p, float4 v) {
   *reinterpret_cast<halfx4 *>(p) = o;
 }
 
+// Output pixel m of an NHWC tensor [B][Ho][Wo] -> (b, ho, wo).
+struct Pixel {
+  int b, ho, wo;
+};
+__device__ __forceinline__ Pixel pixel_of(int m, int Ho, int Wo) {
+  const int wo = m % Wo;
+  const int t = m / Wo;
+  const int ho = t % Ho;
+  const int b = t / Ho;
+  return {b, ho, wo};
+}
+
+// slim `subsample`: shortcut = x[:, ::s, ::s, :].  Element offset of output pixel m's row in the residual tensor
+// [B][res_H][res_W][ld], sampled at (ho res_stride, wo res_stride); p is any of the conv kernels' parameter structs.
+template <typename P>
+__device__ __forceinline__ size_t subsample_offset(const P &p, int m, int ld) {
+  const Pixel px = pixel_of(m, p.Ho, p.Wo);
+  return (((size_t)px.b * p.res_H + (size_t)px.ho * p.res_stride) * p.res_W + (size_t)px.wo * p.res_stride) * ld;
+}
+
 // XCD-aware block remap (bijective for any grid size): the hardware deals consecutive
 // workgroup ids round-robin over the 8 XCDs; give each XCD a contiguous range of logical
 // tiles so that tiles sharing an activation panel / weight panel hit the same 4 MiB L2.

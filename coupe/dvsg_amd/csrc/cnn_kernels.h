@@ -11,6 +11,8 @@
 //   kF16   float16 activations, conv weights as float16 hi / lo pairs, v_mfma_f32_32x32x16_f16 with float32
 //          accumulation; bias, accumulators and the dense head stay float32.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace dvsg {
@@ -76,6 +78,19 @@ inline void record_conv_kernel(int family, int a0 = -1, int a1 = -1, int a2 = -1
   for (int i = 0; i < kConvKernelFields; ++i) g_last_conv_kernel[i] = rec[i];
 }
 inline void reset_conv_kernel() { record_conv_kernel(-1); }
+// Run-time (relu, res) -> compile-time constants, for the conv kernels' RELU and RES template arguments: calls
+// f(std::bool_constant<RELU>, std::integral_constant<int, RES>) with RES = 0 (no residual), 1 (a tensor of the output's
+// shape) or 2 (slim `subsample`: any other value of res)
+template <typename F>
+void with_relu_res(bool relu, int res, F &&f) {
+  auto with_res = [&](auto relu_c) {
+    if (res == 0) f(relu_c, std::integral_constant<int, 0>{});
+    else if (res == 1) f(relu_c, std::integral_constant<int, 1>{});
+    else f(relu_c, std::integral_constant<int, 2>{});
+  };
+  if (relu) with_res(std::true_type{});
+  else with_res(std::false_type{});
+}
 // f32x3 weights: float32 wt [rows][K] (rows % 64 == 0, K % 32 == 0) -> per group of 64 rows and 32-k stage three 4 KB planes
 // of bfloat16 pieces [64 rows][32 k] (p1 = bf16(w), p2 = bf16(w - p1), p3 = bf16(w - p1 - p2)), row R's 16-byte chunk c at
 // position c ^ ((R >> 2) & 3): 6 bytes per weight, [rows / 64][K / 32][3][64][32]

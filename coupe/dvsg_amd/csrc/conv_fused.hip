@@ -179,12 +179,9 @@ void conv3x3_1x1_kernel(ConvFusedDev p) {
     const int chunk = lpos ^ ((row >> 1) & 7);
     const int m = m0 + row;
     const int mm = m < p.M ? m : 0;
-    const int wo = mm % p.Wo;
-    const int t = mm / p.Wo;
-    const int ho = t % p.Ho;
-    const int b = t / p.Ho;
-    const int hi0 = ho * p.stride - 1, wi0 = wo * p.stride - 1;
-    a_off[i] = (((long)b * p.H + hi0) * p.W + wi0) * p.Cin + 4 * chunk;
+    const Pixel px = pixel_of(mm, p.Ho, p.Wo);
+    const int hi0 = px.ho * p.stride - 1, wi0 = px.wo * p.stride - 1;
+    a_off[i] = (((long)px.b * p.H + hi0) * p.W + wi0) * p.Cin + 4 * chunk;
     unsigned mk = 0;
     if (m < p.M) {
 #pragma unroll
@@ -321,7 +318,8 @@ void conv3x3_1x1_kernel(ConvFusedDev p) {
           size_t roff;
           if (RES == 1) {
             roff = (size_t)m * p.Cout + n;
-          } else {  // slim `subsample`: shortcut = x[:, ::s, ::s, :]
+          } else {  // slim `subsample` (cnn_device.h's subsample_offset, written out: through the helper the <2, *> instantiations
+                    // of this kernel come out with their instructions in another order)
             const int wo = m % p.Wo;
             const int t = m / p.Wo;
             const int ho = t % p.Ho;
@@ -444,12 +442,9 @@ void conv3x3_1x1_f16_kernel(ConvFusedF16Dev p) {
     const int chunk = lpos ^ ((row >> 1) & 7);
     const int m = m0 + row;
     const int mm = m < p.M ? m : 0;
-    const int wo = mm % p.Wo;
-    const int t = mm / p.Wo;
-    const int ho = t % p.Ho;
-    const int b = t / p.Ho;
-    const int hi0 = ho * p.stride - 1, wi0 = wo * p.stride - 1;
-    a_off[i] = (((long)b * p.H + hi0) * p.W + wi0) * p.Cin + 8 * chunk;
+    const Pixel px = pixel_of(mm, p.Ho, p.Wo);
+    const int hi0 = px.ho * p.stride - 1, wi0 = px.wo * p.stride - 1;
+    a_off[i] = (((long)px.b * p.H + hi0) * p.W + wi0) * p.Cin + 8 * chunk;
     unsigned mk = 0;
     if (m < p.M) {
 #pragma unroll
@@ -565,16 +560,7 @@ void conv3x3_1x1_f16_kernel(ConvFusedF16Dev p) {
       for (int i = 0; i < 4; ++i) {
         const int mr = m0 + row0 + 32 * i;
         const int m = mr < p.M ? mr : p.M - 1;
-        size_t roff;
-        if (RES == 1) {
-          roff = (size_t)m * p.Cout + n;
-        } else {  // slim `subsample`: shortcut = x[:, ::s, ::s, :]
-          const int wo = m % p.Wo;
-          const int t = m / p.Wo;
-          const int ho = t % p.Ho;
-          const int b = t / p.Ho;
-          roff = (((size_t)b * p.res_H + (size_t)ho * p.res_stride) * p.res_W + (size_t)wo * p.res_stride) * p.Cout + n;
-        }
+        const size_t roff = (RES == 1 ? (size_t)m * p.Cout : subsample_offset(p, m, p.Cout)) + n;
         rv[i] = load4(p.res + roff);
       }
     }
@@ -673,16 +659,13 @@ void conv3x3_1x1_f16h_kernel(ConvFusedF16Dev p) {
     const int m = m0 + row;
     const bool in = m >= 0 && m < p.M;
     const int mm = in ? m : 0;
-    const int wo = mm % p.Wo;
-    const int t = mm / p.Wo;
-    const int ho = t % p.Ho;
-    const int b = t / p.Ho;
-    a_pix[i] = (b * p.H + ho - 1) * p.W + wo;
+    const Pixel px = pixel_of(mm, p.Ho, p.Wo);
+    a_pix[i] = (px.b * p.H + px.ho - 1) * p.W + px.wo;
     unsigned mk = 0;
     if (in) {
 #pragma unroll
       for (int q = 0; q < 3; ++q)
-        if (ho - 1 + q >= 0 && ho - 1 + q < p.H) mk |= 1u << q;
+        if (px.ho - 1 + q >= 0 && px.ho - 1 + q < p.H) mk |= 1u << q;
     }
     a_mask[i] = mk;
   }

@@ -115,12 +115,9 @@ void conv3x3_1x1_x3_kernel(FusedX3Dev p) {
     const int chunk = lpos ^ ((row >> 1) & 7);
     const int m = m0 + row;
     const int mm = m < p.M ? m : 0;
-    const int wo = mm % p.Wo;
-    const int t = mm / p.Wo;
-    const int ho = t % p.Ho;
-    const int b = t / p.Ho;
-    const int hi0 = ho * p.stride - 1, wi0 = wo * p.stride - 1;
-    a_off[i] = (((long)b * p.H + hi0) * p.W + wi0) * p.Cin + 4 * chunk;
+    const Pixel px = pixel_of(mm, p.Ho, p.Wo);
+    const int hi0 = px.ho * p.stride - 1, wi0 = px.wo * p.stride - 1;
+    a_off[i] = (((long)px.b * p.H + hi0) * p.W + wi0) * p.Cin + 4 * chunk;
     unsigned mk = 0;
     if (m < p.M) {
 #pragma unroll
@@ -268,16 +265,7 @@ void conv3x3_1x1_x3_kernel(FusedX3Dev p) {
     for (int i = 0; i < 8; ++i) {
       const int mr = m0 + row0 + 16 * i;
       const int m = mr < p.M ? mr : p.M - 1;
-      size_t roff;
-      if (RES == 1) {
-        roff = (size_t)m * p.Cout + n;
-      } else {  // slim `subsample`: shortcut = x[:, ::s, ::s, :]
-        const int wo = m % p.Wo;
-        const int t = m / p.Wo;
-        const int ho = t % p.Ho;
-        const int b = t / p.Ho;
-        roff = (((size_t)b * p.res_H + (size_t)ho * p.res_stride) * p.res_W + (size_t)wo * p.res_stride) * p.Cout + n;
-      }
+      const size_t roff = (RES == 1 ? (size_t)m * p.Cout : subsample_offset(p, m, p.Cout)) + n;
       rv[i] = load4(p.res + roff);
     }
     if (q + 1 < nq) w3_issue(q + 1);   // (its buffer was read a group ago: everyone is past that since the barrier above)

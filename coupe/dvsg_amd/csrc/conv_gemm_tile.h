@@ -239,12 +239,9 @@ void conv_gemm_kernel(ConvGemmDev p) {
         a_mask[i] = m < p.M ? 0x11u : 0u;
         continue;
       }
-      const int wo = mm % p.Wo;
-      const int t = mm / p.Wo;
-      const int ho = t % p.Ho;
-      const int b = t / p.Ho;
-      const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-      a_off[i] = (((long)b * p.H + hi0) * p.W + wi0) * p.ldx + CHE * chunk;
+      const Pixel px = pixel_of(mm, p.Ho, p.Wo);
+      const int hi0 = px.ho * p.stride - p.pad, wi0 = px.wo * p.stride - p.pad;
+      a_off[i] = (((long)px.b * p.H + hi0) * p.W + wi0) * p.ldx + CHE * chunk;
       unsigned mk = 0;
       if (m < p.M) {
 #pragma unroll
@@ -451,16 +448,7 @@ void conv_gemm_kernel(ConvGemmDev p) {
       for (int i = 0; i < NROW; ++i) {
         const int mr = m0 + row0 + i * RSTEP;
         const int m = mr < p.M ? mr : p.M - 1;
-        size_t roff;
-        if (RES == 1) {
-          roff = (size_t)m * p.res_ld + n;
-        } else {  // slim `subsample`: shortcut = x[:, ::s, ::s, :]
-          const int wo = m % p.Wo;
-          const int t = m / p.Wo;
-          const int ho = t % p.Ho;
-          const int b = t / p.Ho;
-          roff = (((size_t)b * p.res_H + (size_t)ho * p.res_stride) * p.res_W + (size_t)wo * p.res_stride) * p.res_ld + n;
-        }
+        const size_t roff = (RES == 1 ? (size_t)m * p.res_ld : subsample_offset(p, m, p.res_ld)) + n;
         rv[i] = PSPLIT ? load4_p_pair(p.res, roff, col4 & 1) : load4(pres + roff);
       }
     };
@@ -600,16 +588,7 @@ void conv_gemm_kernel(ConvGemmDev p) {
       if (RES != 0) {
         float4 r4;
         if (reduce) {  // the finishing contributor of a split tile loads it here
-          size_t roff;
-          if (RES == 1) {
-            roff = (size_t)m * p.res_ld + n;
-          } else {
-            const int wo = m % p.Wo;
-            const int t = m / p.Wo;
-            const int ho = t % p.Ho;
-            const int b = t / p.Ho;
-            roff = (((size_t)b * p.res_H + (size_t)ho * p.res_stride) * p.res_W + (size_t)wo * p.res_stride) * p.res_ld + n;
-          }
+          const size_t roff = (RES == 1 ? (size_t)m * p.res_ld : subsample_offset(p, m, p.res_ld)) + n;
           r4 = PSPLIT ? load4_p_pair(p.res, roff, col4 & 1) : load4(pres + roff);
         } else {
           r4 = rv[i];
@@ -687,24 +666,21 @@ void conv_gemm_kernel(ConvGemmDev p) {
 template <typename T, int BN, int WM, int WN, int KS, int MODE, bool SPLIT = false, bool X3 = false>
 int launch_cfg(const ConvGemmDev &d, int blocks, bool relu, int res, hipStream_t s) {
   const dim3 grid(blocks), block(64 * WM * WN);
-#define DVSG_LAUNCH(R, Q) hipLaunchKernelGGL((conv_gemm_kernel<T, BN, WM, WN, KS, R, Q, MODE, SPLIT, X3>), grid, block, 0, s, d)
+  auto launch = [&](auto relu_c, auto res_c) {
+    constexpr bool R = decltype(relu_c)::value;
+    constexpr int Q = decltype(res_c)::value;
+    hipLaunchKernelGGL((conv_gemm_kernel<T, BN, WM, WN, KS, R, Q, MODE, SPLIT, X3>), grid, block, 0, s, d);
+  };
   if constexpr (MODE == 2) {
     // stream-K launches never carry a residual (launch_conv_gemm): with one, the finisher's partial sums
     // and residual rows together do not fit the 128-VGPR budget of 4 waves per SIMD (8-13 spills), and
     // no layer of resnet_v1_50 needs it (a residual layer's K is the unit's narrow width)
     if (res != 0) return fail(DVSG_ERR_UNSUPPORTED, "conv_gemm: stream-K launch with a residual");
-    if (relu) DVSG_LAUNCH(true, 0);
-    else DVSG_LAUNCH(false, 0);
-  } else if (relu) {
-    if (res == 0) DVSG_LAUNCH(true, 0);
-    else if (res == 1) DVSG_LAUNCH(true, 1);
-    else DVSG_LAUNCH(true, 2);
+    if (relu) launch(std::true_type{}, std::integral_constant<int, 0>{});   // (the only RES this mode is instantiated for)
+    else launch(std::false_type{}, std::integral_constant<int, 0>{});
   } else {
-    if (res == 0) DVSG_LAUNCH(false, 0);
-    else if (res == 1) DVSG_LAUNCH(false, 1);
-    else DVSG_LAUNCH(false, 2);
+    with_relu_res(relu, res, launch);
   }
-#undef DVSG_LAUNCH
   // the launch record (dvsg_debug_last_conv_config); MODE 2 has returned above unless res == 0
   const int rec[kConvConfigFields] = {sizeof(T) == 4 ? 0 : 1, BN, WM, WN, KS, relu ? 1 : 0, res, MODE, SPLIT, X3,
                                       d.ksplit, MODE == 2 ? d.tile_count : 0, d.mt_fast};

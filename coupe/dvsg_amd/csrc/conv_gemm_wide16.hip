@@ -33,6 +33,7 @@ constexpr int WBM = 256;     // pixels per tile
 constexpr int WBN = 128;     // stacked weight rows per tile (64 output channels)
 constexpr int WROWB = 64;    // bytes of k per row and stage (32 float16)
 constexpr int WBKE = 32;     // k elements per stage
+constexpr int WHM = WBM - 2;  // output pixels per tile of conv_wide16h_kernel
 
 __device__ const floatx4 g_zero16w = {0.f, 0.f, 0.f, 0.f};
 
@@ -56,16 +57,47 @@ __device__ unsigned long long g_w16_stamps[8 * 65536];
 #define W16_STAMP() __builtin_amdgcn_s_memtime()
 #endif
 
+// ----------------------------------------------------------------------------------------
+// What the three kernels below share: 512 threads = 8 waves as 4 x 2, two 32-pixel blocks per wave; the staging prologue
+// of the first two is conv_wide16_rows.inc, the epilogue of all three conv_wide16_epilogue.inc.
+// ----------------------------------------------------------------------------------------
+constexpr int NW = 8, MI = 2;
+
+// the lane's hi and lo weight fragments: rows r and 64 + r of a stage's 128 weight rows, 16 bytes at byte `co`
+__device__ __forceinline__ void wide16_b_frag(const char *b_base, int co, halfx8 &bh, halfx8 &bl) {
+  bh = *reinterpret_cast<const halfx8 *>(b_base + co);
+  bl = *reinterpret_cast<const halfx8 *>(b_base + 64 * WROWB + co);
+}
+
+struct NoStamps {   // the epilogue's stamp hook (conv_wide16_epilogue.inc) of every build but the diagnostic one
+  __device__ __forceinline__ void operator()(int) const {}
+};
+#ifdef DVSG_STAMPS
+// ... and of conv_wide16_kernel in that one.  The epilogue's stamp points: 0 in front of the barrier before the transpose,
+// 1 behind it, 2 behind the transpose stores + barrier, 3 once the residual rows are there
+struct EpilogueStamps {
+  unsigned long long *st;
+  bool res;
+  unsigned long long last = 0;
+  __device__ __forceinline__ void operator()(int point) {
+    if (point == 3 && res) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned long long now = W16_STAMP();
+    // st[4]: barrier before the transpose (the other waves' MFMAs / reads); st[5]: transpose stores + barrier; st[6]: residual
+    // rows not there yet (and, second round, the first round's stores still in flight)
+    if (point > 0) st[3 + point] += now - last;
+    last = now;
+  }
+};
+#endif
+
 // SPLIT = false: the 128 weight rows of a tile are 128 output channels of a PLAIN float16 weight matrix [Cout][K] (layers
 // whose weights do not need the lo piece -- locnet.hip's pair policy): the "lo" accumulators are simply the tile's second
 // 64 channels, same loop, half the bytes and MFMAs per output channel.
 template <int KS, bool RELU, int RES, bool SPLIT = true>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void conv_wide16_kernel(ConvWide16Dev p) {
-  constexpr int NW = 8, MI = 2;
   constexpr int AG = WBM / 16 / NW;   // 2 LDS-DMA instructions (16 rows each) per wave and stage for the pixels
   constexpr int PER = AG + 1;         // + 1 for the 128 weight rows
-  constexpr float kLoScale = 1.0f / 2048.0f;
   __shared__ __attribute__((aligned(16))) char lds[2 * (WBM + WBN) * WROWB];   // 48 KiB
   char *As = lds;
   char *Bs = lds + 2 * WBM * WROWB;
@@ -87,36 +119,9 @@ void conv_wide16_kernel(ConvWide16Dev p) {
   const int mt = tile / p.ntiles, nt = tile - mt * p.ntiles;
   const int m0 = mt * WBM;
 
-  long a_off[AG];
-  unsigned a_mask[AG];
-  const bool dense = KS == 1 && p.stride == 1;   // a 1x1 / stride 1 layer is a row-major GEMM (conv_gemm.hip)
-#pragma unroll
-  for (int i = 0; i < AG; ++i) {
-    const int row = 16 * (wave + NW * i) + lrow;
-    const int chunk = lpos ^ ((row >> 2) & 3);
-    const int m = m0 + row;
-    const int mm = m < p.M ? m : 0;
-    if (dense) {
-      a_off[i] = (long)mm * p.Cin + 8 * chunk;
-      a_mask[i] = m < p.M ? 0x11u : 0u;
-      continue;
-    }
-    const int wo = mm % p.Wo;
-    const int t = mm / p.Wo;
-    const int ho = t % p.Ho;
-    const int b = t / p.Ho;
-    const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-    a_off[i] = (((long)b * p.H + hi0) * p.W + wi0) * p.Cin + 8 * chunk;
-    unsigned mk = 0;
-    if (m < p.M) {
-#pragma unroll
-      for (int q = 0; q < KS; ++q) {
-        if (hi0 + q >= 0 && hi0 + q < p.H) mk |= 1u << q;
-        if (wi0 + q >= 0 && wi0 + q < p.W) mk |= 16u << q;
-      }
-    }
-    a_mask[i] = mk;
-  }
+  constexpr int kRows = 16;
+  auto swz = [](int row) { return (row >> 2) & 3; };
+#include "conv_wide16_rows.inc"
   const _Float16 *wsrc;
   {
     const int row = 16 * wave + lrow;   // stacked weight row of the tile (0..127)
@@ -167,8 +172,8 @@ void conv_wide16_kernel(ConvWide16Dev p) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int co = 16 * ((2 * t + h) ^ sw);
-      const halfx8 bh = *reinterpret_cast<const halfx8 *>(b_base + co);
-      const halfx8 bl = *reinterpret_cast<const halfx8 *>(b_base + 64 * WROWB + co);
+      halfx8 bh, bl;
+      wide16_b_frag(b_base, co, bh, bl);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         const halfx8 a = *reinterpret_cast<const halfx8 *>(a_base + mi * 32 * WROWB + co);
@@ -215,82 +220,13 @@ void conv_wide16_kernel(ConvWide16Dev p) {
   st[3] = t_loop - t_first;   // the K loop, waits included
 #endif
 
-  // ---- epilogue: 64 output channels at a time, rounds of 128 pixels through a [128][64] float32 transpose
-  // (SPLIT: one channel half, hi + 2^-11 lo; plain: two channel halves, the accumulators as they are)
-  float *Cs = reinterpret_cast<float *>(lds);
-  const int col4 = tid & 15, row0 = tid >> 4;   // 16 float4 per row, 32 rows per pass
-  constexpr int NHALF = SPLIT ? 1 : 2;
-#pragma unroll
-  for (int ch = 0; ch < NHALF; ++ch) {
-  const int n = nt * (SPLIT ? 64 : 128) + 64 * ch + 4 * col4;
-  const float4 bias4 = *reinterpret_cast<const float4 *>(p.bias + n);
-#pragma unroll
-  for (int rho = 0; rho < 2; ++rho) {
-    float4 rv[4];
-    if (RES != 0) {   // residual of this round's rows: in flight under the two barriers and the transpose
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int mr = m0 + 128 * rho + row0 + 32 * i;
-        const int m = mr < p.M ? mr : p.M - 1;
-        size_t roff;
-        if (RES == 1) {
-          roff = (size_t)m * p.Cout + n;
-        } else {  // slim `subsample`: shortcut = x[:, ::s, ::s, :]
-          const int wo = m % p.Wo;
-          const int t = m / p.Wo;
-          const int ho = t % p.Ho;
-          const int b = t / p.Ho;
-          roff = (((size_t)b * p.res_H + (size_t)ho * p.res_stride) * p.res_W + (size_t)wo * p.res_stride) * p.Cout + n;
-        }
-        rv[i] = load4(p.res + roff);
-      }
-    }
+  constexpr bool kHalo = false;
 #ifdef DVSG_STAMPS
-    const unsigned long long e0 = W16_STAMP();
+  EpilogueStamps stamp{st, RES != 0};
+#else
+  NoStamps stamp;
 #endif
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();   // the stage buffers (first round) / the previous round's rows have been read
-    asm volatile("" ::: "memory");
-#ifdef DVSG_STAMPS
-    const unsigned long long e1 = W16_STAMP();
-    st[4] += e1 - e0;   // barrier before the transpose (the other waves' MFMAs / reads)
-#endif
-    if ((wm >> 1) == rho) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          Cs[((wm & 1) * 64 + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * 64 + wn * 32 + r] =
-              SPLIT ? acc_hi[mi][q] + acc_lo[mi][q] * kLoScale : (ch == 0 ? acc_hi[mi][q] : acc_lo[mi][q]);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-#ifdef DVSG_STAMPS
-    const unsigned long long e2 = W16_STAMP();
-    st[5] += e2 - e1;   // transpose stores + barrier
-    if (RES != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long e3 = W16_STAMP();
-    st[6] += e3 - e2;   // residual rows not there yet (and, second round, the first round's stores still in flight)
-#endif
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = row0 + 32 * i;
-      const int m = m0 + 128 * rho + row;
-      if (m < p.M) {
-        float4 v = *reinterpret_cast<const float4 *>(Cs + row * 64 + 4 * col4);
-        v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-        if (RES != 0) {
-          v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w;
-        }
-        if (RELU) {
-          v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        }
-        store4(p.y + (size_t)m * p.Cout + n, v);
-      }
-    }
-  }
-  }
+#include "conv_wide16_epilogue.inc"
 #ifdef DVSG_STAMPS
   const unsigned long long t_issued = W16_STAMP();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -317,10 +253,8 @@ void conv_wide16_kernel(ConvWide16Dev p) {
 template <int KS, bool RELU, int RES, bool SPLIT = true>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void conv_wide16a_kernel(ConvWide16Dev p) {
-  constexpr int NW = 8, MI = 2;
   constexpr int AG = WBM / 8 / NW;    // 4 LDS-DMA instructions (8 rows of 128 bytes each) per wave and super-stage
   constexpr int AROWB = 2 * WROWB;    // 128
-  constexpr float kLoScale = 1.0f / 2048.0f;
   __shared__ __attribute__((aligned(16))) char lds[2 * WBM * AROWB + 2 * WBN * WROWB];   // 64 + 16 KiB
   char *As = lds;
   char *Bs = lds + 2 * WBM * AROWB;
@@ -339,36 +273,9 @@ void conv_wide16a_kernel(ConvWide16Dev p) {
   const int mt = tile / p.ntiles, nt = tile - mt * p.ntiles;
   const int m0 = mt * WBM;
 
-  long a_off[AG];
-  unsigned a_mask[AG];
-  const bool dense = KS == 1 && p.stride == 1;   // a 1x1 / stride 1 layer is a row-major GEMM (conv_gemm.hip)
-#pragma unroll
-  for (int i = 0; i < AG; ++i) {
-    const int row = 8 * (wave + NW * i) + lrow;
-    const int chunk = lpos ^ ((row >> 1) & 7);
-    const int m = m0 + row;
-    const int mm = m < p.M ? m : 0;
-    if (dense) {
-      a_off[i] = (long)mm * p.Cin + 8 * chunk;
-      a_mask[i] = m < p.M ? 0x11u : 0u;
-      continue;
-    }
-    const int wo = mm % p.Wo;
-    const int t = mm / p.Wo;
-    const int ho = t % p.Ho;
-    const int b = t / p.Ho;
-    const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-    a_off[i] = (((long)b * p.H + hi0) * p.W + wi0) * p.Cin + 8 * chunk;
-    unsigned mk = 0;
-    if (m < p.M) {
-#pragma unroll
-      for (int q = 0; q < KS; ++q) {
-        if (hi0 + q >= 0 && hi0 + q < p.H) mk |= 1u << q;
-        if (wi0 + q >= 0 && wi0 + q < p.W) mk |= 16u << q;
-      }
-    }
-    a_mask[i] = mk;
-  }
+  constexpr int kRows = 8;
+  auto swz = [](int row) { return (row >> 1) & 7; };
+#include "conv_wide16_rows.inc"
   // weight half-stages: 8 KB each, contiguous in the packed copy, lane l of wave w fetching 16 bytes at 1024 w + 16 l
   const _Float16 *wpk = p.wtp + (size_t)nt * p.K * WBN + wave * 512 + lane * 8;
   auto issue_b = [&](int buf) __attribute__((always_inline)) {
@@ -410,8 +317,8 @@ void conv_wide16a_kernel(ConvWide16Dev p) {
     for (int t = 0; t < 2; ++t) {
       const int co = 16 * ((2 * t + h) ^ sw);
       const int ca = 16 * ((4 * half + 2 * t + h) ^ swa);
-      const halfx8 bh = *reinterpret_cast<const halfx8 *>(b_base + co);
-      const halfx8 bl = *reinterpret_cast<const halfx8 *>(b_base + 64 * WROWB + co);
+      halfx8 bh, bl;
+      wide16_b_frag(b_base, co, bh, bl);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         const halfx8 a = *reinterpret_cast<const halfx8 *>(a_base + mi * 32 * AROWB + ca);
@@ -434,68 +341,9 @@ void conv_wide16a_kernel(ConvWide16Dev p) {
     __builtin_amdgcn_sched_barrier(0);
   }
 
-  // ---- epilogue: 64 output channels at a time, rounds of 128 pixels through a [128][64] float32 transpose
-  // (SPLIT: one channel half, hi + 2^-11 lo; plain: two channel halves, the accumulators as they are)
-  float *Cs = reinterpret_cast<float *>(lds);
-  const int col4 = tid & 15, row0 = tid >> 4;   // 16 float4 per row, 32 rows per pass
-  constexpr int NHALF = SPLIT ? 1 : 2;
-#pragma unroll
-  for (int ch = 0; ch < NHALF; ++ch) {
-  const int n = nt * (SPLIT ? 64 : 128) + 64 * ch + 4 * col4;
-  const float4 bias4 = *reinterpret_cast<const float4 *>(p.bias + n);
-#pragma unroll
-  for (int rho = 0; rho < 2; ++rho) {
-    float4 rv[4];
-    if (RES != 0) {   // residual of this round's rows: in flight under the two barriers and the transpose
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int mr = m0 + 128 * rho + row0 + 32 * i;
-        const int m = mr < p.M ? mr : p.M - 1;
-        size_t roff;
-        if (RES == 1) {
-          roff = (size_t)m * p.Cout + n;
-        } else {  // slim `subsample`: shortcut = x[:, ::s, ::s, :]
-          const int wo = m % p.Wo;
-          const int t = m / p.Wo;
-          const int ho = t % p.Ho;
-          const int b = t / p.Ho;
-          roff = (((size_t)b * p.res_H + (size_t)ho * p.res_stride) * p.res_W + (size_t)wo * p.res_stride) * p.Cout + n;
-        }
-        rv[i] = load4(p.res + roff);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();   // the stage buffers (first round) / the previous round's rows have been read
-    asm volatile("" ::: "memory");
-    if ((wm >> 1) == rho) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          Cs[((wm & 1) * 64 + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * 64 + wn * 32 + r] =
-              SPLIT ? acc_hi[mi][q] + acc_lo[mi][q] * kLoScale : (ch == 0 ? acc_hi[mi][q] : acc_lo[mi][q]);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = row0 + 32 * i;
-      const int m = m0 + 128 * rho + row;
-      if (m < p.M) {
-        float4 v = *reinterpret_cast<const float4 *>(Cs + row * 64 + 4 * col4);
-        v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-        if (RES != 0) {
-          v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w;
-        }
-        if (RELU) {
-          v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        }
-        store4(p.y + (size_t)m * p.Cout + n, v);
-      }
-    }
-  }
-  }
+  constexpr bool kHalo = false;
+  NoStamps stamp;
+#include "conv_wide16_epilogue.inc"
 }
 
 // ----------------------------------------------------------------------------------------
@@ -511,15 +359,11 @@ void conv_wide16a_kernel(ConvWide16Dev p) {
 //     fragments are zeroed for kw = 0 / kw = 2 (what the padding would have supplied);
 //   * K order: 64-channel chunk, kh, kw, half (launch_pack_wide16 order 2).
 // ----------------------------------------------------------------------------------------
-constexpr int WHM = WBM - 2;   // output pixels per tile
-
 template <bool RELU, int RES, bool SPLIT = true>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void conv_wide16h_kernel(ConvWide16Dev p) {
-  constexpr int NW = 8, MI = 2;
   constexpr int AG = WBM / 8 / NW;    // 4 LDS-DMA instructions (8 rows of 128 bytes each) per wave and super-stage
   constexpr int AROWB = 2 * WROWB;    // 128
-  constexpr float kLoScale = 1.0f / 2048.0f;
   __shared__ __attribute__((aligned(16))) char lds[2 * WBM * AROWB + 2 * WBN * WROWB];   // 64 + 16 KiB
   char *As = lds;
   char *Bs = lds + 2 * WBM * AROWB;
@@ -547,16 +391,13 @@ void conv_wide16h_kernel(ConvWide16Dev p) {
     const int m = m0 + row;
     const bool in = m >= 0 && m < p.M;
     const int mm = in ? m : 0;
-    const int wo = mm % p.Wo;
-    const int t = mm / p.Wo;
-    const int ho = t % p.Ho;
-    const int b = t / p.Ho;
-    a_pix[i] = (b * p.H + ho - 1) * p.W + wo;
+    const Pixel px = pixel_of(mm, p.Ho, p.Wo);
+    a_pix[i] = (px.b * p.H + px.ho - 1) * p.W + px.wo;
     unsigned mk = 0;
     if (in) {
 #pragma unroll
       for (int q = 0; q < 3; ++q)
-        if (ho - 1 + q >= 0 && ho - 1 + q < p.H) mk |= 1u << q;
+        if (px.ho - 1 + q >= 0 && px.ho - 1 + q < p.H) mk |= 1u << q;
     }
     a_mask[i] = mk;
   }
@@ -603,8 +444,8 @@ void conv_wide16h_kernel(ConvWide16Dev p) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int co = 16 * ((2 * t + h) ^ sw);
-      const halfx8 bh = *reinterpret_cast<const halfx8 *>(b_base + co);
-      const halfx8 bl = *reinterpret_cast<const halfx8 *>(b_base + 64 * WROWB + co);
+      halfx8 bh, bl;
+      wide16_b_frag(b_base, co, bh, bl);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         int rr = pr0 + 32 * mi + kw - 1;
@@ -636,84 +477,19 @@ void conv_wide16h_kernel(ConvWide16Dev p) {
     }
   }
 
-  // ---- epilogue: as in conv_wide16_kernel, for the tile's rows 1 .. 254
-  float *Cs = reinterpret_cast<float *>(lds);
-  const int col4 = tid & 15, row0 = tid >> 4;
-  constexpr int NHALF = SPLIT ? 1 : 2;
-#pragma unroll
-  for (int ch = 0; ch < NHALF; ++ch) {
-  const int n = nt * (SPLIT ? 64 : 128) + 64 * ch + 4 * col4;
-  const float4 bias4 = *reinterpret_cast<const float4 *>(p.bias + n);
-#pragma unroll
-  for (int rho = 0; rho < 2; ++rho) {
-    float4 rv[4];
-    if (RES != 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int mr = m0 + 128 * rho + row0 + 32 * i;
-        const int m = mr < 0 ? 0 : (mr < p.M ? mr : p.M - 1);
-        size_t roff;
-        if (RES == 1) {
-          roff = (size_t)m * p.Cout + n;
-        } else {
-          const int wo = m % p.Wo;
-          const int t = m / p.Wo;
-          const int ho = t % p.Ho;
-          const int b = t / p.Ho;
-          roff = (((size_t)b * p.res_H + (size_t)ho * p.res_stride) * p.res_W + (size_t)wo * p.res_stride) * p.Cout + n;
-        }
-        rv[i] = load4(p.res + roff);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if ((wm >> 1) == rho) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          Cs[((wm & 1) * 64 + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * 64 + wn * 32 + r] =
-              SPLIT ? acc_hi[mi][q] + acc_lo[mi][q] * kLoScale : (ch == 0 ? acc_hi[mi][q] : acc_lo[mi][q]);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = row0 + 32 * i;
-      const int pr = 128 * rho + row;
-      const int m = m0 + pr;
-      if (pr >= 1 && pr <= WHM && m < p.M) {
-        float4 v = *reinterpret_cast<const float4 *>(Cs + row * 64 + 4 * col4);
-        v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-        if (RES != 0) {
-          v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w;
-        }
-        if (RELU) {
-          v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        }
-        store4(p.y + (size_t)m * p.Cout + n, v);
-      }
-    }
-  }
-  }
+  constexpr bool kHalo = true;   // the tile's rows 1 .. 254
+  NoStamps stamp;
+#include "conv_wide16_epilogue.inc"
 }
 
 template <bool SPLIT>
 int launch_h(const ConvWide16Dev &d, bool relu, int res, hipStream_t s) {
   const dim3 grid(d.mtiles * d.ntiles), block(512);
-#define DVSG_LAUNCH(R, Q) hipLaunchKernelGGL((conv_wide16h_kernel<R, Q, SPLIT>), grid, block, 0, s, d)
-  if (relu) {
-    if (res == 0) DVSG_LAUNCH(true, 0);
-    else if (res == 1) DVSG_LAUNCH(true, 1);
-    else DVSG_LAUNCH(true, 2);
-  } else {
-    if (res == 0) DVSG_LAUNCH(false, 0);
-    else if (res == 1) DVSG_LAUNCH(false, 1);
-    else DVSG_LAUNCH(false, 2);
-  }
-#undef DVSG_LAUNCH
+  with_relu_res(relu, res, [&](auto relu_c, auto res_c) {
+    constexpr bool R = decltype(relu_c)::value;
+    constexpr int Q = decltype(res_c)::value;
+    hipLaunchKernelGGL((conv_wide16h_kernel<R, Q, SPLIT>), grid, block, 0, s, d);
+  });
   record_conv_kernel(3, relu ? 1 : 0, res, SPLIT ? 1 : 0, -1, d.wtp ? 1 : 0);
   return check_launch("conv_wide16h_kernel");
 }
@@ -721,21 +497,12 @@ int launch_h(const ConvWide16Dev &d, bool relu, int res, hipStream_t s) {
 template <int KS, bool SPLIT>
 int launch_ks(const ConvWide16Dev &d, bool relu, int res, hipStream_t s) {
   const dim3 grid(d.mtiles * d.ntiles), block(512);
-#define DVSG_LAUNCH(R, Q)                                                                           \
-  do {                                                                                              \
-    if (d.arows) hipLaunchKernelGGL((conv_wide16a_kernel<KS, R, Q, SPLIT>), grid, block, 0, s, d);   \
-    else hipLaunchKernelGGL((conv_wide16_kernel<KS, R, Q, SPLIT>), grid, block, 0, s, d);            \
-  } while (0)
-  if (relu) {
-    if (res == 0) DVSG_LAUNCH(true, 0);
-    else if (res == 1) DVSG_LAUNCH(true, 1);
-    else DVSG_LAUNCH(true, 2);
-  } else {
-    if (res == 0) DVSG_LAUNCH(false, 0);
-    else if (res == 1) DVSG_LAUNCH(false, 1);
-    else DVSG_LAUNCH(false, 2);
-  }
-#undef DVSG_LAUNCH
+  with_relu_res(relu, res, [&](auto relu_c, auto res_c) {
+    constexpr bool R = decltype(relu_c)::value;
+    constexpr int Q = decltype(res_c)::value;
+    if (d.arows) hipLaunchKernelGGL((conv_wide16a_kernel<KS, R, Q, SPLIT>), grid, block, 0, s, d);
+    else hipLaunchKernelGGL((conv_wide16_kernel<KS, R, Q, SPLIT>), grid, block, 0, s, d);
+  });
   record_conv_kernel(d.arows ? 2 : 1, KS, relu ? 1 : 0, res, SPLIT ? 1 : 0, d.wtp ? 1 : 0);
   return check_launch("conv_wide16_kernel");
 }
@@ -779,9 +546,6 @@ int launch_pack_wide16(const void *wt, void *out, int rows, int Cin, int ksize, 
                      static_cast<_Float16 *>(out), K, Cin, ksize * ksize, order, nchunks);
   return check_launch("pack_wide16_kernel");
 }
-
-namespace {
-}  // namespace
 
 #ifdef DVSG_STAMPS
 int g_w16_stamp_sel = 0;   // KS * 100000000 + Cin * 10000 + Cout of the launches that record
