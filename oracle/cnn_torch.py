@@ -64,7 +64,12 @@ class TorchLocNet:
         return F.relu(y) if relu else y
 
     @torch.no_grad()
-    def features(self, patches_nhwc):
+    def features(self, patches_nhwc, taps=None):
+        """pool5 features [B, 2048]; with a dict `taps`, every stage's activation lands in it as an NHWC tensor under
+        oracle.networks' names ("conv1", "pool1", "block1/unit_1", ..., "pool5")"""
+        def keep(name, t):
+            if taps is not None:
+                taps[name] = t.permute(0, 2, 3, 1).contiguous()
         x = torch.as_tensor(patches_nhwc, dtype=torch.float32).to(self.dtype)
         # scale_RGB (networks.py:6-16): groups of 7 channels reversed, per-group mean
         x = x * 255.0
@@ -73,12 +78,14 @@ class TorchLocNet:
         x = x.permute(0, 3, 1, 2).contiguous()
         rn = self.p + "resnet_v1_50"
         x = self._cb(x, rn + "/conv1", 2, True, 7)
+        keep("conv1", x)
         H, W = x.shape[2], x.shape[3]
         Ho, Wo = -(-H // 2), -(-W // 2)
         ph = max((Ho - 1) * 2 + 3 - H, 0)
         pw = max((Wo - 1) * 2 + 3 - W, 0)
         x = F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
         x = F.max_pool2d(x, 3, 2)
+        keep("pool1", x)
         for bname, base, units, last_stride in BLOCKS:
             for u in range(1, units + 1):
                 stride = last_stride if u == units else 1
@@ -91,6 +98,9 @@ class TorchLocNet:
                 r = self._cb(r, s + "/conv2", stride, True, 3)
                 r = self._cb(r, s + "/conv3", 1, False, 1)
                 x = F.relu(sc + r)
+                keep("%s/unit_%d" % (bname, u), x)
+        if taps is not None:
+            taps["pool5"] = x.mean(dim=(2, 3))
         return x.mean(dim=(2, 3))
 
     @torch.no_grad()

@@ -317,7 +317,8 @@ def test_shortcut_and_conv1_as_one_launch(net, precision, B, H, W):
     concatenated weight rows: the output [M, depth + base] sits in one buffer, conv2 reads its last `base` columns and conv3
     its first `depth` as residual through row strides ("concat_sc"; dvsg_debug_set_option 0 = two launches).  Same products in
     the same K order; the tile decomposition (and with it where split-K / stream-K cut a K loop) may differ: every unit's
-    output and F_t agree to float32 re-association."""
+    output and F_t agree to float32 re-association.  (The per-element criterion of this path -- both settings against one
+    float64 reference of the unit -- is test_units_f64.py's.)"""
     import torch
     from coupe.dvsg_amd import _lib
     x = torch.from_numpy(inputs.window_frames(17 * H + W, B, H, W)).cuda()

@@ -605,8 +605,9 @@ def head_ref(x17, dense):
     return p, tol_p
 
 
-def dense_ref(p, dense, slope=0.2):
-    """F [B, 50] and its bound from the pooled features p [B, 2048] (float64, taken as exact).  Two compositions, the
+def dense_ref(p, dense, slope=0.2, e0=None):
+    """F [B, 50] and its bound from the pooled features p [B, 2048] (float64, taken as exact, or known to within e0 per
+    element: test_units_f64.py carries the network's composed bound into the head).  Two compositions, the
     smaller of which holds: the worst case e_next = e |W| + tau(K_l) S_l (as f64.fused_bound composes two layers; leaky
     slope <= 1 passes the error unamplified) -- which over four layers of 2048, 1024, 512 inputs grows past |F_t| itself
     and would not see a leaky slope of 0 -- and the same in quadrature, q_next = 2 sqrt(q^2 W^2) + tau(K_l) S_l: the
@@ -614,6 +615,8 @@ def dense_ref(p, dense, slope=0.2):
     (sqrt(K) of them), and the factor 2 keeps the envelope's margin through the sum."""
     import torch
     x, e, q = p, torch.zeros_like(p), torch.zeros_like(p)
+    if e0 is not None:
+        e, q = e0.clone(), e0.clone()
     for i, (Wm, b) in enumerate(dense):
         Wm, b = Wm.double(), b.double()
         if i:
