@@ -155,7 +155,10 @@ __global__ __launch_bounds__(kThreads) void frames_to_u8_kernel(const T *__restr
 
 // cv2.resize(src_float64, (out_w, out_h)) with the default INTER_LINEAR, restated from OpenCV's
 // published resize algorithm (OpenCV is not part of the reference tree nor of this image: parity
-// unpinned): pixel centres at (d + 0.5) * scale - 0.5; the fractional weight is computed AND kept
+// unpinned against cv2; held bit for bit by a second restatement and within a derived bound by torch's float64
+// bilinear interpolation, tests/test_frames_f64.py; OpenCV's spelling of the scale, 1. / (dw / sw), gives the
+// same float32 coordinates as sw / dw for all sizes tried, tests/test_frames_ref_cpu.py):
+// pixel centres at (d + 0.5) * scale - 0.5; the fractional weight is computed AND kept
 // as float32; taps left of 0 / right of the last column clamp with weight 0; the row pass runs
 // first (float64 accumulate), then the column pass.  Input is the uint8 frame (eval.py:80 divides by
 // 255. in float64 first), output the float32 TF is fed.

@@ -5,8 +5,14 @@ PARITY STATUS: parity unpinned.  `cv2` is a third-party dependency of the refere
 (eval.py:3; no version pinned anywhere in the tree) and is not installed here, so
 `resize_linear` restates OpenCV's published INTER_LINEAR algorithm for float64 images
 (imgproc/resize.cpp: `resizeGeneric_` with `HResizeLinear<double,double,float>` /
-`VResizeLinear<double,double,float>`) and is pinned only by the known-answer tests in
-tests/test_oracle_kat.py (identity size, constant image, exact 2x case, edge clamping).
+`VResizeLinear<double,double,float>`).  It stays unpinned against cv2 itself.  What holds it: the known-answer
+tests in tests/test_oracle_kat.py (identity size, constant image, exact 2x case, edge clamping); a second
+restatement written from the kernel's comment alone (tests/frames_ref.py: resize_exact), equal to it bit for bit;
+and torch's float64 bilinear interpolation with half-pixel centres, which shares no text with either and from
+which it lies within a derived per-pixel bound (the float32 coordinate and weight: tests/frames_ref.py:
+resize_bound, tests/test_frames_ref_cpu.py).  OpenCV spells the scale 1. / (dw / sw), this file sw / dw: the two
+give identical float32 coordinates for every pair of sizes in 1..399 (159 201 pairs) and for the 289 pairs of the
+usual video sizes (same test file), so the spelling decides nothing.
 """
 import numpy as np
 
