@@ -79,6 +79,10 @@ SIGNATURES = {
     "dvsg_frames_ingest_u8": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp],
     "dvsg_frames_f32_to_u8_slots": [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "dvsg_tps_render_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "dvsg_frames_nv12_to_rgb_u8": [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _i, _i, _i, _i, _i, _vp, _vp],
+    "dvsg_frames_ingest_nv12": [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp],
+    "dvsg_tps_render_nv12": [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _i, _i, _i, _vp, _vp, _vp,
+                             ctypes.c_size_t, ctypes.c_size_t, _vp],
     "dvsg_tps_coverage_workspace_bytes": [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t)],
     "dvsg_tps_coverage_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "dvsg_tps_warp_zoom_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -1266,6 +1266,18 @@ int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const ui
                          u8_x0, stream, zoom);
 }
 
+// dvsg_tps_render_u8 for NV12 frames (nv12.hip): the same T, then both planes warped at their own sizes in one launch.
+// Every argument is checked before the handle is read.
+int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
+                         size_t frame_stride, int n, int H, int W, float *T, uint8_t *out_y, uint8_t *out_uv, size_t out_pitch,
+                         size_t out_frame_stride, void *stream) {
+  DVSG_REQUIRE(net, "dvsg_tps_render_nv12: NULL net");
+  if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride))
+    return rc;
+  return tps_render_nv12_impl(net->winv, net->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv, out_pitch,
+                              out_frame_stride, stream);
+}
+
 // The coverage scan of a clip's F_t rows: the T of dvsg_stabilize_* / dvsg_tps_render_u8 for F_t (written), then
 // dvsg_tps_coverage_f32 on it with V_src.  Shapes and workspace are checked before the first launch.
 int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const float *zoom, int n, int src_H, int src_W,

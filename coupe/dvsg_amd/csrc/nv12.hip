@@ -1,0 +1,385 @@
+// NV12 as a frame format of its own (include/dvsg_amd.h, "NV12 frames"): what a hardware decoder hands over and an
+// encoder takes -- a full-size Y plane and a half-size interleaved UV plane, rows `pitch` bytes apart.
+//
+//   nv12_to_rgb_kernel      Y, UV -> packed RGB / BGR uint8.  Integer arithmetic with shift 20 (OpenCV's published
+//                           COLOR_YUV2RGB_NV12 scheme; OpenCV is not part of this image: parity with cv2 unpinned, as for
+//                           the resize), chroma of luma pixel (i, j) = sample (i / 2, j / 2), no interpolation.  Exact.
+//   ingest_nv12_kernel      that conversion followed by frames_u8_to_f32_kernel's (float)(double(v) / 255.0), into pool
+//   ingest_nv12_resize_kernel  slots; and followed by resize_u8_kernel's float64 bilinear: each output pixel converts its
+//                           (at most four) taps in registers, the source-size RGB image never exists.
+//   nv12_render_kernel      both planes warped by one normalised TPS map with sampler A, each at its own size: luma as a
+//                           1-channel image (H, W), chroma as a 2-channel image (H/2, W/2) centred on 128, so that sampler
+//                           A's black border is luma 0, chroma 128 (neutral) and not a green edge.  One launch renders both
+//                           planes of every frame: blockIdx.x runs over the luma tiles, then the chroma tiles.
+//
+// Every kernel is bit-identical to a composition of pinned entry points (stated at each); this translation unit is compiled
+// with -ffp-contract=off like frames.hip and warp_kernels.hip.  The map comes from tps_stage / tps_map_rows and the blend from
+// sample_a_blend (warp_device.h); only the tap ADDRESSES are formed here, because a plane's rows are `pitch` bytes apart.
+#include <cstdint>
+
+#include "frames_device.h"
+#include "warp_device.h"
+
+namespace dvsg {
+namespace {
+
+// int(round(c * 2**20)) of the matrix's decimals; row = DVSG_YUV_*
+struct YuvCoef {
+  int cy, cvr, cvg, cug, cub;
+};
+constexpr YuvCoef kYuv[2] = {
+    {1220542, 1673527, -852492, -409993, 2116026},   // BT.601 limited: 1.164, 1.596, -0.813, -0.391, 2.018 (OpenCV's)
+    {1220945, 1879825, -558796, -223608, 2215014},   // BT.709 limited: 1.164384, 1.792741, -0.532909, -0.213249, 2.112402
+};
+
+struct Rgb {
+  int c[3];   // R, G, B in [0, 255]
+};
+
+__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// int32 throughout: |sum| < 2^30; >> on a negative int is arithmetic
+__device__ __forceinline__ Rgb yuv_to_rgb(int Y, int U, int V, const YuvCoef k) {
+  const int y = max(0, Y - 16) * k.cy, u = U - 128, v = V - 128;
+  Rgb o;
+  o.c[0] = sat8((y + k.cvr * v + (1 << 19)) >> 20);
+  o.c[1] = sat8((y + k.cvg * v + k.cug * u + (1 << 19)) >> 20);
+  o.c[2] = sat8((y + k.cub * u + (1 << 19)) >> 20);
+  return o;
+}
+
+// the planes of a batch of frames
+struct Nv12 {
+  const uint8_t *y, *uv;
+  size_t pitch, frame_stride;
+};
+
+// 4 consecutive bytes of a row: one dword load where the address allows, byte loads otherwise; `n` (2 or 4) are valid
+__device__ __forceinline__ uint32_t load4(const uint8_t *p, int n) {
+  if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) return *reinterpret_cast<const uint32_t *>(p);
+  uint32_t w = 0;
+  for (int i = 0; i < n; ++i) w |= (uint32_t)p[i] << (8 * i);
+  return w;
+}
+
+// One thread converts a block of 2 rows x 4 columns (8 luma bytes, 2 UV pairs in; 24 bytes out); the last block of a row
+// holds 2 columns when W % 4 == 2.  blockIdx.y is the frame.
+__global__ __launch_bounds__(kThreads) void nv12_to_rgb_kernel(Nv12 s, int H, int W, YuvCoef k, int flip,
+                                                               uint8_t *__restrict__ dst) {
+  const size_t f = blockIdx.y;
+  const uint8_t *yp = s.y + f * s.frame_stride, *uvp = s.uv + f * s.frame_stride;
+  const int per_row = (W + 3) / 4;
+  const size_t nblocks = (size_t)(H / 2) * per_row;
+  for (size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x; g < nblocks; g += (size_t)gridDim.x * kThreads) {
+    const int bi = (int)(g / per_row);
+    const int j0 = 4 * (int)(g - (size_t)bi * per_row);
+    const int ncol = W - j0 < 4 ? W - j0 : 4;
+    const uint32_t cw = load4(uvp + (size_t)bi * s.pitch + j0, ncol);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = 2 * bi + r;
+      const uint32_t yw = load4(yp + (size_t)i * s.pitch + j0, ncol);
+      uint8_t o[12];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int sh = 16 * (q >> 1);
+        const Rgb p = yuv_to_rgb((yw >> (8 * q)) & 255, (cw >> sh) & 255, (cw >> (sh + 8)) & 255, k);
+        o[3 * q] = (uint8_t)p.c[flip ? 2 : 0];
+        o[3 * q + 1] = (uint8_t)p.c[1];
+        o[3 * q + 2] = (uint8_t)p.c[flip ? 0 : 2];
+      }
+      uint8_t *d = dst + ((f * H + i) * W + j0) * 3;
+      if (ncol == 4 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+        uint32_t *d4 = reinterpret_cast<uint32_t *>(d);
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+          d4[w] = (uint32_t)o[4 * w] | ((uint32_t)o[4 * w + 1] << 8) | ((uint32_t)o[4 * w + 2] << 16) | ((uint32_t)o[4 * w + 3] << 24);
+      } else {
+        for (int e = 0; e < 3 * ncol; ++e) d[e] = o[e];
+      }
+    }
+  }
+}
+
+// Same size: one thread converts 4 consecutive pixels of a row (4 luma bytes, 2 UV pairs in; 48 bytes out), the values of
+// frames_u8_to_f32_kernel on the converted bytes.  Frame blockIdx.y goes to pool frame slots[blockIdx.y].
+__global__ __launch_bounds__(kThreads) void ingest_nv12_kernel(Nv12 s, int H, int W, YuvCoef k, float *__restrict__ pool,
+                                                               const int *__restrict__ slots, int n_pool) {
+  const size_t f = blockIdx.y;
+  const int sl = slots[f];
+  if (!slot_ok(sl, n_pool)) return;
+  const uint8_t *yp = s.y + f * s.frame_stride, *uvp = s.uv + f * s.frame_stride;
+  float *dst = pool + (size_t)sl * H * W * 3;
+  const int per_row = (W + 3) / 4;
+  const size_t ngroups = (size_t)H * per_row;
+  for (size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * kThreads) {
+    const int i = (int)(g / per_row);
+    const int j0 = 4 * (int)(g - (size_t)i * per_row);
+    const int ncol = W - j0 < 4 ? W - j0 : 4;
+    const uint32_t yw = load4(yp + (size_t)i * s.pitch + j0, ncol);
+    const uint32_t cw = load4(uvp + (size_t)(i >> 1) * s.pitch + j0, ncol);
+    float v[12];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int sh = 16 * (q >> 1);
+      const Rgb p = yuv_to_rgb((yw >> (8 * q)) & 255, (cw >> sh) & 255, (cw >> (sh + 8)) & 255, k);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[3 * q + c] = (float)((double)p.c[c] / 255.0);
+    }
+    float *d = dst + ((size_t)i * W + j0) * 3;
+    if (ncol == 4 && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+      float4 *d4 = reinterpret_cast<float4 *>(d);
+      d4[0] = make_float4(v[0], v[1], v[2], v[3]);
+      d4[1] = make_float4(v[4], v[5], v[6], v[7]);
+      d4[2] = make_float4(v[8], v[9], v[10], v[11]);
+    } else {
+      for (int e = 0; e < 3 * ncol; ++e) d[e] = v[e];
+    }
+  }
+}
+
+// RGB of luma pixel (i, j) of a frame
+__device__ __forceinline__ Rgb nv12_pixel(const uint8_t *yp, const uint8_t *uvp, size_t pitch, int i, int j, const YuvCoef k) {
+  const uint8_t *c = uvp + (size_t)(i >> 1) * pitch + (j & ~1);
+  return yuv_to_rgb(yp[(size_t)i * pitch + j], c[0], c[1], k);
+}
+
+// resize_u8_kernel (flip = 0, no uint8 half) on the converted frame: the same tap rule, the same float64 operations in the
+// same order; the four taps are converted here instead of read from an RGB image.
+__global__ __launch_bounds__(kThreads) void ingest_nv12_resize_kernel(Nv12 s, int n, int sh, int sw, YuvCoef k,
+                                                                      float *__restrict__ dst, int dh, int dw,
+                                                                      const int *__restrict__ slots, int n_pool) {
+  const double scale_x = (double)sw / dw, scale_y = (double)sh / dh;
+  const size_t total = (size_t)n * dh * dw;
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
+    const int dx = (int)(e % dw);
+    const size_t t = e / dw;
+    const int dy = (int)(t % dh);
+    const size_t f = t / dh;
+    const int sl = slots[f];
+    if (!slot_ok(sl, n_pool)) continue;
+    const size_t de = ((size_t)sl * dh + dy) * dw + dx;
+    const ResizeTap tx = resize_tap(dx, scale_x, sw), ty = resize_tap(dy, scale_y, sh);
+    const uint8_t *yp = s.y + f * s.frame_stride, *uvp = s.uv + f * s.frame_stride;
+    const Rgb q00 = nv12_pixel(yp, uvp, s.pitch, ty.s0, tx.s0, k), q01 = nv12_pixel(yp, uvp, s.pitch, ty.s0, tx.s1, k);
+    const Rgb q10 = nv12_pixel(yp, uvp, s.pitch, ty.s1, tx.s0, k), q11 = nv12_pixel(yp, uvp, s.pitch, ty.s1, tx.s1, k);
+    const double a1 = (double)tx.w1, a0 = (double)(1.f - tx.w1);
+    const double b1 = (double)ty.w1, b0 = (double)(1.f - ty.w1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double p00 = (double)q00.c[c] / 255.0, p01 = (double)q01.c[c] / 255.0;
+      const double p10 = (double)q10.c[c] / 255.0, p11 = (double)q11.c[c] / 255.0;
+      const double h0 = __dadd_rn(__dmul_rn(p00, a0), __dmul_rn(p01, a1));
+      const double h1 = __dadd_rn(__dmul_rn(p10, a0), __dmul_rn(p11, a1));
+      const double v = __dadd_rn(__dmul_rn(h0, b0), __dmul_rn(h1, b1));
+      dst[de * 3 + c] = (float)v;
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------------------
+// Render.
+// ----------------------------------------------------------------------------------------
+// A plane's sample as the float32 image dvsg_tps_warp_f32 would be given.  Luma: (float)((double)Y / 255.0); chroma:
+// (float)(((double)c - 128.0) / 255.0).  One correctly rounded float32 division of the exact integer gives the same value
+// for every byte (exhaustive on the host: tests/test_nv12_cpu.py; the luma case is load_pix<C>(const uint8_t *)'s).
+template <int C>
+__device__ __forceinline__ Pix<C> load_plane(const uint8_t *__restrict__ p) {
+  Pix<C> r;
+  if constexpr (C == 1) {
+    r.v[0] = (float)p[0] / 255.0f;
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) r.v[c] = (float)((int)p[c] - 128) / 255.0f;
+  }
+  return r;
+}
+
+// sample_a_load on a plane whose rows are `pitch` bytes apart: its coordinate, index and weight expressions in its order,
+// C bytes per sample.  The indices are clipped into the plane, so every tap address lies inside it.
+template <int C>
+__device__ __forceinline__ void plane_a_load(const uint8_t *__restrict__ img, size_t pitch, int H, int W, float xs, float ys,
+                                             TapsA<C> &t) {
+  const float x = ((xs + 1.0f) * (float)W) / 2.0f;  // :48
+  const float y = ((ys + 1.0f) * (float)H) / 2.0f;  // :49
+  int x0 = f2i(floorf(x));
+  int y0 = f2i(floorf(y));
+  int x1 = x0 + 1;
+  int y1 = y0 + 1;
+  x0 = clampi(x0, 0, W - 1);  // :57-60
+  x1 = clampi(x1, 0, W - 1);
+  y0 = clampi(y0, 0, H - 1);
+  y1 = clampi(y1, 0, H - 1);
+  const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
+  t.wa = (x1f - x) * (y1f - y);  // :85-88
+  t.wb = (x1f - x) * (y - y0f);
+  t.wc = (x - x0f) * (y1f - y);
+  t.wd = (x - x0f) * (y - y0f);
+  t.a = load_plane<C>(img + (size_t)y0 * pitch + x0 * C);  // (x0,y0)
+  t.b = load_plane<C>(img + (size_t)y1 * pitch + x0 * C);  // (x0,y1)
+  t.c = load_plane<C>(img + (size_t)y0 * pitch + x1 * C);  // (x1,y0)
+  t.d = load_plane<C>(img + (size_t)y1 * pitch + x1 * C);  // (x1,y1)
+}
+
+// chroma back to a byte: clamp(floor((double)v * 255.0 + 128.5), 0, 255); NaN gives 0 like to_u8
+__device__ __forceinline__ uint8_t chroma_u8(float v) {
+  const double d = (double)v * 255.0 + 128.5;
+  return d >= 255.0 ? (uint8_t)255 : (d > 0.0 ? (uint8_t)(int)d : (uint8_t)0);
+}
+
+// One output column and kTpsRows rows of one plane (ph x pw samples of C bytes), source and output of the same size.
+template <int C>
+__device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, size_t pitch, int ph, int pw, int i0, int j,
+                                             const float (&xs)[4], const float (&ys)[4], uint8_t *__restrict__ out,
+                                             size_t out_pitch) {
+  TapsA<C> taps[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (i0 + r >= ph) break;
+    plane_a_load<C>(src, pitch, ph, pw, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = i0 + r;
+    if (i >= ph) break;
+    float v[C];
+    sample_a_blend<C>(taps[r], C, v);
+    uint8_t *d = out + (size_t)i * out_pitch + (size_t)j * C;
+    if constexpr (C == 1) {
+      d[0] = to_u8((double)v[0]);
+    } else {
+      const uint8_t u = chroma_u8(v[0]), w = chroma_u8(v[1]);
+      if ((reinterpret_cast<uintptr_t>(d) & 1) == 0) {
+        *reinterpret_cast<uint16_t *>(d) = (uint16_t)((uint16_t)u | ((uint16_t)w << 8));
+      } else {
+        d[0] = u;
+        d[1] = w;
+      }
+    }
+  }
+}
+
+// blockIdx.y: the frame.  blockIdx.x: the luma tiles (kThreads columns x kTpsRows rows, row-major, gx_l per row group), then
+// from n_l on the chroma tiles (gx_c per row group).  A tile's map is dvsg_tps_warp_f32's on a grid of the plane's size.
+__global__ __launch_bounds__(kThreads) void nv12_render_kernel(Nv12 s, const float *__restrict__ coord,
+                                                               const float *__restrict__ T, int H, int W, int P,
+                                                               float sx_l, float sy_l, float sx_c, float sy_c, int gx_l,
+                                                               int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                               uint8_t *__restrict__ out_uv, size_t out_pitch,
+                                                               size_t out_frame_stride) {
+  __shared__ float4 sp[64];
+  __shared__ float4 sdy[64];
+  __shared__ float sa[6];
+  const int b = blockIdx.y, t = threadIdx.x;
+  int id = blockIdx.x;
+  const bool chroma = id >= n_l;
+  if (chroma) id -= n_l;
+  const int gx = chroma ? gx_c : gx_l;
+  const int i0 = (id / gx) * kTpsRows;
+  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
+  const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
+  tps_stage<true>(coord, 0, T, b, P, t, i0, step_y, sp, sdy, sa);
+  __syncthreads();
+  const int j = (id % gx) * kThreads + t;
+  if (j >= pw) return;
+  const float x_t = -1.0f + step_x * (float)j;  // tf.linspace: start + step * i (:94)
+  float xs[4], ys[4];
+  tps_map_rows<true>(sp, sdy, sa, P, x_t, step_y, i0, xs, ys);
+  const size_t in_off = (size_t)b * s.frame_stride, out_off = (size_t)b * out_frame_stride;
+  if (chroma)
+    render_plane<2>(s.uv + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_uv + out_off, out_pitch);
+  else
+    render_plane<1>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
+}
+
+inline int grid_for(size_t items, int cap = 1 << 16) {
+  const size_t b = (items + kThreads - 1) / kThreads;
+  return (int)(b < (size_t)cap ? (b ? b : 1) : (size_t)cap);
+}
+
+// the layout of a batch of NV12 frames (see the header)
+int check_nv12(const char *fn, const char *what, const void *y, const void *uv, size_t pitch, size_t frame_stride, int n, int H,
+               int W) {
+  DVSG_REQUIRE(y && uv, "%s: NULL %s plane", fn, what);
+  DVSG_REQUIRE(n >= 1 && n <= 65535, "%s: n=%d outside [1, 65535]", fn, n);
+  DVSG_REQUIRE(H >= 4 && W >= 4 && H % 2 == 0 && W % 2 == 0, "%s: NV12 frames are even-sized and at least 4x4, got H=%d W=%d",
+               fn, H, W);
+  DVSG_REQUIRE((long)H * W < (1L << 31), "%s: frame %dx%d too large", fn, H, W);
+  DVSG_REQUIRE(pitch >= (size_t)W, "%s: %s pitch=%zu < W=%d", fn, what, pitch, W);
+  DVSG_REQUIRE(n == 1 || frame_stride >= (size_t)H * pitch, "%s: %s frame_stride=%zu < H * pitch = %zu", fn, what, frame_stride,
+               (size_t)H * pitch);
+  return DVSG_OK;
+}
+
+int check_matrix(const char *fn, int matrix) {
+  DVSG_REQUIRE(matrix == DVSG_YUV_BT601_LIMITED || matrix == DVSG_YUV_BT709_LIMITED,
+               "%s: matrix=%d is neither DVSG_YUV_BT601_LIMITED (0) nor DVSG_YUV_BT709_LIMITED (1)", fn, matrix);
+  return DVSG_OK;
+}
+
+}  // namespace
+
+int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
+                          int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
+                          size_t out_frame_stride) {
+  const char *fn = "dvsg_tps_render_nv12";
+  DVSG_REQUIRE(F_t && T, "%s: NULL pointer", fn);
+  if (int rc = check_nv12(fn, "source", y, uv, pitch, frame_stride, n, H, W)) return rc;
+  return check_nv12(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, H, W);
+}
+
+// the arguments have passed tps_render_nv12_check
+int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
+                         size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
+                         uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream) {
+  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream)) return rc;
+  const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
+  const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(H / 2, kTpsRows);
+  DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);
+  hipStream_t s = as_stream(stream);
+  // algorithmic bytes: both planes once in, once out
+  ProfScope prof(kClsTpsWarp, s, 0.0, 3.0 * n * H * W);
+  hipLaunchKernelGGL(nv12_render_kernel, dim3((unsigned)(n_l + n_c), n), dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride},
+                     coord, T, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y,
+                     out_uv, out_pitch, out_frame_stride);
+  return check_launch("nv12_render_kernel");
+}
+
+}  // namespace dvsg
+
+using namespace dvsg;
+
+extern "C" {
+
+int dvsg_frames_nv12_to_rgb_u8(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int H, int W,
+                               int matrix, int channel_flip, uint8_t *dst, void *stream) {
+  const char *fn = "dvsg_frames_nv12_to_rgb_u8";
+  DVSG_REQUIRE(dst, "%s: NULL dst", fn);
+  if (int rc = check_nv12(fn, "source", y, uv, pitch, frame_stride, n, H, W)) return rc;
+  if (int rc = check_matrix(fn, matrix)) return rc;
+  const size_t blocks = (size_t)(H / 2) * ((W + 3) / 4);
+  hipLaunchKernelGGL(nv12_to_rgb_kernel, dim3(grid_for(blocks), n), dim3(kThreads), 0, as_stream(stream),
+                     Nv12{y, uv, pitch, frame_stride}, H, W, kYuv[matrix], channel_flip ? 1 : 0, dst);
+  return check_launch("nv12_to_rgb_kernel");
+}
+
+int dvsg_frames_ingest_nv12(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int src_H, int src_W,
+                            int matrix, float *pool, int n_pool, const int32_t *slots, int dst_H, int dst_W, void *stream) {
+  const char *fn = "dvsg_frames_ingest_nv12";
+  DVSG_REQUIRE(pool && slots, "%s: NULL pointer", fn);
+  if (int rc = check_nv12(fn, "source", y, uv, pitch, frame_stride, n, src_H, src_W)) return rc;
+  if (int rc = check_matrix(fn, matrix)) return rc;
+  DVSG_REQUIRE(n_pool > 0 && dst_H > 0 && dst_W > 0, "%s: bad shape n_pool=%d dst=%dx%d", fn, n_pool, dst_H, dst_W);
+  const Nv12 s{y, uv, pitch, frame_stride};
+  if (src_H == dst_H && src_W == dst_W) {
+    const size_t groups = (size_t)src_H * ((src_W + 3) / 4);
+    hipLaunchKernelGGL(ingest_nv12_kernel, dim3(grid_for(groups), n), dim3(kThreads), 0, as_stream(stream), s, src_H, src_W,
+                       kYuv[matrix], pool, slots, n_pool);
+    return check_launch("ingest_nv12_kernel");
+  }
+  hipLaunchKernelGGL(ingest_nv12_resize_kernel, dim3(grid_for((size_t)n * dst_H * dst_W)), dim3(kThreads), 0, as_stream(stream),
+                     s, n, src_H, src_W, kYuv[matrix], pool, dst_H, dst_W, slots, n_pool);
+  return check_launch("ingest_nv12_resize_kernel");
+}
+
+}  // extern "C"

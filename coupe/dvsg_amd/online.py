@@ -23,6 +23,9 @@ import torch
 from .clip import SKIP_LENGTH, _check_window, check_skip_length, render_source_into
 
 
+YUV_MATRICES = {"bt601": 0, "bt709": 1}   # DVSG_YUV_BT601_LIMITED, DVSG_YUV_BT709_LIMITED
+
+
 def stream_window_row(k, base, skip_length=SKIP_LENGTH):
     """Window of step k of a stream whose ring starts at pool frame `base`: (row int32 [S], out_slot), where row[s] is
     the pool frame window slot s reads (eval.py:103's `sample_idx` on the ring) and out_slot the history slot that
@@ -65,14 +68,34 @@ class OnlineStabilizer(object):
     the step's F_t warps the source frame itself (`dvsg_tps_render_u8`, one launch per distinct source size, reading the
     device copy ingest made), float32 [H0,W0,3] or uint8 with as_uint8, and side [H0,2 W0,3] = (source bytes | render)
     with side_by_side.  The recurrence is unchanged: the pool, F_t and the model-size history are those of a run
-    without it.  Float frames carry no source beyond the model's size and raise ValueError."""
+    without it.  Float frames carry no source beyond the model's size and raise ValueError.
+
+    frame_format="nv12": frames arrive and leave as a decoder's NV12 surfaces, a 2-D uint8 array or device tensor
+    [3 H0 / 2, W0] (H0 rows of Y, then H0 / 2 rows of interleaved UV; H0, W0 even), converted with yuv_matrix ("bt709" or
+    "bt601", limited range).  source_res is implied: the output of a stream is its stabilised frame in the same layout
+    at source size.  Per distinct source size one `dvsg_frames_ingest_nv12` launch converts and resizes straight into
+    the input slots and one `dvsg_tps_render_nv12` launch warps both planes of the device copy ingest read; the step
+    itself is still the one `dvsg_stabilize_ring_inplace_f32` call, on the same pool of model-size float RGB frames.
+    side_by_side, as_uint8, channel_order="bgr", float frames and odd sizes raise ValueError."""
 
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
-                 as_uint8=False, source_res=False):
+                 as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709"):
         from . import _lib
         from ._tensor import device
         if channel_order not in ("rgb", "bgr"):
             raise ValueError("channel_order must be 'rgb' or 'bgr'")
+        if frame_format not in ("rgb", "nv12"):
+            raise ValueError("frame_format must be 'rgb' or 'nv12', got %r" % (frame_format,))
+        if yuv_matrix not in YUV_MATRICES:
+            raise ValueError("yuv_matrix must be 'bt709' or 'bt601', got %r" % (yuv_matrix,))
+        if frame_format == "nv12":
+            if side_by_side:
+                raise ValueError("frame_format='nv12' has no side_by_side layout: an NV12 frame has two planes")
+            if as_uint8:
+                raise ValueError("frame_format='nv12' always returns uint8 NV12 frames: as_uint8 does not apply")
+            if channel_order != "rgb":
+                raise ValueError("frame_format='nv12' has no channel_order: the pool is RGB, got %r" % (channel_order,))
+            source_res = True
         if model.locnet is None:
             raise _lib.DvsgError("StabNet has no weights: call load_weights()/load_ckpt() first")
         skip = check_skip_length(skip_length)
@@ -87,6 +110,7 @@ class OnlineStabilizer(object):
         self.h, self.w = model.h, model.w
         self.flip = 1 if channel_order == "bgr" else 0
         self.side_by_side, self.as_uint8, self.source_res = bool(side_by_side), bool(as_uint8), bool(source_res)
+        self.frame_format, self.yuv_matrix = frame_format, YUV_MATRICES[yuv_matrix]
         dev = device()
         self.pool = torch.empty((self.max_streams * self.frames_per_stream, self.h, self.w, 3), dtype=torch.float32,
                                 device=dev)
@@ -130,12 +154,28 @@ class OnlineStabilizer(object):
         """`step` for a single stream: its output for `frame`."""
         return self.step({sid: frame})[sid]
 
+    def _slot_tables(self, entries):
+        """The step's slot rows for `entries` (ring at [4], step count at [5]) in batch order: the host array
+        [table B*S | out slots B | input slots B] and its three parts on the device."""
+        from ._tensor import device
+        B, S = len(entries), len(self.skip_length)
+        rows = np.empty(B * S + 2 * B, dtype=np.int32)     # [table B*S | out slots B | input slots B]
+        for i, (_, _, _, _, ring, k) in enumerate(entries):
+            base = ring * self.frames_per_stream
+            rows[i * S:(i + 1) * S], rows[B * S + i] = stream_window_row(k, base, self.skip_length)
+            rows[B * S + B + i] = base + self.span + 1
+        # a fresh pinned buffer per step: the caching host allocator does not hand it out again before this copy is done
+        idx = torch.from_numpy(rows).pin_memory().to(device(), non_blocking=True)
+        return rows, idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:]
+
     def step(self, frames):
         """One step of every stream in `frames` ({sid: frame}); returns {sid: output}."""
         from . import _lib
         from ._tensor import device, ptr, stream
         if not frames:
             return {}
+        if self.frame_format == "nv12":
+            return self._step_nv12(frames)
         dev = device()
         h, w, flip = self.h, self.w, self.flip
         # ---- check everything before the first launch: a bad frame leaves every stream as it was
@@ -162,15 +202,9 @@ class OnlineStabilizer(object):
         # batch order: resized uint8 by source size, same-size uint8, float, float64 -- each group is a contiguous
         # range of the step's slot rows
         entries.sort(key=lambda e: e[0])
-        B, S = len(entries), len(self.skip_length)
-        rows = np.empty(B * S + 2 * B, dtype=np.int32)     # [table B*S | out slots B | input slots B]
-        for i, (_, _, _, _, ring, k) in enumerate(entries):
-            base = ring * self.frames_per_stream
-            rows[i * S:(i + 1) * S], rows[B * S + i] = stream_window_row(k, base, self.skip_length)
-            rows[B * S + B + i] = base + self.span + 1
-        # a fresh pinned buffer per step: the caching host allocator does not hand it out again before this copy is done
-        idx = torch.from_numpy(rows).pin_memory().to(dev, non_blocking=True)
-        table, out_slots, in_slots = idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:]
+        B = len(entries)
+        rows, table, out_slots, in_slots = self._slot_tables(entries)
+        S = len(self.skip_length)
         n_pool = int(self.pool.shape[0])
         side = torch.empty((B, h, 2 * w, 3), dtype=torch.uint8, device=dev) \
             if self.side_by_side and not self.source_res else None
@@ -251,12 +285,67 @@ class OnlineStabilizer(object):
                 res[e[1]] = (o, sd) if self.side_by_side else o
         return res
 
+    def _step_nv12(self, frames):
+        """`step` for frame_format="nv12": ingest per source size, the one stabilise call, render per source size."""
+        from . import _lib
+        from ._tensor import device, ptr, stream
+        dev = device()
+        h, w = self.h, self.w
+        # ---- check everything before the first launch: a bad frame leaves every stream as it was
+        entries = []
+        for sid, fr in frames.items():
+            ring, k = self._stream(sid)
+            host = not isinstance(fr, torch.Tensor)
+            t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
+            if t.dtype.is_floating_point:
+                raise ValueError("stream %r: frame_format='nv12' takes uint8 surfaces, not float frames (%s)" % (sid, t.dtype))
+            if t.dtype != torch.uint8:
+                raise TypeError("stream %r: NV12 frames must be uint8, got %s" % (sid, t.dtype))
+            if t.dim() != 2:
+                raise ValueError("stream %r: an NV12 frame must be [3*H0/2, W0], got %s" % (sid, tuple(t.shape)))
+            R, W0 = int(t.shape[0]), int(t.shape[1])
+            H0 = 2 * R // 3
+            if R % 3 or H0 % 2 or W0 % 2 or H0 < 4 or W0 < 4:
+                raise ValueError("stream %r: an NV12 frame [3*H0/2, W0] needs even H0, W0 >= 4 (odd sizes have no chroma "
+                                 "layout), got %s" % (sid, tuple(t.shape)))
+            entries.append(((H0, W0), sid, host, t, ring, k))
+        entries.sort(key=lambda e: e[0])   # one contiguous batch range per source size
+        B = len(entries)
+        _, table, out_slots, in_slots = self._slot_tables(entries)
+        n_pool = int(self.pool.shape[0])
+        groups = []   # (i, j, device frames [j-i, 3 H0 / 2, W0])
+        i = 0
+        while i < B:
+            (H0, W0), j = entries[i][0], i
+            while j < B and entries[j][0] == (H0, W0):
+                j += 1
+            src = torch.stack([e[3].to(dev) for e in entries[i:j]]).contiguous()
+            _lib.call("dvsg_frames_ingest_nv12", ptr(src), ptr(src) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0,
+                      self.yuv_matrix, ptr(self.pool), n_pool, ptr(in_slots[i:j]), h, w, stream())
+            groups.append((i, j, src))
+            i = j
+        self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
+        for e in entries:
+            self._streams[e[1]][1] += 1
+        res = {}
+        for i, j, src in groups:
+            H0, W0 = entries[i][0]
+            out = torch.empty_like(src)
+            _lib.call("dvsg_tps_render_nv12", self.model.locnet.handle, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * W0, W0,
+                      3 * H0 // 2 * W0, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * W0, W0,
+                      3 * H0 // 2 * W0, stream())
+            out_h = out.cpu().numpy() if any(entries[b][2] for b in range(i, j)) else None
+            for b in range(i, j):
+                res[entries[b][1]] = out_h[b - i] if entries[b][2] else out[b - i]
+        return {sid: res[sid] for sid in frames}
+
 
 def stabilize_clips(model, clips, batch=None, **kw):
     """eval.py:76-124 for K whole clips at once: the clips run through one `OnlineStabilizer` of `batch` streams
     (default K) in lockstep, so each step is one batched call and every clip keeps its own recurrence exactly.  Clips
     may differ in length (a finished clip's ring goes to the next waiting clip).  `kw` are OnlineStabilizer's options.
-    Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips)."""
+    Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips).  With
+    frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result."""
     from ._tensor import device
     K = len(clips)
     if K == 0:
@@ -267,7 +356,10 @@ def stabilize_clips(model, clips, batch=None, **kw):
     dclips = []
     for c, hst in zip(clips, host):
         t = (torch.as_tensor(np.ascontiguousarray(c)) if hst else c).to(dev).contiguous()
-        if t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+        if kw.get("frame_format", "rgb") == "nv12":
+            if t.dim() != 3 or t.shape[0] < 1:
+                raise ValueError("every NV12 clip must be [N,3*H0/2,W0] with N >= 1, got %s" % (tuple(t.shape),))
+        elif t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
             raise ValueError("every clip must be [N,h,w,3] with N >= 1, got %s" % (tuple(t.shape),))
         dclips.append(t)
     on = OnlineStabilizer(model, max_streams=batch, **kw)

@@ -5,6 +5,9 @@ example: a seeded synthetic uint8 source stands in for it, BGR and larger than t
 it over (eval.py:76-81 resizes it).
 
     python examples/stabilize_stream.py [--streams 2] [--frames 48] [--height 288] [--width 512] [--precision f32|f32x3]
+
+--format nv12: the source hands over NV12 surfaces [3 H0 / 2, W0] as a hardware decoder does (built on the host here) and
+each step returns the stabilised surfaces at source size in the same layout, ready for an encoder.
 """
 import argparse
 import os
@@ -30,6 +33,16 @@ def synthetic_source(seed, n, h, w):
         yield np.ascontiguousarray(bank[k % 8])
 
 
+def synthetic_nv12_source(seed, n, h, w):
+    """Yields n NV12 frames [3h/2, w] uint8 (h rows of Y, h/2 rows of U0 V0 U1 V1 ...), limited range, one at a time."""
+    import inputs
+    y = 16 + inputs.smooth_frames(seed, 8, h, w, C=1)[..., 0] * 219
+    c = 16 + inputs.smooth_frames(seed + 100, 8, h // 2, w // 2, C=2) * 224
+    bank = np.concatenate([y, c.reshape(8, h // 2, w)], axis=1).astype(np.uint8)
+    for k in range(n):
+        yield np.ascontiguousarray(bank[k % 8])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=2)
@@ -37,19 +50,31 @@ def main():
     ap.add_argument("--height", type=int, default=288)    # config.py:12-13
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--precision", default="f32", choices=["f32", "f32x3", "f32s", "f16"])
+    ap.add_argument("--format", default="rgb", choices=["rgb", "nv12"])
     args = ap.parse_args()
     net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0))
     net.precision = args.precision
-    stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True)
-    sources = {stab.open(): synthetic_source(s + 1, args.frames, args.height * 3 // 2, args.width * 3 // 2)
-               for s in range(args.streams)}
+    nv12 = args.format == "nv12"
+    if nv12:
+        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709")
+        make = synthetic_nv12_source
+    else:
+        stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True)
+        make = synthetic_source
+    H0, W0 = args.height * 3 // 2, args.width * 3 // 2
+    if nv12:
+        H0, W0 = H0 // 2 * 2, W0 // 2 * 2   # NV12 needs even sizes
+    sources = {stab.open(): make(s + 1, args.frames, H0, W0) for s in range(args.streams)}
     lat = []
     for k in range(args.frames):
         frames = {sid: next(src) for sid, src in sources.items()}
         t0 = time.perf_counter()
         outs = stab.step(frames)            # NumPy in -> NumPy out: the step has finished when it returns
         lat.append(time.perf_counter() - t0)
-        if k == 0:
+        if k == 0 and nv12:
+            out = next(iter(outs.values()))
+            print("per stream and step: stabilised NV12 surface", out.shape, out.dtype)
+        elif k == 0:
             out, side = next(iter(outs.values()))
             print("per stream and step: stabilised", out.shape, out.dtype, "| side-by-side", side.shape, side.dtype)
     for sid in list(sources):

@@ -402,6 +402,57 @@ int dvsg_frames_f32_to_u8_slots(const float *pool, int n_pool, const int32_t *sl
 int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
                        int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream);
 /* ---------------------------------------------------------------------------------------
+ * NV12 frames (coupe.dvsg_amd.online, frame_format="nv12"): what a hardware decoder hands over and an encoder takes.
+ * Layout of a batch of n frames of H x W (H, W even, >= 4):
+ *   y   uint8: row i of frame f at y + f * frame_stride + i * pitch, W bytes used;
+ *   uv  uint8: row i of frame f at uv + f * frame_stride + i * pitch, W bytes used: U0 V0 U1 V1 ..., H / 2 rows;
+ *   pitch  the row pitch in bytes, >= W; frame_stride in bytes (>= H * pitch when n > 1; both planes use the same two).
+ * A packed tensor [n, 3 H / 2, W] has uv = y + H * pitch, pitch = W, frame_stride = 3 H / 2 * W; a decoder surface with an
+ * aligned luma height passes its own uv pointer.  Outputs are described the same way (out_y, out_uv, out_pitch,
+ * out_frame_stride) and must not overlap the inputs; bytes of a row beyond W are never written.
+ *
+ * YUV -> RGB is integer arithmetic with shift 20, exact and the same on every run (OpenCV's published COLOR_YUV2RGB_NV12
+ * scheme; OpenCV is not on the build machine: parity with cv2 is unpinned, as for the resize).  The chroma of luma pixel
+ * (i, j) is the sample (i / 2, j / 2), replicated, no interpolation.  On int32 (the sums stay below 2^30; >> arithmetic):
+ *     y = max(0, Y - 16) * CY;  u = U - 128;  v = V - 128
+ *     R = sat8((y + CVR * v           + 2^19) >> 20)
+ *     G = sat8((y + CVG * v + CUG * u + 2^19) >> 20)
+ *     B = sat8((y + CUB * u           + 2^19) >> 20)
+ *   matrix                      CY       CVR      CVG      CUG      CUB     = int(round(c * 2^20)) of
+ *   DVSG_YUV_BT601_LIMITED (0)  1220542  1673527  -852492  -409993  2116026   1.164, 1.596, -0.813, -0.391, 2.018 (OpenCV's)
+ *   DVSG_YUV_BT709_LIMITED (1)  1220945  1879825  -558796  -223608  2215014   1.164384, 1.792741, -0.532909, -0.213249,
+ *                                                                            2.112402
+ *   dvsg_frames_nv12_to_rgb_u8  the conversion into dst [n,H,W,3] uint8, RGB, or BGR with channel_flip.  n <= 65535.
+ *   dvsg_frames_ingest_nv12  frame i into float32 pool frame slots[i] (int32 [n] on the device) at (dst_H, dst_W), RGB:
+ *          bit-identical to dvsg_frames_nv12_to_rgb_u8(channel_flip = 0) followed by dvsg_frames_ingest_u8(channel_flip = 0,
+ *          u8_dst = NULL), on the same-size path ((float)(v / 255.) of the float64 quotient) and on the resize path (the
+ *          cv2-style float64 bilinear of dvsg_frames_resize_u8_f32: same tap rule, same operations in the same order).  The
+ *          source-size RGB image never exists: each output pixel converts its (at most four) taps.  A slot outside
+ *          [0, n_pool) skips its frame.  n <= 65535.
+ *   dvsg_tps_render_nv12  the stabilised frame at source resolution, NV12 in and out: F_t [n,25,2] -> T [n,2,28] (written
+ *          exactly as dvsg_tps_render_u8 writes it, bit for bit), then ONE launch that warps both planes of all n frames.
+ *          Each plane is an image of its own size warped by the same normalised TPS map with sampler A, i.e.
+ *          dvsg_tps_warp_f32(plane, V_src, T, out = the plane's size) bit for bit on
+ *            luma    C = 1, (H, W):          in (float)((double)Y / 255.0),          out np.uint8(v * 255.) (float64
+ *                                            product, truncation, saturating: dvsg_frames_f32_to_u8's rule);
+ *            chroma  C = 2, (H / 2, W / 2):  in (float)(((double)c - 128.0) / 255.0), out clamp(floor((double)v * 255.0 +
+ *                                            128.5), 0, 255).
+ *          Both byte round trips are exact.  Chroma is warped centred on 128, so sampler A's black border (coincident
+ *          taps) is luma 0 with neutral chroma 128.  The chroma grid is corner-aligned like the luma grid (tf.linspace at
+ *          each plane's size), within one luma pixel of left-sited chroma.  No zoom.  n <= 65535.
+ * Every argument is checked before the first launch.
+ * ------------------------------------------------------------------------------------- */
+#define DVSG_YUV_BT601_LIMITED 0
+#define DVSG_YUV_BT709_LIMITED 1
+int dvsg_frames_nv12_to_rgb_u8(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int H, int W,
+                               int matrix, int channel_flip, uint8_t *dst, void *stream);
+int dvsg_frames_ingest_nv12(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int src_H,
+                            int src_W, int matrix, float *pool, int n_pool, const int32_t *slots, int dst_H, int dst_W,
+                            void *stream);
+int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
+                         size_t frame_stride, int n, int H, int W, float *T, uint8_t *out_y, uint8_t *out_uv,
+                         size_t out_pitch, size_t out_frame_stride, void *stream);
+/* ---------------------------------------------------------------------------------------
  * CROP to the valid region (coupe.dvsg_amd.clip.stabilize_clip(crop=...)).  Sampler A clips its tap indices before it forms
  * the weights, so an output pixel whose source sample lies outside 0 <= x < W - 1, 0 <= y < H - 1 (x = ((x_s + 1) W) / 2 in
  * float32, as the sampler takes it) blends coincident taps with cancelling weights and is 0 (up to the rounding of that sum): the black border of a
