@@ -88,6 +88,11 @@ SIGNATURES = {
     "dvsg_tps_warp_zoom_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "dvsg_tps_coverage_net_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "dvsg_tps_render_zoom_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "dvsg_tps_render_zoom_nv12": [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                  ctypes.c_size_t, ctypes.c_size_t, _vp],
+    "dvsg_tps_coefficients_f32": [_vp, _vp, _i, _vp, _vp],
+    "dvsg_crop_ratchet_f32": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp,
+                              _vp, _vp],
     "dvsg_loss_workspace_bytes": [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t)],
     "dvsg_loss_image_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "dvsg_loss_temporal_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],

@@ -102,6 +102,33 @@ __global__ __launch_bounds__(kThreads) void crop_finish_kernel(const Cover *__re
   }
 }
 
+// The zoom controller of a live stream (dvsg_crop_ratchet_f32): one thread per frame of the step, float64 throughout (this
+// translation unit is compiled with -ffp-contract=off), one rounding to float32 at the end.  state[slot] is read and written
+// by the one thread whose frame names the slot (distinct slots are the caller's contract): no atomics.
+__global__ __launch_bounds__(kThreads) void crop_ratchet_kernel(const int *__restrict__ key_a, int D_a,
+                                                                const int *__restrict__ key_b, int D_b,
+                                                                const int *__restrict__ slots, int n, float *state,
+                                                                int n_state, double margin, double crop_min, double recover,
+                                                                float *__restrict__ zoom, double *__restrict__ free_out) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int sl = slots[i];
+  if (sl < 0 || sl >= n_state) return;
+  double fr = (double)min(key_a[i], D_a) / (double)D_a;
+  if (key_b) {
+    const double fb = (double)min(key_b[i], D_b) / (double)D_b;
+    fr = fb < fr ? fb : fr;
+  }
+  double target = fr - margin;
+  target = target > crop_min ? target : crop_min;
+  target = target < 1.0 ? target : 1.0;
+  const double held = (double)state[sl] + recover;
+  const float z = (float)(target < held ? target : held);
+  state[sl] = z;
+  zoom[i] = z;
+  free_out[i] = fr;
+}
+
 int cover_partials(int out_h, int out_w) { return ceil_div(out_w, kThreads) * ceil_div(out_h, kTpsRows); }
 
 int check_cover_shape(const char *fn, int B, int out_h, int out_w) {
@@ -161,6 +188,22 @@ int dvsg_tps_coverage_f32(const float *coord, const float *T, const float *zoom,
                           void *stream) {
   return tps_coverage_impl("dvsg_tps_coverage_f32", coord, (long)P * 2, T, zoom, B, P, src_H, src_W, out_h, out_w, n_border,
                            key_min, workspace, workspace_bytes, stream);
+}
+
+int dvsg_crop_ratchet_f32(const int32_t *key_min_a, int D_a, const int32_t *key_min_b, int D_b, const int32_t *state_slots,
+                          int n, float *state, int n_state, double margin, double crop_min, double recover, float *zoom,
+                          double *free_out, void *stream) {
+  const char *fn = "dvsg_crop_ratchet_f32";
+  DVSG_REQUIRE(key_min_a && state_slots && state && zoom && free_out, "%s: NULL pointer", fn);
+  DVSG_REQUIRE(n >= 1 && n_state >= 1, "%s: n=%d and n_state=%d must be >= 1", fn, n, n_state);
+  DVSG_REQUIRE(D_a >= 1 && (!key_min_b || D_b >= 1), "%s: D_a=%d, D_b=%d must be >= 1 (D = (out_h - 1)(out_w - 1))", fn, D_a,
+               D_b);
+  DVSG_REQUIRE(margin >= 0.0, "%s: margin=%g must be >= 0", fn, margin);
+  DVSG_REQUIRE(crop_min > 0.0 && crop_min <= 1.0, "%s: crop_min=%g outside (0, 1]", fn, crop_min);
+  DVSG_REQUIRE(recover >= 0.0, "%s: recover=%g must be >= 0", fn, recover);
+  hipLaunchKernelGGL(crop_ratchet_kernel, dim3(ceil_div(n, kThreads)), dim3(kThreads), 0, as_stream(stream), key_min_a, D_a,
+                     key_min_b, D_b, state_slots, n, state, n_state, margin, crop_min, recover, zoom, free_out);
+  return check_launch("crop_ratchet_kernel");
 }
 
 }  // extern "C"

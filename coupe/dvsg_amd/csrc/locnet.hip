@@ -1278,6 +1278,25 @@ int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8
                               out_frame_stride, stream);
 }
 
+// dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
+int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
+                              size_t frame_stride, int n, int H, int W, const float *zoom, float *T, uint8_t *out_y,
+                              uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream) {
+  DVSG_REQUIRE(net, "dvsg_tps_render_zoom_nv12: NULL net");
+  if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
+                                     "dvsg_tps_render_zoom_nv12"))
+    return rc;
+  return tps_render_nv12_impl(net->winv, net->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv, out_pitch,
+                              out_frame_stride, stream, zoom);
+}
+
+// T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)
+int dvsg_tps_coefficients_f32(const dvsg_locnet_t *net, const float *F_t, int n, float *T, void *stream) {
+  DVSG_REQUIRE(net && F_t && T, "dvsg_tps_coefficients_f32: NULL pointer");
+  DVSG_REQUIRE(n >= 1, "dvsg_tps_coefficients_f32: n=%d must be >= 1", n);
+  return tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream);
+}
+
 // The coverage scan of a clip's F_t rows: the T of dvsg_stabilize_* / dvsg_tps_render_u8 for F_t (written), then
 // dvsg_tps_coverage_f32 on it with V_src.  Shapes and workspace are checked before the first launch.
 int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const float *zoom, int n, int src_H, int src_W,

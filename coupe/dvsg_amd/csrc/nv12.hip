@@ -11,6 +11,9 @@
 //                           1-channel image (H, W), chroma as a 2-channel image (H/2, W/2) centred on 128, so that sampler
 //                           A's black border is luma 0, chroma 128 (neutral) and not a green edge.  One launch renders both
 //                           planes of every frame: blockIdx.x runs over the luma tiles, then the chroma tiles.
+//   nv12_render_zoom_kernel that render on the output grid scaled about its centre by zoom[frame] (the crop of a live
+//                           stream): tps_stage / tps_map_rows with kZoom, x_t' = z x_t.  A kernel of its own, so that
+//                           nv12_render_kernel keeps its instructions.
 //
 // Every kernel is bit-identical to a composition of pinned entry points (stated at each); this translation unit is compiled
 // with -ffp-contract=off like frames.hip and warp_kernels.hip.  The map comes from tps_stage / tps_map_rows and the blend from
@@ -292,6 +295,41 @@ __global__ __launch_bounds__(kThreads) void nv12_render_kernel(Nv12 s, const flo
     render_plane<1>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
 }
 
+// nv12_render_kernel on the zoomed grid: each plane is dvsg_tps_warp_zoom_f32 on it, bit for bit (tps_warp_zoom_kernel's
+// z = zoom[b], y_t' = z y_t in the staging and the row terms, x_t' = z x_t here).
+__global__ __launch_bounds__(kThreads) void nv12_render_zoom_kernel(Nv12 s, const float *__restrict__ coord,
+                                                                    const float *__restrict__ T,
+                                                                    const float *__restrict__ zoom, int H, int W, int P,
+                                                                    float sx_l, float sy_l, float sx_c, float sy_c,
+                                                                    int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                                    uint8_t *__restrict__ out_uv, size_t out_pitch,
+                                                                    size_t out_frame_stride) {
+  __shared__ float4 sp[64];
+  __shared__ float4 sdy[64];
+  __shared__ float sa[6];
+  const int b = blockIdx.y, t = threadIdx.x;
+  int id = blockIdx.x;
+  const bool chroma = id >= n_l;
+  if (chroma) id -= n_l;
+  const int gx = chroma ? gx_c : gx_l;
+  const int i0 = (id / gx) * kTpsRows;
+  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
+  const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
+  const float z = zoom[b];
+  tps_stage<true, true>(coord, 0, T, b, P, t, i0, step_y, sp, sdy, sa, z);
+  __syncthreads();
+  const int j = (id % gx) * kThreads + t;
+  if (j >= pw) return;
+  const float x_t = z * (-1.0f + step_x * (float)j);
+  float xs[4], ys[4];
+  tps_map_rows<true, true>(sp, sdy, sa, P, x_t, step_y, i0, xs, ys, z);
+  const size_t in_off = (size_t)b * s.frame_stride, out_off = (size_t)b * out_frame_stride;
+  if (chroma)
+    render_plane<2>(s.uv + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_uv + out_off, out_pitch);
+  else
+    render_plane<1>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
+}
+
 inline int grid_for(size_t items, int cap = 1 << 16) {
   const size_t b = (items + kThreads - 1) / kThreads;
   return (int)(b < (size_t)cap ? (b ? b : 1) : (size_t)cap);
@@ -321,8 +359,7 @@ int check_matrix(const char *fn, int matrix) {
 
 int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
                           int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
-                          size_t out_frame_stride) {
-  const char *fn = "dvsg_tps_render_nv12";
+                          size_t out_frame_stride, const char *fn) {
   DVSG_REQUIRE(F_t && T, "%s: NULL pointer", fn);
   if (int rc = check_nv12(fn, "source", y, uv, pitch, frame_stride, n, H, W)) return rc;
   return check_nv12(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, H, W);
@@ -331,14 +368,20 @@ int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv,
 // the arguments have passed tps_render_nv12_check
 int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
-                         uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream) {
-  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream)) return rc;
+                         uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream, const float *zoom) {
   const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
   const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(H / 2, kTpsRows);
   DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);
+  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream)) return rc;
   hipStream_t s = as_stream(stream);
   // algorithmic bytes: both planes once in, once out
   ProfScope prof(kClsTpsWarp, s, 0.0, 3.0 * n * H * W);
+  if (zoom) {   // dvsg_tps_render_zoom_nv12: the same grid of workgroups on the zoomed output grid
+    hipLaunchKernelGGL(nv12_render_zoom_kernel, dim3((unsigned)(n_l + n_c), n), dim3(kThreads), 0, s,
+                       Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
+                       lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y, out_uv, out_pitch, out_frame_stride);
+    return check_launch("nv12_render_zoom_kernel");
+  }
   hipLaunchKernelGGL(nv12_render_kernel, dim3((unsigned)(n_l + n_c), n), dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride},
                      coord, T, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y,
                      out_uv, out_pitch, out_frame_stride);

@@ -20,7 +20,7 @@ their own lag-1 recurrence and still share batched CNN launches.  The pool never
 import numpy as np
 import torch
 
-from .clip import SKIP_LENGTH, _check_window, check_skip_length, render_source_into
+from .clip import SKIP_LENGTH, _check_crop, _check_crop_grid, _check_window, check_skip_length, render_source_into
 
 
 YUV_MATRICES = {"bt601": 0, "bt709": 1}   # DVSG_YUV_BT601_LIMITED, DVSG_YUV_BT709_LIMITED
@@ -76,12 +76,36 @@ class OnlineStabilizer(object):
     at source size.  Per distinct source size one `dvsg_frames_ingest_nv12` launch converts and resizes straight into
     the input slots and one `dvsg_tps_render_nv12` launch warps both planes of the device copy ingest read; the step
     itself is still the one `dvsg_stabilize_ring_inplace_f32` call, on the same pool of model-size float RGB frames.
-    side_by_side, as_uint8, channel_order="bgr", float frames and odd sizes raise ValueError."""
+    side_by_side, as_uint8, channel_order="bgr", float frames and odd sizes raise ValueError.
+
+    crop: every output frame has a black border (luma 0 / chroma 128 in NV12) wherever sampler A's taps leave the source.
+    None (default) returns the frames as they are.  A zoom z in (0, 1] renders every frame of every stream on the output
+    grid scaled by z about its centre; nothing is scanned.  "auto" keeps ONE zoom per stream on the device and lowers it
+    as the stream goes: per step and per source-size group, after the one stabilise call, the coverage scan of the
+    step's F_t on the output's own grid (`dvsg_tps_coverage_net_f32`), the ratchet (`dvsg_crop_ratchet_f32`:
+    z = min(max(free - crop_margin, crop_min), 1, z_before + crop_recover)) on the stream's entry of a [max_streams]
+    state tensor, and the zoomed render -- `dvsg_tps_render_zoom_u8` (source_res), `dvsg_tps_render_zoom_nv12` (NV12) or,
+    at the model's size, `dvsg_tps_warp_zoom_f32` from a gathered copy of the step's input slots (then
+    `dvsg_frames_f32_to_u8` with as_uint8).  Device tensors in still means nothing synchronised.  With crop_recover = 0
+    (default) the zoom of a stream never grows, so the picture never pumps; after the last frame it equals
+    `clip.crop_zoom` of all the stream's frames.  `open()` starts a stream at crop_start.  NV12 scans both planes --
+    chroma leaves the source one luma pixel before luma does -- and takes the smaller `free`; its default crop_margin is
+    one pixel of the chroma grid's shorter axis, otherwise that of `clip.crop_zoom`.  The recurrence is untouched: the
+    history slots keep uncropped frames, and the pool and F_t are those of a run without crop.  The unstable half of
+    side_by_side stays the uncropped source.  `crop_state(sid)` reports a stream's zoom."""
 
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
-                 as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709"):
+                 as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None,
+                 crop_min=0.5, crop_start=1.0, crop_recover=0.0):
         from . import _lib
         from ._tensor import device
+        crop = _check_crop(crop)
+        if crop_margin is not None and not float(crop_margin) >= 0.0:
+            raise ValueError("crop_margin must be None or >= 0, got %r" % (crop_margin,))
+        if not 0.0 < float(crop_min) <= 1.0 or not 0.0 < float(crop_start) <= 1.0:
+            raise ValueError("crop_min and crop_start must be in (0, 1], got %r and %r" % (crop_min, crop_start))
+        if not float(crop_recover) >= 0.0:
+            raise ValueError("crop_recover must be >= 0, got %r" % (crop_recover,))
         if channel_order not in ("rgb", "bgr"):
             raise ValueError("channel_order must be 'rgb' or 'bgr'")
         if frame_format not in ("rgb", "nv12"):
@@ -117,7 +141,20 @@ class OnlineStabilizer(object):
         self._F = torch.empty((self.max_streams, model.param_dim, 2), dtype=torch.float32, device=dev)
         # the TPS coefficients of a source-size render ([n,2,P+3], written by dvsg_tps_render_u8)
         self._T = torch.empty((self.max_streams, 2, model.param_dim + 3), dtype=torch.float32, device=dev) \
-            if self.source_res else None
+            if self.source_res or crop is not None else None
+        self.crop, self._crop_auto = crop, isinstance(crop, str)
+        self.crop_margin = None if crop_margin is None else float(crop_margin)
+        self.crop_min, self.crop_start, self.crop_recover = float(crop_min), float(crop_start), float(crop_recover)
+        self._crop_zoom = None    # float32 [max_streams]: "auto": the zoom of the stream that owns ring r; else the fixed zoom
+        self._crop_last = {}      # sid -> (free float64 [n] of the stream's last step, its row)
+        self._V = None            # V_src per frame, for the model-size zoomed warp
+        if crop is not None:
+            self._crop_zoom = torch.full((self.max_streams,), self.crop_start if isinstance(crop, str) else float(crop),
+                                         dtype=torch.float32, device=dev)
+            if not self.source_res:
+                from .model import V_SRC
+                _check_crop_grid(self.h, self.w)
+                self._V = torch.from_numpy(V_SRC).to(dev).unsqueeze(0).repeat(self.max_streams, 1, 1).contiguous()
         self._free = list(range(self.max_streams))   # rings no open stream owns
         self._streams = {}                           # sid -> [ring, frames pushed]
         self._next_sid = 0
@@ -134,11 +171,14 @@ class OnlineStabilizer(object):
         sid = self._next_sid
         self._next_sid += 1
         self._streams[sid] = [ring, 0]
+        if self._crop_auto:
+            self._crop_zoom[ring] = self.crop_start   # a device fill: nothing synchronised
         return sid
 
     def close(self, sid):
         ring, _ = self._stream(sid)
         del self._streams[sid]
+        self._crop_last.pop(sid, None)
         self._free.append(ring)
         self._free.sort()
 
@@ -153,6 +193,49 @@ class OnlineStabilizer(object):
     def push(self, sid, frame):
         """`step` for a single stream: its output for `frame`."""
         return self.step({sid: frame})[sid]
+
+    def crop_state(self, sid):
+        """dict(zoom, free) of an open stream, after a synchronise: zoom np.float32, the zoom its last frame was rendered
+        with (crop_start before the first; the fixed zoom with crop=z), and free, the `free` of `clip.crop_scan` for its
+        last frame (NV12: the smaller of the luma and the chroma plane's), None before the first frame or with crop=z."""
+        ring, _ = self._stream(sid)
+        if self.crop is None:
+            raise ValueError("this OnlineStabilizer was made without crop")
+        last = self._crop_last.get(sid)
+        return dict(zoom=np.float32(self._crop_zoom[ring].item()), free=None if last is None else float(last[0][last[1]].item()))
+
+    def _step_zoom(self, entries, i, j, grids):
+        """The zoom of batch rows [i, j) -> float32 [j - i] on the device.  crop=z: the constant.  "auto": one coverage
+        scan of the rows' F_t per grid of `grids` (one (H, W), or the luma and the chroma plane's), each with the source
+        and the output of that size, then the ratchet on the rows' streams; T rows [i, j) are written."""
+        import ctypes
+        from . import _lib
+        from ._tensor import device, ptr, stream
+        n = j - i
+        if not self._crop_auto:
+            return self._crop_zoom[:n]
+        dev = device()
+        rings = np.array([e[4] for e in entries[i:j]], dtype=np.int32)
+        if np.unique(rings).size != n:
+            raise ValueError("two frames of one step share a crop state slot")
+        keys = torch.empty((len(grids), 2, n), dtype=torch.int32, device=dev)   # per grid: n_border | key_min
+        for g, (gh, gw) in enumerate(grids):
+            need = ctypes.c_size_t()
+            _lib.call("dvsg_tps_coverage_workspace_bytes", n, gh, gw, ctypes.byref(need))
+            ws = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=dev)
+            _lib.call("dvsg_tps_coverage_net_f32", self.model.locnet.handle, ptr(self._F[i:j]), None, n, gh, gw, gh, gw,
+                      ptr(self._T[i:j]), ptr(keys[g, 0]), ptr(keys[g, 1]), ptr(ws), ws.numel() * 8, stream())
+        slots = torch.from_numpy(rings).pin_memory().to(dev, non_blocking=True)
+        zoom = torch.empty((n,), dtype=torch.float32, device=dev)
+        free = torch.empty((n,), dtype=torch.float64, device=dev)
+        D = [(gh - 1) * (gw - 1) for gh, gw in grids]
+        margin = 2.0 / (min(grids[-1]) - 1) if self.crop_margin is None else self.crop_margin
+        _lib.call("dvsg_crop_ratchet_f32", ptr(keys[0, 1]), D[0], ptr(keys[1, 1]) if len(grids) > 1 else None,
+                  D[1] if len(grids) > 1 else 0, ptr(slots), n, ptr(self._crop_zoom), self.max_streams, margin, self.crop_min,
+                  self.crop_recover, ptr(zoom), ptr(free), stream())
+        for b in range(i, j):
+            self._crop_last[entries[b][1]] = (free, b - i)
+        return zoom
 
     def _slot_tables(self, entries):
         """The step's slot rows for `entries` (ring at [4], step count at [5]) in batch order: the host array
@@ -188,6 +271,8 @@ class OnlineStabilizer(object):
                 raise ValueError("stream %r: a frame must be [h,w,3], got %s" % (sid, tuple(t.shape)))
             if t.dtype == torch.uint8:
                 kind = (0, int(t.shape[0]), int(t.shape[1])) if tuple(t.shape[:2]) != (h, w) else (1,)
+                if self.crop is not None and self.source_res:
+                    _check_crop_grid(int(t.shape[0]), int(t.shape[1]))
             elif t.dtype.is_floating_point:
                 if self.source_res:
                     raise ValueError("stream %r: source_res renders the uint8 source frame; a float frame has no source "
@@ -247,6 +332,8 @@ class OnlineStabilizer(object):
         if self.source_res:
             res = self._render_source(entries, groups)
             return {sid: res[sid] for sid in frames}
+        if self.crop is not None:
+            return self._egress_cropped(frames, entries, in_slots, side)
         # ---- egress (eval.py:112-113)
         if side is not None:
             _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(out_slots), B, h, w, flip, ptr(side),
@@ -266,6 +353,34 @@ class OnlineStabilizer(object):
             res[e[1]] = (o, sd) if self.side_by_side else o
         return {sid: res[sid] for sid in frames}
 
+    def _egress_cropped(self, frames, entries, in_slots, side):
+        """Egress of a model-size step with crop: the step's unstable frames (a gathered copy of the input slots) warped
+        once more by the step's own T on the zoomed grid (`dvsg_tps_warp_zoom_f32`); the history slots keep the uncropped
+        frames.  `side` arrives with its unstable half written."""
+        from . import _lib
+        from ._tensor import ptr, stream
+        B, h, w, flip = len(entries), self.h, self.w, self.flip
+        zoom = self._step_zoom(entries, 0, B, [(h, w)])
+        if not self._crop_auto:   # no scan has written T
+            _lib.call("dvsg_tps_coefficients_f32", self.model.locnet.handle, ptr(self._F[:B]), B, ptr(self._T[:B]), stream())
+        u = self.pool.index_select(0, in_slots)
+        out = torch.empty_like(u)
+        _lib.call("dvsg_tps_warp_zoom_f32", ptr(u), ptr(self._V[:B]), ptr(self._T[:B]), ptr(zoom), B, h, w, 3,
+                  self.model.param_dim, h, w, ptr(out), None, None, stream())
+        if side is not None:
+            _lib.call("dvsg_frames_f32_to_u8", ptr(out), B, h, w, flip, ptr(side), 2 * w, w, stream())
+        if self.as_uint8:
+            f32, out = out, torch.empty((B, h, w, 3), dtype=torch.uint8, device=out.device)
+            _lib.call("dvsg_frames_f32_to_u8", ptr(f32), B, h, w, flip, ptr(out), w, 0, stream())
+        if any(e[2] for e in entries):
+            out_h = out.cpu().numpy()
+            side_h = side.cpu().numpy() if side is not None else None
+        res = {}
+        for b, e in enumerate(entries):
+            o, sd = (out_h[b], side_h[b] if side is not None else None) if e[2] else (out[b], side[b] if side is not None else None)
+            res[e[1]] = (o, sd) if self.side_by_side else o
+        return {sid: res[sid] for sid in frames}
+
     def _render_source(self, entries, groups):
         """Egress of a source_res step: per source size, one `dvsg_tps_render_u8` launch that warps the uint8 frames by
         this step's F_t rows (contiguous: a group is a contiguous batch range) at their own size."""
@@ -274,7 +389,8 @@ class OnlineStabilizer(object):
             n, H0, W0 = j - i, int(src.shape[1]), int(src.shape[2])
             out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
             side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
-            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side)
+            zoom = self._step_zoom(entries, i, j, [(H0, W0)]) if self.crop is not None else None
+            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom)
             if any(entries[b][2] for b in range(i, j)):
                 out_h = out.cpu().numpy()
                 side_h = side.cpu().numpy() if side is not None else None
@@ -331,9 +447,15 @@ class OnlineStabilizer(object):
         for i, j, src in groups:
             H0, W0 = entries[i][0]
             out = torch.empty_like(src)
-            _lib.call("dvsg_tps_render_nv12", self.model.locnet.handle, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * W0, W0,
-                      3 * H0 // 2 * W0, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * W0, W0,
-                      3 * H0 // 2 * W0, stream())
+            if self.crop is None:
+                _lib.call("dvsg_tps_render_nv12", self.model.locnet.handle, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * W0, W0,
+                          3 * H0 // 2 * W0, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * W0, W0,
+                          3 * H0 // 2 * W0, stream())
+            else:   # chroma leaves the source first: both planes are scanned, each on its own grid
+                zoom = self._step_zoom(entries, i, j, [(H0, W0), (H0 // 2, W0 // 2)])
+                _lib.call("dvsg_tps_render_zoom_nv12", self.model.locnet.handle, ptr(self._F[i:j]), ptr(src),
+                          ptr(src) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]), ptr(out),
+                          ptr(out) + H0 * W0, W0, 3 * H0 // 2 * W0, stream())
             out_h = out.cpu().numpy() if any(entries[b][2] for b in range(i, j)) else None
             for b in range(i, j):
                 res[entries[b][1]] = out_h[b - i] if entries[b][2] else out[b - i]
@@ -345,7 +467,9 @@ def stabilize_clips(model, clips, batch=None, **kw):
     (default K) in lockstep, so each step is one batched call and every clip keeps its own recurrence exactly.  Clips
     may differ in length (a finished clip's ring goes to the next waiting clip).  `kw` are OnlineStabilizer's options.
     Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips).  With
-    frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result."""
+    frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result.  crop=... is OnlineStabilizer's: frame k of a
+    clip is rendered with the zoom the ratchet has reached at frame k, NOT with `stabilize_clip`'s one clip-wide zoom
+    (the two agree from the frame on that sets the clip's minimum)."""
     from ._tensor import device
     K = len(clips)
     if K == 0:

@@ -8,6 +8,10 @@ it over (eval.py:76-81 resizes it).
 
 --format nv12: the source hands over NV12 surfaces [3 H0 / 2, W0] as a hardware decoder does (built on the host here) and
 each step returns the stabilised surfaces at source size in the same layout, ready for an encoder.
+
+--crop auto|Z: the frames come back without sampler A's black border.  Z in (0, 1] is a fixed zoom; "auto" keeps one zoom
+per stream on the device and only ever lowers it (OnlineStabilizer(crop="auto")); the zoom each stream has reached is
+printed at the end.
 """
 import argparse
 import os
@@ -51,15 +55,18 @@ def main():
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--precision", default="f32", choices=["f32", "f32x3", "f32s", "f16"])
     ap.add_argument("--format", default="rgb", choices=["rgb", "nv12"])
+    ap.add_argument("--crop", default=None, help="'auto' or a zoom in (0, 1]")
     args = ap.parse_args()
+    crop = args.crop if args.crop in (None, "auto") else float(args.crop)
     net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0))
     net.precision = args.precision
     nv12 = args.format == "nv12"
     if nv12:
-        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709")
+        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop)
         make = synthetic_nv12_source
     else:
-        stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True)
+        stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True,
+                                crop=crop)
         make = synthetic_source
     H0, W0 = args.height * 3 // 2, args.width * 3 // 2
     if nv12:
@@ -78,6 +85,8 @@ def main():
             out, side = next(iter(outs.values()))
             print("per stream and step: stabilised", out.shape, out.dtype, "| side-by-side", side.shape, side.dtype)
     for sid in list(sources):
+        if crop is not None:
+            print("stream %d: zoom %.4f" % (sid, stab.crop_state(sid)["zoom"]))
         stab.close(sid)
     lat = np.array(lat[1:] if len(lat) > 1 else lat) * 1e3
     print("%d stream(s) of %dx%d, %s: median %.2f ms per step (%.2f ms per frame), %.1f frames/s in all"

@@ -439,7 +439,12 @@ int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t
  *                                            128.5), 0, 255).
  *          Both byte round trips are exact.  Chroma is warped centred on 128, so sampler A's black border (coincident
  *          taps) is luma 0 with neutral chroma 128.  The chroma grid is corner-aligned like the luma grid (tf.linspace at
- *          each plane's size), within one luma pixel of left-sited chroma.  No zoom.  n <= 65535.
+ *          each plane's size), within one luma pixel of left-sited chroma.  No zoom (dvsg_tps_render_zoom_nv12).  n <= 65535.
+ *   dvsg_tps_render_zoom_nv12  dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (float32 [n] ON THE
+ *          DEVICE, one value per frame; see CROP below): each plane is dvsg_tps_warp_zoom_f32(plane, V_src, T, zoom, out =
+ *          the plane's size) bit for bit, with the byte rules, the layout, the argument checks and the n <= 65535 of
+ *          dvsg_tps_render_nv12; T is written as dvsg_tps_render_u8 writes it.  zoom[i] == 1.0f gives dvsg_tps_render_nv12's
+ *          bytes; zoom NULL: dvsg_tps_render_nv12 itself.
  * Every argument is checked before the first launch.
  * ------------------------------------------------------------------------------------- */
 #define DVSG_YUV_BT601_LIMITED 0
@@ -452,6 +457,9 @@ int dvsg_frames_ingest_nv12(const uint8_t *y, const uint8_t *uv, size_t pitch, s
 int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
                          size_t frame_stride, int n, int H, int W, float *T, uint8_t *out_y, uint8_t *out_uv,
                          size_t out_pitch, size_t out_frame_stride, void *stream);
+int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
+                              size_t frame_stride, int n, int H, int W, const float *zoom, float *T, uint8_t *out_y,
+                              uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream);
 /* ---------------------------------------------------------------------------------------
  * CROP to the valid region (coupe.dvsg_amd.clip.stabilize_clip(crop=...)).  Sampler A clips its tap indices before it forms
  * the weights, so an output pixel whose source sample lies outside 0 <= x < W - 1, 0 <= y < H - 1 (x = ((x_s + 1) W) / 2 in
@@ -476,6 +484,22 @@ int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8
  *   dvsg_tps_coverage_net_f32  F_t [n,25,2] -> T [n,2,28] (written: the T of dvsg_tps_render_u8 for that F_t, bit for
  *          bit), then dvsg_tps_coverage_f32 on that T with the handle's V_src.
  *   dvsg_tps_render_zoom_u8  dvsg_tps_render_u8 on the zoomed grid; zoom NULL: dvsg_tps_render_u8 itself.
+ *   dvsg_tps_coefficients_f32  F_t [n,25,2] -> T [n,2,28] alone, exactly as dvsg_tps_render_u8 writes it: for
+ *          dvsg_tps_warp_zoom_f32 on frames that no scan or render has written T for (a fixed zoom at the model's size).
+ *   dvsg_crop_ratchet_f32  the zoom of LIVE streams (coupe.dvsg_amd.online, crop="auto"), kept on the device so that a step
+ *          synchronises nothing.  For the n frames of a step: key_min_a [n] int32 with D_a = (out_h - 1)(out_w - 1) of its
+ *          scan; optionally key_min_b [n] with D_b, a second plane's scan (NULL: absent; NV12 passes luma and chroma);
+ *          state_slots [n] int32, frame i's index into state, float32 [n_state].  Per frame i, in float64, every
+ *          operation rounded on its own:
+ *              free   = min(key_a, D_a) / D_a;  with b: free = min(free, min(key_b, D_b) / D_b)
+ *              target = min(max(free - margin, crop_min), 1.0)
+ *              z      = min(target, (double)state[slot] + recover)
+ *              state[slot] = zoom[i] = (float)z        one rounding to nearest;  free_out[i] = free (float64)
+ *          A slot outside [0, n_state) skips its frame (nothing of it is written).  The slots of one call must be
+ *          distinct (the caller's contract; coupe.dvsg_amd.online checks it on the host).  margin >= 0, 0 < crop_min <= 1,
+ *          recover >= 0, D >= 1, checked before the launch.  recover = 0 is a pure ratchet: a stream's zoom only ever
+ *          shrinks, and from a state of 1 it ends at crop_zoom(all frees, margin, crop_min) of the whole stream bit for
+ *          bit, because min and max commute and the float32 rounding is monotone.  One thread per frame, no atomics.
  * ------------------------------------------------------------------------------------- */
 int dvsg_tps_coverage_workspace_bytes(int B, int out_h, int out_w, size_t *bytes);
 int dvsg_tps_coverage_f32(const float *coord, const float *T, const float *zoom, int B, int P, int src_H, int src_W,
@@ -489,6 +513,10 @@ int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const 
 int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
                             int channel_flip, const float *zoom, float *T, float *out_f32, uint8_t *out_u8, int u8_W,
                             int u8_x0, void *stream);
+int dvsg_tps_coefficients_f32(const dvsg_locnet_t *net, const float *F_t, int n, float *T, void *stream);
+int dvsg_crop_ratchet_f32(const int32_t *key_min_a, int D_a, const int32_t *key_min_b, int D_b, const int32_t *state_slots,
+                          int n, float *state, int n_state, double margin, double crop_min, double recover, float *zoom,
+                          double *free_out, void *stream);
 /* ---------------------------------------------------------------------------------------
  * eval_train.py's evaluation graph (eval_train.py:25-51): unlike model.py's, its CNN input is
  * `patches_masked_t = patches_t * mask` (:43-45), where `random_mask` (:53-64, = model.py:156-167) warps an all-ones

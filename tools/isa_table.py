@@ -53,7 +53,9 @@ def kernels(obj):
             close()
             sym, lines = head.group(1), []
         elif sym is not None and line.startswith("\t"):
-            lines.append(re.sub(r"\s*//.*$", "", line).strip())   # drop "// address: encoding"
+            ins = re.sub(r"\s*//.*$", "", line).strip()           # drop "// address: encoding"
+            if ins != "...":   # objdump's mark for the zero padding up to the next symbol: there once another kernel follows
+                lines.append(ins)
     close()
     return out
 

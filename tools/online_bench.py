@@ -8,6 +8,15 @@ the timed steps, which end in a synchronise) and the median step time (device ev
 stabilize_clip on one clip of the same frames is the K = 1 reference.  One JSON line per measurement.
 
     python tools/online_bench.py [--steps 40] [--warmup 6] [--sizes 720x1280,288x512] [--precisions f32,f32x3] [--out FILE]
+
+--crop: the cost of OnlineStabilizer(crop=...) per step instead.  K streams of device-resident 1080p frames (--source),
+NV12 surfaces and RGB uint8 with source_res (--formats), through a 512x288 f32 model: one OnlineStabilizer per variant
+(--variants none,0.9,auto: crop=None, a fixed zoom, the per-stream ratchet), all warmed up, then --rounds rounds in each of
+which every variant in turn runs --steps steps between device events, so the variants alternate inside a round.  One JSON
+line per (format, K, variant): the median, smallest and largest step over all rounds.  "none" passes no crop argument at
+all, so the same file measures a tree from before the option.
+
+    python tools/online_bench.py --crop [--source 1080x1920] [--formats nv12,rgb] [--variants none,0.9,auto] [--rounds 5]
 """
 import argparse
 import json
@@ -28,6 +37,11 @@ def main():
     ap.add_argument("--precisions", default="f32,f32x3")
     ap.add_argument("--streams", default="1,4,16")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--crop", action="store_true", help="measure the per-step cost of OnlineStabilizer(crop=...)")
+    ap.add_argument("--source", default="1080x1920")
+    ap.add_argument("--formats", default="nv12,rgb")
+    ap.add_argument("--variants", default="none,0.9,auto")
+    ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 1:
         raise SystemExit("--steps and --warmup must be >= 1")
@@ -46,6 +60,17 @@ def main():
     def emit(rec):
         print(json.dumps(rec), flush=True)
         lines.append(rec)
+
+    def flush():
+        if args.out:
+            with open(args.out, "a") as f:
+                for rec in lines:
+                    f.write(json.dumps(rec) + "\n")
+
+    if args.crop:
+        crop_legs(args, weights, emit)
+        flush()
+        return
 
     for size in args.sizes.split(","):
         H, W = (int(v) for v in size.split("x"))
@@ -90,10 +115,64 @@ def main():
                       "pool_frames": int(on.pool.shape[0])})
                 del on
                 torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "a") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
+    flush()
+
+
+def crop_legs(args, weights, emit):
+    import numpy as np
+    import torch
+    import inputs
+    from coupe.dvsg_amd.model import StabNet
+    from coupe.dvsg_amd.online import OnlineStabilizer
+    H0, W0 = (int(v) for v in args.source.split("x"))
+    h, w = 288, 512
+    model = StabNet(h, w).load_weights(weights)
+    model.get_evaluation_model(7)
+    model.precision = "f32"
+    variants = args.variants.split(",")
+    for fmt in args.formats.split(","):
+        # 8 distinct frames on the device; stream s at step k reads frame (k + 3 s) % 8
+        if fmt == "nv12":
+            y = 16 + inputs.smooth_frames(11, 8, H0, W0, C=1, factor=32)[..., 0] * 219
+            c = 16 + inputs.smooth_frames(12, 8, H0 // 2, W0 // 2, C=2, factor=32) * 224
+            bank = torch.from_numpy(np.concatenate([y, c.reshape(8, H0 // 2, W0)], axis=1).astype(np.uint8)).cuda()
+            base = dict(frame_format="nv12")
+        else:
+            bank = torch.from_numpy((inputs.smooth_frames(11, 8, H0, W0, factor=32) * 255).astype(np.uint8)).cuda()
+            base = dict(source_res=True, as_uint8=True)
+        for K in (int(v) for v in args.streams.split(",")):
+            stabs = []
+            for v in variants:
+                kw = dict(base) if v == "none" else dict(base, crop="auto" if v == "auto" else float(v))
+                on = OnlineStabilizer(model, max_streams=K, **kw)
+                stabs.append((v, on, [on.open() for _ in range(K)], []))
+            step_no = 0
+            for _, on, sids, _ in stabs:
+                for k in range(args.warmup):
+                    on.step({sid: bank[(k + 3 * s) % 8] for s, sid in enumerate(sids)})
+            torch.cuda.synchronize()
+            for r in range(args.rounds):
+                for _, on, sids, times in stabs:   # the variants alternate inside the round
+                    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                    for k in range(args.steps):
+                        feed = {sid: bank[(step_no + k + 3 * s) % 8] for s, sid in enumerate(sids)}
+                        ev[k][0].record()
+                        on.step(feed)
+                        ev[k][1].record()
+                    torch.cuda.synchronize()
+                    times.extend(a.elapsed_time(b) for a, b in ev)
+                step_no += args.steps
+            for v, on, sids, times in stabs:
+                t = sorted(times)
+                rec = {"what": "online_crop", "format": fmt, "source_H": H0, "source_W": W0, "H": h, "W": w, "precision": "f32",
+                       "K": K, "crop": v, "rounds": args.rounds, "steps_per_round": args.steps,
+                       "median_step_ms": t[len(t) // 2], "min_step_ms": t[0], "max_step_ms": t[-1],
+                       "p10_step_ms": t[len(t) // 10], "p90_step_ms": t[(9 * len(t)) // 10]}
+                if v == "auto":
+                    rec["zoom"] = [float(on.crop_state(sid)["zoom"]) for sid in sids][:4]
+                emit(rec)
+            del stabs
+            torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
