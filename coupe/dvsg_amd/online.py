@@ -24,6 +24,24 @@ from .clip import SKIP_LENGTH, _check_crop, _check_crop_grid, _check_window, che
 
 
 YUV_MATRICES = {"bt601": 0, "bt709": 1}   # DVSG_YUV_BT601_LIMITED, DVSG_YUV_BT709_LIMITED
+SCENE_STATE_INTS = 68                     # DVSG_SCENE_STATE_INTS: k, cuts, S, 0, the previous histogram [64]
+
+
+def _check_scene_cut(scene_cut):
+    """scene_cut argument of OnlineStabilizer -> None or a float64 threshold in (0, 1]"""
+    if scene_cut is None:
+        return None
+    if isinstance(scene_cut, (str, bytes, bool)) or not np.isscalar(scene_cut):
+        raise ValueError("scene_cut must be None or a threshold in (0, 1], got %r" % (scene_cut,))
+    t = float(scene_cut)
+    if not (t > 0.0 and t <= 1.0):       # NaN fails both
+        raise ValueError("scene_cut must be None or a threshold in (0, 1], got %r" % (scene_cut,))
+    return t
+
+
+def scene_threshold_count(threshold, h, w):
+    """thr_count of dvsg_scene_step_f32: ceil(threshold * 2 h w) in float64, an int in [1, 2 h w]."""
+    return int(np.ceil(np.float64(threshold) * np.float64(2 * int(h) * int(w))))
 
 
 def stream_window_row(k, base, skip_length=SKIP_LENGTH):
@@ -92,14 +110,33 @@ class OnlineStabilizer(object):
     chroma leaves the source one luma pixel before luma does -- and takes the smaller `free`; its default crop_margin is
     one pixel of the chroma grid's shorter axis, otherwise that of `clip.crop_zoom`.  The recurrence is untouched: the
     history slots keep uncropped frames, and the pool and F_t are those of a run without crop.  The unstable half of
-    side_by_side stays the uncropped source.  `crop_state(sid)` reports a stream's zoom."""
+    side_by_side stays the uncropped source.  `crop_state(sid)` reports a stream's zoom.
+
+    scene_cut: a live stream cuts, and after a cut the window would mix two scenes for `span` steps (and crop="auto" would keep
+    the old scene's zoom for good).  None (default) leaves the caller to close() and open(); a step launches what it
+    launches without the option.  A threshold in (0, 1] makes every stream notice its own cuts on the device: per step,
+    after ingest and before the one stabilise call, ONE `dvsg_scene_step_f32` call takes the 64-bin luma histogram of each
+    stream's input slot, S = the L1 distance to the histogram of the stream's previous frame, and declares a cut when
+    S >= ceil(threshold * 2 h w) and at least max(1, scene_min_len) frames have passed since the ring's last start.  A cut
+    at frame f is close(sid) + open() onto the same ring + push(f): f is step 0 of eval.py:93-94, the windows that follow count
+    from f, and with crop="auto" the ring's zoom restarts at crop_start.  History slots that still hold the old scene are
+    never read.  The step count lives in a [max_streams, 68] int32 state tensor on the device and the step's `table` and
+    `out_slots` are written by that call -- the host uploads ring numbers and input slots only, and its per-stream counter
+    is "frames pushed", nothing more.  Device tensors in still means nothing synchronised.  The statistic is taken from
+    the float32 RGB pool at the model's size, so it is the same for uint8, float and NV12 sources.  There is no default
+    threshold (none has been measured on real footage); hard cuts only -- a fade or a dissolve changes the histogram a
+    little per frame and passes.  `scene_state(sid)` reports a stream's cuts; `reset(sid)` is the caller's own cut (a
+    decoder's or an edit list's), with or without scene_cut: the stream's next frame is step 0."""
 
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
                  as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None,
-                 crop_min=0.5, crop_start=1.0, crop_recover=0.0):
+                 crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1):
         from . import _lib
         from ._tensor import device
         crop = _check_crop(crop)
+        scene_cut = _check_scene_cut(scene_cut)
+        if isinstance(scene_min_len, bool) or not isinstance(scene_min_len, (int, np.integer)) or scene_min_len < 0:
+            raise ValueError("scene_min_len must be an integer >= 0, got %r" % (scene_min_len,))
         if crop_margin is not None and not float(crop_margin) >= 0.0:
             raise ValueError("crop_margin must be None or >= 0, got %r" % (crop_margin,))
         if not 0.0 < float(crop_min) <= 1.0 or not 0.0 < float(crop_start) <= 1.0:
@@ -155,8 +192,19 @@ class OnlineStabilizer(object):
                 from .model import V_SRC
                 _check_crop_grid(self.h, self.w)
                 self._V = torch.from_numpy(V_SRC).to(dev).unsqueeze(0).repeat(self.max_streams, 1, 1).contiguous()
+        self.scene_cut, self.scene_min_len = scene_cut, int(scene_min_len)
+        self._scene = None        # int32 [max_streams, 68]: the scene state of the stream that owns ring r (dvsg_scene_step_f32)
+        if scene_cut is not None:
+            import ctypes
+            if 2 * self.h * self.w > 2 ** 31 - 1:
+                raise ValueError("scene_cut: a frame of %d x %d is too large (2 h w must stay below 2^31)" % (self.h, self.w))
+            self._scene_thr = scene_threshold_count(scene_cut, self.h, self.w)
+            self._scene_skip = (ctypes.c_int32 * len(self.skip_length))(*self.skip_length)
+            self._scene = torch.zeros((self.max_streams, SCENE_STATE_INTS), dtype=torch.int32, device=dev)
         self._free = list(range(self.max_streams))   # rings no open stream owns
-        self._streams = {}                           # sid -> [ring, frames pushed]
+        # sid -> [ring, count].  Without scene_cut the count is the stream's step k since open() / reset(); with it k lives on
+        # the device (a cut resets it there) and the count is "frames pushed", which no window is derived from.
+        self._streams = {}
         self._next_sid = 0
 
     @property
@@ -171,9 +219,25 @@ class OnlineStabilizer(object):
         sid = self._next_sid
         self._next_sid += 1
         self._streams[sid] = [ring, 0]
-        if self._crop_auto:
-            self._crop_zoom[ring] = self.crop_start   # a device fill: nothing synchronised
+        self._restart(ring)
         return sid
+
+    def _restart(self, ring):
+        """The device state of `ring` as a stream's first frame wants it: device fills, nothing synchronised."""
+        if self._crop_auto:
+            self._crop_zoom[ring] = self.crop_start
+        if self._scene is not None:
+            self._scene[ring].zero_()
+
+    def reset(self, sid):
+        """The caller's own cut (a decoder's flag, an edit list): the next frame of the stream is step 0 of eval.py, as if the
+        stream had been closed and opened onto the same ring.  With crop="auto" its zoom restarts at crop_start; with
+        scene_cut its device state (frames since the cut, cuts, score, histogram) is zeroed like open() does."""
+        st = self._stream(sid)
+        if self._scene is None:
+            st[1] = 0
+        self._crop_last.pop(sid, None)
+        self._restart(st[0])
 
     def close(self, sid):
         ring, _ = self._stream(sid)
@@ -203,6 +267,16 @@ class OnlineStabilizer(object):
             raise ValueError("this OnlineStabilizer was made without crop")
         last = self._crop_last.get(sid)
         return dict(zoom=np.float32(self._crop_zoom[ring].item()), free=None if last is None else float(last[0][last[1]].item()))
+
+    def scene_state(self, sid):
+        """dict(frames_since_cut, cuts, score) of an open stream, after a synchronise: the frames since the ring's last start
+        (open, reset or a detected cut; the cut frame counts), the cuts detected since open() / reset(), and
+        score = S / (2 h w) of its last frame in [0, 1] (0.0 before the second frame of a run)."""
+        ring, _ = self._stream(sid)
+        if self._scene is None:
+            raise ValueError("this OnlineStabilizer was made without scene_cut")
+        k, cuts, S = (int(v) for v in self._scene[ring, :3].tolist())
+        return dict(frames_since_cut=k, cuts=cuts, score=S / float(2 * self.h * self.w))
 
     def _step_zoom(self, entries, i, j, grids):
         """The zoom of batch rows [i, j) -> float32 [j - i] on the device.  crop=z: the constant.  "auto": one coverage
@@ -239,9 +313,20 @@ class OnlineStabilizer(object):
 
     def _slot_tables(self, entries):
         """The step's slot rows for `entries` (ring at [4], step count at [5]) in batch order: the host array
-        [table B*S | out slots B | input slots B] and its three parts on the device."""
+        [table B*S | out slots B | input slots B], its three parts on the device, and None.  With scene_cut the step count is
+        the device's: the upload is [rings B | input slots B], table and out slots are device buffers that `_scene_step`
+        fills after ingest (their part of the host array is -1), and the last value is the rings on the device."""
         from ._tensor import device
         B, S = len(entries), len(self.skip_length)
+        if self._scene is not None:
+            rings = np.array([e[4] for e in entries], dtype=np.int32)
+            if np.unique(rings).size != B:
+                raise ValueError("two frames of one step share a ring")
+            rows = np.full(B * S + 2 * B, -1, dtype=np.int32)
+            rows[B * S + B:] = rings * self.frames_per_stream + self.span + 1
+            up = torch.from_numpy(np.concatenate([rings, rows[B * S + B:]])).pin_memory().to(device(), non_blocking=True)
+            return rows, torch.empty((B, S), dtype=torch.int32, device=device()), \
+                torch.empty((B,), dtype=torch.int32, device=device()), up[B:], up[:B]
         rows = np.empty(B * S + 2 * B, dtype=np.int32)     # [table B*S | out slots B | input slots B]
         for i, (_, _, _, _, ring, k) in enumerate(entries):
             base = ring * self.frames_per_stream
@@ -249,7 +334,24 @@ class OnlineStabilizer(object):
             rows[B * S + B + i] = base + self.span + 1
         # a fresh pinned buffer per step: the caching host allocator does not hand it out again before this copy is done
         idx = torch.from_numpy(rows).pin_memory().to(device(), non_blocking=True)
-        return rows, idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:]
+        return rows, idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:], None
+
+    def _scene_step(self, rings, table, out_slots):
+        """scene_cut: the one `dvsg_scene_step_f32` call of a step, between ingest and the stabilise call.  It reads the step's
+        input slots, decides every stream's cut and writes `table` and `out_slots`; only crop="auto" hands it the zoom
+        state to restart."""
+        import ctypes
+        from . import _lib
+        from ._tensor import device, ptr, stream
+        B, S = int(table.shape[0]), len(self.skip_length)
+        need = ctypes.c_size_t()
+        _lib.call("dvsg_scene_workspace_bytes", B, ctypes.byref(need))
+        ws = torch.empty((need.value + 3) // 4, dtype=torch.int32, device=device())
+        cut = torch.empty((B,), dtype=torch.int32, device=device())
+        _lib.call("dvsg_scene_step_f32", ptr(self.pool), int(self.pool.shape[0]), self.h, self.w, ptr(rings), B,
+                  self._scene_skip, S, ptr(self._scene), self.max_streams, self._scene_thr, self.scene_min_len,
+                  ptr(self._crop_zoom) if self._crop_auto else None, self.crop_start, ptr(table), ptr(out_slots), ptr(cut),
+                  ptr(ws), ws.numel() * 4, stream())
 
     def step(self, frames):
         """One step of every stream in `frames` ({sid: frame}); returns {sid: output}."""
@@ -288,7 +390,7 @@ class OnlineStabilizer(object):
         # range of the step's slot rows
         entries.sort(key=lambda e: e[0])
         B = len(entries)
-        rows, table, out_slots, in_slots = self._slot_tables(entries)
+        rows, table, out_slots, in_slots, rings = self._slot_tables(entries)
         S = len(self.skip_length)
         n_pool = int(self.pool.shape[0])
         side = torch.empty((B, h, 2 * w, 3), dtype=torch.uint8, device=dev) \
@@ -326,6 +428,8 @@ class OnlineStabilizer(object):
             _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(in_slots[a:b]), b - a, h, w, flip,
                       ptr(side[a:b]), 2 * w, 0, stream())
         # ---- the step: every stream's window from its ring, every result into its history slot (eval.py:101-120)
+        if rings is not None:
+            self._scene_step(rings, table, out_slots)
         self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
         for e in entries:
             self._streams[e[1]][1] += 1
@@ -427,7 +531,7 @@ class OnlineStabilizer(object):
             entries.append(((H0, W0), sid, host, t, ring, k))
         entries.sort(key=lambda e: e[0])   # one contiguous batch range per source size
         B = len(entries)
-        _, table, out_slots, in_slots = self._slot_tables(entries)
+        _, table, out_slots, in_slots, rings = self._slot_tables(entries)
         n_pool = int(self.pool.shape[0])
         groups = []   # (i, j, device frames [j-i, 3 H0 / 2, W0])
         i = 0
@@ -440,6 +544,8 @@ class OnlineStabilizer(object):
                       self.yuv_matrix, ptr(self.pool), n_pool, ptr(in_slots[i:j]), h, w, stream())
             groups.append((i, j, src))
             i = j
+        if rings is not None:
+            self._scene_step(rings, table, out_slots)
         self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
         for e in entries:
             self._streams[e[1]][1] += 1
@@ -465,7 +571,8 @@ class OnlineStabilizer(object):
 def stabilize_clips(model, clips, batch=None, **kw):
     """eval.py:76-124 for K whole clips at once: the clips run through one `OnlineStabilizer` of `batch` streams
     (default K) in lockstep, so each step is one batched call and every clip keeps its own recurrence exactly.  Clips
-    may differ in length (a finished clip's ring goes to the next waiting clip).  `kw` are OnlineStabilizer's options.
+    may differ in length (a finished clip's ring goes to the next waiting clip).  `kw` are OnlineStabilizer's options,
+    scene_cut and scene_min_len among them: every clip then restarts its own history at its own cuts.
     Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips).  With
     frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result.  crop=... is OnlineStabilizer's: frame k of a
     clip is rendered with the zoom the ratchet has reached at frame k, NOT with `stabilize_clip`'s one clip-wide zoom

@@ -12,6 +12,11 @@ each step returns the stabilised surfaces at source size in the same layout, rea
 --crop auto|Z: the frames come back without sampler A's black border.  Z in (0, 1] is a fixed zoom; "auto" keeps one zoom
 per stream on the device and only ever lowers it (OnlineStabilizer(crop="auto")); the zoom each stream has reached is
 printed at the end.
+
+--scene-cut THR: every stream notices its own scene cuts on the device and restarts its history (and its crop zoom) at the
+cut frame (OnlineStabilizer(scene_cut=THR), THR in (0, 1]; 0.75 separates the two synthetic scenes).  The synthetic source
+then cuts from a dark scene to a bright one half way through; the frame each stream's cut was detected at is printed from
+`scene_state`.
 """
 import argparse
 import os
@@ -29,22 +34,30 @@ from coupe.dvsg_amd.online import OnlineStabilizer          # noqa: E402
 from coupe.dvsg_amd.weights import make_synthetic_weights   # noqa: E402
 
 
-def synthetic_source(seed, n, h, w):
+def _scene(x, k, cut_at):
+    """Frame k of a source in [0, 1]: as it is, or with a cut at frame `cut_at` the dark scene [0.05, 0.45] before it and the
+    bright scene [0.55, 0.95] from it on."""
+    if cut_at is None:
+        return x
+    return (0.05 if k < cut_at else 0.55) + 0.4 * x
+
+
+def synthetic_source(seed, n, h, w, cut_at=None):
     """Yields n BGR uint8 frames [h,w,3], one at a time."""
     import inputs
-    bank = (inputs.smooth_frames(seed, 8, h, w) * 255).astype(np.uint8)[..., ::-1]
+    bank = inputs.smooth_frames(seed, 8, h, w)[..., ::-1]
     for k in range(n):
-        yield np.ascontiguousarray(bank[k % 8])
+        yield np.ascontiguousarray((_scene(bank[k % 8], k, cut_at) * 255).astype(np.uint8))
 
 
-def synthetic_nv12_source(seed, n, h, w):
+def synthetic_nv12_source(seed, n, h, w, cut_at=None):
     """Yields n NV12 frames [3h/2, w] uint8 (h rows of Y, h/2 rows of U0 V0 U1 V1 ...), limited range, one at a time."""
     import inputs
-    y = 16 + inputs.smooth_frames(seed, 8, h, w, C=1)[..., 0] * 219
-    c = 16 + inputs.smooth_frames(seed + 100, 8, h // 2, w // 2, C=2) * 224
-    bank = np.concatenate([y, c.reshape(8, h // 2, w)], axis=1).astype(np.uint8)
+    y = inputs.smooth_frames(seed, 8, h, w, C=1)[..., 0]
+    c = (16 + inputs.smooth_frames(seed + 100, 8, h // 2, w // 2, C=2) * 224).reshape(8, h // 2, w)
     for k in range(n):
-        yield np.ascontiguousarray(bank[k % 8])
+        yk = 16 + _scene(y[k % 8], k, cut_at) * 219
+        yield np.ascontiguousarray(np.concatenate([yk, c[k % 8]], axis=0).astype(np.uint8))
 
 
 def main():
@@ -56,22 +69,25 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "f32x3", "f32s", "f16"])
     ap.add_argument("--format", default="rgb", choices=["rgb", "nv12"])
     ap.add_argument("--crop", default=None, help="'auto' or a zoom in (0, 1]")
+    ap.add_argument("--scene-cut", type=float, default=None, metavar="THR", help="detect scene cuts: a threshold in (0, 1]")
     args = ap.parse_args()
+    scene = dict(scene_cut=args.scene_cut) if args.scene_cut is not None else {}
+    cut_at = args.frames // 2 if scene else None
     crop = args.crop if args.crop in (None, "auto") else float(args.crop)
     net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0))
     net.precision = args.precision
     nv12 = args.format == "nv12"
     if nv12:
-        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop)
+        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop, **scene)
         make = synthetic_nv12_source
     else:
         stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True,
-                                crop=crop)
+                                crop=crop, **scene)
         make = synthetic_source
     H0, W0 = args.height * 3 // 2, args.width * 3 // 2
     if nv12:
         H0, W0 = H0 // 2 * 2, W0 // 2 * 2   # NV12 needs even sizes
-    sources = {stab.open(): make(s + 1, args.frames, H0, W0) for s in range(args.streams)}
+    sources = {stab.open(): make(s + 1, args.frames, H0, W0, cut_at) for s in range(args.streams)}
     lat = []
     for k in range(args.frames):
         frames = {sid: next(src) for sid, src in sources.items()}
@@ -84,9 +100,17 @@ def main():
         elif k == 0:
             out, side = next(iter(outs.values()))
             print("per stream and step: stabilised", out.shape, out.dtype, "| side-by-side", side.shape, side.dtype)
+        for sid in sources if scene else ():
+            st = stab.scene_state(sid)
+            if k > 0 and st["frames_since_cut"] == 1:
+                print("stream %d: cut detected at frame %d (the source cuts at %d)" % (sid, k, cut_at))
     for sid in list(sources):
         if crop is not None:
             print("stream %d: zoom %.4f" % (sid, stab.crop_state(sid)["zoom"]))
+        if scene:
+            st = stab.scene_state(sid)
+            print("stream %d: %d cut(s), %d frames since the last, last score %.3f"
+                  % (sid, st["cuts"], st["frames_since_cut"], st["score"]))
         stab.close(sid)
     lat = np.array(lat[1:] if len(lat) > 1 else lat) * 1e3
     print("%d stream(s) of %dx%d, %s: median %.2f ms per step (%.2f ms per frame), %.1f frames/s in all"

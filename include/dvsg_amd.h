@@ -402,6 +402,47 @@ int dvsg_frames_f32_to_u8_slots(const float *pool, int n_pool, const int32_t *sl
 int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
                        int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream);
 /* ---------------------------------------------------------------------------------------
+ * ONLINE streams, SCENE CUTS (coupe.dvsg_amd.online, scene_cut=threshold): a live stream cuts, and after a cut the window of
+ * the next span steps would mix two scenes.  dvsg_scene_step_f32 notices the cut on the device and restarts the ring's
+ * history at that frame; it WRITES the step's `table` and `out_slots` for dvsg_stabilize_ring_inplace_f32, so the host
+ * uploads ring numbers only and nothing is synchronised.  A cut at a stream's frame f is close() + open() onto the same ring
+ * + push(f): f is step 0 (every window entry the input slot), the rows that follow count k from f, and the crop zoom of the
+ * ring restarts.  History slots that still hold the old scene are never read: step k >= 1 of the new run reads frames
+ * 0 .. k - 1 of that run only.
+ *   The statistic, of pool frame base + span + 1 (the ring's input slot, float32 RGB at the model's size, after ingest --
+ *   the same for uint8, float and NV12 sources), every float32 operation rounded on its own:
+ *       Y   = fl(fl(fl(0.299f r) + fl(0.587f g)) + fl(0.114f b))
+ *       q   = clamp((int)floorf(fl(Y 255f) + 0.5f), 0, 255), NaN -> 0;   bin = q >> 2: 64 bins of int32 counts over H W pixels
+ *       S   = sum over bins |cur - prev|, an int32 in [0, 2 H W];  S = 0 at a ring's first frame (k == 0: no previous)
+ *       cut <=> k >= max(1, min_len) and S >= thr_count              thr_count = ceil(threshold 2 H W), the host's, in float64
+ *   Integer after the one quantisation: exact, the same on every run, in whatever order the workgroups arrive.
+ *   state  int32 [n_state, DVSG_SCENE_STATE_INTS] on the device, row r of ring r: [0] k, the frames since the ring's last
+ *          start (open, reset or cut); [1] the cuts so far; [2] the last S; [3] 0; [4, 68) the previous histogram.  A row
+ *          of zeros is a ring before its first frame.  k is an int32: restart a ring before 2^31 - 1 frames.
+ *   dvsg_scene_step_f32  per row b of the step, with r = rings[b] (int32 [B] ON THE DEVICE), span = skip_host[S - 1]
+ *          (skip_host: the S skip lengths, int32 on the HOST, >= 0 and strictly increasing) and base = r (span + 2):
+ *            1. the histogram of pool frame base + span + 1;  2. the decision above;
+ *            3. on a cut: k = 0, state[r][1] += 1, and zoom_state[r] = crop_start when zoom_state (float32 [n_state], the
+ *               state of dvsg_crop_ratchet_f32) is not NULL;
+ *            4. table[b] [S] = the window of step k (ONLINE above), out_slots[b] = base + k % (span + 1), cut[b] = 0 / 1;
+ *            5. state[r] = (k + 1, cuts, S, 0, the current histogram).
+ *          A ring outside [0, n_state), or one whose input slot lies outside [0, n_pool), gets a table row of -1, an out
+ *          slot of -1 and cut 0 and touches no state (the skipped-slot convention of dvsg_crop_ratchet_f32; an out slot
+ *          of -1 makes dvsg_stabilize_ring_inplace_f32 store no frame).  The rings of one call must be distinct: the
+ *          caller's contract, not checked on the device.  Checked before any device work: NULL pointers (zoom_state may
+ *          be NULL), 1 <= B <= 65535, 1 <= S <= 16, 2 H W < 2^31, 1 <= thr_count <= 2 H W, min_len >= 0.  workspace:
+ *          dvsg_scene_workspace_bytes(B) bytes, 16-byte aligned (DVSG_ERR_WORKSPACE if short): [B,64] int32, zeroed by the
+ *          call.  One memset and two launches: the histogram pass (16-byte loads, one LDS histogram per wave, one global
+ *          int32 atomic per non-zero bin and workgroup; pixels off the 16-byte grid at either end of a frame take a scalar
+ *          path, nothing is padded) and the decision pass (one wave per row, lane = bin).  The pool is only read.
+ * ------------------------------------------------------------------------------------- */
+#define DVSG_SCENE_STATE_INTS 68
+int dvsg_scene_workspace_bytes(int B, size_t *bytes);
+int dvsg_scene_step_f32(const float *pool, int n_pool, int H, int W, const int32_t *rings, int B, const int32_t *skip_host,
+                        int S, int32_t *state, int n_state, int thr_count, int min_len, float *zoom_state, float crop_start,
+                        int32_t *table, int32_t *out_slots, int32_t *cut, void *workspace, size_t workspace_bytes,
+                        void *stream);
+/* ---------------------------------------------------------------------------------------
  * NV12 frames (coupe.dvsg_amd.online, frame_format="nv12"): what a hardware decoder hands over and an encoder takes.
  * Layout of a batch of n frames of H x W (H, W even, >= 4):
  *   y   uint8: row i of frame f at y + f * frame_stride + i * pitch, W bytes used;

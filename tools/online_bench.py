@@ -17,6 +17,14 @@ line per (format, K, variant): the median, smallest and largest step over all ro
 all, so the same file measures a tree from before the option.
 
     python tools/online_bench.py --crop [--source 1080x1920] [--formats nv12,rgb] [--variants none,0.9,auto] [--rounds 5]
+
+--scene-cut [THR]: the cost of OnlineStabilizer(scene_cut=THR) per step (default 0.75).  For each size of --sizes and each
+K of --streams, same-size uint8 frames on the device through the first precision of --precisions: one OnlineStabilizer with
+the option off and one with it on, measured like --crop (warmed up, the two alternating inside each of --rounds rounds).  One
+JSON line per (size, K, variant) with the cuts the run detected.  "off" passes no scene argument at all, so
+`--scene-cut --variants off` of this file measures a tree from before the option.
+
+    python tools/online_bench.py --scene-cut [0.75] [--sizes 720x1280,288x512] [--variants off,on] [--rounds 5]
 """
 import argparse
 import json
@@ -40,7 +48,9 @@ def main():
     ap.add_argument("--crop", action="store_true", help="measure the per-step cost of OnlineStabilizer(crop=...)")
     ap.add_argument("--source", default="1080x1920")
     ap.add_argument("--formats", default="nv12,rgb")
-    ap.add_argument("--variants", default="none,0.9,auto")
+    ap.add_argument("--variants", default=None, help="--crop: none,0.9,auto (default: all); --scene-cut: off,on")
+    ap.add_argument("--scene-cut", type=float, nargs="?", const=0.75, default=None, metavar="THR",
+                    help="measure the per-step cost of OnlineStabilizer(scene_cut=THR)")
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 1:
@@ -67,8 +77,13 @@ def main():
                 for rec in lines:
                     f.write(json.dumps(rec) + "\n")
 
-    if args.crop:
-        crop_legs(args, weights, emit)
+    if args.crop or args.scene_cut is not None:
+        if args.crop:
+            args.variants = args.variants or "none,0.9,auto"
+            crop_legs(args, weights, emit)
+        else:
+            args.variants = args.variants or "off,on"
+            scene_legs(args, weights, emit)
         flush()
         return
 
@@ -146,22 +161,7 @@ def crop_legs(args, weights, emit):
                 kw = dict(base) if v == "none" else dict(base, crop="auto" if v == "auto" else float(v))
                 on = OnlineStabilizer(model, max_streams=K, **kw)
                 stabs.append((v, on, [on.open() for _ in range(K)], []))
-            step_no = 0
-            for _, on, sids, _ in stabs:
-                for k in range(args.warmup):
-                    on.step({sid: bank[(k + 3 * s) % 8] for s, sid in enumerate(sids)})
-            torch.cuda.synchronize()
-            for r in range(args.rounds):
-                for _, on, sids, times in stabs:   # the variants alternate inside the round
-                    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-                    for k in range(args.steps):
-                        feed = {sid: bank[(step_no + k + 3 * s) % 8] for s, sid in enumerate(sids)}
-                        ev[k][0].record()
-                        on.step(feed)
-                        ev[k][1].record()
-                    torch.cuda.synchronize()
-                    times.extend(a.elapsed_time(b) for a, b in ev)
-                step_no += args.steps
+            _alternate(stabs, bank, args)
             for v, on, sids, times in stabs:
                 t = sorted(times)
                 rec = {"what": "online_crop", "format": fmt, "source_H": H0, "source_W": W0, "H": h, "W": w, "precision": "f32",
@@ -170,6 +170,64 @@ def crop_legs(args, weights, emit):
                        "p10_step_ms": t[len(t) // 10], "p90_step_ms": t[(9 * len(t)) // 10]}
                 if v == "auto":
                     rec["zoom"] = [float(on.crop_state(sid)["zoom"]) for sid in sids][:4]
+                emit(rec)
+            del stabs
+            torch.cuda.empty_cache()
+
+
+def _alternate(stabs, bank, args):
+    """Warm every (variant, stabiliser, stream ids, times) of `stabs` up, then --rounds rounds in each of which every variant
+    in turn runs --steps steps between device events; the step times in ms are appended to `times`.  Stream s at step k
+    reads frame (k + 3 s) % 8 of `bank`."""
+    import torch
+    for _, on, sids, _ in stabs:
+        for k in range(args.warmup):
+            on.step({sid: bank[(k + 3 * s) % 8] for s, sid in enumerate(sids)})
+    torch.cuda.synchronize()
+    step_no = 0
+    for r in range(args.rounds):
+        for _, on, sids, times in stabs:   # the variants alternate inside the round
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+            for k in range(args.steps):
+                feed = {sid: bank[(step_no + k + 3 * s) % 8] for s, sid in enumerate(sids)}
+                ev[k][0].record()
+                on.step(feed)
+                ev[k][1].record()
+            torch.cuda.synchronize()
+            times.extend(a.elapsed_time(b) for a, b in ev)
+        step_no += args.steps
+
+
+def scene_legs(args, weights, emit):
+    import numpy as np
+    import torch
+    import inputs
+    from coupe.dvsg_amd.model import StabNet
+    from coupe.dvsg_amd.online import OnlineStabilizer
+    variants = args.variants.split(",")
+    if any(v not in ("off", "on") for v in variants):
+        raise SystemExit("--scene-cut takes --variants off, on or off,on")
+    prec = args.precisions.split(",")[0]
+    for size in args.sizes.split(","):
+        H, W = (int(v) for v in size.split("x"))
+        model = StabNet(H, W).load_weights(weights)
+        model.get_evaluation_model(7)
+        model.precision = prec
+        bank = torch.from_numpy((inputs.smooth_frames(11, 8, H, W) * 255).astype(np.uint8)).cuda()
+        for K in (int(v) for v in args.streams.split(",")):
+            stabs = []
+            for v in variants:
+                on = OnlineStabilizer(model, max_streams=K, **(dict(scene_cut=args.scene_cut) if v == "on" else {}))
+                stabs.append((v, on, [on.open() for _ in range(K)], []))
+            _alternate(stabs, bank, args)
+            for v, on, sids, times in stabs:
+                t = sorted(times)
+                rec = {"what": "online_scene", "H": H, "W": W, "precision": prec, "K": K,
+                       "scene_cut": args.scene_cut if v == "on" else "off", "rounds": args.rounds,
+                       "steps_per_round": args.steps, "median_step_ms": t[len(t) // 2], "min_step_ms": t[0],
+                       "max_step_ms": t[-1], "p10_step_ms": t[len(t) // 10], "p90_step_ms": t[(9 * len(t)) // 10]}
+                if v == "on":
+                    rec["cuts"] = sum(on.scene_state(sid)["cuts"] for sid in sids)
                 emit(rec)
             del stabs
             torch.cuda.empty_cache()
