@@ -109,6 +109,8 @@ SIGNATURES = {
     "dvsg_debug_conv3x3_1x1": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dvsg_debug_calibrate_f16_weights": [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp],
     "dvsg_locnet_calibrate_f16": [_vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp],
+    "dvsg_debug_calibration_means": [_vp, _vp, _vp],
+    "dvsg_debug_plain_weights_f16": [_vp, _i, _i, _vp, ctypes.c_size_t, ctypes.POINTER(_i)],
     "dvsg_markers_enabled": [],
     "dvsg_prof_begin": [_i],
     "dvsg_prof_end": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_double),

@@ -82,6 +82,11 @@ struct dvsg_locnet {
   // float16 mode: which layers multiply by hi / lo weight PAIRS (bit 4 * kind + block, see DebugOptions::f16_pair_mask).  All of them
   // until dvsg_locnet_calibrate_f16 has re-rounded the plain copies of blocks 2-4 with error feedback: then block 1 only.
   int f16_pair_mask = 0xFFFF;
+  // what the last calibrate_f16 of this handle re-rounded against (dvsg_debug_calibration_means): the channel means mu
+  // [48][2048] that redo() read and the rows summed per slot; 1.0 and 0 rows where no means were measured (a new handle,
+  // mode 0, mode 1)
+  std::vector<double> calib_mu = std::vector<double>((size_t)48 * 2048, 1.0);
+  double calib_rows[48] = {0};
   std::vector<void *> allocs;
 };
 
@@ -1105,6 +1110,7 @@ int dvsg_debug_set_option(const char *name, int value) {
 static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, int W, int mode, void *workspace,
                          size_t workspace_bytes, hipStream_t s) {
   std::vector<double> mu((size_t)48 * 2048, 1.0);
+  double rows[48] = {0};
   if (mode == 2) {   // calibrated channel means
     Calib calib;   // the recorder of this pass alone: forward() of other handles and threads never see it
     void *sums = nullptr, *part = nullptr, *F = nullptr;
@@ -1128,7 +1134,11 @@ static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, i
     if (rc) return rc;
     for (int slot = 0; slot < 48; ++slot)
       for (int c = 0; c < 2048; ++c) mu[(size_t)slot * 2048 + c] = calib.rows[slot] > 0 ? mu[(size_t)slot * 2048 + c] / calib.rows[slot] : 1.0;
+    std::copy(calib.rows, calib.rows + 48, rows);
   }
+  // kept in the handle, and redo() reads them THERE: what dvsg_debug_calibration_means shows is what the weights were chosen by
+  net->calib_mu = mu;
+  std::copy(rows, rows + 48, net->calib_rows);
   auto f16_bits = [](_Float16 v) { unsigned short b; std::memcpy(&b, &v, 2); return b; };
   auto f16_from = [](unsigned short b) { _Float16 v; std::memcpy(&v, &b, 2); return v; };
   auto neighbour = [&](_Float16 q, bool up) -> _Float16 {   // next float16 above / below q
@@ -1165,7 +1175,7 @@ static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, i
   };
   int ui = 0;
   for (Unit &u : net->units) {
-    const double *mx = mu.data() + (size_t)(3 * ui) * 2048;
+    const double *mx = net->calib_mu.data() + (size_t)(3 * ui) * 2048;
     if (u.has_shortcut) if (int rc = redo(u.shortcut, mx)) return rc;
     if (int rc = redo(u.c1, mx)) return rc;
     if (int rc = redo(u.c2, mx + 2048)) return rc;
@@ -1192,6 +1202,30 @@ int dvsg_debug_calibrate_f16_weights(dvsg_locnet_t *net, const float *patches, i
                                      size_t workspace_bytes, void *stream) {
   DVSG_REQUIRE(net && patches && workspace && mode >= 0 && mode <= 2, "dvsg_debug_calibrate_f16_weights: bad arguments");
   return calibrate_f16(net, patches, B, H, W, mode, workspace, workspace_bytes, as_stream(stream));
+}
+
+int dvsg_debug_calibration_means(const dvsg_locnet_t *net, double *means, double *rows) {
+  DVSG_REQUIRE(net && means && rows, "dvsg_debug_calibration_means: NULL pointer");
+  std::copy(net->calib_mu.begin(), net->calib_mu.end(), means);
+  std::copy(net->calib_rows, net->calib_rows + 48, rows);
+  return DVSG_OK;
+}
+
+int dvsg_debug_plain_weights_f16(const dvsg_locnet_t *net, int unit, int kind, void *w16, size_t w16_bytes, int *dims) {
+  DVSG_REQUIRE(net && dims, "dvsg_debug_plain_weights_f16: NULL pointer");
+  DVSG_REQUIRE(unit >= 0 && unit < (int)net->units.size(), "dvsg_debug_plain_weights_f16: unit %d outside 0..%d", unit,
+               (int)net->units.size() - 1);
+  DVSG_REQUIRE(kind >= kKindC1 && kind <= kKindSc, "dvsg_debug_plain_weights_f16: kind %d outside 0..3", kind);
+  const Unit &u = net->units[unit];
+  DVSG_REQUIRE(kind != kKindSc || u.has_shortcut, "dvsg_debug_plain_weights_f16: unit %d has no shortcut convolution", unit);
+  const ConvLayer &L = kind == kKindC1 ? u.c1 : kind == kKindC2 ? u.c2 : kind == kKindC3 ? u.c3 : u.shortcut;
+  const int K = L.ksize * L.ksize * L.cin;
+  dims[0] = L.cout; dims[1] = K; dims[2] = L.cin;
+  if (!w16) return DVSG_OK;
+  const size_t bytes = (size_t)L.cout * K * sizeof(_Float16);
+  DVSG_REQUIRE(w16_bytes >= bytes, "dvsg_debug_plain_weights_f16: buffer %zu bytes < %zu", w16_bytes, bytes);
+  DVSG_HIP(hipMemcpy(w16, L.wt16, bytes, hipMemcpyDeviceToHost));
+  return DVSG_OK;
 }
 
 int dvsg_stabilize_f32(const dvsg_locnet_t *net, const float *patches_t, const float *u_t, int B, int H, int W,

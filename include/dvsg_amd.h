@@ -655,6 +655,19 @@ int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float
  * mu = 1 (measured: useless -- channel means are far from uniform); 2: calibrated channel means. */
 int dvsg_debug_calibrate_f16_weights(dvsg_locnet_t *net, const float *patches, int B, int H, int W, int mode, void *workspace,
                                      size_t workspace_bytes, void *stream);
+/* What the last calibration of this handle re-rounded against (dvsg_locnet_calibrate_f16, dvsg_debug_calibrate_f16_weights),
+ * copied to host memory: means [48][2048] float64, slot 3 u + {0: unit u's input (conv1, shortcut), 1: conv1's output
+ * (conv2), 2: conv2's output (conv3)}, u = 0..15 in network order, and rows [48] float64, the pixels summed per slot.  They
+ * are the values the weights were chosen by, kept in the handle, not a second measurement.  Channels past a slot's tensor
+ * hold 0 and are never read.  A new handle, mode 0, patches == NULL and mode 1 leave every mean at the 1.0 the rule then
+ * uses, and every row count at 0.  No device work. */
+int dvsg_debug_calibration_means(const dvsg_locnet_t *net, double *means, double *rows);
+/* The PLAIN float16 copy of one convolution's folded weights as the handle holds it now (what a float16 layer without the
+ * hi / lo pair multiplies; its stage-packed copies are made from it): unit 0..15 in network order, kind 0 conv1, 1 conv2,
+ * 2 conv3, 3 shortcut (DVSG_ERR_INVALID_ARG where the unit has none).  dims [3] receives cout, K = ksize^2 cin and cin;
+ * w16 (host memory, [cout][K] float16, k = (kh, kw, c); w16_bytes its size) may be NULL to ask for dims alone.
+ * Synchronous. */
+int dvsg_debug_plain_weights_f16(const dvsg_locnet_t *net, int unit, int kind, void *w16, size_t w16_bytes, int *dims);
 
 /* ---------------------------------------------------------------------------------------
  * Test-time losses: trainer.py:95-123 `build_loss_train` on get_train_model(is_train = False), the score

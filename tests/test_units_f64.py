@@ -14,9 +14,11 @@ the mode holds them, reproduced in NumPy float32 with one rounding per operation
                 dvsg_locnet_calibrate_f16 and 0x1111 after it, i.e. block 1 alone.  A layer without the pair multiplies the
                 plain copy.  After calibration that copy is NOT f16(w): calibrate_f16's redo() takes, weight by weight, f16(w)
                 or its float16 neighbour on the other side of w (`neighbour(q0, q0 < w32)`), chosen by a running sum over
-                channel means of a pass whose r1 and r2 no tap shows.  The reference therefore multiplies the midpoint of the
-                two candidates and the bound carries conv(|a|, half their distance): the one term of this file that is an
-                interval of the operand and not a rounding of the arithmetic (half a float16 ulp of w, 2^-12 relative).
+                channel means of a pass whose r1 and r2 no tap shows.  The reference of THIS file's cases therefore multiplies
+                the midpoint of the two candidates and the bound carries conv(|a|, half their distance): the one term of this
+                file that is an interval of the operand and not a rounding of the arithmetic (half a float16 ulp of w, 2^-12
+                relative).  test_calibration_f64.py reads the copy back from the handle, holds it to the rule that chose it,
+                fills PLAIN with it and runs _check_units without the interval (MEASURED, row "f16cal known").
 
 The intermediates r1, r2 and bufS cannot be observed, so the bound is composed through the unit; ReLU is 1-Lipschitz and
 every |w| is known.  B_k(S) = f64.bound(prec, K_k, S) + the bias slack (float16: tau(K) S + K 2^-126, the interval's E):
@@ -32,7 +34,8 @@ every |w| is known.  B_k(S) = f64.bound(prec, K_k, S) + the bias slack (float16:
     include single storage roundings of half-width h (P format, float16): by Hoeffding a sum of independent errors bounded by
     h_i |w_i| exceeds 8 sqrt(sum h_i^2 w_i^2) with probability 2 e^-32 per element.  The calibrated float16 net keeps the worst
     case alone: its largest term, which of two float16 neighbours a re-rounded weight is, is one value for the nine taps of
-    conv2's window and not independent between them.
+    conv2's window and not independent between them.  Where PLAIN holds the copies the term is gone and the float16 mode's
+    8 applies.
     st(v): f32, f32x3 0 (the output rounding is tau's C_ONE);  f32s 2^-22 (|v| + E) + 2^-25 (P format, cnn_device.h);
            f16 ulp16(|v| + E) / 2
     f32, f32s, f32x3:  |y - relu(pre)| <= E3 + st(y);      f16:  RN16(relu(pre - E3)) <= y <= RN16(relu(pre + E3))  (check16)
@@ -85,7 +88,7 @@ MASK_PAIRS_EVERYWHERE, MASK_CALIBRATED = 0xFFFF, 0x1111
 MODES = ("f32", "f32s", "f32x3", "f16", "f16cal")
 SHAPES = [(2, 64, 96), (1, 70, 100), (3, 33, 47), (1, 8, 8), (1, 20, 4), (16, 32, 48)]
 WIRING_SHAPES = SHAPES[:2]
-C_QUAD = {"f32": 2.0, "f32x3": 2.0, "f32s": 8.0, "f16": 8.0, "f16cal": None}     # see the module docstring; None: worst case only
+C_QUAD = {"f32": 2.0, "f32x3": 2.0, "f32s": 8.0, "f16": 8.0, "f16cal": None}     # see the module docstring; None: worst case only (PLAIN empty)
 OLD_REL = 2e-5          # test_gpu_cnn.py / test_gpu_f32x3.py: max |act - ref| <= 2e-5 max |ref| per stage
 
 # Measured on one MI355X (worst |y - ref| / bound over all shapes, options and sources; float16: |y - relu(pre)| /
@@ -98,9 +101,12 @@ MEASURED = """
     f32x3    0.047 0.016 0.013      0.020 0.006 0.006 0.004     0.017 0.003 0.004 0.003 0.003 0.003    0.004 0.002 0.002
     f16      0.152 0.191 0.245      0.194 0.287 0.232 0.187     0.233 0.176 0.187 0.153 0.190 0.175    0.322 0.237 0.229
     f16cal   0.152 0.191 0.245      0.016 0.016 0.012 0.010     0.009 0.005 0.005 0.004 0.004 0.004    0.004 0.003 0.002
+    f16cal known (test_calibration_f64.py: PLAIN filled from the handle, two shapes, five settings of the wide16 options)
+             0.118 0.123 0.152      0.138 0.133 0.151 0.111     0.159 0.128 0.153 0.129 0.135 0.105    0.145 0.156 0.127
 The f32 and f32x3 modes sit at 0.002-0.06 with the quadrature carry (0.001-0.008 with the worst case alone); f32s gains
 little from it (C_QUAD 8 against conv3's sqrt(64)).  The float16 interval is the sharp one, 0.15-0.32.  After calibration
-blocks 2-4 carry the half-ulp interval of the re-rounded weights, ten times wider.  F_t against the float64 network of the
+blocks 2-4 carry the half-ulp interval of the re-rounded weights, ten times wider, in this file's own cases; with the plain
+copy read back from the handle the interval goes and they read 0.10-0.16, like the paired class.  F_t against the float64 network of the
 mode's operands at 2 x 64 x 96: f32 2.7e-8, f32s 3.5e-8, f32x3 3.0e-8, f16 2.9e-5, f16 calibrated 3.1e-5; the chained bound
 there is 4e10 (f32, f32x3), 3e38 (f32s) and the 1e100 cap (float16)."""
 
@@ -216,12 +222,22 @@ def weight_class(mode, block, kind):
     return "f16p" if f16_pairs(mask, block, kind) else "f16c"
 
 
-def held(w, cls):
+# The exact plain float16 copy of a layer, {scope of the conv: float16 [cout][K]}, for the "f16c" class.  Empty unless a test
+# fills it from the library's read-back (test_calibration_f64.py, which first holds that copy to the rule that chose it);
+# every case of this file runs with it empty and keeps the interval below.
+PLAIN = {}
+
+
+def held(w, cls, plain=None):
     """(the value the kernels multiply, its magnitude for S, the half-width of the operand's interval or None), float64
-    torch tensors [cout][K]"""
+    torch tensors [cout][K].  plain: the "f16c" class's exact copy where it is known -- no interval then"""
     import torch
     rad = None
-    if cls == "f16p":
+    if cls == "f16c" and plain is not None:
+        assert plain.dtype == np.float16 and plain.shape == w.shape
+        v = plain.astype(np.float64)
+        a = np.abs(v)
+    elif cls == "f16p":
         hi, lo = unrows_hi_lo(rows_hi_lo(w))
         hi, lo = hi.astype(np.float64), lo.astype(np.float64) / 2048.0
         v, a = hi + lo, np.abs(hi) + np.abs(lo)
@@ -285,7 +301,8 @@ def _layer(weights, U, kind, mode, x, Ex, Qx, stride, exact, opts, extra_S=None,
     if mut:
         w, b = mut(kind, w, b)
     cls = "f32" if exact else weight_class(mode, U.block, kind)
-    w64, wabs, rad = held(w, cls)
+    known = None if mut else PLAIN.get(U.scope + name + "/")
+    w64, wabs, rad = held(w, cls, known)
     k = 3 if kind == "c2" else 1
     K = w.shape[1]
     b64 = torch.from_numpy(b.astype(np.float64))
@@ -306,16 +323,18 @@ def _layer(weights, U, kind, mode, x, Ex, Qx, stride, exact, opts, extra_S=None,
     E, Q = own, own
     if bool((Ex > 0).any()):
         E = own + conv64(Ex, wabs, k, stride)
-        c = C_QUAD[mode]
+        # (calibrated net, plain copy known: no shared interval is carried any more, the float16 mode's quadrature holds)
+        c = C_QUAD["f16" if mode == "f16cal" and PLAIN else mode]
         Q = own + (c * torch.sqrt(conv64(Qx * Qx, wabs * wabs, k, stride)) if c else conv64(Qx, wabs, k, stride))
     return pre, E, Q, S
 
 
-def unit_ref(weights, U, mode, x, Ex=None, opts=None, exact=False, mut=None, last_only=False):
+def unit_ref(weights, U, mode, x, Ex=None, opts=None, exact=False, mut=None, last_only=False, inter=None):
     """float64 reference of unit U in `mode` from its input x [B, h, w, cin] (float64), known to within Ex per element:
     (pre, E3) of the docstring, E3 the smaller of the worst-case and the quadrature composition; the unit's output is
     relu(pre) stored in the mode's format.  last_only: B_3(S3) alone, around the float64 intermediates taken as exact -- what
-    a check of the unit's last GEMM on its own would allow, below which no composition of the B_k can go"""
+    a check of the unit's last GEMM on its own would allow, below which no composition of the B_k can go.  inter: a dict that
+    receives the intermediates a1, a2 (float64) and E1, E2, the bounds within which r1 and r2 hold them"""
     import torch
     opts = opts or {}
     Ex = torch.zeros_like(x) if Ex is None else Ex
@@ -326,6 +345,8 @@ def unit_ref(weights, U, mode, x, Ex=None, opts=None, exact=False, mut=None, las
     pre2, E2, Q2, _ = _layer(weights, U, "c2", mode, a1, E1, Q1, s, exact, opts, mut=mut)
     a2 = pre2.clamp_min(0.0)
     E2, Q2 = E2 + st(a2, E2, mode), Q2 + st(a2, Q2, mode)
+    if inter is not None:
+        inter.update(a1=a1, E1=torch.minimum(E1, Q1), a2=a2, E2=torch.minimum(E2, Q2))
     if U.has_sc:
         sc, Esc, Qsc, Ssc = _layer(weights, U, "sc", mode, x, Ex, Ex, 1, exact, opts, mut=mut)
         Esc = torch.minimum(Esc, Qsc)
