@@ -1109,6 +1109,9 @@ int dvsg_debug_set_option(const char *name, int value) {
 // 2.7e-6 (hi / lo pairs everywhere: 1.6e-6), 22 % less time per step.
 static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, int W, int mode, void *workspace,
                          size_t workspace_bytes, hipStream_t s) {
+  // "synchronous" in every mode: redo() rewrites the weights with blocking copies on the legacy stream, which do not wait for
+  // a non-blocking stream, so a float16 forward still queued on the caller's stream would otherwise run on the new weights
+  DVSG_HIP(hipStreamSynchronize(s));
   std::vector<double> mu((size_t)48 * 2048, 1.0);
   double rows[48] = {0};
   if (mode == 2) {   // calibrated channel means

@@ -14,7 +14,10 @@
 //     Y = fl(fl(fl(0.299f r) + fl(0.587f g)) + fl(0.114f b));  q = clamp((int)floorf(fl(Y 255f) + 0.5f), 0, 255), NaN -> 0
 //     bin = q >> 2 (64 bins, int32 counts);  S = sum_b |cur[b] - prev[b]| in [0, 2 H W];  cut <=> k >= max(1, min_len) and S >= thr
 //
-// Two launches behind one memset of the workspace ([B,64] int32), stream-ordered, nothing synchronised:
+// Three launches, stream-ordered, nothing synchronised:
+//   scene_zero_kernel    zeroes the workspace ([B,64] int32).  A kernel, not hipMemsetAsync: a memset node captured into a
+//                        HIP graph did not take effect on the second and later replays on ROCm 7.2 (cnn_kernels.h,
+//                        launch_zero_tickets), and the histograms of a replayed step would add up.
 //   scene_hist_kernel    grid (blocks per frame, B).  A frame is 3 H W contiguous floats: four pixels are three 16-byte loads.
 //                        The pixels in front of the first 16-byte boundary (at most 3; a frame of an odd pixel count starts
 //                        anywhere) and behind the last whole quad (at most 3) take a scalar path in block 0 -- no padding.
@@ -58,6 +61,11 @@ __device__ __forceinline__ long scene_input_slot(int r, int n_state, int span, i
   if (r < 0 || r >= n_state) return -1;
   const long slot = (long)r * (span + 2) + span + 1;
   return slot < (long)n_pool ? slot : -1;
+}
+
+__global__ __launch_bounds__(kThreads) void scene_zero_kernel(int *__restrict__ hist, int n) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i < n) hist[i] = 0;
 }
 
 __global__ __launch_bounds__(kThreads) void scene_hist_kernel(const float *__restrict__ pool, int n_pool, int n_pix,
@@ -196,7 +204,8 @@ int dvsg_scene_step_f32(const float *pool, int n_pool, int H, int W, const int32
                 need);
   hipStream_t s = as_stream(stream);
   int *hist = static_cast<int *>(workspace);
-  DVSG_HIP(hipMemsetAsync(hist, 0, need, s));
+  hipLaunchKernelGGL(scene_zero_kernel, dim3(ceil_div(B * kBins, kThreads)), dim3(kThreads), 0, s, hist, B * kBins);
+  if (int rc = check_launch("scene_zero_kernel")) return rc;
   const int per_frame = ceil_div(n_pix, 4 * kQuadsPerThread * kThreads);
   dim3 grid(per_frame < kMaxBlocksPerFrame ? per_frame : kMaxBlocksPerFrame, B);
   hipLaunchKernelGGL(scene_hist_kernel, grid, dim3(kThreads), 0, s, pool, n_pool, n_pix, rings, n_state, span, hist);

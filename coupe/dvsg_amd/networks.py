@@ -38,7 +38,7 @@ def _entry(base, precision):
 
 
 class LocNet(object):
-    """Owns the device-side network (`dvsg_locnet_t`) and a growable workspace."""
+    """Owns the device-side network (`dvsg_locnet_t`) and one growable workspace per stream that uses it."""
 
     def __init__(self, weights):
         device()
@@ -68,16 +68,25 @@ class LocNet(object):
         except Exception:
             pass
 
-    def workspace(self, B, H, W, slot=0):
+    def workspace(self, B, H, W, slot=0, stream=None):
+        """(buffer, bytes needed) for a [B,H,W,c_in] batch.  Buffers are PER STREAM: the C ABI lets calls on distinct streams
+        run concurrently only on distinct workspaces (include/dvsg_amd.h, Conventions), so the buffer is keyed by
+        (slot, the stream it will be used on) -- `stream`, a torch stream, default the current one -- and two callers that
+        share this LocNet under two streams never share scratch.  It is allocated with that stream current, so the caching
+        allocator orders a later free behind the work queued there.  The same stream gets the same buffer back (it grows,
+        never shrinks); memory grows only for callers that really use several streams."""
+        import torch
         need = ctypes.c_size_t()
         _lib.call("dvsg_locnet_workspace_bytes", self.handle, B, H, W, ctypes.byref(need))
         if self._ws is None:
             self._ws = {}
-        ws = self._ws.get(slot)
+        s = torch.cuda.current_stream() if stream is None else stream
+        key = (slot, s.device_index, s.cuda_stream)
+        ws = self._ws.get(key)
         if ws is None or ws.numel() < need.value:
-            import torch
-            self._ws[slot] = None
-            ws = self._ws[slot] = torch.empty(need.value, dtype=torch.uint8, device=device())
+            self._ws[key] = None
+            with torch.cuda.stream(s):
+                ws = self._ws[key] = torch.empty(need.value, dtype=torch.uint8, device=device())
         return ws, need.value
 
     def stabilize(self, patches, u_t, out, F, xs=None, ys=None, n_streams=1, precision="f32", mask=None):
@@ -130,7 +139,7 @@ class LocNet(object):
             if b0 >= b1:
                 break
             side.wait_event(fork)
-            ws, nbytes = self.workspace(b1 - b0, H, W, slot=1 + i)
+            ws, nbytes = self.workspace(b1 - b0, H, W, slot=1 + i, stream=side)
             _lib.call(fn, self.handle, ptr(patches[b0:b1]), ptr(u_t[b0:b1]), b1 - b0, H, W,
                       ptr(out[b0:b1]), ptr(F[b0:b1]), ptr(xs[b0 * H * W:b1 * H * W]) if xs is not None else 0,
                       ptr(ys[b0 * H * W:b1 * H * W]) if ys is not None else 0, ptr(ws), nbytes, side.cuda_stream)

@@ -18,7 +18,17 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream).  All
  *     calls are asynchronous and stream-ordered; none allocates, frees or synchronises.
  *     Calls on distinct streams are re-entrant as long as their output / workspace buffers
- *     are distinct.
+ *     are distinct.  tests/test_gpu_streams.py holds every entry point with a `stream` to this:
+ *     captured into a HIP graph and replayed on fresh values, and in pairs on two streams of one
+ *     handle.  The exceptions say "synchronous" in their own comment (the float16 calibration:
+ *     it waits for `stream`, in every mode, before it rewrites the handle's weights).  Found
+ *     with that module and fixed: dvsg_scene_step_f32 zeroed its histograms with a memset node,
+ *     which did not take effect on the second and later replays of a captured step (it is a
+ *     kernel now); the undo form of dvsg_locnet_calibrate_f16 and modes 0 / 1 of
+ *     dvsg_debug_calibrate_f16_weights did not wait for `stream`, so a float16 forward still
+ *     queued there ran on the rewritten weights; and the Python facade's LocNet.workspace kept
+ *     one buffer for all streams, breaking the distinct-workspace condition on its callers'
+ *     behalf (it is keyed by stream now).
  *   - optional outputs may be NULL.
  */
 #ifndef DVSG_AMD_H
@@ -432,8 +442,8 @@ int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t
  *          caller's contract, not checked on the device.  Checked before any device work: NULL pointers (zoom_state may
  *          be NULL), 1 <= B <= 65535, 1 <= S <= 16, 2 H W < 2^31, 1 <= thr_count <= 2 H W, min_len >= 0.  workspace:
  *          dvsg_scene_workspace_bytes(B) bytes, 16-byte aligned (DVSG_ERR_WORKSPACE if short): [B,64] int32, zeroed by the
- *          call.  One memset and two launches: the histogram pass (16-byte loads, one LDS histogram per wave, one global
- *          int32 atomic per non-zero bin and workgroup; pixels off the 16-byte grid at either end of a frame take a scalar
+ *          call.  Three launches: a fill of the workspace (a kernel: a captured memset node does not replay), the histogram
+ *          pass (16-byte loads, one LDS histogram per wave, one global int32 atomic per non-zero bin and workgroup; pixels off the 16-byte grid at either end of a frame take a scalar
  *          path, nothing is padded) and the decision pass (one wave per row, lane = bin).  The pool is only read.
  * ------------------------------------------------------------------------------------- */
 #define DVSG_SCENE_STATE_INTS 68
@@ -652,7 +662,8 @@ int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float
                            int B, int H, int W, int Cin, int Cout, int stride, int res_stride, void *stream);
 /* The A/B form of dvsg_locnet_calibrate_f16 (tools/f16_ef_sweep.py): re-rounds the plain float16 weight copies and leaves
  * the pair policy to "f16_pair_mask".  mode 0: round to nearest (what dvsg_locnet_create makes); 1: error feedback with
- * mu = 1 (measured: useless -- channel means are far from uniform); 2: calibrated channel means. */
+ * mu = 1 (measured: useless -- channel means are far from uniform); 2: calibrated channel means.  Synchronous like it, in
+ * every mode: it waits for `stream` before it rewrites the weights. */
 int dvsg_debug_calibrate_f16_weights(dvsg_locnet_t *net, const float *patches, int B, int H, int W, int mode, void *workspace,
                                      size_t workspace_bytes, void *stream);
 /* What the last calibration of this handle re-rounded against (dvsg_locnet_calibrate_f16, dvsg_debug_calibrate_f16_weights),

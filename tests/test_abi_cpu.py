@@ -45,6 +45,41 @@ def test_python_binding_covers_every_declared_symbol():
     assert set(declared_symbols()) == bound
 
 
+def stream_entry_points():
+    """name -> the comment block in front of its declaration group, for every declared function with a `void *stream`
+    parameter; whitespace runs collapsed."""
+    text = open(HEADER).read()
+    out = {}
+    for m in re.finditer(r"\bint\s+(dvsg_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", re.sub(r"/\*.*?\*/", lambda c: " " * len(c.group(0)), text, flags=re.S)):
+        if re.search(r"\bvoid\s*\*\s*stream\b", m.group(2)):
+            comments = re.findall(r"/\*.*?\*/", text[:m.start()], flags=re.S)
+            out[m.group(1)] = " ".join(comments[-1].split()) if comments else ""
+    return out
+
+
+def test_every_stream_entry_point_is_held_to_the_stream_contract_or_exempt():
+    """tests/test_gpu_streams.py registers every entry point that takes a stream (CASES) or names the header's own phrase that
+    documents it as synchronous, host-side or debug-only (EXEMPT).  A new entry point fails here until someone decides which.
+    Imported without torch: the registry's builders only run on the GPU."""
+    import sys
+    had_torch = "torch" in sys.modules
+    import test_gpu_streams as streams
+    assert had_torch or "torch" not in sys.modules, "tests/test_gpu_streams.py imports torch at module level"
+    entries = stream_entry_points()
+    assert len(entries) >= 60 and "dvsg_stabilize_f32" in entries and "dvsg_scene_step_f32" in entries
+    assert "dvsg_locnet_create" not in entries and "dvsg_debug_set_option" not in entries
+    cases, exempt = set(streams.CASES), set(streams.EXEMPT)
+    assert not cases & exempt, sorted(cases & exempt)
+    missing = sorted(set(entries) - cases - exempt)
+    assert not missing, "no stream test and no exemption for %s" % missing
+    stale = sorted((cases | exempt) - set(entries))
+    assert not stale, "registered, but the header declares no such entry point with a stream: %s" % stale
+    assert all(streams.CASES[n] for n in cases)
+    for name, reason in streams.EXEMPT.items():     # the reason is the header's phrase, in front of that declaration
+        assert " ".join(reason.split()) in entries[name], "%s: the header does not say %r" % (name, reason)
+        assert re.search(r"synchronous|host|debug", reason + " " + name, flags=re.I), name
+
+
 def test_bad_arguments_return_status_not_abort(lib):
     from coupe.dvsg_amd import DvsgError, _lib
     assert lib.dvsg_tps_solve_f32(None, None, 1, 1, 25, None, None) == -1
