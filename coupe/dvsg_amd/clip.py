@@ -95,7 +95,7 @@ def sharded_map(n, batch, produce, frame_shape, like, group=None, dst=0):
 
 
 def stabilize_windows_sharded(run_fn, patches_t, u_t, batch=16, group=None, dst=0):
-    """Stabilise `patches_t` [N,H,W,21] / `u_t` [N,H,W,3] (every rank passes the same N) with
+    """Stabilise `patches_t` [N,H,W,3S] / `u_t` [N,H,W,3] (every rank passes the same N) with
     the windows sharded over the ranks of `group`; returns [N,H,W,3] on rank `dst`, None
     elsewhere.  `run_fn(patches, u) -> [b,H,W,3]` is the per-batch hot path (e.g.
     `lambda p, u: sess.run(outputs['s_t_pred'], {inputs['patches_t']: p, inputs['u_t']: u})`)."""
@@ -262,7 +262,7 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     Video decode / encode (cv2.VideoCapture / VideoWriter) is host I/O and out of scope.
 
     The clip lives in one HBM pool [2N,h,w,3] float32 (unstable | stabilised).  Each step is ONE call,
-    `dvsg_stabilize_ring_f32`: conv1 assembles the 21-channel window of eval.py:103-104 in its load stage
+    `dvsg_stabilize_ring_f32`: conv1 assembles the 3S-channel window of eval.py:103-104 in its load stage
     from the pool frames `window_index_table` names, and the result is written straight into its pool
     slot; the write-back of eval.py:116-120 is the index table, not a copy.  `session` is accepted for call-site
     symmetry with eval.py and not used.
@@ -328,8 +328,8 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     else:
         raise TypeError("frames must be uint8 or floating point, got %s" % fr.dtype)
     F = torch.empty((N, model.param_dim, 2), dtype=torch.float32, device=dev)   # F_t of every frame
-    # one call per frame: conv1 picks the 7 window frames out of the pool through table[k] (eval.py:103-104 fused
-    # into its load stage: no window tensor, no gather launch), the warp reads u_t = pool[table[k, 6]] = pool[k],
+    # one call per frame: conv1 picks the S window frames out of the pool through table[k] (eval.py:103-104 fused
+    # into its load stage: no window tensor, no gather launch), the warp reads u_t = pool[table[k, S - 1]] = pool[k],
     # and the result lands in its history slot pool[N + k] (:116), which no slot of window k reads
     for k in range(N):                                                             # eval.py:101
         model.locnet.stabilize_ring(pool, table[k:k + 1], pool[N + k:N + k + 1], F[k:k + 1],
@@ -526,7 +526,7 @@ def stabilize_clip_teacher_forced(model, unstable, stable, batch=16, skip_length
         b = b1 - b0
         out = torch.empty((b, h, w, 3), dtype=torch.float32, device=dev)
         # windows b0..b1 straight from the pool (uint8 when the clips came as same-size RGB uint8 frames: the / 255. of
-        # eval_train.py's frame reader happens in conv1's load stage); u_t of window k is pool frame table[k, 6] = k + 32
+        # eval_train.py's frame reader happens in conv1's load stage); u_t of window k is pool frame table[k, S - 1] = k + skip_length[-1]
         plane = random_mask_plane(Ht[b0:b1], h, w) if Ht is not None else None      # eval_train.py:43 (one plane per window)
         model.locnet.stabilize_ring(pool, table[b0:b1], out, F[:b], precision=model.precision, mask=plane)
         if not as_uint8:

@@ -158,9 +158,17 @@ constexpr int kConv1LdH = 168;
 // p1 = bf16(w), p2 = bf16(w - p1), p3 = bf16(w - p1 - p2); rows zero-padded from 80 to 88.
 constexpr int kConv1X3Ld = 88;
 constexpr int kConv1X3StageElems = 3 * 64 * kConv1X3Ld;   // 16 896 bfloat16 per half kernel row
+// Any other window length S (cin = 3 S, 1 <= S <= kRootMaxFrames) runs rootconv_kernel, which takes cin as an argument and
+// reads the float32 image only: wt1 is then [7][64][rootconv_ld(cin)], tap (kw, c) of kernel row kh at kw * pitch + c with
+// pitch = rootconv_pitch(cin) -- the LDS pixel pitch, cin made odd (see the kernel) -- and zeros everywhere else.
+constexpr int kRootMaxFrames = 16;
+constexpr int rootconv_pitch(int cin) { return cin | 1; }
+constexpr int rootconv_kpad(int cin) { return (7 * rootconv_pitch(cin) + 3) & ~3; }   // a whole number of 4-k MFMA steps
+constexpr int rootconv_ld(int cin) { return rootconv_kpad(cin) + 2; }                 // 2 x odd, like kConv1Ld
 // diagnostic record of the root and the head of the last network call (dvsg_debug_last_root_kernel): conv1 family (0
 // conv1_kernel, 1 conv1_f16_kernel, 2 conv1_f16_pair_kernel, 3 conv1_f16_march_kernel, 4 conv1_split_kernel, 5
-// conv1_x3_kernel), its template arguments NW, TO (0 float, 1 _Float16), SRC (-1 where the family has none), the marching
+// conv1_x3_kernel, 6 rootconv_kernel: cin != 21), its template arguments NW, TO (0 float, 1 _Float16, 2 the P format:
+// rootconv_kernel only), SRC (-1 where the family has none; rootconv_kernel records NW = 4), the marching
 // kernel's bands and quads_per_band (else -1), the max pool kernel (0 maxpool_kernel<float>, 1 maxpool_kernel<_Float16>, 2
 // maxpool_h8_kernel, 3 maxpool_p_kernel), the average pool kernel (0 avgpool_partial_kernel<float>, 1 <_Float16>, 2
 // avgpool_partial_p_kernel) and the number of dense batch chunks.  Reset to -1 by forward(), written where launch_conv1,
@@ -186,13 +194,16 @@ constexpr int conv1_src(int kind, bool aligned, bool masked) {
 }
 struct Conv1Src {
   const void *base;   // window tensor, or frame pool
-  const int *table;   // ring: [B,7] pool indices (device); an index outside [0, n_pool) stages zeros
+  const int *table;   // ring: [B,S] pool indices (device), S = cin / 3; an index outside [0, n_pool) stages zeros
   int n_pool;
-  const float *mask = nullptr;   // optional [B,H,W]: eval_train.py:43-45,53-64 -- the 18 history channels of window b are multiplied
+  const float *mask = nullptr;   // optional [B,H,W]: eval_train.py:43-45,53-64 -- the 3 (S - 1) history channels of window b are multiplied
                                  // by mask[b] (one plane: the warp of an all-ones image is the same in every channel) in the load stage
 };
 int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *wt1, const void *wt1h, const void *wt1s,
-                 const void *wt1x, const float *bias, void *y, int B, int H, int W, int Ho, int Wo, hipStream_t s);
+                 const void *wt1x, const float *bias, void *y, int B, int H, int W, int Ho, int Wo, int cin, hipStream_t s);
+// rootconv_kernel declares its LDS per launch (up to 140 KB at cin = 48): raises every instantiation's dynamic LDS limit.
+// Called once per handle by dvsg_locnet_create for cin != 21, outside any stream operation
+int prepare_rootconv();
 
 // 3x3 stride-2 TF-SAME max pool (slim resnet root), C % 8 == 0.
 int launch_maxpool(int prec, const void *x, void *y, int B, int H, int W, int C, int Ho, int Wo, int pad_top,

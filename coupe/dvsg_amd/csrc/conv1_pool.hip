@@ -556,6 +556,183 @@ void conv1_kernel(const Conv1Src src, const float *__restrict__ wt1, const float
 }
 
 // ----------------------------------------------------------------------------------------
+// The root conv for any other window length: 7x7 / stride 2 / pad 3, cin = 3 S -> 64, 1 <= S <= kRootMaxFrames, cin a
+// kernel ARGUMENT.  It is conv1_kernel<4, float, SRC> generalised: the same tile (128 output pixels of one output row x 64
+// channels, 4 waves as 2 x 2, two 32-pixel MFMA blocks per wave), the same exact float32 products on
+// v_mfma_f32_32x32x2_f32 in two chains per block (even / odd taps, joined once in the epilogue), the same scale_RGB in the
+// load stage (x * 255 - mean_g, two roundings; with a mask (x * m) * 255 - mean_g on the first 3 (S - 1) channels; the pad
+// ring 0 in the SCALED domain; a table index outside [0, n_pool) a frame of raw zeros) and the same epilogue.
+//
+// LDS, sized per launch from cin (rootconv_lds_bytes): the raw row segment of 261 pixels at a pitch of
+// rootconv_pitch(cin) floats, and the kernel row's weights [64][rootconv_ld(cin)].
+// Pitch rule: lane r of an A fragment reads 8 bytes at float offset 2 pitch r + const, which visits every even bank once
+// over r = 0..31 exactly when pitch is odd.  cin odd (S odd): pitch = cin, the 7 cin taps of a pixel are one contiguous run,
+// as in conv1_kernel.  cin even (S even): pitch = cin + 1, one pad float behind each pixel's channels; the run of a pixel
+// then is 7 pitch long with a zero WEIGHT at every pad position (make_conv1 lays the weight rows out at the same pitch) and
+// the pad floats are zeroed once, so the layout costs 1 / (cin + 1) more MFMA steps (2 % at S = 16, 14 % at S = 2) and no
+// conflict.  The weight rows' stride is 2 x odd like kConv1Ld.
+//
+// Staging is by (pixel, frame) items of three floats, frame-major: consecutive lanes take consecutive pixels of one frame
+// (12-byte neighbours in a frame ring, LDS stores `pitch` floats apart: conflict-free).  It runs between the two barriers
+// of a kernel row, not prefetched into registers as conv1_kernel does (the item count depends on S); for small S several
+// workgroups share a CU and overlap it, at S = 16 it is ~1/8 of a row's MFMA time.  The aligned bit of SRC changes nothing
+// here (every load is a dword or a byte); it is kept because SRC is the launch record's vocabulary.
+// ----------------------------------------------------------------------------------------
+struct PPieces {};   // TO of the f32s precision: the output stored as float16 pieces (P format, store4_p)
+
+constexpr int rootconv_seg(int cin) { return C1_RING_PX * rootconv_pitch(cin) + 4; }   // floats; the last A read ends at 254 pitch + kpad
+constexpr int rootconv_wstage(int cin) { return 64 * rootconv_ld(cin) > C1_TILE * C1_LDC ? 64 * rootconv_ld(cin) : C1_TILE * C1_LDC; }
+constexpr size_t rootconv_lds_bytes(int cin) { return sizeof(float) * (size_t)(rootconv_wstage(cin) + rootconv_seg(cin)); }
+static_assert(rootconv_lds_bytes(3 * kRootMaxFrames) <= 160 * 1024, "the largest window must fit one workgroup's LDS");
+
+template <typename TO, int SRC>
+__global__ __launch_bounds__(256)
+void rootconv_kernel(const Conv1Src src, const float *__restrict__ wt1, const float *__restrict__ bias, void *__restrict__ y,
+                     int H, int W, int Ho, int Wo, int wtiles, int cin) {
+  constexpr int NT = 256, MI = 2;
+  constexpr int kKind = SRC >> kSrcKindShift & 3;
+  constexpr bool kMasked = (SRC & kSrcMasked) != 0;
+  static_assert(SRC >= 0 && SRC < 16 && kKind <= kSrcRingU8, "no such conv1 source");
+  extern __shared__ __attribute__((aligned(16))) float rc_lds[];
+  const int S = cin / 3, pitch = rootconv_pitch(cin), ldw = rootconv_ld(cin), steps = rootconv_kpad(cin) / 4;
+  const int welems = 64 * ldw, seg = rootconv_seg(cin);
+  float *w_s = rc_lds;
+  float *in_s = rc_lds + rootconv_wstage(cin);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r = lane & 31, h = lane >> 5;
+
+  int blk = xcd_remap(blockIdx.x, gridDim.x);   // see conv1_kernel
+  const int wt_i = blk % wtiles;
+  blk /= wtiles;
+  const int ho = blk % Ho;
+  const int b = blk / Ho;
+  const int wo0 = wt_i * C1_TILE;
+
+  for (int e = tid; e < seg; e += NT) in_s[e] = 0.f;   // the pad floats and the tail stay zero: they meet zero weights
+
+  const float *mplane = nullptr;
+  if constexpr (kMasked) mplane = src.mask + (size_t)b * H * W;
+  const int items = C1_RING_PX * S;
+  // kernel row kh: input row 2 ho + kh - 3, scaled, into in_s; the row's weights into w_s
+  auto stage = [&](int kh) __attribute__((always_inline)) {
+    const int hi = 2 * ho + kh - 3;
+    const bool row_ok = hi >= 0 && hi < H;   // uniform
+    for (int q = tid; q < items; q += NT) {
+      const int f = q / C1_RING_PX, p = q - f * C1_RING_PX;
+      const int col = 2 * wo0 - 3 + p;
+      float a[3] = {0.f, 0.f, 0.f};
+      if (row_ok && col >= 0 && col < W) {
+        const size_t px = (size_t)hi * W + col;
+        float m = 1.0f;
+        bool masked = false;
+        if constexpr (kMasked) {
+          masked = f < S - 1;   // the newest frame is never masked (eval_train.py:62)
+          if (masked) m = mplane[px];
+        }
+        float s3[3];   // the raw value times 255
+        if constexpr (kKind == kSrcWindow) {
+          const float *x = static_cast<const float *>(src.base) + ((size_t)b * H * W + px) * cin + 3 * f;
+#pragma unroll
+          for (int j = 0; j < 3; ++j) s3[j] = masked ? (x[j] * m) * 255.0f : x[j] * 255.0f;
+        } else {
+          const int fi = src.table[b * S + f];
+          const bool frame_ok = fi >= 0 && fi < src.n_pool;   // a missing frame is a frame of raw zeros
+          const size_t e0 = ((size_t)(frame_ok ? fi : 0) * H * W + px) * 3;
+          if constexpr (kKind == kSrcRingU8) {
+            const uint8_t *x = static_cast<const uint8_t *>(src.base) + e0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+              const float v = (float)x[j];   // == f32(v / 255.) * 255.f exactly (Conv1RingRow)
+              if (masked) {
+                const float q0 = v * (1.0f / 255.0f);
+                const float xf = __builtin_fmaf(__builtin_fmaf(-q0, 255.0f, v), 1.0f / 255.0f, q0);   // f32(v / 255.), correctly rounded
+                s3[j] = (xf * m) * 255.0f;
+              } else {
+                s3[j] = v;
+              }
+            }
+          } else {
+            const float *x = static_cast<const float *>(src.base) + e0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) s3[j] = masked ? (x[j] * m) * 255.0f : x[j] * 255.0f;
+          }
+          if (!frame_ok) s3[0] = s3[1] = s3[2] = 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int c = 3 * f + j, g = (c >= S) + (c >= 2 * S);   // raw group c / S gets the mean of scaled group 2 - g
+          a[j] = s3[j] - (g == 0 ? 123.68f : (g == 1 ? 116.779f : 103.939f));
+        }
+      }
+      float *dst = in_s + p * pitch + 3 * f;
+      dst[0] = a[0];
+      dst[1] = a[1];
+      dst[2] = a[2];
+    }
+    const floatx4 *wsrc = reinterpret_cast<const floatx4 *>(wt1 + (size_t)kh * welems);
+    for (int q = tid; q < welems / 4; q += NT) reinterpret_cast<floatx4 *>(w_s)[q] = wsrc[q];
+  };
+
+  floatx16 acc[MI], acc2[MI];   // even and odd taps (conv1_kernel)
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[mi][q] = acc2[mi][q] = 0.f;
+
+  const float *a0 = in_s + 2 * pitch * (wm * 32 * MI + r) + 2 * h;
+  const float *a1 = a0 + 2 * pitch * 32;
+  const float *bp = w_s + (wn * 32 + r) * ldw + 2 * h;
+  for (int kh = 0; kh < 7; ++kh) {
+    __syncthreads();   // everyone is done reading the previous kernel row (the first time: the zeros have landed)
+    stage(kh);
+    __syncthreads();
+    auto step = [&](int u) __attribute__((always_inline)) {
+      const float2 x0 = *reinterpret_cast<const float2 *>(a0 + 4 * u);
+      const float2 x1 = *reinterpret_cast<const float2 *>(a1 + 4 * u);
+      const float2 wv = *reinterpret_cast<const float2 *>(bp + 4 * u);
+      acc[0] = mfma32(x0.x, wv.x, acc[0]);
+      acc[1] = mfma32(x1.x, wv.x, acc[1]);
+      acc2[0] = mfma32(x0.y, wv.y, acc2[0]);
+      acc2[1] = mfma32(x1.y, wv.y, acc2[1]);
+    };
+    int u = 0;
+    for (; u + 1 < steps; u += 2) {   // two steps per trip: the reads of the second are issued under the MFMAs of the first
+      step(u);
+      step(u + 1);
+    }
+    if (u < steps) step(u);
+  }
+
+  // ---- epilogue: conv1_kernel's, through the weight stage (at least C1_TILE * C1_LDC floats: rootconv_wstage)
+  float *Cs = w_s;
+  __syncthreads();
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      Cs[(wm * 32 * MI + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + wn * 32 + r] = acc[mi][q] + acc2[mi][q];
+  __syncthreads();
+  const int col4 = tid & 15, row0 = tid >> 4;
+  const float4 b4 = *reinterpret_cast<const float4 *>(bias + 4 * col4);
+  const size_t e0 = (((size_t)b * Ho + ho) * Wo + wo0) * 64 + 4 * col4;
+#pragma unroll 4
+  for (int row = row0; row < C1_TILE; row += NT / 16) {
+    if (wo0 + row >= Wo) break;
+    float4 v = *reinterpret_cast<const float4 *>(Cs + row * C1_LDC + 4 * col4);
+    v.x = fmaxf(v.x + b4.x, 0.f);
+    v.y = fmaxf(v.y + b4.y, 0.f);
+    v.z = fmaxf(v.z + b4.z, 0.f);
+    v.w = fmaxf(v.w + b4.w, 0.f);
+    if constexpr (std::is_same<TO, PPieces>::value)
+      store4_p(y, e0 + (size_t)row * 64, v);
+    else
+      store4(static_cast<TO *>(y) + e0 + (size_t)row * 64, v);
+  }
+}
+
+// ----------------------------------------------------------------------------------------
 // 3x3 / stride 2 max pool with TF 'SAME' padding (pad_before = pad_total / 2: nothing on
 // the top/left for even sizes).  One thread = one output pixel x 4 channels.
 // ----------------------------------------------------------------------------------------
@@ -1765,19 +1942,37 @@ bool with_conv1_src(int src, F &&f) {
 int g_last_root_kernel[kRootKernelFields] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
 
 int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *wt1, const void *wt1h, const void *wt1s,
-                 const void *wt1x, const float *bias, void *y, int B, int H, int W, int Ho, int Wo, hipStream_t s) {
+                 const void *wt1x, const float *bias, void *y, int B, int H, int W, int Ho, int Wo, int cin, hipStream_t s) {
+  DVSG_REQUIRE(cin % 3 == 0 && cin >= 3 && cin <= 3 * kRootMaxFrames, "conv1: %d input channels", cin);
   const int wtiles = ceil_div(Wo, C1_TILE);
   const long blocks = (long)wtiles * Ho * B;
   DVSG_REQUIRE(blocks > 0 && blocks < (1L << 31), "conv1: grid of %ld workgroups out of range", blocks);
-  DVSG_REQUIRE((long)W * kConv1Cin < (1L << 31), "conv1: input row too long");
+  DVSG_REQUIRE((long)W * cin < (1L << 31), "conv1: input row too long");
   DVSG_REQUIRE(src_kind == kSrcWindow || (src.table && src.n_pool > 0), "conv1: a frame ring needs its index table");
   const double in_bytes = src_kind == kSrcRingU8 ? 1.0 : 4.0;   // each window element once (ring frames are shared by windows:
-  ProfScope prof(kClsConv1, s, 2.0 * (double)B * Ho * Wo * 64 * 49 * kConv1Cin,   // an upper bound of the algorithmic read)
-                 in_bytes * (double)B * H * W * kConv1Cin + (double)elem_size(out_prec) * B * Ho * Wo * 64);
+  ProfScope prof(kClsConv1, s, 2.0 * (double)B * Ho * Wo * 64 * 49 * cin,   // an upper bound of the algorithmic read)
+                 in_bytes * (double)B * H * W * cin + (double)elem_size(out_prec) * B * Ho * Wo * 64);
   const dim3 grid((unsigned)blocks);
   // rows that start on 16-byte boundaries (4-byte for uint8 frames): the staged segment then consists of whole aligned groups
   const bool aligned = W % 4 == 0 && reinterpret_cast<uintptr_t>(src.base) % (src_kind == kSrcRingU8 ? 4 : 16) == 0;
   const int SRC = conv1_src(src_kind, aligned, src.mask != nullptr);
+  if (cin != kConv1Cin) {   // any other window length: one kernel for every precision, whatever conv1_variant says
+    DVSG_REQUIRE(wt1, "conv1: no float32 weight image");
+    const int to = out_prec == kF16 ? 1 : (out_prec == kF32S ? 2 : 0);
+    const size_t lds = rootconv_lds_bytes(cin);
+    const bool known = with_conv1_src<true>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(6, 4, to, S);
+      if (to == 1)
+        hipLaunchKernelGGL((rootconv_kernel<_Float16, S>), grid, dim3(256), lds, s, src, wt1, bias, y, H, W, Ho, Wo, wtiles, cin);
+      else if (to == 2)
+        hipLaunchKernelGGL((rootconv_kernel<PPieces, S>), grid, dim3(256), lds, s, src, wt1, bias, y, H, W, Ho, Wo, wtiles, cin);
+      else
+        hipLaunchKernelGGL((rootconv_kernel<float, S>), grid, dim3(256), lds, s, src, wt1, bias, y, H, W, Ho, Wo, wtiles, cin);
+    });
+    DVSG_REQUIRE(known, "conv1: no kernel for source %d", SRC);
+    return check_launch("rootconv_kernel");
+  }
   // the f32s activations are float16 pieces (P format): only conv1_split_kernel writes them, whatever the A/B switch says
   // (the float32 kernel's output would be read back as pieces: silent garbage)
   if (out_prec == kF32S && !wt1s) return fail(DVSG_ERR_UNSUPPORTED, "conv1: the f32s precision needs the piece weights");
@@ -1853,6 +2048,24 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *w
   }
   DVSG_REQUIRE(legal, "conv1: no kernel for source %d", SRC);
   return check_launch("conv1_kernel");
+}
+
+int prepare_rootconv() {
+  const int bytes = (int)rootconv_lds_bytes(3 * kRootMaxFrames);
+  hipError_t err = hipSuccess;
+  auto raise = [&](const void *fn) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (err == hipSuccess) err = e;
+  };
+  for (int src = 0; src < 16; ++src)
+    with_conv1_src<true>(src, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      raise(reinterpret_cast<const void *>(&rootconv_kernel<float, S>));
+      raise(reinterpret_cast<const void *>(&rootconv_kernel<_Float16, S>));
+      raise(reinterpret_cast<const void *>(&rootconv_kernel<PPieces, S>));
+    });
+  DVSG_HIP(err);
+  return DVSG_OK;
 }
 
 #ifdef DVSG_STAMPS

@@ -238,7 +238,7 @@ int make_conv(dvsg_locnet *net, const ArrayMap &m, const std::string &scope, Con
   return upload(net, shift, &L->bias);
 }
 
-// conv1: [7][64][kConv1Ld]; within a kernel row a zero tap, then the taps (kw, raw channel c) in input
+// conv1 (cin = 21): [7][64][kConv1Ld]; within a kernel row a zero tap, then the taps (kw, raw channel c) in input
 // memory order (cnn_kernels.h).  scale_RGB's group reversal (networks.py:10-14) is folded here: raw channel
 // c multiplies the weight of scaled-tensor channel (2 - c/G) * G + c % G.
 int make_conv1(dvsg_locnet *net, const ArrayMap &m, const std::string &scope, ConvLayer *L) {
@@ -247,6 +247,21 @@ int make_conv1(dvsg_locnet *net, const ArrayMap &m, const std::string &scope, Co
   std::vector<float> scale, shift;
   if (int rc = bn_fold(m, scope, 64, &scale, &shift)) return rc;
   const int cin = L->cin, G = cin / 3;
+  if (cin != kConv1Cin) {
+    // any other window length (rootconv_kernel): the float32 image only, [7][64][rootconv_ld(cin)], tap (kw, c) at
+    // kw * pitch + c -- no zero tap in front; the pad float of an even cin and the row's tail are zero weights
+    const int pitch = rootconv_pitch(cin), ld = rootconv_ld(cin);
+    std::vector<float> wr((size_t)7 * 64 * ld, 0.f);
+    for (int kh = 0; kh < 7; ++kh)
+      for (int kw = 0; kw < 7; ++kw)
+        for (int c = 0; c < cin; ++c) {
+          const int cs = (2 - c / G) * G + c % G;
+          for (int n = 0; n < 64; ++n)
+            wr[((size_t)kh * 64 + n) * ld + kw * pitch + c] = w->data[(((size_t)kh * 7 + kw) * cin + cs) * 64 + n] * scale[n];
+        }
+    if (int rc = upload(net, wr, &L->wt)) return rc;
+    return upload(net, shift, &L->bias);
+  }
   std::vector<float> wt((size_t)7 * 64 * kConv1Ld, 0.f);
   for (int kh = 0; kh < 7; ++kh)
     for (int kw = 0; kw < 7; ++kw)
@@ -507,7 +522,7 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
   {
   MarkerRange mr("dvsg/conv1");
   DVSG_RUN(launch_conv1(gprec == kF32X && g_opt.x3_conv1 ? kF32X : prec, src, src_kind, net->conv1.wt, net->conv1.wt16, net->conv1.wt32s,
-                        net->conv1.wt3x, net->conv1.bias, ws.bufA, B, H, W, d.H1, d.W1, s));
+                        net->conv1.wt3x, net->conv1.bias, ws.bufA, B, H, W, d.H1, d.W1, net->c_in, s));
   }
   DVSG_TAP(0, ws.bufA, d.H1, d.W1, 64);
   {
@@ -637,13 +652,12 @@ int forward(const dvsg_locnet *net, int prec, const float *patches, int B, int H
 }
 
 // What stabilize() and stabilize_ring() share, behind their own NULL and range checks (`fn` names the caller in the
-// messages): F_t = localizationNet(src), T = the TPS of F_t on the constant V_src, then the caller's warp(T).  A source
-// that only a 7-frame window can take (a mask, a ring) passes the message for any other handle in `needs_window`.
+// messages): F_t = localizationNet(src), T = the TPS of F_t on the constant V_src, then the caller's warp(T).  (Every
+// handle's c_in is 3 S, so a mask or a ring fits any of them: S - 1 history frames, tables of S columns.)
 template <typename Warp>
-int stabilize_from(const char *fn, const dvsg_locnet *net, int prec, const char *needs_window, const Conv1Src &src, int src_kind,
+int stabilize_from(const char *fn, const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
                    int B, int H, int W, float *F_t, void *workspace, size_t workspace_bytes, void *stream, Warp warp) {
   DVSG_REQUIRE(prec == kF32 || prec == kF16 || prec == kF32S || prec == kF32X, "%s: unknown precision %d", fn, prec);
-  DVSG_REQUIRE(!needs_window || net->c_in == 21, "%s", needs_window);
   const Workspace ws = plan(static_cast<char *>(workspace), B, H, W);
   if (ws.total > workspace_bytes)
     return fail(DVSG_ERR_WORKSPACE, "%s: workspace %zu bytes < required %zu", fn, workspace_bytes, ws.total);
@@ -664,15 +678,14 @@ int stabilize(const dvsg_locnet *net, int prec, const float *patches_t, const fl
   DVSG_REQUIRE(B > 0 && B <= 65535, "dvsg_stabilize: B=%d out of range", B);
   Conv1Src src{patches_t, nullptr, 0};
   src.mask = mask;   // eval_train.py:43-45: the CNN sees patches * mask, the warp below the unmasked u_t
-  return stabilize_from("dvsg_stabilize", net, prec,
-                        mask ? "dvsg_stabilize_masked: the mask covers the 18 history channels of a 7-frame window" : nullptr, src,
-                        kSrcWindow, B, H, W, F_t, workspace, workspace_bytes, stream, [&](const float *T) {
+  return stabilize_from("dvsg_stabilize", net, prec, src, kSrcWindow, B, H, W, F_t, workspace, workspace_bytes, stream,
+                        [&](const float *T) {
                           return tps_warp_impl(u_t, net->v_src, 0, T, B, H, W, 3, 25, H, W, s_t_pred, x_s, y_s, stream);
                         });
 }
 
-// The evaluation graph fed from a frame ring: window b = pool frames table[b][0..6], u_t = its newest
-// frame table[b][6]; conv1 assembles the window in its load stage (eval.py:103-104) and, for a uint8 pool, applies the
+// The evaluation graph fed from a frame ring: window b = pool frames table[b][0..S-1] with S = c_in / 3,
+// u_t = its newest frame table[b][S-1]; conv1 assembles the window in its load stage (eval.py:103-104) and, for a uint8 pool, applies the
 // / 255. of eval.py:80 there; the warp reads u_t from the pool through the same table.  With out_slots, s_t_pred is the
 // float32 pool and sample b's frame lands in its frame out_slots[b] (the history slot of an online stream).
 int stabilize_ring(const dvsg_locnet *net, int prec, const void *pool, int pool_is_u8, int n_pool, const int32_t *table,
@@ -682,10 +695,11 @@ int stabilize_ring(const dvsg_locnet *net, int prec, const void *pool, int pool_
   DVSG_REQUIRE(B > 0 && B <= 65535 && n_pool > 0, "dvsg_stabilize_ring: B=%d n_pool=%d out of range", B, n_pool);
   Conv1Src src{pool, table, n_pool};
   src.mask = mask;
-  return stabilize_from("dvsg_stabilize_ring", net, prec, "dvsg_stabilize_ring: the ring holds RGB frames, 7 per window", src,
+  const int S = net->c_in / 3;
+  return stabilize_from("dvsg_stabilize_ring", net, prec, src,
                         pool_is_u8 ? kSrcRingU8 : kSrcRingF32, B, H, W, F_t, workspace, workspace_bytes, stream,
                         [&](const float *T) {
-                          return tps_warp_ring_impl(pool, pool_is_u8, n_pool, table + 6, 7, net->v_src, 0, T, B, H, W, 25,
+                          return tps_warp_ring_impl(pool, pool_is_u8, n_pool, table + (S - 1), S, net->v_src, 0, T, B, H, W, 25,
                                                     s_t_pred, x_s, y_s, stream, out_slots);
                         });
 }
@@ -838,8 +852,9 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
   if (it == m.end()) return fail(DVSG_ERR_WEIGHTS, "checkpoint array missing: %s/conv1/weights", rn.c_str());
   if (it->second.nd != 4) return fail(DVSG_ERR_WEIGHTS, "conv1/weights must be 4-D");
   const int c_in = (int)it->second.dims[2];
-  if (c_in != kConv1Cin)
-    return fail(DVSG_ERR_UNSUPPORTED, "conv1 has %d input channels; this build supports the 7-frame window (21)", c_in);
+  if (c_in < 3 || c_in > 3 * kRootMaxFrames || c_in % 3 != 0)
+    return fail(DVSG_ERR_UNSUPPORTED, "conv1 has %d input channels; this build supports windows of S RGB frames, c_in = 3 S, S <= %d",
+                c_in, kRootMaxFrames);
 
   dvsg_locnet *net = new dvsg_locnet();
   net->c_in = c_in;
@@ -850,6 +865,7 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
   };
   net->conv1 = ConvLayer{7, c_in, 64, 2, true};
   if ((rc = make_conv1(net, m, rn + "/conv1", &net->conv1))) return bail(rc);
+  if (c_in != kConv1Cin && (rc = prepare_rootconv())) return bail(rc);
   int depth_in = 64;
   for (const BlockSpec &bs : kBlocks) {
     for (int u = 1; u <= bs.units; ++u) {
@@ -1379,14 +1395,13 @@ int dvsg_stabilize_ring_masked_u8(const dvsg_locnet_t *net, int precision, const
 }
 
 // The CNN alone on a masked source -- F_t [B,25,2] into `out` (stage = -1) or the parity tap of `stage` (0..18).
-// src_kind 0: `src` is a window tensor [B,H,W,21] (n_pool, table unused); 1 / 2: a float32 / uint8 frame pool + table.
+// src_kind 0: `src` is a window tensor [B,H,W,c_in] (n_pool, table unused); 1 / 2: a float32 / uint8 frame pool + table [B,c_in/3].
 int dvsg_locnet_forward_masked(const dvsg_locnet_t *net, int precision, const void *src_ptr, int src_kind, int n_pool,
                                const int32_t *table, const float *mask, int B, int H, int W, int stage, float *out,
                                size_t out_bytes, int *act_dims_host, void *workspace, size_t workspace_bytes, void *stream) {
   DVSG_REQUIRE(net && src_ptr && mask && out, "dvsg_locnet_forward_masked: NULL pointer");
   DVSG_REQUIRE(src_kind >= 0 && src_kind <= 2 && (src_kind == 0 || (table && n_pool > 0)),
                "dvsg_locnet_forward_masked: bad source (kind %d)", src_kind);
-  DVSG_REQUIRE(net->c_in == 21, "dvsg_locnet_forward_masked: the mask covers the 18 history channels of a 7-frame window");
   DVSG_REQUIRE(stage >= -1 && stage <= 18 && (stage < 0 || act_dims_host), "dvsg_locnet_forward_masked: stage %d outside [-1,18]", stage);
   DVSG_REQUIRE(stage >= 0 || out_bytes >= (size_t)B * 50 * sizeof(float), "dvsg_locnet_forward_masked: F_t needs B*50 floats");
   const int prec = ring_precision(precision);

@@ -2,13 +2,13 @@
 
 eval_train.py does not use `StabNet.get_evaluation_model`: it builds its own graph
 (eval_train.py:25-51) in which the regressor's input is `patches_masked_t = patches_t * mask`
-(:43-45), `random_mask` (:53-64) being model.py:156-167 -- an all-ones image of the 18 history
+(:43-45), `random_mask` (:53-64) being model.py:156-167 -- an all-ones image of the 3 (S - 1) history (18 of 21 at sample_num 7)
 channels warped by `ProjectiveTransformer` with a near-identity random homography; the TPS warps
 still sample the UNMASKED `u_t` (:48-49).  Same call surface:
 
     inputs, outputs = get_evaluation_model(sample_num, param_dim, num_control_points, h, w)
     model_of(outputs).load_weights(npz_dict)            # stands in for ckpt_manager.load_ckpt(sess)
-    s_t_pred = Session().run(outputs['s_t_pred'], {inputs['patches_t']: x, inputs['u_t']: x[..., 18:]})
+    s_t_pred = Session().run(outputs['s_t_pred'], {inputs['patches_t']: x, inputs['u_t']: x[..., -3:]})
 
 The graph's only stochastic op, `tf.random_uniform` (:55), is drawn with `torch.rand` per `run`
 (`model_of(outputs).mask_generator` seeds it) unless the OPTIONAL extra feed `inputs['random_H']`

@@ -7,7 +7,7 @@ Reference surface kept (model.py:14-25, 98-123, eval.py:46-56,106-110):
     sess = Session()                                   # stands in for tf.Session
     net.load_ckpt(ckpt_dir) | net.load_weights(dict)   # stands in for CKPT_Manager.load_ckpt
     s_t_pred = sess.run(outputs['s_t_pred'],
-                        {inputs['patches_t']: frames21, inputs['u_t']: frames21[..., 18:]})
+                        {inputs['patches_t']: frames21, inputs['u_t']: frames21[..., -3:]})
 
 `inputs` / `outputs` are OrderedDicts with the reference's keys; their values are symbolic
 handles (Placeholder / Fetch) because nothing is computed until `run`.  As in TF, only what

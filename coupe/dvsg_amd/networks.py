@@ -42,7 +42,10 @@ class LocNet(object):
 
     def __init__(self, weights):
         device()
-        w = _weights.validate(weights)
+        # the window length is the checkpoint's own: conv1/weights [7,7,3S,64] fixes the channel count every other array is
+        # checked against; which counts load is the library's decision (dvsg_locnet_create: 3 S, S <= 16)
+        conv1 = _weights.normalize_names(weights).get(_weights.PREFIX + "resnet_v1_50/conv1/weights")
+        w = _weights.validate(weights, int(conv1.shape[2]) if conv1 is not None and conv1.ndim == 4 else 21)
         names = sorted(w)
         n = len(names)
         self._keep = [np.ascontiguousarray(w[k], dtype=np.float32) for k in names]
@@ -91,7 +94,7 @@ class LocNet(object):
 
     def stabilize(self, patches, u_t, out, F, xs=None, ys=None, n_streams=1, precision="f32", mask=None):
         """`dvsg_stabilize_f32` on device tensors (with `mask` [B,H,W]: `dvsg_stabilize_masked_f32`, eval_train.py's
-        graph -- the plane multiplies the 18 history channels inside conv1's load stage), optionally with the batch split over
+        graph -- the plane multiplies the 3 (S - 1) history channels inside conv1's load stage), optionally with the batch split over
         `n_streams` side streams: every conv launch covers the chip in a few rounds of tiles and
         its last round is only partly full; launches from two independent half batches fill each
         other's tails (+4 % at B=16 720p before the stream-K tail, <1 % since).  Results do not
@@ -151,15 +154,14 @@ class LocNet(object):
 
     def _check_ring(self, pool, table):
         import torch
-        if self.in_channels != 21:
-            raise ValueError("a frame ring feeds 7-frame windows; conv1 of the loaded checkpoint has %d input channels"
-                             % self.in_channels)
+        S = self.in_channels // 3   # the window length is the checkpoint's: conv1 reads table rows of S entries
         if pool.dim() != 4 or pool.shape[3] != 3 or pool.dtype not in (torch.float32, torch.uint8) \
                 or not pool.is_cuda or not pool.is_contiguous():
             raise ValueError("pool must be a contiguous [n,H,W,3] float32 or uint8 device tensor")
-        if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 7 or not table.is_cuda \
+        if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != S or not table.is_cuda \
                 or not table.is_contiguous():
-            raise ValueError("table must be a contiguous [B,7] int32 device tensor (clip.window_index_table)")
+            raise ValueError("table must be a contiguous [B,%d] int32 device tensor (clip.window_index_table; conv1 of the "
+                             "loaded checkpoint has %d input channels)" % (S, self.in_channels))
         return int(table.shape[0]), int(pool.shape[1]), int(pool.shape[2])
 
     @staticmethod
@@ -172,13 +174,13 @@ class LocNet(object):
     def random_mask_plane(self, H_theta, h, w):
         """`dvsg_random_mask_plane_f32`: model.py:156-167 / eval_train.py:53-64's mask for homographies H_theta [B,8]
         (the value after the scale and identity offset of :162-163) as ONE plane [B,h,w] -- the projective warp of an
-        all-ones image is the same in each of the 18 history channels."""
+        all-ones image is the same in each of the 3 (S - 1) history channels."""
         return random_mask_plane(H_theta, h, w)
 
     def stabilize_ring(self, pool, table, out, F, xs=None, ys=None, precision="f32", mask=None):
         """`dvsg_stabilize_ring_f32` / `_u8`: the evaluation graph on windows assembled inside conv1's load stage
-        from the frame pool [n,H,W,3] (float32 in [0,1], or raw uint8) through the index table [B,7]
-        (eval.py:103-104 and, for uint8, the / 255. of :80, fused); u_t of window b is pool frame table[b,6].
+        from the frame pool [n,H,W,3] (float32 in [0,1], or raw uint8) through the index table [B,S],
+        S = in_channels / 3 (eval.py:103-104 and, for uint8, the / 255. of :80, fused); u_t of window b is pool frame table[b,S-1].
         With `mask` [B,H,W] (`random_mask_plane`): `dvsg_stabilize_ring_masked_*`, eval_train.py's graph."""
         import torch
         B, H, W = self._check_ring(pool, table)
@@ -235,13 +237,13 @@ class LocNet(object):
     def forward_masked(self, src, mask, table=None, precision="f32", stage=-1):
         """`dvsg_locnet_forward_masked`: F_t [B,25,2] (stage -1) or the parity tap of `stage` (0 conv1, 1 pool1) with
         the mask plane [B,H,W] multiplied into the history channels in conv1's load stage.  `src` is a window tensor
-        [B,H,W,21] (table None) or a frame pool [n,H,W,3] float32 / uint8 with its index table [B,7]."""
+        [B,H,W,in_channels] (table None) or a frame pool [n,H,W,3] float32 / uint8 with its index table [B,in_channels/3]."""
         import torch
         if table is None:
             t = as_dev(src)
             B, H, W, C = t.shape
-            if C != self.in_channels or C != 21:
-                raise ValueError("a masked window has 21 channels, got %d (conv1: %d)" % (C, self.in_channels))
+            if C != self.in_channels:
+                raise ValueError("a masked window has %d channels (conv1 of the loaded checkpoint), got %d" % (self.in_channels, C))
             kind, n_pool = 0, 0
         else:
             t = src
@@ -287,7 +289,7 @@ class LocNet(object):
 
     def calibrate_f16(self, patches):
         """`dvsg_locnet_calibrate_f16`: measure the mean activation of every convolution input on the calibration windows
-        `patches` [B,H,W,21] (a few frames of the clip about to be stabilised) and re-round the plain float16 weights of
+        `patches` [B,H,W,in_channels] (a few frames of the clip about to be stabilised) and re-round the plain float16 weights of
         blocks 2-4 with error feedback, after which precision="f16" runs those blocks without the lo weight piece: 22 %
         less time, F_t within 1e-6 of the paired mode on frames of the calibration windows' statistics.  `None` undoes it."""
         if patches is None:

@@ -17,6 +17,10 @@ printed at the end.
 cut frame (OnlineStabilizer(scene_cut=THR), THR in (0, 1]; 0.75 separates the two synthetic scenes).  The synthetic source
 then cuts from a dark scene to a bright one half way through; the frame each stream's cut was detected at is printed from
 `scene_state`.
+
+--skip-length 0,16,24,28,32: another window (the reference's `skip_length`, config.py:48): S strictly increasing frame offsets,
+1 <= S <= 16.  The window length belongs to the checkpoint -- its root conv has 3 S input channels -- so the synthetic
+checkpoint is made for it (15 channels for the five offsets above; the default is the reference's seven).
 """
 import argparse
 import os
@@ -70,19 +74,24 @@ def main():
     ap.add_argument("--format", default="rgb", choices=["rgb", "nv12"])
     ap.add_argument("--crop", default=None, help="'auto' or a zoom in (0, 1]")
     ap.add_argument("--scene-cut", type=float, default=None, metavar="THR", help="detect scene cuts: a threshold in (0, 1]")
+    ap.add_argument("--skip-length", default=None, metavar="A,B,...",
+                    help="the window's frame offsets, oldest first (default: the reference's 0,16,24,28,30,31,32)")
     args = ap.parse_args()
+    window = dict(skip_length=tuple(int(v) for v in args.skip_length.split(","))) if args.skip_length else {}
+    S = len(window["skip_length"]) if window else 7
     scene = dict(scene_cut=args.scene_cut) if args.scene_cut is not None else {}
     cut_at = args.frames // 2 if scene else None
     crop = args.crop if args.crop in (None, "auto") else float(args.crop)
-    net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0))
+    net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0, c_in=3 * S))
+    net.get_evaluation_model(S)
     net.precision = args.precision
     nv12 = args.format == "nv12"
     if nv12:
-        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop, **scene)
+        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop, **scene, **window)
         make = synthetic_nv12_source
     else:
         stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True,
-                                crop=crop, **scene)
+                                crop=crop, **scene, **window)
         make = synthetic_source
     H0, W0 = args.height * 3 // 2, args.width * 3 // 2
     if nv12:

@@ -140,17 +140,21 @@ typedef struct dvsg_locnet dvsg_locnet_t;
  * dims is [n_arrays][4] (unused trailing entries ignored), ndims[i] in 1..4.  Unknown names
  * are ignored; a missing or mis-shaped array is DVSG_ERR_WEIGHTS (the reference silently
  * runs on random weights instead, ckpt_manager.py:21-22).  BatchNorm (eps 1e-5, moving
- * statistics) is folded into per-channel scale/shift here.  Allocates device memory. */
+ * statistics) is folded into per-channel scale/shift here.  Allocates device memory.
+ * The window length is the checkpoint's: conv1/weights [7,7,c_in,64] with c_in = 3 S loads for 1 <= S <= 16 (the
+ * reference's `sample_num`, config.py:47); any other c_in is DVSG_ERR_UNSUPPORTED, decided before any device work.
+ * S = 7 runs the conv1 kernels tuned for it; any other S runs one root-conv kernel that takes c_in as an argument
+ * (exact float32 products, the output converted to the precision's format: see the precision paragraphs below). */
 int dvsg_locnet_create(int n_arrays, const char *const *names, const float *const *host_data,
                        const int *ndims, const int64_t *dims, dvsg_locnet_t **net);
 int dvsg_locnet_destroy(dvsg_locnet_t *net);
-/* input channels of the loaded conv1 (21 for the 7-frame window) */
+/* input channels of the loaded conv1: 3 S for a window of S frames (21 for the 7-frame window) */
 int dvsg_locnet_in_channels(const dvsg_locnet_t *net);
 /* bytes of scratch `forward` needs for a [B,H,W,c_in] batch (256-byte aligned). */
 int dvsg_locnet_workspace_bytes(const dvsg_locnet_t *net, int B, int H, int W, size_t *bytes);
 
 /* patches [B,H,W,c_in] in [0,1] -> F_t [B,25,2].  float32 storage, exact-f32 MFMA
- * (v_mfma_f32_32x32x2_f32) accumulation. */
+ * (v_mfma_f32_32x32x2_f32) accumulation.  c_in != 21: conv1 is the same arithmetic in the root-conv kernel. */
 int dvsg_locnet_forward_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W,
                             float *F_t, void *workspace, size_t workspace_bytes, void *stream);
 
@@ -191,7 +195,7 @@ int dvsg_conv_gemm_f32(const float *x, const float *wt, const float *bias, const
  * accumulation, their weights kept as float16 hi / lo pairs (see dvsg_conv_gemm_f16s: a plain float16
  * weight is off by up to 2^-12 relative at EVERY pixel alike, which the global average pool does not
  * average away -- it was 9/10 of this mode's error in F_t); conv1 multiplies float16 copies of the
- * scaled frames and writes f16; BatchNorm shift, the dense head, the TPS solve and the warp stay float32.  Not bit-compatible with the
+ * scaled frames and writes f16 (c_in != 21: conv1 multiplies the float32 scaled frames exactly and rounds only its output to f16); BatchNorm shift, the dense head, the TPS solve and the warp stay float32.  Not bit-compatible with the
  * float32 reference path: tests/test_gpu_f16.py states the measured F_t / pixel error.
  * The workspace of dvsg_locnet_workspace_bytes is sufficient (half of it is used).
  * ------------------------------------------------------------------------------------- */
@@ -222,7 +226,8 @@ int dvsg_locnet_calibrate_f16(dvsg_locnet_t *net, const float *patches, int B, i
  * "f32s": float32 storage, float32 accumulation, float32-equivalent PRODUCTS from the float16 matrix
  * cores.  Same tensors, same workspace, same launch sequence as the *_f32 entry points (the dense head, the
  * TPS solve and the warp are the float32 kernels themselves; the max and average pools join the two pieces of
- * a value, which is exact); in conv1 (conv1_split_kernel) and the 52 1x1 / 3x3
+ * a value, which is exact; c_in != 21: conv1 forms exact float32 products and only stores its output as the two pieces);
+ * in conv1 (conv1_split_kernel) and the 52 1x1 / 3x3
  * convolutions every operand enters the matrix cores as two float16 pieces, x ~ f16(x) + f16(x - f16(x))
  * (22 significant bits while |x| >= 2^-3;
  * the second piece is NOT scaled, so below that it falls into float16's subnormal range -- absolute step 2^-24 --
@@ -277,7 +282,8 @@ int dvsg_pieces_to_f32(const void *x, float *y, size_t n, void *stream);
  * fused conv2 + conv3: conv3's operand once per tile); weights once at load (dvsg_locnet_create; dvsg_pack_weights_f32x3 for
  * a single layer).  The pools, the dense head, the TPS solve and the warp are the float32 kernels themselves.  Measured
  * against float64 evaluations it is as close as the exact path is, layer by layer and end to end (tests/test_gpu_f32x3.py,
- * tests/test_f32x3_numerics_cpu.py); bitwise reproducible.  A separately named precision: dvsg_*_f32 stays the path whose
+ * tests/test_f32x3_numerics_cpu.py); bitwise reproducible.  c_in != 21: conv1 is the float32 path's own kernel, bit for bit, and
+ * the pieces begin behind it.  A separately named precision: dvsg_*_f32 stays the path whose
  * matrix instructions are float32 ones.
  * ------------------------------------------------------------------------------------- */
 int dvsg_locnet_forward_f32x3(const dvsg_locnet_t *net, const float *patches, int B, int H, int W,
@@ -343,16 +349,17 @@ int dvsg_window_gather_f32(const float *pool, int n_pool, int H, int W, const in
 
 /* ---------------------------------------------------------------------------------------
  * The evaluation graph fed straight from a FRAME RING: what eval.py:76-81,103-110 does on the
- * host -- frames / 255., np.concatenate of the 7 window frames on the channel axis, u_t = the newest of them --
- * happens inside conv1's load stage and the warp's tap loads, so the [B,H,W,21] window tensor never exists.
+ * host -- frames / 255., np.concatenate of the S window frames on the channel axis (S = dvsg_locnet_in_channels / 3;
+ * 7 in the reference's configuration), u_t = the newest of them -- happens inside conv1's load stage and the warp's tap
+ * loads, so the [B,H,W,3S] window tensor never exists.
  *   pool   [n_pool,H,W,3] RGB frames on the device: float32 in [0,1] (dvsg_stabilize_ring_f32; e.g. the history of
  *          eval.py:93-124, whose write-back of s_t_pred is a float frame), or the raw uint8 frames
  *          (dvsg_stabilize_ring_u8: eval_train.py's clips, independent windows; 4x less input traffic).  uint8:
  *          float32(v / 255.) * 255 == v exactly for every byte value, so conv1's scaled input float(v) - mean is
  *          bit-identical to the float path's on the converted frame.
- *   table  [B,7] int32 ON THE DEVICE: pool frame of window slot s of window b, oldest to newest (the `sample_idx`
+ *   table  [B,S] int32 ON THE DEVICE, S = dvsg_locnet_in_channels / 3: pool frame of window slot s of window b, oldest to newest (the `sample_idx`
  *          of eval.py:103; coupe.dvsg_amd.clip.window_index_table builds it for a whole clip).  u_t of window b is
- *          frame table[b][6].  An index outside [0, n_pool) reads as a frame of zeros (dvsg_window_gather_f32).
+ *          frame table[b][S-1].  An index outside [0, n_pool) reads as a frame of zeros (dvsg_window_gather_f32).
  *   precision  DVSG_PRECISION_F32 (the reference's arithmetic: bit-identical to dvsg_window_gather_f32 +
  *          dvsg_stabilize_f32 on the same frames), DVSG_PRECISION_F16, DVSG_PRECISION_F32S (same as the *_f16 / *_f32s
  *          entry points on the gathered window).
@@ -571,7 +578,7 @@ int dvsg_crop_ratchet_f32(const int32_t *key_min_a, int D_a, const int32_t *key_
 /* ---------------------------------------------------------------------------------------
  * eval_train.py's evaluation graph (eval_train.py:25-51): unlike model.py's, its CNN input is
  * `patches_masked_t = patches_t * mask` (:43-45), where `random_mask` (:53-64, = model.py:156-167) warps an all-ones
- * image of the 18 history channels with ProjectiveTransformer and a near-identity homography H and leaves the newest
+ * image of the 3 (S - 1) history channels (18 of 21 in the reference) with ProjectiveTransformer and a near-identity homography H and leaves the newest
  * frame's 3 channels unmasked; the TPS warp still samples the UNMASKED u_t (:48).
  *   dvsg_random_mask_plane_f32  theta [B,8] (the homography of :55-57 AFTER its scale and identity offset; the
  *          reference draws it with tf.random_uniform inside the graph, here the caller supplies it) -> mask [B,H,W]:
@@ -579,11 +586,11 @@ int dvsg_crop_ratchet_f32(const int32_t *key_min_a, int D_a, const int32_t *key_
  *          sampler B's blend (:545-562) on taps that read 1 inside the image and 0 on the zero ring.  The warp of an
  *          all-ones image is the same in every channel, so ONE plane stands for `random_masks_t[..., :18]`.
  *   dvsg_stabilize_masked_f32 / dvsg_stabilize_ring_masked_{f32,u8}: dvsg_stabilize_* / dvsg_stabilize_ring_* with that
- *          plane multiplied into the 18 history channels INSIDE conv1's load stage ((x * m) * 255 - mean, three
- *          roundings like the TF ops); neither a [B,H,W,21] product tensor nor a multiply launch exists.  A plane of
+ *          plane multiplied into the 3 (S - 1) history channels INSIDE conv1's load stage ((x * m) * 255 - mean, three
+ *          roundings like the TF ops); neither a [B,H,W,3S] product tensor nor a multiply launch exists.  A plane of
  *          exact ones reproduces the unmasked entry points bit for bit.  precision: DVSG_PRECISION_*.
  *   dvsg_locnet_forward_masked: the CNN alone (stage -1: F_t into `out`) or a parity tap (stage 0..18) from a masked
- *          source; src_kind 0 = window tensor [B,H,W,21], 1 = float32 frame pool + table, 2 = uint8 frame pool + table.
+ *          source; src_kind 0 = window tensor [B,H,W,3S], 1 = float32 frame pool + table, 2 = uint8 frame pool + table.
  * ------------------------------------------------------------------------------------- */
 int dvsg_random_mask_plane_f32(const float *theta, int B, int H, int W, float *mask, void *stream);
 int dvsg_stabilize_masked_f32(const dvsg_locnet_t *net, int precision, const float *patches_t, const float *u_t,
@@ -644,8 +651,9 @@ int dvsg_debug_last_conv_config(int *fields, int n);
 int dvsg_debug_last_conv_kernel(int *fields, int n);
 /* Which root and head kernels the last network call (dvsg_locnet_forward_*, dvsg_stabilize_*, their ring / masked / tap
  * forms) ran, recorded on the host when they were launched; no synchronisation.  fields (n >= 9): conv1 family (0 conv1_kernel,
- * 1 conv1_f16_kernel, 2 conv1_f16_pair_kernel, 3 conv1_f16_march_kernel, 4 conv1_split_kernel, 5 conv1_x3_kernel), its template
- * arguments NW, TO (0 float, 1 _Float16) and SRC (2 x source kind + rows on the 16-byte grid + 8 x masked), -1 where the family
+ * 1 conv1_f16_kernel, 2 conv1_f16_pair_kernel, 3 conv1_f16_march_kernel, 4 conv1_split_kernel, 5 conv1_x3_kernel, 6
+ * rootconv_kernel: every launch of a handle whose c_in is not 21, recorded with NW = 4), its template
+ * arguments NW, TO (0 float, 1 _Float16, 2 the float16 pieces of "f32s": family 6 only) and SRC (2 x source kind + rows on the 16-byte grid + 8 x masked), -1 where the family
  * has none; the marching kernel's bands and quads_per_band (else -1); the max pool kernel (0 maxpool_kernel<float>, 1
  * maxpool_kernel<_Float16>, 2 maxpool_h8_kernel, 3 maxpool_p_kernel); the average pool kernel (0 avgpool_partial_kernel<float>,
  * 1 avgpool_partial_kernel<_Float16>, 2 avgpool_partial_p_kernel); the number of dense batch chunks of <= 16 samples.  A
