@@ -1,0 +1,367 @@
+"""Uncompressed video over pipes: YUV4MPEG2 (Y4M) and header-less NV12 readers and writers, and the planar <-> semi-planar
+chroma repack between them.  No codec: a decoder and an encoder sit at either end of a pipe and speak these two formats
+(`ffmpeg -f yuv4mpegpipe -pix_fmt yuv420p`, `ffmpeg -f rawvideo -pix_fmt nv12`).
+
+A Y4M stream is one header line
+
+    YUV4MPEG2 W<width> H<height> F<num>:<den> [I<p|?>] [A<num>:<den>] [C<chroma>] [X<anything> ...]\\n
+
+followed by frames, each `FRAME[ params]\\n` and W H 3 / 2 bytes: H rows of Y, then the U plane and the V plane, each
+H/2 x W/2 (I420).  `Y4MReader` hands a frame over as one uint8 array [3 H / 2, W] holding those bytes as they lie in the
+stream; `OnlineStabilizer(frame_format="nv12")` wants the two chroma planes interleaved, which is `i420_to_nv12` (on the
+device, in the pipeline).  `RawNV12Reader` yields NV12 [3 H / 2, W] directly, and nothing is repacked.
+
+Chroma siting and range tags are carried through unchanged and interpreted nowhere: `C420jpeg`, `C420mpeg2` and `C420paldv`
+differ in where the chroma samples sit, `XCOLORRANGE=FULL` says the bytes span [0, 255] instead of [16, 235].  The render
+warps the Y plane and the UV plane directly (`dvsg_tps_render_nv12`), so an output pixel keeps the range and the siting of
+the input, and a writer that repeats the input's tags describes the output correctly.  The YUV matrix (`yuv_matrix`, limited
+range) only decides what the CNN sees at the model's size; Y4M carries no matrix, so `default_yuv_matrix` picks one by height
+as players do.  Full-range footage therefore reaches the CNN through a limited-range matrix (slightly more contrast, clipped
+at both ends); its effect on F_t has not been measured.
+
+Readers and writers share one small interface, which `pipe.stabilize_pipes` relies on: `width`, `height`, `layout` ("i420"
+or "nv12"), `frame_shape` ([3 H / 2, W]), `frame_bytes`; a reader has `readinto(buf) -> bool` (False at a clean end of the
+stream) and iterates over fresh arrays; a writer has `write(frame)` and `flush()`.
+"""
+import numpy as np
+
+MAGIC = b"YUV4MPEG2"
+FRAME_MAGIC = b"FRAME"
+CHROMA_420 = ("420", "420jpeg", "420mpeg2", "420paldv")   # 8-bit 4:2:0; they differ in chroma siting only
+MAX_HEADER = 4096                                          # bytes of one header line, the newline included
+
+
+class Y4MError(ValueError):
+    """A stream that is not the Y4M / raw NV12 this module reads: a malformed or unsupported header, or a truncated frame."""
+
+
+def _read_exact(f, view):
+    """Fill the writable byte view from `f`, across short reads; returns the bytes received (less than asked for at the end
+    of the stream only)."""
+    n, got = len(view), 0
+    readinto = getattr(f, "readinto", None)
+    while got < n:
+        if readinto is not None:
+            k = readinto(view[got:])
+        else:
+            chunk = f.read(n - got)
+            k = None if chunk is None else len(chunk)
+            if k:
+                view[got:got + k] = chunk
+        if k is None:
+            raise Y4MError("the stream is in non-blocking mode and has no data: give the reader a blocking file object")
+        if k == 0:
+            break
+        got += k
+    return got
+
+
+def _read_line(f, first=b""):
+    """The bytes up to and without the next newline, read one at a time (a pipe cannot be given anything back); None at the
+    end of the stream before any byte."""
+    line = bytearray(first)
+    one = bytearray(1)
+    while True:
+        if _read_exact(f, memoryview(one)) == 0:
+            if not line:
+                return None
+            raise Y4MError("the stream ends inside a header line: %r" % bytes(line[:40]))
+        if one == b"\n":
+            return bytes(line)
+        line += one
+        if len(line) >= MAX_HEADER:
+            raise Y4MError("a header line of more than %d bytes: %r ..." % (MAX_HEADER, bytes(line[:40])))
+
+
+def _ratio(tag):
+    """'F30000:1001' -> (30000, 1001)"""
+    try:
+        num, den = tag[1:].split(":")
+        num, den = int(num), int(den)
+    except ValueError:
+        raise Y4MError("tag %s: expected %s<num>:<den>" % (tag, tag[:1])) from None
+    if num < 0 or den < 0:
+        raise Y4MError("tag %s: negative ratio" % tag)
+    return num, den
+
+
+def _as_ratio(value, what):
+    """A Fraction, (num, den), an int or 'N/D' / 'N:D' / 'N' -> (num, den)"""
+    if isinstance(value, str):
+        parts = value.replace(":", "/").split("/")
+        try:
+            value = (int(parts[0]), int(parts[1]) if len(parts) > 1 else 1)
+            if len(parts) > 2:
+                raise ValueError
+        except (ValueError, IndexError):
+            raise ValueError("%s must be N or N/D, got %r" % (what, value)) from None
+    elif hasattr(value, "numerator"):
+        value = (int(value.numerator), int(value.denominator))
+    num, den = (int(v) for v in value)
+    if num < 0 or den < 0:
+        raise ValueError("%s must not be negative, got %d:%d" % (what, num, den))
+    return num, den
+
+
+def check_size(width, height, wtag="width", htag="height"):
+    """OnlineStabilizer's NV12 rule: both even and at least 4."""
+    for tag, v in ((wtag, width), (htag, height)):
+        if v % 2 or v < 4:
+            raise Y4MError("%s%d: 4:2:0 frames need an even width and height of at least 4" % (tag, v))
+
+
+def _frame_view(buf, nbytes):
+    """`buf` (anything with the buffer protocol, a pinned tensor's .numpy() included) as a flat byte view of nbytes."""
+    view = memoryview(buf)
+    if not view.contiguous:
+        raise ValueError("a frame buffer must be contiguous")
+    view = view.cast("B") if view.ndim != 1 or view.format != "B" else view
+    if len(view) != nbytes:
+        raise ValueError("a frame buffer of %d bytes, the frame has %d" % (len(view), nbytes))
+    return view
+
+
+class _Reader(object):
+    layout = None
+
+    def _init_frames(self, fileobj, width, height):
+        self.fileobj, self.width, self.height = fileobj, int(width), int(height)
+        self.frame_shape = (3 * self.height // 2, self.width)
+        self.frame_bytes = self.frame_shape[0] * self.width
+        self.frames_read = 0
+
+    def _payload(self, view):
+        got = _read_exact(self.fileobj, view)
+        if got != len(view):
+            raise Y4MError("frame %d is truncated: %d of %d bytes received" % (self.frames_read, got, len(view)))
+
+    def read(self):
+        """The next frame as a fresh uint8 array [3 H / 2, W], or None at the end of the stream."""
+        frame = np.empty(self.frame_shape, dtype=np.uint8)
+        return frame if self.readinto(frame) else None
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        frame = self.read()
+        if frame is None:
+            raise StopIteration
+        return frame
+
+
+class Y4MReader(_Reader):
+    """Y4M from any binary file object, a pipe that returns short reads included.  The header is parsed on construction:
+    `width`, `height`, `fps` and `aspect` ((num, den) as written, None without the tag), `interlace` ("p", "?" or None),
+    `colorspace` (the C tag's value, None without one: 4:2:0 by default) and `tags`, every other tag verbatim and in order
+    (the X tags, `XCOLORRANGE=FULL` among them).  Frames are I420, [3 H / 2, W] uint8: H rows of Y, then the U plane and the
+    V plane as they lie in the stream.  `readinto(buf)` fills a caller's buffer of `frame_bytes` (pinned memory, say) without
+    a copy.
+
+    Accepted: C420, C420jpeg, C420mpeg2, C420paldv or no C tag; Ip, I? or no I tag.  Everything else -- another chroma
+    format or bit depth, interlaced material, an odd or tiny or missing W / H, a wrong magic -- raises Y4MError naming the
+    tag, before any frame is read.  A stream that ends inside a frame raises Y4MError with the frame's index and the bytes
+    received; one that ends after the header yields no frames."""
+    layout = "i420"
+
+    def __init__(self, fileobj):
+        line = _read_line(fileobj)
+        if line is None:
+            raise Y4MError("an empty stream: no YUV4MPEG2 header")
+        tokens = [t for t in line.split(b" ") if t]
+        if not tokens or tokens[0] != MAGIC:
+            raise Y4MError("not a Y4M stream: it starts with %r, not YUV4MPEG2" % bytes(line[:16]))
+        width = height = None
+        self.fps = self.aspect = self.interlace = self.colorspace = None
+        tags = []
+        for tok in tokens[1:]:
+            tag = tok.decode("latin-1")
+            key = tag[0]
+            try:
+                if key == "W":
+                    width = int(tag[1:])
+                elif key == "H":
+                    height = int(tag[1:])
+            except ValueError:
+                raise Y4MError("tag %s: not a size" % tag) from None
+            if key == "F":
+                self.fps = _ratio(tag)
+            elif key == "A":
+                self.aspect = _ratio(tag)
+            elif key == "I":
+                if tag[1:] not in ("p", "?"):
+                    raise Y4MError("tag %s: interlaced material is not supported (progressive Ip or I? only)" % tag)
+                self.interlace = tag[1:]
+            elif key == "C":
+                if tag[1:] not in CHROMA_420:
+                    raise Y4MError("tag %s: only 8-bit 4:2:0 is supported (%s)" % (tag, ", ".join("C" + c for c in CHROMA_420)))
+                self.colorspace = tag[1:]
+            elif key not in "WH":
+                tags.append(tag)
+        if width is None or height is None:
+            raise Y4MError("the Y4M header has no %s tag: %r" % ("W" if width is None else "H", line[:80]))
+        check_size(width, height, "W", "H")
+        self.tags = tuple(tags)
+        self._init_frames(fileobj, width, height)
+
+    def readinto(self, buf):
+        view = _frame_view(buf, self.frame_bytes)
+        head = bytearray(len(FRAME_MAGIC) + 1)
+        got = _read_exact(self.fileobj, memoryview(head))
+        if got == 0:
+            return False
+        if got < len(head):
+            raise Y4MError("frame %d is truncated: the stream ends inside its FRAME header (%d bytes received)"
+                           % (self.frames_read, got))
+        if head[:-1] != FRAME_MAGIC or head[-1:] not in (b"\n", b" "):
+            raise Y4MError("frame %d does not start with FRAME: %r" % (self.frames_read, bytes(head)))
+        if head[-1:] == b" " and _read_line(self.fileobj, b" ") is None:   # frame parameters: accepted and ignored
+            raise Y4MError("frame %d is truncated: the stream ends inside its FRAME header" % self.frames_read)
+        self._payload(view)
+        self.frames_read += 1
+        return True
+
+
+class RawNV12Reader(_Reader):
+    """Header-less NV12 (`-f rawvideo -pix_fmt nv12`): frames of W H 3 / 2 bytes, [3 H / 2, W] uint8 with H rows of Y and H / 2
+    rows of interleaved U V.  The size comes from the caller; the interface is Y4MReader's."""
+    layout = "nv12"
+    fps = aspect = interlace = colorspace = None
+    tags = ()
+
+    def __init__(self, fileobj, width, height):
+        check_size(int(width), int(height))
+        self._init_frames(fileobj, width, height)
+
+    def readinto(self, buf):
+        view = _frame_view(buf, self.frame_bytes)
+        got = _read_exact(self.fileobj, view)
+        if got == 0:
+            return False
+        if got != self.frame_bytes:
+            raise Y4MError("frame %d is truncated: %d of %d bytes received" % (self.frames_read, got, self.frame_bytes))
+        self.frames_read += 1
+        return True
+
+
+class _Writer(object):
+    layout = None
+
+    def _init_frames(self, fileobj, width, height):
+        self.fileobj, self.width, self.height = fileobj, int(width), int(height)
+        check_size(self.width, self.height)
+        self.frame_shape = (3 * self.height // 2, self.width)
+        self.frame_bytes = self.frame_shape[0] * self.width
+        self.frames_written = 0
+
+    def _write_all(self, data):
+        view = memoryview(data)
+        while len(view):           # a raw file object may take less than it is given
+            k = self.fileobj.write(view)
+            if k is None:
+                k = len(view)
+            view = view[k:]
+
+    def flush(self):
+        flush = getattr(self.fileobj, "flush", None)
+        if flush is not None:
+            flush()
+
+
+class Y4MWriter(_Writer):
+    """Writes the stream header once, then `FRAME\\n` and the I420 bytes per `write(frame)`.  fps and aspect are a
+    Fraction, (num, den), an int or "N/D"; aspect, interlace and colorspace of None leave their tag out; `tags` are appended
+    verbatim (a reader's `tags`, to carry XCOLORRANGE and the like through)."""
+    layout = "i420"
+
+    def __init__(self, fileobj, width, height, fps, aspect=None, colorspace="420jpeg", tags=(), interlace="p"):
+        self._init_frames(fileobj, width, height)
+        self.fps = _as_ratio(fps, "fps")
+        self.aspect = None if aspect is None else _as_ratio(aspect, "aspect")
+        if colorspace is not None and colorspace not in CHROMA_420:
+            raise Y4MError("colorspace %r: only 8-bit 4:2:0 is written (%s)" % (colorspace, ", ".join(CHROMA_420)))
+        if interlace not in (None, "p", "?"):
+            raise Y4MError("interlace %r: progressive only ('p', '?' or None)" % (interlace,))
+        self.colorspace, self.interlace, self.tags = colorspace, interlace, tuple(tags)
+        for t in self.tags:
+            if not t or any(c in t for c in " \n"):
+                raise Y4MError("tag %r: a tag is one word" % (t,))
+        head = ["YUV4MPEG2", "W%d" % self.width, "H%d" % self.height, "F%d:%d" % self.fps]
+        if interlace is not None:
+            head.append("I" + interlace)
+        if self.aspect is not None:
+            head.append("A%d:%d" % self.aspect)
+        if colorspace is not None:
+            head.append("C" + colorspace)
+        self._write_all((" ".join(head + list(self.tags)) + "\n").encode("latin-1"))
+
+    def write(self, frame):
+        view = _frame_view(frame, self.frame_bytes)
+        self._write_all(b"FRAME\n")
+        self._write_all(view)
+        self.frames_written += 1
+
+
+class RawNV12Writer(_Writer):
+    """Header-less NV12: `write(frame)` writes the W H 3 / 2 bytes of an NV12 frame [3 H / 2, W]."""
+    layout = "nv12"
+
+    def __init__(self, fileobj, width, height):
+        self._init_frames(fileobj, width, height)
+
+    def write(self, frame):
+        self._write_all(_frame_view(frame, self.frame_bytes))
+        self.frames_written += 1
+
+
+def _planes(t):
+    """A frame [3 H / 2, W] or a batch [n, 3 H / 2, W] as views: (y [n, H W], chroma [n, H W / 2], H, W)."""
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3:
+        raise ValueError("a frame is [3 H / 2, W] and a batch [n, 3 H / 2, W], got %s" % (tuple(t.shape),))
+    n, R, W = (int(v) for v in t.shape)
+    H = 2 * R // 3
+    if R % 3 or H % 2 or W % 2:
+        raise ValueError("4:2:0 frames [3 H / 2, W] need even H and W, got %s" % (tuple(t.shape),))
+    if n > 0 and (t.stride(2) != 1 or t.stride(1) != W):
+        raise ValueError("the rows of a frame must be contiguous (strides %s)" % (tuple(t.stride()),))
+    flat = t.as_strided((n, R * W), (t.stride(0), 1), t.storage_offset())
+    return flat[:, :H * W], flat[:, H * W:], H, W
+
+
+def _repack(src, out, to_nv12):
+    import torch
+    if out is None:
+        out = torch.empty(src.shape, dtype=src.dtype, device=src.device)
+    elif out.shape != src.shape or out.dtype != src.dtype or out.device != src.device:
+        raise ValueError("out must have the shape, dtype and device of src: %s %s %s against %s %s %s"
+                         % (tuple(out.shape), out.dtype, out.device, tuple(src.shape), src.dtype, src.device))
+    if out.data_ptr() == src.data_ptr() and src.numel():
+        raise ValueError("out must not be src: the repack is not done in place")
+    sy, sc, H, W = _planes(src)
+    oy, oc, _, _ = _planes(out)
+    n, q = int(sy.shape[0]), H * W // 4
+    oy.copy_(sy)
+    if to_nv12:   # U plane | V plane -> U0 V0 U1 V1 ...
+        oc.view(n, q, 2).copy_(sc.view(n, 2, q).transpose(1, 2))
+    else:
+        oc.view(n, 2, q).copy_(sc.view(n, q, 2).transpose(1, 2))
+    return out
+
+
+def i420_to_nv12(src, out=None):
+    """I420 (Y, the U plane, the V plane) -> NV12 (Y, interleaved U V) for a uint8 tensor [3 H / 2, W] or a batch
+    [n, 3 H / 2, W] on any device: two strided copies on the current stream, no synchronise, and no allocation when `out`
+    (same shape, not `src` itself) is given.  Returns out."""
+    return _repack(src, out, True)
+
+
+def nv12_to_i420(src, out=None):
+    """The inverse of `i420_to_nv12`, with the same contract."""
+    return _repack(src, out, False)
+
+
+def default_yuv_matrix(height):
+    """Y4M names no matrix: "bt709" from 720 rows up and "bt601" below, as players assume."""
+    return "bt709" if int(height) >= 720 else "bt601"

@@ -2,7 +2,8 @@
 """Live use of the drop-in: frames arrive one at a time (a camera or a decoder) for one or several streams, and each
 step returns every stream's stabilised frame (eval.py:93-124, online).  Decoding is host I/O and not part of this
 example: a seeded synthetic uint8 source stands in for it, BGR and larger than the model's size as cv2 would hand
-it over (eval.py:76-81 resizes it).
+it over (eval.py:76-81 resizes it).  For real footage, `python -m coupe.dvsg_amd.pipe` runs this loop between a decoder and
+an encoder that speak uncompressed Y4M or raw NV12 over pipes (coupe/dvsg_amd/pipe.py).
 
     python examples/stabilize_stream.py [--streams 2] [--frames 48] [--height 288] [--width 512] [--precision f32|f32x3]
 
