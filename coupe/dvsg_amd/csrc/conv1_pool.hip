@@ -380,6 +380,49 @@ struct Conv1RowSel {
                                           kAligned, kMasked>> type;
 };
 
+// ----------------------------------------------------------------------------------------
+// What the conv1 kernels share beyond the staged row: which tile a workgroup owns, and the way its 128 pixels x 64 channels
+// of float32 results leave through a [C1_TILE][C1_LDC] transpose tile in LDS (profiles/r18_conv1_dedup_isa_diff.txt: the
+// machine code of every kernel against the hand-written copies these replaced).
+// ----------------------------------------------------------------------------------------
+struct Conv1Tile {
+  int b, ho, wo0;   // window, output row (row pair, band: whatever `rows` counted), first output pixel
+};
+// Each XCD takes a contiguous range of tiles: the 3-4 output rows that share an input row run on the same L2 (consecutive
+// block ids are dealt round-robin over the 8 XCDs).  Column tiles fastest, then `rows` per window.
+__device__ __forceinline__ Conv1Tile conv1_tile(int wtiles, int rows) {
+  int blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int wt_i = blk % wtiles;
+  blk /= wtiles;
+  const int ho = blk % rows;
+  const int b = blk / rows;
+  return {b, ho, wt_i * C1_TILE};
+}
+// A wave's 32 pixels (from PIX0) x 32 channels (from COL0) of the lane (r, h in scope) into the transpose tile Cs: VALUE, an
+// expression in q, is register q of the 32x32 MFMA result -- pixel (q & 3) + 8 (q >> 2) + 4 h of the block, channel r.
+// (A macro: as a function that takes the value as a callable it moved the register allocation of 92 of the 102 kernels.)
+#define C1_TILE_PUT(Cs, PIX0, COL0, VALUE) \
+  _Pragma("unroll") for (int q = 0; q < 16; ++q) Cs[(PIX0 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + COL0 + r] = VALUE
+// The tile's way out: thread tid takes channels 4 (tid & 15) .. + 3 (their bias: conv1_tile_bias) of the pixels tid >> 4,
+// + STEP, ... (STEP = threads / 16) that lie inside the output row: bias, ReLU, then store(pixel of the tile, four values).
+__device__ __forceinline__ float4 conv1_tile_bias(const float *__restrict__ bias, int tid) {
+  return *reinterpret_cast<const float4 *>(bias + 4 * (tid & 15));
+}
+template <int STEP, typename STORE>
+__device__ __forceinline__ void conv1_tile_out(const float *Cs, const float4 b4, int tid, int wo0, int Wo, STORE store) {
+  const int col4 = tid & 15, row0 = tid >> 4;
+#pragma unroll 4
+  for (int row = row0; row < C1_TILE; row += STEP) {
+    if (wo0 + row >= Wo) break;
+    float4 v = *reinterpret_cast<const float4 *>(Cs + row * C1_LDC + 4 * col4);
+    v.x = fmaxf(v.x + b4.x, 0.f);
+    v.y = fmaxf(v.y + b4.y, 0.f);
+    v.z = fmaxf(v.z + b4.z, 0.f);
+    v.w = fmaxf(v.w + b4.w, 0.f);
+    store(row, v);
+  }
+}
+
 #ifdef DVSG_STAMPS  // diagnostic build (tools/stamp_probe_conv1.py): per-workgroup phase times of conv1_kernel
 __device__ unsigned long long g_c1_stamps[8 * 65536];
 #define C1_STAMP() __builtin_amdgcn_s_memtime()
@@ -401,14 +444,8 @@ void conv1_kernel(const Conv1Src src, const float *__restrict__ wt1, const float
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 31, h = lane >> 5;
 
-  // each XCD takes a contiguous range of tiles: the 3-4 output rows that share an input row run on
-  // the same L2 (consecutive block ids are dealt round-robin over the 8 XCDs)
-  int blk = xcd_remap(blockIdx.x, gridDim.x);
-  const int wt_i = blk % wtiles;
-  blk /= wtiles;
-  const int ho = blk % Ho;
-  const int b = blk / Ho;
-  const int wo0 = wt_i * C1_TILE;
+  const Conv1Tile tile = conv1_tile(wtiles, Ho);
+  const int b = tile.b, ho = tile.ho, wo0 = tile.wo0;
 
   typedef typename Conv1RowSel<NT, IN4, SRC>::type Row;
   Row row;
@@ -526,23 +563,11 @@ void conv1_kernel(const Conv1Src src, const float *__restrict__ wt1, const float
   __syncthreads();
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      Cs[(wm * 32 * MI + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + wn * 32 + r] = acc[mi][q] + acc2[mi][q];
+    C1_TILE_PUT(Cs, wm * 32 * MI + mi * 32, wn * 32, acc[mi][q] + acc2[mi][q]);
   __syncthreads();
-  const int col4 = tid & 15, row0 = tid >> 4;
-  const float4 b4 = *reinterpret_cast<const float4 *>(bias + 4 * col4);
-  TO *yrow = y + (((size_t)b * Ho + ho) * Wo + wo0) * 64 + 4 * col4;
-#pragma unroll 4
-  for (int row = row0; row < C1_TILE; row += NT / 16) {
-    if (wo0 + row >= Wo) break;
-    float4 v = *reinterpret_cast<const float4 *>(Cs + row * C1_LDC + 4 * col4);
-    v.x = fmaxf(v.x + b4.x, 0.f);
-    v.y = fmaxf(v.y + b4.y, 0.f);
-    v.z = fmaxf(v.z + b4.z, 0.f);
-    v.w = fmaxf(v.w + b4.w, 0.f);
-    store4(yrow + (size_t)row * 64, v);
-  }
+  TO *yrow = y + (((size_t)b * Ho + ho) * Wo + wo0) * 64 + 4 * (tid & 15);
+  conv1_tile_out<NT / 16>(Cs, conv1_tile_bias(bias, tid), tid, wo0, Wo,
+                          [&](int row, float4 v) __attribute__((always_inline)) { store4(yrow + (size_t)row * 64, v); });
 #ifdef DVSG_STAMPS
   if (tid == 0 && blockIdx.x < 65536) {
     unsigned long long *o = g_c1_stamps + (size_t)blockIdx.x * 8;
@@ -561,7 +586,8 @@ void conv1_kernel(const Conv1Src src, const float *__restrict__ wt1, const float
 // channels, 4 waves as 2 x 2, two 32-pixel MFMA blocks per wave), the same exact float32 products on
 // v_mfma_f32_32x32x2_f32 in two chains per block (even / odd taps, joined once in the epilogue), the same scale_RGB in the
 // load stage (x * 255 - mean_g, two roundings; with a mask (x * m) * 255 - mean_g on the first 3 (S - 1) channels; the pad
-// ring 0 in the SCALED domain; a table index outside [0, n_pool) a frame of raw zeros) and the same epilogue.
+// ring 0 in the SCALED domain; a table index outside [0, n_pool) a frame of raw zeros), the tile decode and the epilogue
+// are the shared ones (conv1_tile, C1_TILE_PUT, conv1_tile_out).
 //
 // LDS, sized per launch from cin (rootconv_lds_bytes): the raw row segment of 261 pixels at a pitch of
 // rootconv_pitch(cin) floats, and the kernel row's weights [64][rootconv_ld(cin)].
@@ -603,12 +629,8 @@ void rootconv_kernel(const Conv1Src src, const float *__restrict__ wt1, const fl
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 31, h = lane >> 5;
 
-  int blk = xcd_remap(blockIdx.x, gridDim.x);   // see conv1_kernel
-  const int wt_i = blk % wtiles;
-  blk /= wtiles;
-  const int ho = blk % Ho;
-  const int b = blk / Ho;
-  const int wo0 = wt_i * C1_TILE;
+  const Conv1Tile tile = conv1_tile(wtiles, Ho);
+  const int b = tile.b, ho = tile.ho, wo0 = tile.wo0;
 
   for (int e = tid; e < seg; e += NT) in_s[e] = 0.f;   // the pad floats and the tail stay zero: they meet zero weights
 
@@ -710,26 +732,15 @@ void rootconv_kernel(const Conv1Src src, const float *__restrict__ wt1, const fl
   __syncthreads();
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      Cs[(wm * 32 * MI + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + wn * 32 + r] = acc[mi][q] + acc2[mi][q];
+    C1_TILE_PUT(Cs, wm * 32 * MI + mi * 32, wn * 32, acc[mi][q] + acc2[mi][q]);
   __syncthreads();
-  const int col4 = tid & 15, row0 = tid >> 4;
-  const float4 b4 = *reinterpret_cast<const float4 *>(bias + 4 * col4);
-  const size_t e0 = (((size_t)b * Ho + ho) * Wo + wo0) * 64 + 4 * col4;
-#pragma unroll 4
-  for (int row = row0; row < C1_TILE; row += NT / 16) {
-    if (wo0 + row >= Wo) break;
-    float4 v = *reinterpret_cast<const float4 *>(Cs + row * C1_LDC + 4 * col4);
-    v.x = fmaxf(v.x + b4.x, 0.f);
-    v.y = fmaxf(v.y + b4.y, 0.f);
-    v.z = fmaxf(v.z + b4.z, 0.f);
-    v.w = fmaxf(v.w + b4.w, 0.f);
+  const size_t e0 = (((size_t)b * Ho + ho) * Wo + wo0) * 64 + 4 * (tid & 15);
+  conv1_tile_out<NT / 16>(Cs, conv1_tile_bias(bias, tid), tid, wo0, Wo, [&](int row, float4 v) __attribute__((always_inline)) {
     if constexpr (std::is_same<TO, PPieces>::value)
       store4_p(y, e0 + (size_t)row * 64, v);
     else
       store4(static_cast<TO *>(y) + e0 + (size_t)row * 64, v);
-  }
+  });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -820,6 +831,21 @@ constexpr int C1H_LD = 168;                        // halfs per weight row in LD
 constexpr int C1H_WBYTES = 64 * C1H_LD * 2;        // 21504 bytes per kernel row = 21 LDS-DMA pieces
 constexpr int C1H_SEG = 5504;                      // halfs per staged input row (5481 + zero tail)
 constexpr int C1H_IN4 = (C1H_SEG / 4 + 255) / 256;     // 6 groups of four elements per thread
+typedef const __attribute__((address_space(1))) void *gptr_t;
+typedef __attribute__((address_space(3))) void *lptr_t;
+
+// Weights of kernel row kh for the one- and two-row kernels (four waves): 21 pieces of 1 KiB, piece j by wave j % 4, straight
+// into the LDS image `w_dst`.  (conv1_f16_march_kernel, whose staging waves are waves 4-7, keeps its own unrolled form: its
+// vmcnt arithmetic counts on the exact order of its loads.)
+__device__ __forceinline__ void weights_dma(const _Float16 *wt1h, int kh, char *w_dst, int wave, int lane) {
+  const char *wsrc = reinterpret_cast<const char *>(wt1h) + (size_t)kh * C1H_WBYTES;
+  for (int j = wave; j < C1H_WBYTES / 1024; j += 4)
+    __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + j * 1024 + lane * 16), (lptr_t)(w_dst + j * 1024), 16, 0, 0);
+}
+// The row store that follows it -- scatter for rings, else scaled groups rounded once to float16 -- is written out in both
+// kernels (and, with its two differences, in the marching kernel): as one function it changed the register counts or more
+// than 1 % of the instructions of conv1_f16_kernel<_Float16, 0 / 1> and conv1_f16_pair_kernel<_Float16, 0 / 1 / 8 / 9>
+// (profiles/README.md, r18).
 
 template <typename TO, int SRC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -833,12 +859,8 @@ void conv1_f16_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h, con
   const int lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;   // wave w: pixels [32 w, 32 w + 32) x all 64 channels (see conv1_split_kernel)
 
-  int blk = xcd_remap(blockIdx.x, gridDim.x);  // see conv1_kernel
-  const int wt_i = blk % wtiles;
-  blk /= wtiles;
-  const int ho = blk % Ho;
-  const int b = blk / Ho;
-  const int wo0 = wt_i * C1_TILE;
+  const Conv1Tile tile = conv1_tile(wtiles, Ho);
+  const int b = tile.b, ho = tile.ho, wo0 = tile.wo0;
 
   typedef typename Conv1RowSel<256, C1H_IN4, SRC>::type Row;
   Row row;
@@ -848,15 +870,9 @@ void conv1_f16_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h, con
     __syncthreads();   // the first scatter writes halves of words other threads zero: the zeros must land first
   }
 
-  typedef const __attribute__((address_space(1))) void *gptr_t;
-  typedef __attribute__((address_space(3))) void *lptr_t;
   typename Row::Data rd;
   auto load_stage = [&](int kh, int buf) __attribute__((always_inline)) {
-    // weights of kernel row kh: 21 pieces of 1 KiB, piece j by wave j % 4, straight into LDS
-    const char *wsrc = reinterpret_cast<const char *>(wt1h) + (size_t)kh * C1H_WBYTES;
-    for (int j = wave; j < C1H_WBYTES / 1024; j += 4)
-      __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + j * 1024 + lane * 16), (lptr_t)(w_s + buf * C1H_WBYTES + j * 1024),
-                                       16, 0, 0);
+    weights_dma(wt1h, kh, w_s + buf * C1H_WBYTES, wave, lane);
     row.load(rd, 2 * ho + kh - 3);
   };
   auto store_stage = [&](int buf) __attribute__((always_inline)) {
@@ -925,23 +941,11 @@ void conv1_f16_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h, con
   float *Cs = reinterpret_cast<float *>(lds);
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      Cs[(wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + ni * 32 + r] = acc[ni][q];
+    C1_TILE_PUT(Cs, wave * 32, ni * 32, acc[ni][q]);
   __syncthreads();
-  const int col4 = tid & 15, row0 = tid >> 4;
-  const float4 b4 = *reinterpret_cast<const float4 *>(bias + 4 * col4);
-  TO *yrow = y + (((size_t)b * Ho + ho) * Wo + wo0) * 64 + 4 * col4;
-#pragma unroll 4
-  for (int row = row0; row < C1_TILE; row += 16) {
-    if (wo0 + row >= Wo) break;
-    float4 v = *reinterpret_cast<const float4 *>(Cs + row * C1_LDC + 4 * col4);
-    v.x = fmaxf(v.x + b4.x, 0.f);
-    v.y = fmaxf(v.y + b4.y, 0.f);
-    v.z = fmaxf(v.z + b4.z, 0.f);
-    v.w = fmaxf(v.w + b4.w, 0.f);
-    store4(yrow + (size_t)row * 64, v);
-  }
+  TO *yrow = y + (((size_t)b * Ho + ho) * Wo + wo0) * 64 + 4 * (tid & 15);
+  conv1_tile_out<16>(Cs, conv1_tile_bias(bias, tid), tid, wo0, Wo,
+                     [&](int row, float4 v) __attribute__((always_inline)) { store4(yrow + (size_t)row * 64, v); });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -976,12 +980,8 @@ void conv1_f16_pair_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h
   const int lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;   // wave w: pixels [32 w, 32 w + 32) x all 64 channels x both rows
 
-  int blk = xcd_remap(blockIdx.x, gridDim.x);  // see conv1_kernel
-  const int wt_i = blk % wtiles;
-  blk /= wtiles;
-  const int ho0 = 2 * (blk % hpairs);
-  const int b = blk / hpairs;
-  const int wo0 = wt_i * C1_TILE;
+  const Conv1Tile tile = conv1_tile(wtiles, hpairs);
+  const int b = tile.b, ho0 = 2 * tile.ho, wo0 = tile.wo0;
 
   typedef typename Conv1RowSel<256, C1H_IN4, SRC>::type Row;
   Row row;
@@ -991,15 +991,6 @@ void conv1_f16_pair_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h
     __syncthreads();   // the first scatter writes halves of words other threads zero: the zeros must land first
   }
   typename Row::Data d0, d1;
-
-  typedef const __attribute__((address_space(1))) void *gptr_t;
-  typedef __attribute__((address_space(3))) void *lptr_t;
-  auto weights_dma = [&](int kh, int wbuf) __attribute__((always_inline)) {
-    const char *wsrc = reinterpret_cast<const char *>(wt1h) + (size_t)kh * C1H_WBYTES;
-    for (int j = wave; j < C1H_WBYTES / 1024; j += 4)
-      __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + j * 1024 + lane * 16), (lptr_t)(w_s + wbuf * C1H_WBYTES + j * 1024),
-                                       16, 0, 0);
-  };
   auto store_row = [&](const typename Row::Data &d, int buf) __attribute__((always_inline)) {
     typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
     if constexpr (Row::kRing) {
@@ -1032,7 +1023,7 @@ void conv1_f16_pair_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h
   // prologue: rows a, a + 2 and the weights of kernel row 0
   row.load(d0, a);
   row.load(d1, a + 2);
-  weights_dma(0, 0);
+  weights_dma(wt1h, 0, w_s, wave, lane);
   store_row(d0, 0);
   store_row(d1, 1);
   __syncthreads();
@@ -1047,7 +1038,7 @@ void conv1_f16_pair_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h
     if (khn >= 0) {
       row.load(d0, chain ? a + khn + 2 : a + khn);
       if (!chain) row.load(d1, a + khn + 2);
-      weights_dma(khn, (s + 1) & 1);
+      weights_dma(wt1h, khn, w_s + ((s + 1) & 1) * C1H_WBYTES, wave, lane);
     }
     __builtin_amdgcn_sched_barrier(0);
     const unsigned *a0 = reinterpret_cast<const unsigned *>(in_s + lo * C1H_SEG * 2) + kConv1Cin * (wave * 32 + r) + 4 * h;
@@ -1105,29 +1096,18 @@ void conv1_f16_pair_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1h
   step(std::integral_constant<int, 6>{});
 
   float *Cs = reinterpret_cast<float *>(lds);
-  const int col4 = tid & 15, row0 = tid >> 4;
-  const float4 b4 = *reinterpret_cast<const float4 *>(bias + 4 * col4);
+  const float4 b4 = conv1_tile_bias(bias, tid);   // once for both rows
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     if (j) __syncthreads();   // the first row's tile has been read
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        Cs[(wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + ni * 32 + r] = acc[j][ni][q];
+      C1_TILE_PUT(Cs, wave * 32, ni * 32, acc[j][ni][q]);
     __syncthreads();
     if (ho0 + j < Ho) {
-      TO *yrow = y + (((size_t)b * Ho + ho0 + j) * Wo + wo0) * 64 + 4 * col4;
-#pragma unroll 4
-      for (int rw = row0; rw < C1_TILE; rw += 16) {
-        if (wo0 + rw >= Wo) break;
-        float4 v = *reinterpret_cast<const float4 *>(Cs + rw * C1_LDC + 4 * col4);
-        v.x = fmaxf(v.x + b4.x, 0.f);
-        v.y = fmaxf(v.y + b4.y, 0.f);
-        v.z = fmaxf(v.z + b4.z, 0.f);
-        v.w = fmaxf(v.w + b4.w, 0.f);
-        store4(yrow + (size_t)rw * 64, v);
-      }
+      TO *yrow = y + (((size_t)b * Ho + ho0 + j) * Wo + wo0) * 64 + 4 * (tid & 15);
+      conv1_tile_out<16>(Cs, b4, tid, wo0, Wo,
+                         [&](int row, float4 v) __attribute__((always_inline)) { store4(yrow + (size_t)row * 64, v); });
     }
   }
 }
@@ -1176,12 +1156,8 @@ void conv1_f16_march_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1
   const bool stager = wave >= 4;
   const int r = lane & 31, h = lane >> 5;
 
-  int blk = xcd_remap(blockIdx.x, gridDim.x);        // an XCD takes neighbouring column tiles / bands of one image
-  const int wt_i = blk % wtiles;
-  blk /= wtiles;
-  const int band = blk % bands;
-  const int b = blk / bands;
-  const int wo0 = wt_i * C1_TILE;
+  const Conv1Tile tile = conv1_tile(wtiles, bands);  // an XCD takes neighbouring column tiles / bands of one image
+  const int b = tile.b, band = tile.ho, wo0 = tile.wo0;
   const int rb0 = band * quads_per_band * C1M_QUAD;                       // first output row of the band
   const int nq = min(quads_per_band, (Ho - rb0 + C1M_QUAD - 1) / C1M_QUAD);
   const int nsteps = 7 * nq;
@@ -1196,8 +1172,6 @@ void conv1_f16_march_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1
     const int u = (row + 64) >> 1;                   // rows >= -3: non-negative
     return (((row & 1) ? 0 : C1M_RING) + u % C1M_RING) * C1H_SEG;
   };
-  typedef const __attribute__((address_space(1))) void *gptr_t;
-  typedef __attribute__((address_space(3))) void *lptr_t;
 
   if (stager) {
     // ------------------------------------------------------------------------------ staging waves
@@ -1214,7 +1188,8 @@ void conv1_f16_march_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1
       for (int e = st; e < C1M_RING * C1H_SEG; e += 256) reinterpret_cast<unsigned *>(in_s)[e] = 0u;
     }
     __syncthreads();              // (every wave of the workgroup: nobody's first row store may be overtaken by the zeroing)
-    auto weights_dma = [&](int kh, int wbuf) __attribute__((always_inline)) {
+    // (this kernel's form of weights_dma: unrolled, over waves 4-7, in the load order step_barrier counts on)
+    auto march_weights_dma = [&](int kh, int wbuf) __attribute__((always_inline)) {
       const char *wsrc = reinterpret_cast<const char *>(wt1h) + (size_t)kh * C1H_WBYTES;
 #pragma unroll
       for (int i = 0; i < (C1H_WBYTES / 1024 + 3) / 4; ++i) {   // 21 pieces of 1 KiB over the 4 staging waves
@@ -1279,7 +1254,7 @@ void conv1_f16_march_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1
         store_row(extra[0], top - 4);
         store_row(extra[1], top - 6);
       }
-      weights_dma(kh, (7 * quad + ks) & 1);
+      march_weights_dma(kh, (7 * quad + ks) & 1);
     };
     // End of a step for a staging wave: its LDS stores and everything OLDER than the `newer` row loads it has just issued
     // (this step's weight DMA in particular) must have landed; the row loads themselves stay in flight across the barrier
@@ -1556,12 +1531,8 @@ void conv1_split_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1s, c
   const int r = lane & 31, h = lane >> 5;   // wave w: pixels [32 w, 32 w + 32) x all 64 channels (two 32-channel blocks):
                                             // an activation fragment is read once for both blocks (the LDS is this kernel's bound)
 
-  int blk = xcd_remap(blockIdx.x, gridDim.x);  // see conv1_kernel
-  const int wt_i = blk % wtiles;
-  blk /= wtiles;
-  const int ho = blk % Ho;
-  const int b = blk / Ho;
-  const int wo0 = wt_i * C1_TILE;
+  const Conv1Tile tile = conv1_tile(wtiles, Ho);
+  const int b = tile.b, ho = tile.ho, wo0 = tile.wo0;
 
   typedef typename Conv1RowSel<NT, C1S_IN4, SRC>::type Row;
   Row row;
@@ -1672,22 +1643,12 @@ void conv1_split_kernel(const Conv1Src src, const _Float16 *__restrict__ wt1s, c
   __syncthreads();
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      Cs[(wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + ni * 32 + r] = acc[ni][q] + accl[ni][q] * (1.0f / 2048.0f);
+    C1_TILE_PUT(Cs, wave * 32, ni * 32, acc[ni][q] + accl[ni][q] * (1.0f / 2048.0f));
   __syncthreads();
-  const int col4 = tid & 15, row0 = tid >> 4;
-  const float4 b4 = *reinterpret_cast<const float4 *>(bias + 4 * col4);
-#pragma unroll 4
-  for (int row = row0; row < C1_TILE; row += 16) {
-    if (wo0 + row >= Wo) break;
-    float4 v = *reinterpret_cast<const float4 *>(Cs + row * C1_LDC + 4 * col4);
-    v.x = fmaxf(v.x + b4.x, 0.f);
-    v.y = fmaxf(v.y + b4.y, 0.f);
-    v.z = fmaxf(v.z + b4.z, 0.f);
-    v.w = fmaxf(v.w + b4.w, 0.f);
+  const int col4 = tid & 15;
+  conv1_tile_out<16>(Cs, conv1_tile_bias(bias, tid), tid, wo0, Wo, [&](int row, float4 v) __attribute__((always_inline)) {
     store4_p(y, (((size_t)b * Ho + ho) * Wo + wo0 + row) * 64 + 4 * col4, v);   // float16 pieces (cnn_device.h)
-  }
+  });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1718,12 +1679,8 @@ void conv1_x3_kernel(const Conv1Src src, const unsigned short *__restrict__ wt1x
   const int lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;   // wave w: pixels [32 w, 32 w + 32) x all 64 channels (two 32-channel blocks)
 
-  int blk = xcd_remap(blockIdx.x, gridDim.x);  // see conv1_kernel
-  const int wt_i = blk % wtiles;
-  blk /= wtiles;
-  const int ho = blk % Ho;
-  const int b = blk / Ho;
-  const int wo0 = wt_i * C1_TILE;
+  const Conv1Tile tile = conv1_tile(wtiles, Ho);
+  const int b = tile.b, ho = tile.ho, wo0 = tile.wo0;
 
   typedef typename Conv1RowSel<NT, C1X_IN4, SRC>::type Row;
   Row row;
@@ -1854,22 +1811,12 @@ void conv1_x3_kernel(const Conv1Src src, const unsigned short *__restrict__ wt1x
   __syncthreads();
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      Cs[(wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * C1_LDC + ni * 32 + r] = acc[ni][q] + accs[ni][q];
+    C1_TILE_PUT(Cs, wave * 32, ni * 32, acc[ni][q] + accs[ni][q]);
   __syncthreads();
-  const int col4 = tid & 15, row0 = tid >> 4;
-  const float4 b4 = *reinterpret_cast<const float4 *>(bias + 4 * col4);
-#pragma unroll 4
-  for (int row = row0; row < C1_TILE; row += 16) {
-    if (wo0 + row >= Wo) break;
-    float4 v = *reinterpret_cast<const float4 *>(Cs + row * C1_LDC + 4 * col4);
-    v.x = fmaxf(v.x + b4.x, 0.f);
-    v.y = fmaxf(v.y + b4.y, 0.f);
-    v.z = fmaxf(v.z + b4.z, 0.f);
-    v.w = fmaxf(v.w + b4.w, 0.f);
+  const int col4 = tid & 15;
+  conv1_tile_out<16>(Cs, conv1_tile_bias(bias, tid), tid, wo0, Wo, [&](int row, float4 v) __attribute__((always_inline)) {
     store4(y + (((size_t)b * Ho + ho) * Wo + wo0 + row) * 64 + 4 * col4, v);
-  }
+  });
 }
 
 // max pool on a P-format tensor ("f32s"): the pieces are joined (exact), compared, and the maximum's pieces stored

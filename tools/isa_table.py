@@ -3,11 +3,18 @@
 
     tools/isa_table.py OBJ_DIR               symbol | instructions | sha1
     tools/isa_table.py PARENT_DIR NOW_DIR    symbol | instructions parent | instructions now | sha1 parent | sha1 now | same
+    tools/isa_table.py --resources PARENT_DIR NOW_DIR    the same, then one line per differing symbol (below)
 
 For every .o: the fat binary section is dumped with llvm-objcopy, its gfx950 member unbundled with clang-offload-bundler
 and disassembled with llvm-objdump -d; addresses and encodings are stripped and the remaining instruction text is hashed
 per symbol.  With two directories the exit status is 1 if a symbol differs or the two sets of symbols differ: the check
 that a change of source text left every kernel's machine code as it was.
+
+--resources: for every symbol whose hash differs, the code object's metadata note (VGPR, AGPR and SGPR counts, LDS and scratch
+bytes, spill counts) and the counts of matrix, LDS, global / buffer memory and barrier instructions, parent -> now where
+they differ, and a verdict: "allocation only" when all of those are equal and the instruction count is within 1 % of the
+parent's (registers renamed, independent instructions reordered, a wait more or less), "DIFFERENT" otherwise.  The table in
+front of it and the exit status are the same with and without the option.
 """
 import hashlib
 import os
@@ -28,8 +35,33 @@ def tool(name):
     return path
 
 
-def kernels(obj):
-    """{symbol: (instructions, sha1[:12])} of the gfx950 member of one object; {} if it holds no device code."""
+META = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size",
+        "vgpr_spill_count", "sgpr_spill_count")
+CLASSES = (("mfma", r"v_mfma"), ("lds", r"ds_"), ("vmem", r"(global|buffer|flat|scratch)_"), ("barrier", r"s_barrier"))
+
+
+def metadata(co):
+    """{symbol: {field of META: int}} from the AMDGPU metadata note of a code object."""
+    text = subprocess.run([tool("llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+    out, cur = {}, None
+    for line in text.splitlines():
+        m = re.match(r"^(  - |    )\.(\w+):\s*(\S*)$", line)   # a kernel's own keys: its arguments are indented further
+        if not m:
+            continue
+        if m.group(1) == "  - ":
+            cur = {}
+        if cur is None:
+            continue
+        if m.group(2) == "name":
+            out[m.group(3)] = cur
+        elif m.group(2) in META:
+            cur[m.group(2)] = int(m.group(3))
+    return out
+
+
+def kernels(obj, res=None):
+    """{symbol: (instructions, sha1[:12])} of the gfx950 member of one object; {} if it holds no device code.
+    With a dict `res`: res[symbol] = the symbol's metadata fields and instruction class counts."""
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "gfx950.co")
         dump = subprocess.run([tool("llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj, os.path.join(tmp, "copy.o")],
@@ -41,11 +73,16 @@ def kernels(obj):
         if os.path.getsize(co) == 0:
             return {}
         text = subprocess.run([tool("llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
+        meta = metadata(co) if res is not None else {}
     out, sym, lines = {}, None, []
 
     def close():
         if sym is not None:
             out[sym] = (len(lines), hashlib.sha1("\n".join(lines).encode()).hexdigest()[:12])
+            if res is not None:
+                res[sym] = dict(meta.get(sym, {}))
+                for name, pat in CLASSES:
+                    res[sym][name] = sum(1 for ins in lines if re.match(pat, ins))
 
     for line in text.splitlines():
         head = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
@@ -64,7 +101,21 @@ def objects(d):
     return sorted(f for f in os.listdir(d) if f.endswith(".o"))
 
 
+def verdict(ia, ib, ra, rb):
+    """One --resources line of a symbol that is on both sides with different hashes."""
+    fields = META + tuple(name for name, _ in CLASSES)
+    missing = [f for f in fields if f not in ra or f not in rb]
+    moved = [f for f in fields if f not in missing and ra[f] != rb[f]]
+    ok = not missing and not moved and abs(ib - ia) * 100 <= ia
+    cells = ["%s %s" % (f, ra.get(f, "?")) if f not in moved and f not in missing else
+             "%s %s -> %s" % (f, ra.get(f, "?"), rb.get(f, "?")) for f in fields]
+    return "%s | instructions %+d (%+.2f %%) | %s" % ("allocation only" if ok else "DIFFERENT", ib - ia,
+                                                    100.0 * (ib - ia) / ia, " | ".join(cells))
+
+
 def main(argv):
+    resources = "--resources" in argv
+    argv = [a for a in argv if a != "--resources"]
     if len(argv) == 2:
         for o in objects(argv[1]):
             k = kernels(os.path.join(argv[1], o))
@@ -76,10 +127,11 @@ def main(argv):
         sys.exit(__doc__)
     a_dir, b_dir = argv[1], argv[2]
     names = sorted(set(objects(a_dir)) | set(objects(b_dir)))
-    rows, total, differing = [], 0, 0
+    rows, total, differing, detail = [], 0, 0, []
     for o in names:
-        a = kernels(os.path.join(a_dir, o)) if os.path.exists(os.path.join(a_dir, o)) else {}
-        b = kernels(os.path.join(b_dir, o)) if os.path.exists(os.path.join(b_dir, o)) else {}
+        ra, rb = ({}, {}) if resources else (None, None)
+        a = kernels(os.path.join(a_dir, o), ra) if os.path.exists(os.path.join(a_dir, o)) else {}
+        b = kernels(os.path.join(b_dir, o), rb) if os.path.exists(os.path.join(b_dir, o)) else {}
         rows.append("\n%s: %d symbols parent, %d now" % (o, len(a), len(b)))
         for s in sorted(set(a) | set(b)):
             ia, ha = a.get(s, ("-", "-"))
@@ -88,10 +140,16 @@ def main(argv):
             total += 1
             differing += not same
             rows.append("%s | %s | %s | %s | %s | %s" % (s, ia, ib, ha, hb, "yes" if same else "NO"))
+            if resources and not same:
+                detail.append("%s | %s" % (s, verdict(ia, ib, ra[s], rb[s]) if s in a and s in b else "DIFFERENT | on one side only"))
     print("%d objects, %d kernel symbols, %s" % (len(names), total, "every one identical" if not differing else
                                                   "%d DIFFERING or on one side only" % differing))
     print("symbol | instructions parent | instructions now | sha1 parent | sha1 now | same")
     print("\n".join(rows))
+    if resources:
+        print("\nresources of the %d differing symbols: verdict | instructions now - parent | metadata and instruction classes"
+              % len(detail))
+        print("\n".join(detail))
     return 1 if differing else 0
 
 
