@@ -167,9 +167,10 @@ constexpr int rootconv_kpad(int cin) { return (7 * rootconv_pitch(cin) + 3) & ~3
 constexpr int rootconv_ld(int cin) { return rootconv_kpad(cin) + 2; }                 // 2 x odd, like kConv1Ld
 // diagnostic record of the root and the head of the last network call (dvsg_debug_last_root_kernel): conv1 family (0
 // conv1_kernel, 1 conv1_f16_kernel, 2 conv1_f16_pair_kernel, 3 conv1_f16_march_kernel, 4 conv1_split_kernel, 5
-// conv1_x3_kernel, 6 rootconv_kernel: cin != 21), its template arguments NW, TO (0 float, 1 _Float16, 2 the P format:
-// rootconv_kernel only), SRC (-1 where the family has none; rootconv_kernel records NW = 4), the marching
-// kernel's bands and quads_per_band (else -1), the max pool kernel (0 maxpool_kernel<float>, 1 maxpool_kernel<_Float16>, 2
+// conv1_x3_kernel, 6 rootconv_kernel: cin != 21, 7 root_band_kernel), its template arguments NW, TO (0 float, 1 _Float16, 2
+// the P format: rootconv_kernel only), SRC (-1 where the family has none; rootconv_kernel records NW = 4, root_band_kernel
+// NW = 8 and TO = 0), the marching kernel's bands and quads_per_band or the band kernel's bands and (longest band's) row
+// pairs per band (else -1), the max pool kernel (0 maxpool_kernel<float>, 1 maxpool_kernel<_Float16>, 2
 // maxpool_h8_kernel, 3 maxpool_p_kernel), the average pool kernel (0 avgpool_partial_kernel<float>, 1 <_Float16>, 2
 // avgpool_partial_p_kernel) and the number of dense batch chunks.  Reset to -1 by forward(), written where launch_conv1,
 // launch_maxpool, launch_avgpool_partial and forward() issue the launches.  Host-only
@@ -204,6 +205,9 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *w
 // rootconv_kernel declares its LDS per launch (up to 140 KB at cin = 48): raises every instantiation's dynamic LDS limit.
 // Called once per handle by dvsg_locnet_create for cin != 21, outside any stream operation
 int prepare_rootconv();
+// root_band_kernel (float32, cin = 21, big unmasked launches) declares 142 656 bytes of LDS: raises its instantiations'
+// dynamic LDS limit.  Called once per handle by dvsg_locnet_create for cin == 21, outside any stream operation
+int prepare_root_band();
 
 // 3x3 stride-2 TF-SAME max pool (slim resnet root), C % 8 == 0.
 int launch_maxpool(int prec, const void *x, void *y, int B, int H, int W, int C, int Ho, int Wo, int pad_top,

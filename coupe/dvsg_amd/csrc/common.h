@@ -75,7 +75,8 @@ struct DebugOptions {
   int conv_variant = 0;        // 0 = auto, 1 = 4 waves, 2 = 8 waves, 3 = no split-K, 4 = 64-wide tiles only,
                                // 5 = no 256 x 128 float16 tiles, 6 = no stream-K tail (conv_gemm.hip)
   int conv1_variant = 0;       // 0 = auto; 1 = float32 kernel with 8 waves; 2 = float16 output from the float32 multiply;
-                               // 3 = float16, one output row per workgroup; 4 = never the marching kernel; 5 = always
+                               // 3 = float16, one output row per workgroup; 4 = never the marching kernel; 5 = always;
+                               // float32: 6 = always the band kernel (unmasked sources), 7 = always the one-row kernel
   int wide16_min_tiles = 128;  // float16 mode: 256 x 128 tiles from this many of them (a quarter of a round of 512 workgroups).
                                // Round 2 measured 256 (128 and below lost at batch 1-2 with the kernels of then); with packed
                                // weight stages, 128-byte activation rows and the 3x3 row reuse 128 is -0.5 % at batch 16, -4.5 %

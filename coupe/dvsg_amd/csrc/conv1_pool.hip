@@ -581,6 +581,239 @@ void conv1_kernel(const Conv1Src src, const float *__restrict__ wt1, const float
 }
 
 // ----------------------------------------------------------------------------------------
+// conv1 in exact float32 for big launches: one workgroup of 8 waves per CU owns a 128-pixel column tile and walks down a
+// BAND of output-row pairs (ho, ho + 1).  A wave is (row of the pair, pixel half, channel half) with two 32-pixel MFMA
+// blocks: conv1_kernel<4, float, SRC>'s wave, operands, instruction and order of summation -- kh ascending, steps
+// ascending, even taps into one chain and odd taps into the other, the chains joined once, then bias and ReLU -- so every
+// output element is that kernel's, bit for bit (tests/test_root_band.py).  What differs is what surrounds the MFMA loops:
+//   * step t = 0..6 of a pair is kernel row kh = t of BOTH rows: the upper row reads input row 2 ho + t - 3, the lower
+//     one input row 2 ho + t - 1.  Input row 2 ho - 3 + i (i = 0..8) is the lower row's operand at step i - 2 and the upper
+//     row's at step i: nine input rows and seven weight rows staged per pair where two one-row tiles stage fourteen of each;
+//   * three input-row slots (row i in slot i mod 3: step t reads rows t and t + 2, row t + 1 waits in the third) and two
+//     weight-row buffers: 3 x 21 952 + 2 x 38 400 = 142 656 bytes, one workgroup per CU.  Weight row t + 1 goes from its
+//     prefetch registers into the idle buffer in the middle of step t's MFMAs, behind no barrier of its own; input row
+//     t + 3 is fetched under step t's MFMAs and written into the slot step t frees, between the step's two barriers: 3
+//     ds_write_b128 per thread there where the one-row kernel writes 16;
+//   * the index set-up (Row::init depends on the column tile only) runs once per band, the next pair's first three rows and
+//     first weight row are requested before the pair's output leaves (as soon as the accumulators have given up their
+//     registers), and the epilogue is the shared one, a transpose tile per row in the two weight buffers.
+// A band's last pair may have no lower row (Ho odd): its waves multiply rows that Row::load clamps into the image and
+// nothing of theirs is stored.  Band `i` of a column tile holds ppb pairs if i < nbig, else ppb - 1 (launch_conv1).
+// ----------------------------------------------------------------------------------------
+constexpr int RB_NT = 512;
+constexpr int RB_IN4 = (C1_SEG_PAD / 4 + RB_NT - 1) / RB_NT;     // 3 groups of four elements per thread and input row
+constexpr int RB_WLOADS = (C1_WELEMS / 4 + RB_NT - 1) / RB_NT;   // 5 float4 per thread and weight row
+constexpr int RB_SLOTS = 3;
+constexpr size_t RB_LDS = sizeof(float) * (size_t)(2 * C1_WELEMS + RB_SLOTS * C1_SEG_PAD);   // 142 656 bytes
+static_assert(RB_LDS <= 160 * 1024, "the band kernel's LDS must fit a CU");
+
+template <int SRC>
+__global__ __launch_bounds__(RB_NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void root_band_kernel(const Conv1Src src, const float *__restrict__ wt1, const float *__restrict__ bias,
+                      float *__restrict__ y, int H, int W, int Ho, int Wo, int wtiles, int bands, int ppb, int nbig) {
+  constexpr int NT = RB_NT, MI = 2;
+  static_assert(C1_TILE * C1_LDC <= C1_WELEMS, "epilogue tile must fit in a weight buffer");
+  extern __shared__ __attribute__((aligned(16))) float rb_lds[];
+  float *const w_s = rb_lds;                      // [2][C1_WELEMS]
+  float *const in_s = rb_lds + 2 * C1_WELEMS;     // [RB_SLOTS][C1_SEG_PAD]
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
+  const int r = lane & 31, h = lane >> 5;
+
+  const Conv1Tile tile = conv1_tile(wtiles, bands);
+  const int b = tile.b, band = tile.ho, wo0 = tile.wo0;
+  const int pairs = (Ho + 1) / 2;
+  const int p0 = band * ppb - (band > nbig ? band - nbig : 0);
+  const int p1 = min(p0 + (band < nbig ? ppb : ppb - 1), pairs);
+  if (p0 >= p1) return;
+
+#ifdef DVSG_STAMPS
+  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const unsigned long long t_begin = C1_STAMP(), r_begin = __builtin_amdgcn_s_memrealtime();
+#endif
+  typedef typename Conv1RowSel<NT, RB_IN4, SRC>::type Row;
+  Row row;
+  row.init(src, tid, b, wo0, H, W, C1_SEG_PAD);
+  if constexpr (Row::kRing) {   // elements the scatter never writes (the zero tap's slot, the tail) must be finite
+    for (int e = tid; e < RB_SLOTS * C1_SEG_PAD; e += NT) in_s[e] = 0.f;
+    __syncthreads();
+  }
+  typename Row::Data rd[3];
+  floatx4 w_reg[RB_WLOADS];
+  auto load_w = [&](int kh) __attribute__((always_inline)) {
+    const floatx4 *wsrc = reinterpret_cast<const floatx4 *>(wt1 + (size_t)kh * C1_WELEMS);
+#pragma unroll
+    for (int i = 0; i < RB_WLOADS; ++i) {
+      const int q = tid + NT * i;
+      w_reg[i] = wsrc[q < C1_WELEMS / 4 ? q : 0];
+    }
+  };
+  auto put_w = [&](int i, float *dst) __attribute__((always_inline)) {
+    const int q = tid + NT * i;
+    if (q < C1_WELEMS / 4) reinterpret_cast<floatx4 *>(dst)[q] = w_reg[i];
+  };
+  auto put_row = [&](const typename Row::Data &d, float *slot) __attribute__((always_inline)) {
+    if constexpr (Row::kRing) {
+      row.scatter(d, [&](int e, float v) __attribute__((always_inline)) { slot[e] = v; });
+    } else {
+#pragma unroll
+      for (int i = 0; i < RB_IN4; ++i) {
+        const int q = tid + NT * i;
+        const floatx4 v = row.scaled(d, i);
+        if (q < C1_SEG_PAD / 4) reinterpret_cast<floatx4 *>(slot)[q] = v;
+      }
+    }
+  };
+  // the first three input rows and the first weight row of the pair whose upper row is ho_
+  auto load_first = [&](int ho_) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) row.load(rd[i], 2 * ho_ - 3 + i);
+    load_w(0);
+  };
+#ifdef DVSG_STAMPS
+  st[0] = C1_STAMP() - t_begin;
+#endif
+  load_first(2 * p0);
+
+  for (int p = p0; p < p1; ++p) {
+    const int ho = 2 * p;
+#ifdef DVSG_STAMPS
+    const unsigned long long f0 = C1_STAMP();
+#endif
+    // (the barrier that ends the pair before this one freed every slot and both weight buffers)
+#pragma unroll
+    for (int i = 0; i < RB_WLOADS; ++i) put_w(i, w_s);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      __builtin_amdgcn_sched_barrier(0);   // one row's scatter at a time: interleaved, a frame ring's three run out of registers
+      put_row(rd[i], in_s + i * C1_SEG_PAD);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    floatx16 acc[MI], acc2[MI];   // even and odd taps: see conv1_kernel
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[mi][q] = acc2[mi][q] = 0.f;
+#ifdef DVSG_STAMPS
+    const unsigned long long f1 = C1_STAMP();
+    __syncthreads();
+    st[2] += f1 - f0;
+    st[3] += C1_STAMP() - f1;
+#else
+    __syncthreads();
+#endif
+
+    int s_up = 0;   // slot of the upper row's operand: t mod 3
+    for (int t = 0; t < 7; ++t) {
+#ifdef DVSG_STAMPS
+      const unsigned long long s3 = C1_STAMP();
+#endif
+      if (t < 6) {
+        row.load(rd[0], 2 * ho + t);   // input row i = t + 3 of the pair
+        load_w(t + 1);
+      }
+#ifdef DVSG_STAMPS
+      st[4] += C1_STAMP() - s3;
+#endif
+      __builtin_amdgcn_sched_barrier(0);  // prefetch stays ahead of the MFMA loop
+      const int s_lo = s_up == 0 ? 2 : s_up - 1;   // (t + 2) mod 3
+      const float *a0 = in_s + (wr ? s_lo : s_up) * C1_SEG_PAD + 2 * kConv1Cin * (wm * 32 * MI + r) + 2 * h;
+      const float *bp = w_s + (t & 1) * C1_WELEMS + (wn * 32 + r) * kConv1Ld + 2 * h;
+      // kernel row t + 1 into the idle buffer, one store per request from the middle of the loop on.  (At t = 6 the
+      // registers still hold kernel row 6 and the idle buffer nothing anyone reads: the stores stay unconditional.)
+      float *w_next = w_s + ((t + 1) & 1) * C1_WELEMS;
+      // conv1_kernel's loop: the operands of step u + 1 are requested before the MFMAs of step u are issued
+      constexpr int STEPS = kConv1Kpad / 4, PAIRS = (STEPS + 1) / 2;   // two steps per request: one ds_read2_b64 per operand
+      constexpr int WPUT0 = PAIRS / 2;
+      float2 va[2][2][MI], vb[2][2];
+      auto read_pair = [&](int slot, int g) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if (2 * g + j >= STEPS) break;
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi)
+            va[slot][j][mi] = *reinterpret_cast<const float2 *>(a0 + mi * (2 * kConv1Cin * 32) + 4 * (2 * g + j));
+          vb[slot][j] = *reinterpret_cast<const float2 *>(bp + 4 * (2 * g + j));
+        }
+      };
+      read_pair(0, 0);
+#pragma unroll
+      for (int g = 0; g < PAIRS; ++g) {
+        if (g + 1 < PAIRS) read_pair((g + 1) & 1, g + 1);
+        if (g >= WPUT0 && g < WPUT0 + RB_WLOADS) put_w(g - WPUT0, w_next);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if (2 * g + j >= STEPS) break;
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) acc[mi] = mfma32(va[g & 1][j][mi].x, vb[g & 1][j].x, acc[mi]);
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) acc2[mi] = mfma32(va[g & 1][j][mi].y, vb[g & 1][j].y, acc2[mi]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (t < 6) {
+#ifdef DVSG_STAMPS  // (each stamp drains lgkmcnt: the phase times are upper bounds)
+        const unsigned long long s0 = C1_STAMP();
+        __syncthreads();
+        const unsigned long long s1 = C1_STAMP();
+        put_row(rd[0], in_s + s_up * C1_SEG_PAD);
+        const unsigned long long s2 = C1_STAMP();
+        __syncthreads();
+        st[1] += s1 - s0;
+        st[2] += s2 - s1;
+        st[3] += C1_STAMP() - s2;
+#else
+        __syncthreads();   // everyone is done with input row t
+        put_row(rd[0], in_s + s_up * C1_SEG_PAD);
+        __syncthreads();
+#endif
+      }
+      s_up = s_up == 2 ? 0 : s_up + 1;
+    }
+
+    // ---- epilogue: the next pair's first loads fly under it; one transpose tile per row in the (idle) weight buffers
+#ifdef DVSG_STAMPS
+    const unsigned long long e0 = C1_STAMP();
+#endif
+    __syncthreads();
+    float *Cs = w_s + wr * C1_WELEMS;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+      C1_TILE_PUT(Cs, wm * 32 * MI + mi * 32, wn * 32, acc[mi][q] + acc2[mi][q]);
+    __builtin_amdgcn_sched_barrier(0);   // (the accumulators are dead: their registers take the rows in flight)
+    if (p + 1 < p1) load_first(ho + 2);
+    // (the thread's place in the epilogue is derived here, per pair: held in registers across the band, the addresses and
+    // the bias that follow from it push the frame ring's instantiations past 256 registers)
+    int tid_e = tid;
+    asm volatile("" : "+v"(tid_e));
+    const float4 b4 = conv1_tile_bias(bias, tid_e);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (ho + j >= Ho) break;   // a last pair of one row
+      float *yrow = y + (((size_t)b * Ho + ho + j) * Wo + wo0) * 64 + 4 * (tid_e & 15);
+      conv1_tile_out<NT / 16>(w_s + j * C1_WELEMS, b4, tid_e, wo0, Wo,
+                              [&](int row_, float4 v) __attribute__((always_inline)) { store4(yrow + (size_t)row_ * 64, v); });
+    }
+    __syncthreads();
+#ifdef DVSG_STAMPS
+    st[5] += C1_STAMP() - e0;
+#endif
+  }
+#ifdef DVSG_STAMPS
+  if (tid == 0 && blockIdx.x < 65536) {
+    unsigned long long *o = g_c1_stamps + (size_t)blockIdx.x * 8;
+    o[0] = st[0]; o[1] = st[1]; o[2] = st[2]; o[3] = st[3]; o[4] = st[4]; o[5] = st[5];
+    o[6] = C1_STAMP() - t_begin;
+    o[7] = __builtin_amdgcn_s_memrealtime() - r_begin;
+  }
+#endif
+}
+
+// ----------------------------------------------------------------------------------------
 // The root conv for any other window length: 7x7 / stride 2 / pad 3, cin = 3 S -> 64, 1 <= S <= kRootMaxFrames, cin a
 // kernel ARGUMENT.  It is conv1_kernel<4, float, SRC> generalised: the same tile (128 output pixels of one output row x 64
 // channels, 4 waves as 2 x 2, two 32-pixel MFMA blocks per wave), the same exact float32 products on
@@ -1866,6 +2099,33 @@ int march_bands(int B, int Ho, int wtiles, int *quads_per_band) {
   return 0;
 }
 
+// Bands of root_band_kernel, one workgroup per CU: among 3 .. 6 rounds of the 256 CUs the number of bands per column tile
+// and image whose workgroups fill their last round best (the fewest rounds on a tie), with at least 3 x 256 workgroups and
+// at least 4 row pairs per band -- B = 16 at 1280 x 720: 80 column tiles x 16 bands = 1280 workgroups, five rounds exactly.
+// 0 = do not use the kernel.  A function of (B, Ho, wtiles) alone: every source of one shape takes the same kernel.
+// *pairs_per_band is the longest band, *nbig the number of bands of that length (the others hold one pair less).
+int root_bands(int B, int Ho, int wtiles, int *pairs_per_band, int *nbig) {
+  const int pairs = (Ho + 1) / 2;
+  const long cols = (long)B * wtiles;
+  int best = 0;
+  double best_fill = 0.0;
+  for (int rounds = 3; rounds <= 6; ++rounds) {
+    const long fit = 256L * rounds / cols, bands = fit < pairs / 4 ? fit : pairs / 4;
+    if (bands < 1 || cols * bands < 3 * 256) continue;
+    const double fill = (double)(cols * bands) / (256.0 * rounds);
+    if (fill > best_fill) {
+      best_fill = fill;
+      best = (int)bands;
+    }
+  }
+  if (best > 0) {
+    const int ppb = (pairs + best - 1) / best;
+    if (pairs_per_band) *pairs_per_band = ppb;
+    if (nbig) *nbig = pairs - best * (ppb - 1);
+  }
+  return best;
+}
+
 // Run-time SRC -> compile-time constant: calls f(std::integral_constant<int, SRC>) for the legal value equal to `src`: every
 // Conv1SrcKind, aligned or not, unmasked, and with MASKED_TOO the same six with kSrcMasked.  False, and no call, for any other.
 template <int S>
@@ -1981,7 +2241,24 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *w
     record_conv1_kernel(0, 4, 1, 0);
     hipLaunchKernelGGL((conv1_kernel<4, _Float16, 0>), grid, dim3(256), 0, s, src, wt1, bias, static_cast<_Float16 *>(y), H, W,
                        Ho, Wo, wtiles);
-  } else if (variant != 0 && src_kind == kSrcWindow && !src.mask) {
+  } else if (!src.mask && (variant == 6 || (variant == 0 && root_bands(B, Ho, wtiles, nullptr, nullptr) > 0))) {
+    // big float32 launches: row pairs in bands, one workgroup per CU (root_band_kernel); a masked source takes the one-row
+    // kernel below, like the float16 marching kernel's.  (conv1_variant 6 forces it at any size, bands of <= 3 pairs: the
+    // parity tests run it on small frames; 7 never takes it)
+    int ppb = 0, nbig = 0;
+    int bands = root_bands(B, Ho, wtiles, &ppb, &nbig);
+    if (variant == 6) {
+      ppb = 3;
+      bands = nbig = ((Ho + 1) / 2 + ppb - 1) / ppb;
+    }
+    const dim3 bgrid((unsigned)((long)wtiles * bands * B));
+    legal = with_conv1_src<false>(SRC, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      record_conv1_kernel(7, 8, 0, S, bands, ppb);
+      hipLaunchKernelGGL((root_band_kernel<S>), bgrid, dim3(RB_NT), RB_LDS, s, src, wt1, bias, static_cast<float *>(y), H, W, Ho,
+                         Wo, wtiles, bands, ppb, nbig);
+    });
+  } else if (variant != 0 && variant != 7 && src_kind == kSrcWindow && !src.mask) {
     record_conv1_kernel(0, 8, 0, 0);
     hipLaunchKernelGGL((conv1_kernel<8, float, 0>), grid, dim3(512), 0, s, src, wt1, bias, static_cast<float *>(y), H, W, Ho,
                        Wo, wtiles);
@@ -2010,6 +2287,19 @@ int prepare_rootconv() {
       raise(reinterpret_cast<const void *>(&rootconv_kernel<float, S>));
       raise(reinterpret_cast<const void *>(&rootconv_kernel<_Float16, S>));
       raise(reinterpret_cast<const void *>(&rootconv_kernel<PPieces, S>));
+    });
+  DVSG_HIP(err);
+  return DVSG_OK;
+}
+
+int prepare_root_band() {
+  hipError_t err = hipSuccess;
+  for (int src = 0; src < 16; ++src)
+    with_conv1_src<false>(src, [&](auto src_c) {
+      constexpr int S = decltype(src_c)::value;
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&root_band_kernel<S>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)RB_LDS);
+      if (err == hipSuccess) err = e;
     });
   DVSG_HIP(err);
   return DVSG_OK;

@@ -865,7 +865,7 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
   };
   net->conv1 = ConvLayer{7, c_in, 64, 2, true};
   if ((rc = make_conv1(net, m, rn + "/conv1", &net->conv1))) return bail(rc);
-  if (c_in != kConv1Cin && (rc = prepare_rootconv())) return bail(rc);
+  if ((rc = c_in != kConv1Cin ? prepare_rootconv() : prepare_root_band())) return bail(rc);
   int depth_in = 64;
   for (const BlockSpec &bs : kBlocks) {
     for (int u = 1; u <= bs.units; ++u) {

@@ -624,7 +624,9 @@ int dvsg_conv3x3_1x1_f32(const float *x, const float *wt2, const float *bias2, c
                          void *stream);
 
 /* Diagnostic A/B switches for kernel experiments, process-global; an unknown name is DVSG_ERR_INVALID_ARG.  The 17
- * names and their defaults: "conv_variant" 0, "conv1_variant" 0 (0 = the launch policy's own choice of kernel), "fuse_conv" 1,
+ * names and their defaults: "conv_variant" 0, "conv1_variant" 0 (0 = the launch policy's own choice of kernel; in
+ * float32, 6 = root_band_kernel -- row pairs in bands, one workgroup per CU -- at any size for unmasked sources, in bands of at
+ * most 3 pairs, and 7 = the one-row conv1_kernel at any size: the two are equal bit for bit), "fuse_conv" 1,
  * "fuse_shortcut" 1, "concat_sc" 1 (block 1's conv2 + conv3 in one kernel, its shortcut conv in that kernel too, the
  * shortcut + conv1 of blocks 2-4's opening units as one launch; 0 selects the separate launches), "x3_conv1" 1, "x3_fuse" 3
  * (the f32x3 precision's own conv1 kernel and block-1 fusion; 0 the float32 kernel / never fused), "f16_split" 1,
@@ -652,9 +654,11 @@ int dvsg_debug_last_conv_kernel(int *fields, int n);
 /* Which root and head kernels the last network call (dvsg_locnet_forward_*, dvsg_stabilize_*, their ring / masked / tap
  * forms) ran, recorded on the host when they were launched; no synchronisation.  fields (n >= 9): conv1 family (0 conv1_kernel,
  * 1 conv1_f16_kernel, 2 conv1_f16_pair_kernel, 3 conv1_f16_march_kernel, 4 conv1_split_kernel, 5 conv1_x3_kernel, 6
- * rootconv_kernel: every launch of a handle whose c_in is not 21, recorded with NW = 4), its template
+ * rootconv_kernel: every launch of a handle whose c_in is not 21, recorded with NW = 4, 7 root_band_kernel: big unmasked
+ * float32 launches, recorded with NW = 8 and TO = 0), its template
  * arguments NW, TO (0 float, 1 _Float16, 2 the float16 pieces of "f32s": family 6 only) and SRC (2 x source kind + rows on the 16-byte grid + 8 x masked), -1 where the family
- * has none; the marching kernel's bands and quads_per_band (else -1); the max pool kernel (0 maxpool_kernel<float>, 1
+ * has none; the marching kernel's bands and quads_per_band, or the band kernel's bands and the row pairs of its longest band
+ * (else -1); the max pool kernel (0 maxpool_kernel<float>, 1
  * maxpool_kernel<_Float16>, 2 maxpool_h8_kernel, 3 maxpool_p_kernel); the average pool kernel (0 avgpool_partial_kernel<float>,
  * 1 avgpool_partial_kernel<_Float16>, 2 avgpool_partial_p_kernel); the number of dense batch chunks of <= 16 samples.  A
  * field is -1 when the call stopped (parity tap) before that launch, or none was made. */

@@ -2,7 +2,7 @@
 """One line per conv1 case: the launch record and the sha1 of the output bytes, for comparing two builds of the library.
 
 The cases are the tests' own tables -- CASES and MARCH_CASES of tests/test_root_head_f64.py (every instantiation of the six
-S = 7 kernels) and CASES of tests/test_rootconv_f64.py (every rootconv_kernel instantiation, S = 1, 2, 5, 8, 16) -- with the
+S = 7 kernels), BAND_CASES of tests/test_root_band.py (root_band_kernel) and CASES of tests/test_rootconv_f64.py (every rootconv_kernel instantiation, S = 1, 2, 5, 8, 16) -- with the
 tests' seeded inputs; each is one tap-0 network call.  Run it once per library in a fresh process,
 
     DVSG_AMD_LIB=parent/libdvsg_amd.so python tools/conv1_digest.py > parent.txt
@@ -21,6 +21,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_root_head_f64 as rh                              # noqa: E402
 import test_rootconv_f64 as rc                               # noqa: E402
+import test_root_band as rb                                  # noqa: E402
 from coupe.dvsg_amd.weights import make_synthetic_weights    # noqa: E402
 
 
@@ -41,6 +42,17 @@ def main():
         try:
             rh._set_variant(variant)
             y, rec = rh.run_net(net, prec, kind, masked, src, tab, mask, n, B, H, W, 0, B * Ho * Wo * 64)
+        finally:
+            rh._set_variant(0)
+        line(rh.case_id(case), rec, y)
+    for shape, off, kind, inputs in rb.BAND_CASES:      # root_band_kernel, forced at the parity tests' small shapes
+        case = ("f32", 6, kind, 0, off, shape, inputs, None)
+        net, _ = rh._net(weights, False)
+        src, tab, mask, n, _, _ = rh.place_inputs(case, dev)
+        (B, H, W), Ho, Wo = shape, (shape[1] - 1) // 2 + 1, (shape[2] - 1) // 2 + 1
+        try:
+            rh._set_variant(6)
+            y, rec = rh.run_net(net, "f32", kind, 0, src, tab, None, n, B, H, W, 0, B * Ho * Wo * 64)
         finally:
             rh._set_variant(0)
         line(rh.case_id(case), rec, y)

@@ -141,7 +141,10 @@ def main(argv):
             differing += not same
             rows.append("%s | %s | %s | %s | %s | %s" % (s, ia, ib, ha, hb, "yes" if same else "NO"))
             if resources and not same:
-                detail.append("%s | %s" % (s, verdict(ia, ib, ra[s], rb[s]) if s in a and s in b else "DIFFERENT | on one side only"))
+                one = ra.get(s) or rb.get(s) or {}
+                detail.append("%s | %s" % (s, verdict(ia, ib, ra[s], rb[s]) if s in a and s in b else
+                                           "DIFFERENT | on one side only (%s) | %s" % (
+                                               "parent" if s in a else "now", " | ".join("%s %s" % kv for kv in one.items()))))
     print("%d objects, %d kernel symbols, %s" % (len(names), total, "every one identical" if not differing else
                                                   "%d DIFFERING or on one side only" % differing))
     print("symbol | instructions parent | instructions now | sha1 parent | sha1 now | same")
