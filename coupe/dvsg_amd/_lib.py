@@ -33,6 +33,8 @@ SIGNATURES = {
                            ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_vp)],
     "dvsg_locnet_destroy": [_vp],
     "dvsg_locnet_in_channels": [_vp],
+    "dvsg_locnet_view_create": [_vp, _i, ctypes.POINTER(_vp)],
+    "dvsg_locnet_render_filter": [_vp],     # returns the filter (DVSG_RENDER_*), not a status
     "dvsg_locnet_workspace_bytes": [_vp, _i, _i, _i, ctypes.POINTER(ctypes.c_size_t)],
     "dvsg_locnet_forward_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp],
     "dvsg_locnet_forward_tap_f32": [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t,

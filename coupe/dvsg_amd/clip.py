@@ -250,7 +250,8 @@ def _check_crop(crop):
 
 
 def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side=False, channel_order="rgb",
-                   as_uint8=False, source_res=False, crop=None, crop_margin=None, crop_min=0.5, crop_info=None):
+                   as_uint8=False, source_res=False, crop=None, crop_margin=None, crop_min=0.5, crop_info=None,
+                   render_filter="bilinear"):
     """eval.py:76-124 for one clip, entirely on the device.
 
     frames: [N,h0,w0,3], NumPy or torch.
@@ -275,6 +276,9 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     source_res=True (uint8 frames only): the outputs are at the frames' own size [N,h0,w0,3] (side [N,h0,2 w0,3], the
     unstable half the source bytes): after the loop, each frame's F_t warps its source frame (`dvsg_tps_render_u8`, in
     launches of at most RENDER_BATCH_BYTES of output).  The loop itself is unchanged.
+    render_filter="bicubic" (source_res only, else ValueError) renders them with the bicubic filter of a view
+    (`LocNet.view`: 16 taps, bytes rounded to nearest; include/dvsg_amd.h, "Views and the render filter"); the default
+    "bilinear" is sampler A.  F_t, the pool and the crop's zoom do not depend on it.
 
     crop: every stabilised frame has a black border wherever sampler A's taps leave the frame (at F_t = 0 already its last
     row and column).  None (default) returns the frames as the reference does.  "auto" or a zoom z in (0, 1] renders them
@@ -289,6 +293,8 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     crop = _check_crop(crop)
     from . import _lib
     from ._tensor import device, ptr, stream
+    from .networks import check_render_filter
+    check_render_filter(render_filter, bool(source_res))
     if channel_order not in ("rgb", "bgr"):
         raise ValueError("channel_order must be 'rgb' or 'bgr'")
     if model.locnet is None:
@@ -347,7 +353,7 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
         for b0 in range(0, N, batch):
             b1 = min(N, b0 + batch)
             render_source_into(model, fr[b0:b1], F[b0:b1], T, flip, out[b0:b1], side[b0:b1] if side is not None else None,
-                               zoom[b0:b1] if zoom is not None else None)
+                               zoom[b0:b1] if zoom is not None else None, render_filter)
         if host:
             out = out.cpu().numpy()
             side = side.cpu().numpy() if side is not None else None
@@ -394,14 +400,16 @@ def _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info):
     return zoom, T
 
 
-def render_source_into(model, src, F, T, flip, out, side=None, zoom=None):
+def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render_filter="bilinear"):
     """`dvsg_tps_render_u8` for the uint8 frames src [n,H0,W0,3] (device) and their F_t rows F [n,25,2]: the stabilised
     frames at source size into `out` [n,H0,W0,3] (float32, or uint8: np.uint8(x * 255.) in the channel order of src)
     and, if given, `side` [n,H0,2 W0,3] uint8 = (source bytes | uint8 render).  T [n,2,28] receives the TPS
     coefficients.  One render launch; a uint8 `out` is copied into the right half of `side`.  zoom float32 [n] (device):
-    `dvsg_tps_render_zoom_u8`, the render on the grid scaled by zoom[i] about its centre."""
+    `dvsg_tps_render_zoom_u8`, the render on the grid scaled by zoom[i] about its centre.  render_filter: the filter of the
+    handle the render is given (`LocNet.view`)."""
     from . import _lib
     from ._tensor import ptr, stream
+    net = model.locnet.view(render_filter)
     n, H0, W0 = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
     if side is not None:
         side[:, :, :W0] = src   # np.uint8(v / 255. * 255.) == v for every byte: the unstable half is the source
@@ -410,10 +418,10 @@ def render_source_into(model, src, F, T, flip, out, side=None, zoom=None):
     else:                       # one launch writes the float32 render and the right half of side
         f32, u8, u8_W, u8_x0 = out, side, 2 * W0, W0
     if zoom is not None:
-        _lib.call("dvsg_tps_render_zoom_u8", model.locnet.handle, ptr(F), ptr(src), n, H0, W0, flip, ptr(zoom), ptr(T), ptr(f32),
+        _lib.call("dvsg_tps_render_zoom_u8", net, ptr(F), ptr(src), n, H0, W0, flip, ptr(zoom), ptr(T), ptr(f32),
                   ptr(u8), u8_W, u8_x0, stream())
     else:
-        _lib.call("dvsg_tps_render_u8", model.locnet.handle, ptr(F), ptr(src), n, H0, W0, flip, ptr(T), ptr(f32), ptr(u8),
+        _lib.call("dvsg_tps_render_u8", net, ptr(F), ptr(src), n, H0, W0, flip, ptr(T), ptr(f32), ptr(u8),
                   u8_W, u8_x0, stream())
     if side is not None and out.dtype == torch.uint8:
         side[:, :, W0:] = out

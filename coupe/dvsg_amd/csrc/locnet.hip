@@ -2,6 +2,7 @@
 // (model.py:98-123): checkpoint ingestion (BatchNorm folding, weight re-layout for the MFMA
 // fragment scheme of conv_gemm.hip / conv1_pool.hip, float16 copies), workspace planning and the
 // launch sequence for both storage precisions.
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -88,7 +89,16 @@ struct dvsg_locnet {
   std::vector<double> calib_mu = std::vector<double>((size_t)48 * 2048, 1.0);
   double calib_rows[48] = {0};
   std::vector<void *> allocs;
+  // A VIEW (dvsg_locnet_view_create) is one of these with nothing in it but `parent` and its own render filter: every entry
+  // point reads the network and the TPS constants through base() at call time, so a later calibration of the parent is seen
+  // through its views.  n_views: the live views of a parent, which dvsg_locnet_destroy refuses to pull the network from under.
+  const dvsg_locnet *parent = nullptr;
+  int render_filter = DVSG_RENDER_BILINEAR;
+  mutable std::atomic<int> n_views{0};
 };
+
+// the handle that owns the network `net` shows: itself, or a view's parent
+static inline const dvsg_locnet *base(const dvsg_locnet *net) { return net && net->parent ? net->parent : net; }
 
 namespace dvsg {
 namespace {
@@ -480,6 +490,7 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
   const Workspace ws = plan(static_cast<char *>(workspace), B, H, W);
   if (ws.total > workspace_bytes)
     return fail(DVSG_ERR_WORKSPACE, "locnet forward: workspace %zu bytes < required %zu", workspace_bytes, ws.total);
+  net = base(net);   // a view runs its parent's network; the handle is first read here, behind every check
   const Dims d = root_dims(H, W);
   // f32x3: float32 tensors throughout; conv1, the pools, block 1's fused kernel and the head are the float32 kernels
   // themselves, the conv GEMMs multiply bfloat16 pieces (run_conv)
@@ -667,8 +678,9 @@ int stabilize_from(const char *fn, const dvsg_locnet *net, int prec, const Conv1
     return rc;
   // model.py:120: stn(u_t, V_src, F_t, [h, w]) with V_src tiled over the batch (:111); float32
   MarkerRange mr("dvsg/tps");
+  net = base(net);
   if (int rc = tps_apply_impl(net->winv, net->v_src, F, 1, B, 25, ws.T, stream)) return rc;
-  return warp(ws.T);
+  return warp(net, ws.T);
 }
 
 int stabilize(const dvsg_locnet *net, int prec, const float *patches_t, const float *u_t, const float *mask, int B, int H,
@@ -679,7 +691,7 @@ int stabilize(const dvsg_locnet *net, int prec, const float *patches_t, const fl
   Conv1Src src{patches_t, nullptr, 0};
   src.mask = mask;   // eval_train.py:43-45: the CNN sees patches * mask, the warp below the unmasked u_t
   return stabilize_from("dvsg_stabilize", net, prec, src, kSrcWindow, B, H, W, F_t, workspace, workspace_bytes, stream,
-                        [&](const float *T) {
+                        [&](const dvsg_locnet *net, const float *T) {
                           return tps_warp_impl(u_t, net->v_src, 0, T, B, H, W, 3, 25, H, W, s_t_pred, x_s, y_s, stream);
                         });
 }
@@ -695,10 +707,10 @@ int stabilize_ring(const dvsg_locnet *net, int prec, const void *pool, int pool_
   DVSG_REQUIRE(B > 0 && B <= 65535 && n_pool > 0, "dvsg_stabilize_ring: B=%d n_pool=%d out of range", B, n_pool);
   Conv1Src src{pool, table, n_pool};
   src.mask = mask;
-  const int S = net->c_in / 3;
   return stabilize_from("dvsg_stabilize_ring", net, prec, src,
                         pool_is_u8 ? kSrcRingU8 : kSrcRingF32, B, H, W, F_t, workspace, workspace_bytes, stream,
-                        [&](const float *T) {
+                        [&](const dvsg_locnet *net, const float *T) {
+                          const int S = net->c_in / 3;
                           return tps_warp_ring_impl(pool, pool_is_u8, n_pool, table + (S - 1), S, net->v_src, 0, T, B, H, W, 25,
                                                     s_t_pred, x_s, y_s, stream, out_slots);
                         });
@@ -949,12 +961,37 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
 
 int dvsg_locnet_destroy(dvsg_locnet_t *net) {
   if (!net) return DVSG_OK;
+  if (net->parent) {   // a view owns nothing
+    net->parent->n_views.fetch_sub(1);
+    delete net;
+    return DVSG_OK;
+  }
+  const int views = net->n_views.load();
+  DVSG_REQUIRE(views == 0, "dvsg_locnet_destroy: the handle still has %d view(s); destroy them first", views);
   for (void *p : net->allocs) (void)hipFree(p);
   delete net;
   return DVSG_OK;
 }
 
-int dvsg_locnet_in_channels(const dvsg_locnet_t *net) { return net ? net->c_in : 0; }
+int dvsg_locnet_view_create(const dvsg_locnet_t *net, int render_filter, dvsg_locnet_t **view) {
+  DVSG_REQUIRE(net, "dvsg_locnet_view_create: NULL net");
+  DVSG_REQUIRE(view, "dvsg_locnet_view_create: NULL view");
+  *view = nullptr;
+  DVSG_REQUIRE(render_filter == DVSG_RENDER_BILINEAR || render_filter == DVSG_RENDER_BICUBIC,
+               "dvsg_locnet_view_create: render_filter=%d is neither DVSG_RENDER_BILINEAR (0) nor DVSG_RENDER_BICUBIC (1)",
+               render_filter);
+  dvsg_locnet *v = new dvsg_locnet();
+  v->calib_mu = std::vector<double>();   // (a view keeps no calibration record of its own)
+  v->parent = base(net);                 // a view of a view is a view of the parent
+  v->render_filter = render_filter;
+  v->parent->n_views.fetch_add(1);
+  *view = v;
+  return DVSG_OK;
+}
+
+int dvsg_locnet_render_filter(const dvsg_locnet_t *net) { return net ? net->render_filter : DVSG_RENDER_BILINEAR; }
+
+int dvsg_locnet_in_channels(const dvsg_locnet_t *net) { return net ? base(net)->c_in : 0; }
 
 int dvsg_locnet_workspace_bytes(const dvsg_locnet_t *net, int B, int H, int W, size_t *bytes) {
   DVSG_REQUIRE(net && bytes, "dvsg_locnet_workspace_bytes: NULL pointer");
@@ -1207,6 +1244,7 @@ static int calibrate_f16(dvsg_locnet *net, const float *patches, int B, int H, i
 int dvsg_locnet_calibrate_f16(dvsg_locnet_t *net, const float *patches, int B, int H, int W, void *workspace,
                               size_t workspace_bytes, void *stream) {
   DVSG_REQUIRE(net && workspace, "dvsg_locnet_calibrate_f16: NULL pointer");
+  DVSG_REQUIRE(!net->parent, "dvsg_locnet_calibrate_f16: net is a view; calibrate its parent");
   if (!patches) {   // undo: round-to-nearest plain copies, pairs everywhere
     net->f16_pair_mask = 0xFFFF;
     return calibrate_f16(net, nullptr, 0, 0, 0, 0, workspace, workspace_bytes, as_stream(stream));
@@ -1220,11 +1258,13 @@ int dvsg_locnet_calibrate_f16(dvsg_locnet_t *net, const float *patches, int B, i
 int dvsg_debug_calibrate_f16_weights(dvsg_locnet_t *net, const float *patches, int B, int H, int W, int mode, void *workspace,
                                      size_t workspace_bytes, void *stream) {
   DVSG_REQUIRE(net && patches && workspace && mode >= 0 && mode <= 2, "dvsg_debug_calibrate_f16_weights: bad arguments");
+  DVSG_REQUIRE(!net->parent, "dvsg_debug_calibrate_f16_weights: net is a view; calibrate its parent");
   return calibrate_f16(net, patches, B, H, W, mode, workspace, workspace_bytes, as_stream(stream));
 }
 
 int dvsg_debug_calibration_means(const dvsg_locnet_t *net, double *means, double *rows) {
   DVSG_REQUIRE(net && means && rows, "dvsg_debug_calibration_means: NULL pointer");
+  net = base(net);
   std::copy(net->calib_mu.begin(), net->calib_mu.end(), means);
   std::copy(net->calib_rows, net->calib_rows + 48, rows);
   return DVSG_OK;
@@ -1232,6 +1272,7 @@ int dvsg_debug_calibration_means(const dvsg_locnet_t *net, double *means, double
 
 int dvsg_debug_plain_weights_f16(const dvsg_locnet_t *net, int unit, int kind, void *w16, size_t w16_bytes, int *dims) {
   DVSG_REQUIRE(net && dims, "dvsg_debug_plain_weights_f16: NULL pointer");
+  net = base(net);
   DVSG_REQUIRE(unit >= 0 && unit < (int)net->units.size(), "dvsg_debug_plain_weights_f16: unit %d outside 0..%d", unit,
                (int)net->units.size() - 1);
   DVSG_REQUIRE(kind >= kKindC1 && kind <= kKindSc, "dvsg_debug_plain_weights_f16: kind %d outside 0..3", kind);
@@ -1306,8 +1347,8 @@ int dvsg_stabilize_ring_inplace_f32(const dvsg_locnet_t *net, int precision, flo
 int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
                        int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_u8: NULL net");
-  return tps_render_impl(net->winv, net->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8, u8_W,
-                         u8_x0, stream);
+  return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
+                         u8_W, u8_x0, stream, nullptr, net->render_filter);
 }
 
 // dvsg_tps_render_u8 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_u8 itself)
@@ -1315,8 +1356,8 @@ int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const ui
                             int channel_flip, const float *zoom, float *T, float *out_f32, uint8_t *out_u8, int u8_W,
                             int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_zoom_u8: NULL net");
-  return tps_render_impl(net->winv, net->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8, u8_W,
-                         u8_x0, stream, zoom);
+  return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
+                         u8_W, u8_x0, stream, zoom, net->render_filter);
 }
 
 // dvsg_tps_render_u8 for NV12 frames (nv12.hip): the same T, then both planes warped at their own sizes in one launch.
@@ -1327,8 +1368,8 @@ int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8
   DVSG_REQUIRE(net, "dvsg_tps_render_nv12: NULL net");
   if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride))
     return rc;
-  return tps_render_nv12_impl(net->winv, net->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv, out_pitch,
-                              out_frame_stride, stream);
+  return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
+                              out_pitch, out_frame_stride, stream, nullptr, net->render_filter);
 }
 
 // dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
@@ -1339,14 +1380,15 @@ int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const 
   if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
                                      "dvsg_tps_render_zoom_nv12"))
     return rc;
-  return tps_render_nv12_impl(net->winv, net->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv, out_pitch,
-                              out_frame_stride, stream, zoom);
+  return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
+                              out_pitch, out_frame_stride, stream, zoom, net->render_filter);
 }
 
 // T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)
 int dvsg_tps_coefficients_f32(const dvsg_locnet_t *net, const float *F_t, int n, float *T, void *stream) {
   DVSG_REQUIRE(net && F_t && T, "dvsg_tps_coefficients_f32: NULL pointer");
   DVSG_REQUIRE(n >= 1, "dvsg_tps_coefficients_f32: n=%d must be >= 1", n);
+  net = base(net);
   return tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream);
 }
 
@@ -1364,6 +1406,7 @@ int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const 
   if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || workspace_bytes < need)
     return fail(DVSG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed, 8-byte aligned (dvsg_tps_coverage_workspace_bytes)",
                 fn, workspace_bytes, need);
+  net = base(net);
   if (int rc = tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream)) return rc;
   return tps_coverage_impl(fn, net->v_src, 0, T, zoom, n, 25, src_H, src_W, out_h, out_w, n_border, key_min, workspace,
                            workspace_bytes, stream);

@@ -1,6 +1,8 @@
 // The body of tps_warp_kernel and tps_warp_zoom_kernel (warp_kernels.hip), included inside both.  The including kernel
-// declares the parameters documented there and `constexpr bool kZoom`; names it has no parameter for (zoom; u_index,
-// u_stride, n_pool, out_index) it declares as constants.
+// declares the parameters documented there, `constexpr bool kZoom` and `constexpr bool kCubic`; names it has no parameter for
+// (zoom; u_index, u_stride, n_pool, out_index) it declares as constants.  kCubic (tps_render_cubic_kernel: uint8 RGB in,
+// the uint8 output form) swaps what follows the map -- sampler A's four taps -- for the bicubic filter of warp_device.h; the
+// map, the thread layout and the output addresses are this one text's.
   constexpr bool kU8Out = std::is_same<TO, uint8_t>::value;
   static_assert(!kU8Out || (C == 3 && std::is_same<TU, uint8_t>::value), "the uint8 output form reads uint8 RGB frames");
   __shared__ float4 sp[64];      // {px, py, T[0][3+k], T[1][3+k]}
@@ -61,6 +63,28 @@
   for (int k = 0; k < P; ++k) tps_basis_point(sp[k], sdy[k], x_t, xs2, ys2);
   const float xs[4] = {xs2[0].x, xs2[0].y, xs2[1].x, xs2[1].y};
   const float ys[4] = {ys2[0].x, ys2[0].y, ys2[1].x, ys2[1].y};
+  if constexpr (kCubic) {
+    if (!out && !out_rgb) return;
+    CubicTaps<3> ct[4];
+    cubic_load_rows<3>(img, (size_t)W * 3, H, W, out_h - i0, xs, ys, ct);  // all 16 row loads in flight
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = i0 + r;
+      if (i >= out_h) break;
+      float v[3];
+      cubic_blend<3, false>(ct[r], v);
+      if (out_rgb) {
+        const float rgb[3] = {v[flip ? 2 : 0], v[1], v[flip ? 0 : 2]};
+        store_pix<3>(out_rgb, (out_frame * out_h + i) * out_w + j, 3, rgb);
+      }
+      if (out) {
+        uint8_t *d = out + ((out_frame * out_h + i) * out_row + out_x0 + j) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = cubic_u8(v[c], 0.5);
+      }
+    }
+    return;
+  }
   TapsA<C> taps[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {

@@ -124,6 +124,151 @@ __device__ __forceinline__ void sample_a_blend(const TapsA<C> &t, int Cn, float 
   }
 }
 
+// ----------------------------------------------------------------------------------------
+// The bicubic filter of the source-size renders (a view with DVSG_RENDER_BICUBIC): sampler A's coordinates and validity,
+// OpenCV's INTER_CUBIC weights (A = -0.75), 4 x 4 taps with edge-replicated indices, rows blended first.  Every operation
+// is a separately rounded float32 one in the order the header states; tests/bicubic_ref.py restates it in NumPy.
+// A plane is ph x pw samples of C bytes whose rows are `pitch` bytes apart.
+//
+// Tap fetch: the 4 taps of a row are 4 C contiguous bytes, so a row is ONE load of C dwords at byte granularity (gfx950
+// serves a global load at any alignment) instead of 4 C byte loads: 16 loads of 4 / 8 / 12 bytes per thread and 4 rows, C
+// packed registers each -- 64 taps in flight in 16 C VGPRs.  The window starts at column clamp(x0 - 1, 0, pw - 4), so it
+// lies wholly inside the row's pw C used bytes wherever the row has 4 samples; at the two edges (x0 = 0, x0 = pw - 2: the
+// window is one column off the taps) the replicated taps are picked out of it in registers (CubicTaps::d).  A plane with
+// pw < 4 has no such window and takes one byte load per tap component, column indices clamped: the same packed layout.
+// No load touches a byte outside the row's pw C used bytes.  DVSG_CUBIC_BYTE_TAPS (a build switch for the A/B of DESIGN
+// 5.bicubic, never set in the product) sends every plane down the byte path.
+// ----------------------------------------------------------------------------------------
+template <int C>
+struct CubicTaps {
+  uint32_t raw[4][C];   // row r: byte k C + c = component c of window column k
+  float wx[4], wy[4];
+  int d;                // taps' first column minus the window's: -1, 0 or 1
+  bool valid;
+};
+
+// w[k] for the taps at floor(x) - 1 + k, t = x - floor(x)
+__device__ __forceinline__ void cubic_weights(float t, float (&w)[4]) {
+  const float u = t + 1.0f;
+  w[0] = ((-0.75f * u - -3.75f) * u + -6.0f) * u - -3.0f;   // ((A u - 5A) u + 8A) u - 4A
+  w[1] = ((1.25f * t - 2.25f) * t) * t + 1.0f;               // ((A + 2) t - (A + 3)) t t + 1
+  const float v = 1.0f - t;
+  w[2] = ((1.25f * v - 2.25f) * v) * v + 1.0f;
+  w[3] = ((1.0f - w[0]) - w[1]) - w[2];
+}
+
+// C dwords from any byte address
+template <int C>
+__device__ __forceinline__ void load_bytes_x4(const uint8_t *__restrict__ p, uint32_t (&raw)[C]) {
+  if constexpr (C == 1) {
+    typedef uint32_t u32_a1 __attribute__((aligned(1)));
+    raw[0] = *reinterpret_cast<const u32_a1 *>(p);
+  } else {
+    typedef uint32_t u32xc __attribute__((ext_vector_type(C)));
+    typedef u32xc u32xc_a1 __attribute__((aligned(1)));
+    const u32xc v = *reinterpret_cast<const u32xc_a1 *>(p);
+#pragma unroll
+    for (int c = 0; c < C; ++c) raw[c] = v[c];
+  }
+}
+
+// Coordinates, validity, weights, and the 4 row loads (only ISSUED here, like sample_a_load).  kWide: pw >= 4.
+template <int C, bool kWide>
+__device__ __forceinline__ void cubic_load(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, float xs, float ys,
+                                           CubicTaps<C> &t) {
+  const float x = ((xs + 1.0f) * (float)pw) / 2.0f;  // sampler A's (:48-49)
+  const float y = ((ys + 1.0f) * (float)ph) / 2.0f;
+  t.valid = sample_a_valid(ph, pw, xs, ys);
+  // a valid sample has 0 <= x0 <= pw - 2 and 0 <= y0 <= ph - 2; an invalid one stores 0 and only needs addresses inside the plane
+  const int x0 = t.valid ? f2i(floorf(x)) : 0, y0 = t.valid ? f2i(floorf(y)) : 0;
+  cubic_weights(x - (float)x0, t.wx);   // x - x0 is exact
+  cubic_weights(y - (float)y0, t.wy);
+  if constexpr (kWide) {
+    const int xw = clampi(x0 - 1, 0, pw - 4);
+    t.d = x0 - 1 - xw;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) load_bytes_x4<C>(img + (size_t)clampi(y0 - 1 + r, 0, ph - 1) * pitch + (size_t)xw * C, t.raw[r]);
+    return;
+  }
+  t.d = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint8_t *row = img + (size_t)clampi(y0 - 1 + r, 0, ph - 1) * pitch;
+#pragma unroll
+    for (int c = 0; c < C; ++c) t.raw[r][c] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint8_t *p = row + (size_t)clampi(x0 - 1 + k, 0, pw - 1) * C;
+#pragma unroll
+      for (int c = 0; c < C; ++c) t.raw[r][(k * C + c) / 4] |= (uint32_t)p[c] << (8 * ((k * C + c) % 4));
+    }
+  }
+}
+
+// cubic_load for the rows i0 .. i0 + n_rows - 1 (n_rows <= 4) of one output column: every load of the thread in flight
+// together.  Which path a plane takes is decided once, outside the rows (a load under a per-row branch is waited for there).
+template <int C>
+__device__ __forceinline__ void cubic_load_rows(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, int n_rows,
+                                                const float (&xs)[4], const float (&ys)[4], CubicTaps<C> (&ct)[4]) {
+#ifndef DVSG_CUBIC_BYTE_TAPS
+  if (pw >= 4) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (r >= n_rows) break;
+      cubic_load<C, true>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
+    }
+    return;
+  }
+#endif
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (r >= n_rows) break;
+    cubic_load<C, false>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
+  }
+}
+
+// v[c] of one pixel; kBias: the chroma plane's samples, (b - 128) / 255.  An invalid pixel is exactly 0.
+template <int C, bool kBias>
+__device__ __forceinline__ void cubic_blend(const CubicTaps<C> &t, float (&v)[C]) {
+  float h[4][C];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float p[4][C];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int byte = (int)((t.raw[r][(k * C + c) / 4] >> (8 * ((k * C + c) % 4))) & 0xffu);
+        p[k][c] = kBias ? (float)(byte - 128) / 255.0f : (float)byte / 255.0f;
+      }
+    }
+    if (t.d != 0) {   // the window is one column off the taps: edge replicate
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float a = p[0][c], b = p[1][c], e = p[2][c], f = p[3][c];
+        p[0][c] = t.d < 0 ? a : b;
+        p[1][c] = t.d < 0 ? a : e;
+        p[2][c] = t.d < 0 ? b : f;
+        p[3][c] = t.d < 0 ? e : f;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) h[r][c] = ((t.wx[0] * p[0][c] + t.wx[1] * p[1][c]) + t.wx[2] * p[2][c]) + t.wx[3] * p[3][c];
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float s = ((t.wy[0] * h[0][c] + t.wy[1] * h[1][c]) + t.wy[2] * h[2][c]) + t.wy[3] * h[3][c];
+    v[c] = t.valid ? s : 0.0f;
+  }
+}
+
+// the bicubic render's bytes round to nearest: clamp(floor((double)v * 255.0 + bias + 0.5), 0, 255), bias 0 (RGB, luma) or
+// 128 (chroma); NaN gives 0
+__device__ __forceinline__ uint8_t cubic_u8(float v, double half) {
+  const double d = (double)v * 255.0 + half;
+  return d >= 255.0 ? (uint8_t)255 : (d > 0.0 ? (uint8_t)(int)d : (uint8_t)0);
+}
+
 // Samplers B and C share this tail (spatial_transformer.py:517-562,
 // warp_with_optical_flow.py:128-173): (x, y) in unpadded pixel units, clamped to [-1,W] /
 // [-1,H], +1 into the zero-ringed image, floor, upper index min()-ed, weights from the

@@ -37,6 +37,20 @@ def _entry(base, precision):
     return "%s_%s" % (base, precision)
 
 
+RENDER_FILTERS = {"bilinear": 0, "bicubic": 1}     # DVSG_RENDER_BILINEAR, DVSG_RENDER_BICUBIC
+
+
+def check_render_filter(render_filter, source_size_render=True):
+    """render_filter argument -> its name.  "bicubic" where no source-size render happens (RGB at the model's size, float
+    frames) is a ValueError that names source_res: only the source-size renders have a filter."""
+    if not isinstance(render_filter, str) or render_filter not in RENDER_FILTERS:
+        raise ValueError("render_filter must be 'bilinear' or 'bicubic', got %r" % (render_filter,))
+    if render_filter != "bilinear" and not source_size_render:
+        raise ValueError("render_filter=%r filters the source-size render only: it needs source_res=True (uint8 frames) or "
+                         "frame_format='nv12'; frames at the model's size are warped by sampler A" % (render_filter,))
+    return render_filter
+
+
 class LocNet(object):
     """Owns the device-side network (`dvsg_locnet_t`) and one growable workspace per stream that uses it."""
 
@@ -59,12 +73,30 @@ class LocNet(object):
         _lib.call("dvsg_locnet_create", n, c_names, c_data, c_nd,
                   dims.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(handle))
         self.handle = handle
+        self._views = {}   # render filter -> view handle (dvsg_locnet_view_create), made on first use
         self._keep = None  # the library copied everything to the device
         self._ws = None
         self.in_channels = _lib.load().dvsg_locnet_in_channels(self.handle)
 
+    def view(self, render_filter="bilinear"):
+        """The handle the source-size renders take for `render_filter`: this network itself for "bilinear", else a view of it
+        (`dvsg_locnet_view_create`: the same network, nothing copied, its own filter), made once per filter and kept until
+        the network goes."""
+        check_render_filter(render_filter)
+        if render_filter == "bilinear":
+            return self.handle
+        v = self._views.get(render_filter)
+        if v is None:
+            v = ctypes.c_void_p()
+            _lib.call("dvsg_locnet_view_create", self.handle, RENDER_FILTERS[render_filter], ctypes.byref(v))
+            self._views[render_filter] = v
+        return v
+
     def __del__(self):
         try:
+            for v in getattr(self, "_views", {}).values():   # views first: a parent with views is not destroyed
+                _lib.load().dvsg_locnet_destroy(v)
+            self._views = {}
             if getattr(self, "handle", None):
                 _lib.load().dvsg_locnet_destroy(self.handle)
                 self.handle = None

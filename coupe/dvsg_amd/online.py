@@ -96,6 +96,12 @@ class OnlineStabilizer(object):
     itself is still the one `dvsg_stabilize_ring_inplace_f32` call, on the same pool of model-size float RGB frames.
     side_by_side, as_uint8, channel_order="bgr", float frames and odd sizes raise ValueError.
 
+    render_filter: the filter of the source-size render (source_res=True or frame_format="nv12", with and without crop).
+    "bilinear" (default) is sampler A; "bicubic" gives the render calls a view of the network with that filter
+    (`LocNet.view`, include/dvsg_amd.h "Views and the render filter": 16 taps, OpenCV's INTER_CUBIC weights, bytes rounded
+    to nearest, the same black border).  The pool, F_t, the history and the crop's zoom are identical for both.  "bicubic"
+    without a source-size render (RGB at the model's size) raises ValueError, as does a float frame pushed into it.
+
     crop: every output frame has a black border (luma 0 / chroma 128 in NV12) wherever sampler A's taps leave the source.
     None (default) returns the frames as they are.  A zoom z in (0, 1] renders every frame of every stream on the output
     grid scaled by z about its centre; nothing is scanned.  "auto" keeps ONE zoom per stream on the device and lowers it
@@ -130,9 +136,11 @@ class OnlineStabilizer(object):
 
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
                  as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None,
-                 crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1):
+                 crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1, render_filter="bilinear"):
         from . import _lib
         from ._tensor import device
+        from .networks import check_render_filter
+        check_render_filter(render_filter, bool(source_res) or frame_format == "nv12")
         crop = _check_crop(crop)
         scene_cut = _check_scene_cut(scene_cut)
         if isinstance(scene_min_len, bool) or not isinstance(scene_min_len, (int, np.integer)) or scene_min_len < 0:
@@ -172,6 +180,7 @@ class OnlineStabilizer(object):
         self.flip = 1 if channel_order == "bgr" else 0
         self.side_by_side, self.as_uint8, self.source_res = bool(side_by_side), bool(as_uint8), bool(source_res)
         self.frame_format, self.yuv_matrix = frame_format, YUV_MATRICES[yuv_matrix]
+        self.render_filter = render_filter
         dev = device()
         self.pool = torch.empty((self.max_streams * self.frames_per_stream, self.h, self.w, 3), dtype=torch.float32,
                                 device=dev)
@@ -494,7 +503,7 @@ class OnlineStabilizer(object):
             out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
             side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
             zoom = self._step_zoom(entries, i, j, [(H0, W0)]) if self.crop is not None else None
-            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom)
+            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, self.render_filter)
             if any(entries[b][2] for b in range(i, j)):
                 out_h = out.cpu().numpy()
                 side_h = side.cpu().numpy() if side is not None else None
@@ -550,16 +559,17 @@ class OnlineStabilizer(object):
         for e in entries:
             self._streams[e[1]][1] += 1
         res = {}
+        net = self.model.locnet.view(self.render_filter)
         for i, j, src in groups:
             H0, W0 = entries[i][0]
             out = torch.empty_like(src)
             if self.crop is None:
-                _lib.call("dvsg_tps_render_nv12", self.model.locnet.handle, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * W0, W0,
+                _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * W0, W0,
                           3 * H0 // 2 * W0, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * W0, W0,
                           3 * H0 // 2 * W0, stream())
             else:   # chroma leaves the source first: both planes are scanned, each on its own grid
                 zoom = self._step_zoom(entries, i, j, [(H0, W0), (H0 // 2, W0 // 2)])
-                _lib.call("dvsg_tps_render_zoom_nv12", self.model.locnet.handle, ptr(self._F[i:j]), ptr(src),
+                _lib.call("dvsg_tps_render_zoom_nv12", net, ptr(self._F[i:j]), ptr(src),
                           ptr(src) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]), ptr(out),
                           ptr(out) + H0 * W0, W0, 3 * H0 // 2 * W0, stream())
             out_h = out.cpu().numpy() if any(entries[b][2] for b in range(i, j)) else None

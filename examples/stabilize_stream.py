@@ -75,6 +75,8 @@ def main():
     ap.add_argument("--format", default="rgb", choices=["rgb", "nv12"])
     ap.add_argument("--crop", default=None, help="'auto' or a zoom in (0, 1]")
     ap.add_argument("--scene-cut", type=float, default=None, metavar="THR", help="detect scene cuts: a threshold in (0, 1]")
+    ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"],
+                    help="filter of the source-size render; bicubic with --format rgb turns source_res on")
     ap.add_argument("--skip-length", default=None, metavar="A,B,...",
                     help="the window's frame offsets, oldest first (default: the reference's 0,16,24,28,30,31,32)")
     args = ap.parse_args()
@@ -88,11 +90,13 @@ def main():
     net.precision = args.precision
     nv12 = args.format == "nv12"
     if nv12:
-        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop, **scene, **window)
+        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop,
+                                render_filter=args.render_filter, **scene, **window)
         make = synthetic_nv12_source
     else:
         stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True,
-                                crop=crop, **scene, **window)
+                                crop=crop, source_res=args.render_filter != "bilinear", render_filter=args.render_filter,
+                                **scene, **window)
         make = synthetic_source
     H0, W0 = args.height * 3 // 2, args.width * 3 // 2
     if nv12:

@@ -153,6 +153,47 @@ int dvsg_locnet_in_channels(const dvsg_locnet_t *net);
 /* bytes of scratch `forward` needs for a [B,H,W,c_in] batch (256-byte aligned). */
 int dvsg_locnet_workspace_bytes(const dvsg_locnet_t *net, int B, int H, int W, size_t *bytes);
 
+/* Views and the render filter.  The filter of the four source-size renders (dvsg_tps_render_u8, dvsg_tps_render_zoom_u8,
+ * dvsg_tps_render_nv12, dvsg_tps_render_zoom_nv12) is a property of the immutable handle they are given, not an argument
+ * and not a setter: one network shared by several stabilisers, threads, streams and captured graphs renders with the
+ * filter of the handle each call passes.  Both functions are host-side: no stream, no device work.
+ *   dvsg_locnet_view_create  a VIEW of `net`: the same network and TPS constants, nothing copied, with its own render
+ *          filter (DVSG_RENDER_BILINEAR or DVSG_RENDER_BICUBIC).  Every entry point that takes a dvsg_locnet_t accepts a
+ *          view, and everything but the four renders behaves exactly as on the parent, bit for bit.  A view resolves to
+ *          its parent at call time (it copies no pointers), so a later dvsg_locnet_calibrate_f16 of the parent is seen
+ *          through its views; calibrating THROUGH a view is DVSG_ERR_INVALID_ARG.  A view of a view is a view of the
+ *          parent.  dvsg_locnet_destroy(view) frees the view only; destroying a parent that still has views is
+ *          DVSG_ERR_INVALID_ARG and destroys nothing.  An unknown filter or a NULL pointer is DVSG_ERR_INVALID_ARG,
+ *          decided before anything is allocated.
+ *   dvsg_locnet_render_filter  the handle's filter: 0 for every handle of dvsg_locnet_create (and for NULL).
+ *
+ * DVSG_RENDER_BILINEAR: sampler A, what the renders' own paragraphs below describe.
+ * DVSG_RENDER_BICUBIC: what a render launch does after T is written changes; T and the TPS map do not.  For every sample
+ * of a plane -- ph x pw samples of C components: the RGB image (C = 3), NV12 luma (C = 1), NV12 chroma (C = 2, ph = H / 2,
+ * pw = W / 2) -- x_s, y_s are the bits the grid-only form of dvsg_tps_warp_zoom_f32 (U == NULL, out == NULL, coord =
+ * V_src, the same T and zoom, out = the plane's size) gives.  Every float32 operation below is rounded on its own.
+ *   1. x = ((x_s + 1) * (float)pw) / 2, y = ((y_s + 1) * (float)ph) / 2: sampler A's coordinates.
+ *   2. The sample is valid iff sampler A blends four distinct taps there: 0 <= x < pw - 1, 0 <= y < ph - 1, not NaN.  An
+ *      invalid sample is exactly 0.0f (byte 0 for RGB and luma, 128 for chroma, 0.0f in out_f32): the set of valid
+ *      samples is the bilinear render's, so dvsg_tps_coverage_* and the crop need no change.  A plane with pw == 1 or
+ *      ph == 1 has no valid sample and is rendered all invalid.
+ *   3. x0 = (int)floorf(x), t = x - (float)x0 (exact).  With A = -0.75 (OpenCV's published INTER_CUBIC kernel; parity
+ *      with cv2 unpinned): u = t + 1, w0 = ((A u - 5A) u + 8A) u - 4A; w1 = ((1.25f t - 2.25f) t) t + 1; v = 1 - t,
+ *      w2 = ((1.25f v - 2.25f) v) v + 1; w3 = ((1 - w0) - w1) - w2.  The same for y with y0.
+ *   4. Taps: columns x0 - 1 .. x0 + 2, rows y0 - 1 .. y0 + 2, each index clamped into the plane (edge replicate); a
+ *      sample's value is what the bilinear path blends: (float)b / 255.0f, chroma (float)((int)b - 128) / 255.0f.
+ *   5. Rows first: h_r = ((w0 p0 + w1 p1) + w2 p2) + w3 p3, then v = ((wy0 h0 + wy1 h1) + wy2 h2) + wy3 h3.
+ *   6. The overshoot of a cubic is not clamped in float32 (out_f32).  Bytes round to NEAREST -- the weights sum to 1
+ *      only up to rounding, and truncation would make flat areas flicker between k - 1 and k --:
+ *      clamp(floor((double)v * 255.0 + 0.5), 0, 255), chroma clamp(floor((double)v * 255.0 + 128.5), 0, 255); NaN gives 0.
+ *      channel_flip, u8_W / u8_x0, pitch / frame_stride and the NULL-output rules are the bilinear render's.
+ * No load of the bicubic kernels touches a byte outside the pw * C used bytes of the source row it reads (not the pitch
+ * padding, not the next frame). */
+#define DVSG_RENDER_BILINEAR 0
+#define DVSG_RENDER_BICUBIC 1
+int dvsg_locnet_view_create(const dvsg_locnet_t *net, int render_filter, dvsg_locnet_t **view);
+int dvsg_locnet_render_filter(const dvsg_locnet_t *net);
+
 /* patches [B,H,W,c_in] in [0,1] -> F_t [B,25,2].  float32 storage, exact-f32 MFMA
  * (v_mfma_f32_32x32x2_f32) accumulation.  c_in != 21: conv1 is the same arithmetic in the root-conv kernel. */
 int dvsg_locnet_forward_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W,

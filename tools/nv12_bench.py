@@ -11,7 +11,9 @@ The fused ingest is checked bit for bit against the two-launch route before anyt
 ALTERNATE inside every round; device events around `--reps` calls; 7 rounds; median and spread (min .. max) per call.
 One JSON line per measurement.
 
-    python tools/nv12_bench.py [--reps 20] [--out FILE]
+--render-filter bicubic renders through a bicubic view of the network (both renders; every record names the filter).
+
+    python tools/nv12_bench.py [--reps 20] [--render-filter bilinear|bicubic] [--out FILE]
 """
 import argparse
 import json
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--model-height", type=int, default=288)
     ap.add_argument("--model-width", type=int, default=512)
+    ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import torch
@@ -39,6 +42,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("nv12_bench needs the GPU")
     net = LocNet(make_synthetic_weights(seed=0))
+    handle = net.view(args.render_filter)
     s = lambda: torch.cuda.current_stream().cuda_stream
     h, w, M = args.model_height, args.model_width, 1   # BT.709
     lines = []
@@ -60,7 +64,7 @@ def main():
                 per[name].append(e0.elapsed_time(e1) / args.reps)
         for name, _ in versions:
             v = sorted(per[name])
-            rec = dict(what=what, version=name, frames=n, height=H, width=W, ms_median=round(v[3], 4), ms_min=round(v[0], 4),
+            rec = dict(what=what, version=name, render_filter=args.render_filter, frames=n, height=H, width=W, ms_median=round(v[3], 4), ms_min=round(v[0], 4),
                        ms_max=round(v[-1], 4), us_per_frame=round(1e3 * v[3] / n, 2))
             print(json.dumps(rec), flush=True)
             lines.append(rec)
@@ -88,11 +92,11 @@ def main():
                           0, 0, s())
 
             def render_nv12():
-                _lib.call("dvsg_tps_render_nv12", net.handle, F.data_ptr(), y, uv, W, fs, n, H, W, T.data_ptr(), out.data_ptr(),
+                _lib.call("dvsg_tps_render_nv12", handle, F.data_ptr(), y, uv, W, fs, n, H, W, T.data_ptr(), out.data_ptr(),
                           out.data_ptr() + H * W, W, fs, s())
 
             def render_rgb():
-                _lib.call("dvsg_tps_render_u8", net.handle, F.data_ptr(), rgb.data_ptr(), n, H, W, 0, T.data_ptr(), None,
+                _lib.call("dvsg_tps_render_u8", handle, F.data_ptr(), rgb.data_ptr(), n, H, W, 0, T.data_ptr(), None,
                           out8.data_ptr(), W, 0, s())
 
             def route_nv12():

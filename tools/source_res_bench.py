@@ -10,7 +10,10 @@
    the timed steps (which end in a synchronise).
 One JSON line per measurement.
 
-    python tools/source_res_bench.py [--steps 30] [--warmup 5] [--sources 1080x1920,2160x3840] [--streams 1,4,16] [--out FILE]
+--render-filter bicubic measures the renders through a bicubic view of the network (every record names its filter).
+
+    python tools/source_res_bench.py [--steps 30] [--warmup 5] [--sources 1080x1920,2160x3840] [--streams 1,4,16]
+                                     [--render-filter bilinear|bicubic] [--out FILE]
 """
 import argparse
 import ctypes
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--sources", default="1080x1920,2160x3840")
     ap.add_argument("--streams", default="1,4,16")
     ap.add_argument("--precision", default="f32")
+    ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 1 or args.reps < 1:
@@ -52,7 +56,7 @@ def main():
     model = StabNet(h, w).load_weights(make_synthetic_weights(seed=0))
     model.get_evaluation_model(7)
     model.precision = args.precision
-    handle = model.locnet.handle
+    handle = model.locnet.view(args.render_filter)
     lines = []
 
     def emit(rec):
@@ -111,7 +115,7 @@ def main():
         _lib.check(lib.dvsg_prof_end(ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by)),
                    "dvsg_prof_end")
         k_ms = ms.value / max(cnt.value, 1)
-        emit({"what": "render_vs_three_launches", "H0": H0, "W0": W0, "n": n,
+        emit({"what": "render_vs_three_launches", "render_filter": args.render_filter, "H0": H0, "W0": W0, "n": n,
               "render_us_per_frame": 1e3 * t_render / n, "three_launch_us_per_frame": 1e3 * t_three / n,
               "speedup": t_three / t_render, "render_kernel_us_per_frame": 1e3 * k_ms / n,
               "render_kernel_GBps": by.value / max(cnt.value, 1) / (k_ms * 1e-3) / 1e9 if k_ms > 0 else None})
@@ -120,7 +124,8 @@ def main():
         H0, W0 = (int(v) for v in size.split("x"))
         for K in (int(v) for v in args.streams.split(",")):
             for source_res in (False, True):
-                on = OnlineStabilizer(model, max_streams=K, as_uint8=True, source_res=source_res)
+                on = OnlineStabilizer(model, max_streams=K, as_uint8=True, source_res=source_res,
+                                      render_filter=args.render_filter if source_res else "bilinear")
                 sids = [on.open() for _ in range(K)]
 
                 def feed(k):
@@ -133,7 +138,8 @@ def main():
                     on.step(feed(args.warmup + k))
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
-                emit({"what": "online", "model": [h, w], "H0": H0, "W0": W0, "K": K, "source_res": source_res,
+                emit({"what": "online", "render_filter": on.render_filter, "model": [h, w], "H0": H0, "W0": W0, "K": K,
+                      "source_res": source_res,
                       "precision": args.precision, "steps": args.steps, "frames_per_s": K * args.steps / dt,
                       "ms_per_frame": 1e3 * dt / (K * args.steps)})
                 del on
