@@ -1,15 +1,21 @@
 // Launch interface of the localizationNet kernels (conv_gemm.hip, conv1_pool.hip, head.hip),
 // used by locnet.hip.
 //
-// Three precisions share the kernels through template parameters:
+// `Precision` is the network's notion: what an entry point was asked for, and the storage of the activations between layers.
 //   kF32   float32 activations / weights, exact-f32 matrix cores (v_mfma_f32_32x32x2_f32): the path of record
-//   kF32S  4 bytes per value and float32 accumulation, but every operand enters the float16 matrix cores as two
-//          float16 pieces (22 significant bits for |x| >= 2^-3, absolute step 2^-24 below: the second piece is unscaled)
-//          and the activation tensors between layers hold those pieces;
+//   kF32S  4 bytes per value and float32 accumulation, but every product is formed on the float16 matrix cores from two
+//          float16 pieces per operand (22 significant bits for |x| >= 2^-3, absolute step 2^-24 below: the second piece is
+//          unscaled; conv_gemm.hip), and the activation tensors between the layers hold those pieces (P format, cnn_device.h);
 //          values must stay inside float16's range (|x| < 65504), which post-BatchNorm activations and BN-folded
 //          weights do by orders of magnitude
-//   kF16   float16 activations, conv weights as float16 hi / lo pairs, v_mfma_f32_32x32x16_f16 with float32
-//          accumulation; bias, accumulators and the dense head stay float32.
+//   kF16   float16 activations, v_mfma_f32_32x32x16_f16 with float32 accumulation; bias, accumulators and the dense head
+//          stay float32
+//   kF32X  ("f32x3") float32 tensors everywhere, exactly as kF32; inside the 52 conv GEMMs every product is formed on the
+//          bfloat16 matrix cores from THREE bfloat16 pieces per operand -- all 24 significant bits of both float32 operands,
+//          at any magnitude -- as six v_mfma_f32_32x32x16_bf16 with float32 accumulation (conv_gemm_tile.h, X3)
+// `ConvMath` is one conv launch's: what it multiplies, which fixes the weight image it reads (ConvWeights) and the tensors'
+// element type (storage_of).  kF16 has two: a layer's weights as float16 hi / lo pairs or as one plain float16 (locnet.hip's
+// pair policy chooses per layer).  All five share the kernels through template parameters.
 #pragma once
 #include <type_traits>
 
@@ -17,22 +23,41 @@
 
 namespace dvsg {
 
-// kF32S: 4 bytes per value and float32 accumulation like kF32, but every product is formed on the float16
-// matrix cores from two float16 pieces per operand (22 significant bits down to |x| = 2^-3; conv_gemm.hip), and the activation
-// tensors between the layers hold those two pieces (P format, cnn_device.h) instead of one float32.
-// kF32X ("f32x3"): float32 tensors everywhere, exactly as kF32; inside the 52 conv GEMMs every product is formed on the
-// bfloat16 matrix cores from THREE bfloat16 pieces per operand -- all 24 significant bits of both float32 operands, at any
-// magnitude -- as six v_mfma_f32_32x32x16_bf16 with float32 accumulation (conv_gemm_tile.h, X3).
 enum Precision { kF32 = 0, kF16 = 1, kF32S = 2, kF32X = 3 };
-inline size_t elem_size(int prec) { return prec == kF16 ? 2 : 4; }
+constexpr size_t elem_size(int prec) { return prec == kF16 ? 2 : 4; }
+// kMathF32       float32 tensors and weight rows, exact products
+// kMathF32S      P-format tensors; weights [Cout][K/32][32 hi halves | 32 lo halves], products from float16 pieces
+// kMathF32X      float32 tensors; weights are the layer's packed bfloat16 piece stages (launch_pack_x3)
+// kMathF16Pairs  float16 tensors; weights stacked [Cout/64][128][K] (64 hi rows, then 64 lo rows)
+// kMathF16Plain  float16 tensors; weights [Cout][K] float16
+enum ConvMath { kMathF32, kMathF32S, kMathF32X, kMathF16Pairs, kMathF16Plain };
+constexpr Precision storage_of(ConvMath m) { return m == kMathF32S ? kF32S : m == kMathF16Pairs || m == kMathF16Plain ? kF16 : kF32; }
+constexpr ConvMath math_of(int prec, bool pairs) {
+  return prec == kF16 ? (pairs ? kMathF16Pairs : kMathF16Plain) : prec == kF32S ? kMathF32S : prec == kF32X ? kMathF32X : kMathF32;
+}
+constexpr size_t elem_size(ConvMath m) { return elem_size((int)storage_of(m)); }
+static_assert(storage_of(kMathF32) == kF32 && storage_of(kMathF32X) == kF32 && storage_of(kMathF32S) == kF32S &&
+              storage_of(kMathF16Pairs) == kF16 && storage_of(kMathF16Plain) == kF16, "ConvMath -> storage format");
+static_assert(math_of(kF32, false) == kMathF32 && math_of(kF32, true) == kMathF32 && math_of(kF32S, false) == kMathF32S &&
+              math_of(kF32S, true) == kMathF32S && math_of(kF32X, false) == kMathF32X && math_of(kF32X, true) == kMathF32X &&
+              math_of(kF16, true) == kMathF16Pairs && math_of(kF16, false) == kMathF16Plain, "(Precision, pairs) -> ConvMath");
+static_assert(elem_size(kMathF32) == 4 && elem_size(kMathF32S) == 4 && elem_size(kMathF32X) == 4 &&
+              elem_size(kMathF16Pairs) == 2 && elem_size(kMathF16Plain) == 2, "ConvMath -> bytes per tensor element");
+
+// One layer's weights as a ConvMath reads them: the row matrix, and for the float16 maths optionally its rows packed stage
+// by stage for conv_gemm_wide16.hip (launch_pack_wide16): order 0, order 1 (its 128-byte-activation-row kernel) and order 2
+// (its 3x3 stride-1 kernel: a kernel row's taps from one staged run)
+struct ConvWeights {
+  const void *rows = nullptr, *packed = nullptr, *packed_a = nullptr, *packed_h = nullptr;
+};
 
 // Implicit-GEMM convolution (1x1 or 3x3, NHWC, C_in % 64 == 0 (f16) / 32 (f32), C_out % 64 == 0):
 //   y[m, n] = act( sum_k A[m, k] * wt[n, k] + bias[n] (+ res[...]) )
-// with m = (b, ho, wo), k = (kh, kw, c).  wt is [C_out][K] (K contiguous, BN scale folded in).
+// with m = (b, ho, wo), k = (kh, kw, c).  The weights are [C_out][K] in the math's layout (K contiguous, BN scale folded in).
 struct ConvGemm {
-  int prec;           // kF32 / kF16: element type of x, wt, res, y
+  ConvMath math;      // what is multiplied; x, res, y are tensors of storage_of(math)
   const void *x;      // [B,H,W,Cin]
-  const void *wt;     // [Cout][ksize*ksize*Cin]
+  ConvWeights w;
   const float *bias;  // [Cout]
   const void *res;    // optional residual [B,res_H,res_W,Cout], sampled at (ho*res_stride, wo*res_stride)
   void *y;            // [B,Ho,Wo,Cout]
@@ -40,17 +65,10 @@ struct ConvGemm {
   int ksize, stride, pad;
   int res_H, res_W, res_stride;
   int relu;
-  // float32 / f32s only (0 / -1 = the dense defaults): x and res may be column ranges of wider tensors -- ldx, res_ld elements
+  // 4-byte storage only (0 / -1 = the dense defaults): x and res may be column ranges of wider tensors -- ldx, res_ld elements
   // between two pixels -- and, with relu == 0, output channels >= relu_from get the ReLU all the same: a unit's `shortcut`
   // (no ReLU) and `conv1` (ReLU) read the same input and run as ONE launch over their concatenated weight rows (locnet.hip)
   int ldx = 0, res_ld = 0, relu_from = -1;
-  const void *wt_packed = nullptr;   // kF16, optional: the rows of `wt` packed stage by stage for conv_gemm_wide16.hip (launch_pack_wide16, order 0)
-  const void *wt_packed_a = nullptr; // ... in order 1, for its 128-byte-activation-row kernel
-  const void *wt_packed_h = nullptr; // ... in order 2, for its 3x3 stride-1 kernel (a kernel row's taps from one staged run)
-  int x3 = 0;         // kF32 only: wt is the layer's packed bfloat16 piece stages (launch_pack_x3) and the products are formed
-                      // from three bfloat16 pieces per operand (conv_gemm_tile.h, X3); x, res, y stay float32
-  int wsplit = 0;     // kF16: wt is the stacked layout [Cout/64][128][K] (64 hi rows, then 64 lo rows); kF32: wt is
-                      // [Cout][K/32][32 hi halves | 32 lo halves] and products are formed from float16 pieces (conv_gemm.hip)
   // optional split-K scratch (small batches): partial-tile slabs and kSplitKMaxTiles zeroed int tickets
   void *splitk_scratch = nullptr;
   size_t splitk_scratch_bytes = 0;
@@ -106,33 +124,28 @@ int launch_pack_wide16(const void *wt, void *out, int rows, int Cin, int ksize, 
 int launch_zero_tickets(int *tickets, size_t n, hipStream_t s);
 // conv2 (3x3, Cin -> 64, stride 1/2, pad 1, + bias + ReLU) followed by conv3 (1x1, 64 -> Cout, + bias +
 // residual + ReLU) of a bottleneck unit whose middle width is 64 (block 1), fused: the [M,64]
-// intermediate stays in LDS.  float32, "f32s" pieces, or the float16 mode (stacked hi / lo weights).
+// intermediate stays in LDS.
 struct ConvFused {
-  const float *x;      // [B,H,W,Cin]
-  const float *wt2;    // [64][9*Cin]
+  // every math but kMathF16Plain (the float16 kernels multiply by the stacked pairs only); x, res / sc_x, y are tensors of
+  // storage_of(math) and wt2, wt3, sc_wt the layers' ConvWeights::rows for it.  kMathF32X: the residual is a tensor (no fused
+  // shortcut), conv_fused_x3.hip
+  ConvMath math = kMathF32;
+  const void *x;       // [B,H,W,Cin]
+  const void *wt2;     // [64][9*Cin]
   const float *bias2;  // [64]
-  const float *wt3;    // [Cout][64]
+  const void *wt3;     // [Cout][64]
   const float *bias3;  // [Cout]
-  const float *res;    // [B,res_H,res_W,Cout], sampled at (ho*res_stride, wo*res_stride); NULL with sc_x
-  float *y;            // [B,Ho,Wo,Cout]
+  const void *res;     // [B,res_H,res_W,Cout], sampled at (ho*res_stride, wo*res_stride); NULL with sc_x
+  void *y;             // [B,Ho,Wo,Cout]
   int B, H, W, Cin, Ho, Wo, Cout;
   int stride;
   int res_H, res_W, res_stride;
   // the unit that opens a block: residual = 1x1 `shortcut` conv (+ BN) of the unit's input, computed in the
   // kernel from sc_x [B,Ho,Wo,sc_cin] (stride 1), sc_wt [Cout][sc_cin], sc_bias [Cout]; the tensor never exists
-  const float *sc_x = nullptr;
-  const float *sc_wt = nullptr;
+  const void *sc_x = nullptr;
+  const void *sc_wt = nullptr;
   const float *sc_bias = nullptr;
   int sc_cin = 0;
-  // "f32s": x, res / sc_x, y hold float16 pieces (P format) and wt2, wt3, sc_wt are the layers' piece matrices
-  // ([rows][K/32][32 hi | 32 lo]); same bytes per value, same addressing (pass them through the float pointers)
-  int pieces = 0;
-  // float16 mode: x, res / sc_x, y are float16 tensors and wt2, wt3, sc_wt the layers' stacked [hi | lo] float16 matrices
-  // ([cout/64][128][K], conv_gemm.hip SPLIT), passed through the float pointers
-  int f16 = 0;
-  // "f32x3": x, res, y are float32 tensors as in the float32 form; wt2, wt3 are the layers' packed bfloat16 piece stages
-  // (launch_pack_x3), passed through the float pointers; the residual is a tensor (no fused shortcut): conv_fused_x3.hip
-  int x3 = 0;
 };
 int launch_conv3x3_1x1_x3(const ConvFused &p, hipStream_t s);
 bool conv_fusable(int prec, int Cin, int Cmid, int Cout, int ksize);   // a predicate of precision and shape alone
@@ -200,8 +213,16 @@ struct Conv1Src {
   const float *mask = nullptr;   // optional [B,H,W]: eval_train.py:43-45,53-64 -- the 3 (S - 1) history channels of window b are multiplied
                                  // by mask[b] (one plane: the warp of an all-ones image is the same in every channel) in the load stage
 };
-int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *wt1, const void *wt1h, const void *wt1s,
-                 const void *wt1x, const float *bias, void *y, int B, int H, int W, int Ho, int Wo, int cin, hipStream_t s);
+// conv1's weight images (the layouts above); the images a precision does not use may be NULL, and cin != 21 has `f32` only
+struct Conv1Weights {
+  const float *f32;            // wt1
+  const _Float16 *f16;         // wt1h
+  const _Float16 *pieces;      // wt1s
+  const unsigned short *x3;    // wt1x
+  const float *bias;           // [64]
+};
+int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const Conv1Weights &wt, void *y, int B, int H, int W, int Ho,
+                 int Wo, int cin, hipStream_t s);
 // rootconv_kernel declares its LDS per launch (up to 140 KB at cin = 48): raises every instantiation's dynamic LDS limit.
 // Called once per handle by dvsg_locnet_create for cin != 21, outside any stream operation
 int prepare_rootconv();

@@ -2148,8 +2148,11 @@ bool with_conv1_src(int src, F &&f) {
 
 int g_last_root_kernel[kRootKernelFields] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
 
-int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *wt1, const void *wt1h, const void *wt1s,
-                 const void *wt1x, const float *bias, void *y, int B, int H, int W, int Ho, int Wo, int cin, hipStream_t s) {
+int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const Conv1Weights &wt, void *y, int B, int H, int W, int Ho,
+                 int Wo, int cin, hipStream_t s) {
+  const float *const wt1 = wt.f32, *const bias = wt.bias;
+  const _Float16 *const wt1h = wt.f16, *const wt1s = wt.pieces;
+  const unsigned short *const wt1x = wt.x3;
   DVSG_REQUIRE(cin % 3 == 0 && cin >= 3 && cin <= 3 * kRootMaxFrames, "conv1: %d input channels", cin);
   const int wtiles = ceil_div(Wo, C1_TILE);
   const long blocks = (long)wtiles * Ho * B;
@@ -2192,21 +2195,21 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *w
     legal = with_conv1_src<true>(SRC, [&](auto src_c) {
       constexpr int S = decltype(src_c)::value;
       record_conv1_kernel(5, -1, -1, S);
-      hipLaunchKernelGGL((conv1_x3_kernel<S>), grid, dim3(256), 0, s, src, static_cast<const unsigned short *>(wt1x), bias,
+      hipLaunchKernelGGL((conv1_x3_kernel<S>), grid, dim3(256), 0, s, src, wt1x, bias,
                          static_cast<float *>(y), H, W, Ho, Wo, wtiles);
     });
   } else if (out_prec == kF32S) {
     legal = with_conv1_src<true>(SRC, [&](auto src_c) {
       constexpr int S = decltype(src_c)::value;
       record_conv1_kernel(4, -1, 0, S);
-      hipLaunchKernelGGL((conv1_split_kernel<float, S>), grid, dim3(256), 0, s, src, static_cast<const _Float16 *>(wt1s), bias,
+      hipLaunchKernelGGL((conv1_split_kernel<float, S>), grid, dim3(256), 0, s, src, wt1s, bias,
                          static_cast<float *>(y), H, W, Ho, Wo, wtiles);
     });
   } else if (out_prec == kF16 && wt1h && variant == 3 && !src.mask) {   // A/B: one output row per workgroup, never with a mask
     legal = with_conv1_src<false>(SRC, [&](auto src_c) {
       constexpr int S = decltype(src_c)::value;
       record_conv1_kernel(1, -1, 1, S);
-      hipLaunchKernelGGL((conv1_f16_kernel<_Float16, S>), grid, dim3(256), 0, s, src, static_cast<const _Float16 *>(wt1h), bias,
+      hipLaunchKernelGGL((conv1_f16_kernel<_Float16, S>), grid, dim3(256), 0, s, src, wt1h, bias,
                          static_cast<_Float16 *>(y), H, W, Ho, Wo, wtiles);
     });
   } else if (out_prec == kF16 && wt1h && variant != 2 && variant != 4 && !src.mask &&
@@ -2224,7 +2227,7 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *w
     legal = with_conv1_src<false>(SRC, [&](auto src_c) {
       constexpr int S = decltype(src_c)::value;
       record_conv1_kernel(3, -1, -1, S, bands, qpb);
-      hipLaunchKernelGGL((conv1_f16_march_kernel<S>), mgrid, dim3(512), 0, s, src, static_cast<const _Float16 *>(wt1h), bias,
+      hipLaunchKernelGGL((conv1_f16_march_kernel<S>), mgrid, dim3(512), 0, s, src, wt1h, bias,
                          static_cast<_Float16 *>(y), H, W, Ho, Wo, wtiles, bands, qpb);
     });
   } else if (out_prec == kF16 && wt1h && variant != 2) {   // two output rows per workgroup (conv1_f16_pair_kernel)
@@ -2233,7 +2236,7 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const float *w
     legal = with_conv1_src<true>(SRC, [&](auto src_c) {
       constexpr int S = decltype(src_c)::value;
       record_conv1_kernel(2, -1, 1, S);
-      hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, S>), pgrid, dim3(256), 0, s, src, static_cast<const _Float16 *>(wt1h), bias,
+      hipLaunchKernelGGL((conv1_f16_pair_kernel<_Float16, S>), pgrid, dim3(256), 0, s, src, wt1h, bias,
                          static_cast<_Float16 *>(y), H, W, Ho, Wo, wtiles, hpairs);
     });
   } else if (out_prec == kF16) {  // conv1_variant 2: f32 multiply, f16 output (window tensors only)

@@ -897,12 +897,12 @@ static int launch_conv3x3_1x1_f16(const ConvFused &p, hipStream_t s) {
   const long M = (long)p.B * p.Ho * p.Wo;
   DVSG_REQUIRE(M > 0 && M < (1L << 31) - BM, "conv3x3_1x1: M=%ld out of range", M);
   ConvFusedF16Dev d;
-  d.x = reinterpret_cast<const _Float16 *>(p.x);
-  d.wt2 = reinterpret_cast<const _Float16 *>(p.wt2); d.bias2 = p.bias2;
-  d.wt3 = reinterpret_cast<const _Float16 *>(p.wt3); d.bias3 = p.bias3;
-  d.res = reinterpret_cast<const _Float16 *>(sc ? p.sc_x : p.res);
-  d.wts = reinterpret_cast<const _Float16 *>(p.sc_wt); d.biass = p.sc_bias;
-  d.y = reinterpret_cast<_Float16 *>(p.y);
+  d.x = static_cast<const _Float16 *>(p.x);
+  d.wt2 = static_cast<const _Float16 *>(p.wt2); d.bias2 = p.bias2;
+  d.wt3 = static_cast<const _Float16 *>(p.wt3); d.bias3 = p.bias3;
+  d.res = static_cast<const _Float16 *>(sc ? p.sc_x : p.res);
+  d.wts = static_cast<const _Float16 *>(p.sc_wt); d.biass = p.sc_bias;
+  d.y = static_cast<_Float16 *>(p.y);
   d.H = p.H; d.W = p.W; d.Cin = p.Cin; d.Ho = p.Ho; d.Wo = p.Wo; d.Cout = p.Cout;
   d.stride = p.stride;
   d.res_H = p.res_H; d.res_W = p.res_W; d.res_stride = p.res_stride;
@@ -931,8 +931,10 @@ static int launch_conv3x3_1x1_f16(const ConvFused &p, hipStream_t s) {
 
 int launch_conv3x3_1x1(const ConvFused &p, hipStream_t s) {
   reset_conv_kernel();
-  if (p.f16) return launch_conv3x3_1x1_f16(p, s);
-  if (p.x3) return launch_conv3x3_1x1_x3(p, s);
+  DVSG_REQUIRE(p.math != kMathF16Plain, "conv3x3_1x1 (float16): the fused kernels multiply by the stacked hi / lo weights only");
+  if (p.math == kMathF16Pairs) return launch_conv3x3_1x1_f16(p, s);
+  if (p.math == kMathF32X) return launch_conv3x3_1x1_x3(p, s);
+  const bool pieces = p.math == kMathF32S;   // P-format tensors and piece matrices: 4 bytes per value, the float32 form's addressing
   DVSG_REQUIRE(p.Cin % 32 == 0 && p.Cin >= 64 && p.Cout % 128 == 0, "conv3x3_1x1: Cin=%d must be a multiple of 32 (>= 64), Cout=%d of 128",
                p.Cin, p.Cout);
   const bool sc = p.sc_x != nullptr;  // the residual is the 1x1 shortcut conv of sc_x, computed in the kernel
@@ -943,8 +945,9 @@ int launch_conv3x3_1x1(const ConvFused &p, hipStream_t s) {
   const long M = (long)p.B * p.Ho * p.Wo;
   DVSG_REQUIRE(M > 0 && M < (1L << 31) - BM, "conv3x3_1x1: M=%ld out of range", M);
   ConvFusedDev d;
-  d.x = p.x; d.wt2 = p.wt2; d.bias2 = p.bias2; d.wt3 = p.wt3; d.bias3 = p.bias3; d.y = p.y;
-  d.res = sc ? p.sc_x : p.res; d.wts = p.sc_wt; d.biass = p.sc_bias;
+  d.x = static_cast<const float *>(p.x); d.wt2 = static_cast<const float *>(p.wt2); d.bias2 = p.bias2;
+  d.wt3 = static_cast<const float *>(p.wt3); d.bias3 = p.bias3; d.y = static_cast<float *>(p.y);
+  d.res = static_cast<const float *>(sc ? p.sc_x : p.res); d.wts = static_cast<const float *>(p.sc_wt); d.biass = p.sc_bias;
   d.H = p.H; d.W = p.W; d.Cin = p.Cin; d.Ho = p.Ho; d.Wo = p.Wo; d.Cout = p.Cout;
   d.stride = p.stride;
   d.res_H = p.res_H; d.res_W = p.res_W; d.res_stride = p.res_stride;
@@ -957,7 +960,7 @@ int launch_conv3x3_1x1(const ConvFused &p, hipStream_t s) {
                  4.0 * ((double)p.B * p.H * p.W * p.Cin + (double)CMID * 9 * p.Cin + (double)p.Cout * CMID +
                         (sc ? (double)M * CSC + (double)p.Cout * CSC + (double)M * p.Cout : 2.0 * (double)M * p.Cout)));
   const dim3 grid(d.mtiles), block(512);
-  if (p.pieces) {
+  if (pieces) {
     if (res == 1) hipLaunchKernelGGL((conv3x3_1x1_kernel<1, true>), grid, block, 0, s, d);
     else if (res == 2) hipLaunchKernelGGL((conv3x3_1x1_kernel<2, true>), grid, block, 0, s, d);
     else hipLaunchKernelGGL((conv3x3_1x1_kernel<3, true>), grid, block, 0, s, d);
@@ -966,7 +969,7 @@ int launch_conv3x3_1x1(const ConvFused &p, hipStream_t s) {
     else if (res == 2) hipLaunchKernelGGL((conv3x3_1x1_kernel<2>), grid, block, 0, s, d);
     else hipLaunchKernelGGL((conv3x3_1x1_kernel<3>), grid, block, 0, s, d);
   }
-  record_conv_kernel(4, res, p.pieces ? 1 : 0);
+  record_conv_kernel(4, res, pieces ? 1 : 0);
   return check_launch("conv3x3_1x1_kernel");
 }
 

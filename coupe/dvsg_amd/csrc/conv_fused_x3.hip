@@ -314,10 +314,10 @@ int launch_conv3x3_1x1_x3(const ConvFused &p, hipStream_t s) {
   const long M = (long)p.B * p.Ho * p.Wo;
   DVSG_REQUIRE(M > 0 && M < (1L << 31) - BM, "conv3x3_1x1: M=%ld out of range", M);
   FusedX3Dev d;
-  d.x = p.x;
-  d.wt2x = reinterpret_cast<const unsigned short *>(p.wt2); d.bias2 = p.bias2;
-  d.wt3x = reinterpret_cast<const unsigned short *>(p.wt3); d.bias3 = p.bias3;
-  d.res = p.res; d.y = p.y;
+  d.x = static_cast<const float *>(p.x);
+  d.wt2x = static_cast<const unsigned short *>(p.wt2); d.bias2 = p.bias2;
+  d.wt3x = static_cast<const unsigned short *>(p.wt3); d.bias3 = p.bias3;
+  d.res = static_cast<const float *>(p.res); d.y = static_cast<float *>(p.y);
   d.H = p.H; d.W = p.W; d.Cin = p.Cin; d.Ho = p.Ho; d.Wo = p.Wo; d.Cout = p.Cout;
   d.stride = p.stride;
   d.res_H = p.res_H; d.res_W = p.res_W; d.res_stride = p.res_stride;

@@ -46,22 +46,28 @@ int launch_zero_tickets(int *tickets, size_t n, hipStream_t s) {
 int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   g_last_conv_config[0] = -1;   // until launch_cfg records this call's launch
   reset_conv_kernel();
-  DVSG_REQUIRE(p.prec == kF32 || p.prec == kF16, "conv_gemm: unknown precision %d", p.prec);
+  // the math in the policy's terms, here alone: the tensors' element type, and which of the three piece schemes multiplies
+  const bool f16 = storage_of(p.math) == kF16;
+  const size_t es = elem_size(p.math);
+  const bool split = p.math == kMathF16Pairs;             // f16: hi / lo weight rows stacked along N
+  const bool x3 = p.math == kMathF32X;                    // f32x3: float32 tensors, products from three bfloat16 pieces per operand
+  const bool psplit = p.math == kMathF32S || x3;          // f32s: 4-byte storage, products from float16 pieces
+                                                          // (f32x3 shares its launch policy: tiles several times cheaper than exact ones)
   DVSG_REQUIRE(p.ksize == 1 || p.ksize == 3, "conv_gemm: kernel size %d unsupported", p.ksize);
-  const int bke = ROWB / (int)elem_size(p.prec);
+  const int bke = ROWB / (int)es;
   DVSG_REQUIRE(p.Cin % bke == 0 && p.Cout % 64 == 0, "conv_gemm: Cin=%d must be a multiple of %d and Cout=%d of 64",
                p.Cin, bke, p.Cout);
   const long M = (long)p.B * p.Ho * p.Wo;
   DVSG_REQUIRE(M > 0 && M < (1L << 31) - BM, "conv_gemm: M=%ld out of range", M);
   ConvGemmDev d;
-  d.x = p.x; d.wt = p.wt; d.bias = p.bias; d.res = p.res; d.y = p.y;
+  d.x = p.x; d.wt = p.w.rows; d.bias = p.bias; d.res = p.res; d.y = p.y;
   d.H = p.H; d.W = p.W; d.Cin = p.Cin; d.Ho = p.Ho; d.Wo = p.Wo; d.Cout = p.Cout;
   d.stride = p.stride; d.pad = p.pad;
   d.res_H = p.res_H; d.res_W = p.res_W; d.res_stride = p.res_stride;
   d.ldx = p.ldx > 0 ? p.ldx : p.Cin;
   d.res_ld = p.res_ld > 0 ? p.res_ld : p.Cout;
   d.relu_from = p.relu_from >= 0 ? p.relu_from : 0x7fffffff;
-  DVSG_REQUIRE(p.prec != kF16 || (d.ldx == p.Cin && d.res_ld == p.Cout && p.relu_from < 0),
+  DVSG_REQUIRE(!f16 || (d.ldx == p.Cin && d.res_ld == p.Cout && p.relu_from < 0),
                "conv_gemm: row strides / a partial ReLU are the float32 kernels' only");
   DVSG_REQUIRE(d.ldx >= p.Cin && d.ldx % bke == 0 && d.res_ld >= p.Cout && d.res_ld % 4 == 0 && (p.relu_from < 0 || (p.relu_from % 64 == 0 && !p.relu)),
                "conv_gemm: bad strides ldx=%d res_ld=%d relu_from=%d", d.ldx, d.res_ld, p.relu_from);
@@ -70,18 +76,12 @@ int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   d.mtiles = (int)((M + BM - 1) / BM);
   const int res = !p.res ? 0 : (p.res_stride == 1 && p.res_H == p.Ho && p.res_W == p.Wo ? 1 : 2);
   // algorithmic work: 2 M N K flops; bytes = input + weights + output (+ residual) once each
-  const double es = (double)elem_size(p.prec);
   ProfScope prof(p.ksize == 3 ? kClsConv3x3 : kClsConv1x1, s, 2.0 * (double)M * p.Cout * d.K,
-                 es * ((double)p.B * p.H * p.W * p.Cin + (double)p.Cout * d.K +
+                 (double)es * ((double)p.B * p.H * p.W * p.Cin + (double)p.Cout * d.K +
                        (double)M * p.Cout * (p.res ? 2.0 : 1.0)));
   // 128-wide n tiles when there are enough of them to fill the chip, else 64-wide -- except that a
   // launch of 256..511 wide tiles (230 measured: no gain) with a long K loop runs wide as ONE stream-K round (block 4 at
   // batch 16, 720p: 460 wide tiles, or 920 narrow ones = 1.8 rounds, both 90 % full otherwise).
-  const bool split = p.wsplit != 0 && p.prec == kF16;    // f16: hi / lo weight rows stacked along N
-  const bool x3 = p.x3 != 0;                             // f32x3: float32 tensors, products from three bfloat16 pieces per operand
-  DVSG_REQUIRE(!x3 || (p.prec == kF32 && p.wsplit == 0), "conv_gemm: f32x3 runs on float32 tensors");
-  const bool psplit = (p.wsplit != 0 && p.prec == kF32) || x3;   // f32s: float32 storage, products from float16 pieces
-                                                         // (f32x3 shares its launch policy: tiles several times cheaper than exact ones)
   // split weights: 128 physical weight rows per 64 output channels, always one 128-wide tile each
   const long tiles128 = split ? (long)d.mtiles * (p.Cout / 64) : p.Cout % 128 == 0 ? (long)d.mtiles * (p.Cout / 128) : 0;
   const int kt_all = d.K / bke;
@@ -97,11 +97,11 @@ int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   // panels, and its stream-K workgroups stream them at 512 different K phases, so each tile fetched
   // its whole panel past the 4 MB L2 (1.2 GB per launch).  With mt fastest an XCD stays on one or
   // two panels and re-reads the (much smaller) activations instead.
-  d.mt_fast = d.ntiles > 1 && (size_t)(wide ? 128 : 64) * d.K * elem_size(p.prec) >= ((size_t)2 << 20);
+  d.mt_fast = d.ntiles > 1 && (size_t)(wide ? 128 : 64) * d.K * es >= ((size_t)2 << 20);
   // float16 mode: a launch of several rounds of tiles runs in the 256 x 128 / 64-byte-stage geometry (conv_gemm_wide16.hip)
   if (split && g_opt.conv_variant != 5 && (long)((M + 255) / 256) * (p.Cout / 64) >= g_opt.wide16_min_tiles) return launch_conv_wide16(p, s);
   // ... and so does a plain-float16 layer (no lo piece: locnet.hip's pair policy) whose 128-channel tiles fill the chip
-  if (p.prec == kF16 && !split && g_opt.conv_variant != 5 && p.Cout % 128 == 0 && p.Cin % 64 == 0 &&
+  if (f16 && !split && g_opt.conv_variant != 5 && p.Cout % 128 == 0 && p.Cin % 64 == 0 &&
       (long)((M + 255) / 256) * (p.Cout / 128) >= g_opt.wide16_min_tiles)
     return launch_conv_wide16(p, s);
   d.ksplit = 1;
@@ -144,7 +144,7 @@ int launch_conv_gemm(const ConvGemm &p, hipStream_t s) {
   if (psplit)
     return p.ksize == 1 ? launch_ks<float, 1, true>(d, wide, streamk_tail, p.relu != 0, res, s)
                         : launch_ks<float, 3, true>(d, wide, streamk_tail, p.relu != 0, res, s);
-  if (p.prec == kF32)
+  if (!f16)
     return p.ksize == 1 ? launch_ks<float, 1>(d, wide, streamk_tail, p.relu != 0, res, s)
                         : launch_ks<float, 3>(d, wide, streamk_tail, p.relu != 0, res, s);
   if (split)

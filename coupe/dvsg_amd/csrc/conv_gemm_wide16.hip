@@ -560,37 +560,38 @@ extern "C" int dvsg_debug_read_wide16_stamps(void *host, size_t bytes) {
 }
 #endif
 
-// p: a float16 layer -- stacked [hi | lo] weights (p.wsplit, Cout % 64 == 0) or plain ones (Cout % 128 == 0) -- with
+// p: a float16 layer -- stacked [hi | lo] weights (kMathF16Pairs, Cout % 64 == 0) or plain ones (Cout % 128 == 0) -- with
 // Cin % 64 == 0; the caller has opened the ProfScope
 int launch_conv_wide16(const ConvGemm &p, hipStream_t s) {
   reset_conv_kernel();
+  const bool split = p.math == kMathF16Pairs;
   const long M = (long)p.B * p.Ho * p.Wo;
   ConvWide16Dev d;
-  d.x = static_cast<const _Float16 *>(p.x); d.wt = static_cast<const _Float16 *>(p.wt);
+  d.x = static_cast<const _Float16 *>(p.x); d.wt = static_cast<const _Float16 *>(p.w.rows);
   d.res = static_cast<const _Float16 *>(p.res); d.bias = p.bias; d.y = static_cast<_Float16 *>(p.y);
   // (K = 128 -- two super-stages -- keeps the 64-byte rows: block 2's conv3 2.48 against 2.55 ms)
-  d.arows = g_opt.wide16_arows && p.wt_packed_a != nullptr && (g_opt.wide16_arows == 2 || p.ksize * p.ksize * p.Cin >= 256);
-  d.wtp = d.arows ? static_cast<const _Float16 *>(p.wt_packed_a) : g_opt.wide16_packed ? static_cast<const _Float16 *>(p.wt_packed) : nullptr;
+  d.arows = g_opt.wide16_arows && p.w.packed_a != nullptr && (g_opt.wide16_arows == 2 || p.ksize * p.ksize * p.Cin >= 256);
+  d.wtp = d.arows ? static_cast<const _Float16 *>(p.w.packed_a) : g_opt.wide16_packed ? static_cast<const _Float16 *>(p.w.packed) : nullptr;
   d.H = p.H; d.W = p.W; d.Cin = p.Cin; d.Ho = p.Ho; d.Wo = p.Wo; d.Cout = p.Cout;
   d.stride = p.stride; d.pad = p.pad;
   d.res_H = p.res_H; d.res_W = p.res_W; d.res_stride = p.res_stride;
   d.M = (int)M;
   d.K = p.ksize * p.ksize * p.Cin;
   d.mtiles = (int)((M + WBM - 1) / WBM);
-  d.ntiles = p.wsplit ? p.Cout / 64 : p.Cout / 128;
-  const bool hreuse = g_opt.wide16_hreuse && p.wt_packed_h != nullptr && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.H == p.Ho && p.W == p.Wo;
+  d.ntiles = split ? p.Cout / 64 : p.Cout / 128;
+  const bool hreuse = g_opt.wide16_hreuse && p.w.packed_h != nullptr && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.H == p.Ho && p.W == p.Wo;
   if (hreuse) {
-    d.wtp = static_cast<const _Float16 *>(p.wt_packed_h);
+    d.wtp = static_cast<const _Float16 *>(p.w.packed_h);
     d.mtiles = (int)((M + WHM - 1) / WHM);
     const int resh = !p.res ? 0 : (p.res_stride == 1 && p.res_H == p.Ho && p.res_W == p.Wo ? 1 : 2);
-    return p.wsplit ? launch_h<true>(d, p.relu != 0, resh, s) : launch_h<false>(d, p.relu != 0, resh, s);
+    return split ? launch_h<true>(d, p.relu != 0, resh, s) : launch_h<false>(d, p.relu != 0, resh, s);
   }
 #ifdef DVSG_STAMPS
   d.stamp = g_w16_stamp_sel == p.ksize * 100000000 + p.Cin * 10000 + p.Cout;
   if (d.stamp) std::fprintf(stderr, "wide16 stamps: ks %d Cin %d Cout %d M %ld tiles %d x %d res %d relu %d\n", p.ksize, p.Cin, p.Cout, M, d.mtiles, d.ntiles, p.res != nullptr, p.relu);
 #endif
   const int res = !p.res ? 0 : (p.res_stride == 1 && p.res_H == p.Ho && p.res_W == p.Wo ? 1 : 2);
-  if (p.wsplit) return p.ksize == 3 ? launch_ks<3, true>(d, p.relu != 0, res, s) : launch_ks<1, true>(d, p.relu != 0, res, s);
+  if (split) return p.ksize == 3 ? launch_ks<3, true>(d, p.relu != 0, res, s) : launch_ks<1, true>(d, p.relu != 0, res, s);
   DVSG_REQUIRE(p.Cout % 128 == 0, "conv_wide16: plain weights need Cout %% 128 == 0, got %d", p.Cout);
   return p.ksize == 3 ? launch_ks<3, false>(d, p.relu != 0, res, s) : launch_ks<1, false>(d, p.relu != 0, res, s);
 }

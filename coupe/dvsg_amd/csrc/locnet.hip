@@ -42,11 +42,17 @@ struct ConvLayer {
   _Float16 *wt32s = nullptr;  // device, "f32s" pieces [cout][k*k*cin/32][32 hi | 32 lo] (conv_gemm.hip SPLIT, T = float; not for conv1)
   unsigned short *wt3x = nullptr;  // device, "f32x3" bfloat16 pieces, packed stage by stage (launch_pack_x3; not for conv1)
   float *bias = nullptr;      // device, [cout] float32
-  const void *weights(int prec, bool split) const {
-    if (prec == kF32S) return wt32s;
-    if (prec == kF32X) return wt3x;
-    return prec == kF16 ? (split ? (const void *)wt16s : (const void *)wt16) : (const void *)wt;
+  // the weight image a math multiplies by: the one place that pairs the two up
+  ConvWeights image(ConvMath math) const {
+    switch (math) {
+      case kMathF32S: return {wt32s};
+      case kMathF32X: return {wt3x};
+      case kMathF16Pairs: return {wt16s, wt16p, wt16pa, wt16ph};
+      case kMathF16Plain: return {wt16, wt16q, wt16qa, wt16qh};
+      default: return {wt};
+    }
   }
+  Conv1Weights conv1_images() const { return {wt, wt16, wt32s, wt3x, bias}; }   // (conv1 keeps its images in the same members)
 };
 
 struct Unit {
@@ -126,13 +132,21 @@ int find(const ArrayMap &m, const std::string &name, std::initializer_list<int64
   return DVSG_OK;
 }
 
+// Device memory that lives as long as the handle: registered in net->allocs as soon as it exists, so dvsg_locnet_destroy
+// frees it whatever fails afterwards
+template <typename T>
+int device_alloc(dvsg_locnet *net, size_t bytes, T **ptr) {
+  void *p = nullptr;
+  DVSG_HIP(hipMalloc(&p, bytes));
+  net->allocs.push_back(p);
+  *ptr = static_cast<T *>(p);
+  return DVSG_OK;
+}
+
 template <typename T>
 int upload(dvsg_locnet *net, const std::vector<T> &h, T **dev) {
-  void *p = nullptr;
-  DVSG_HIP(hipMalloc(&p, h.size() * sizeof(T)));
-  net->allocs.push_back(p);
-  DVSG_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  *dev = static_cast<T *>(p);
+  if (int rc = device_alloc(net, h.size() * sizeof(T), dev)) return rc;
+  DVSG_HIP(hipMemcpy(*dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   return DVSG_OK;
 }
 
@@ -153,28 +167,31 @@ int bn_fold(const ArrayMap &m, const std::string &scope, int c, std::vector<floa
   return DVSG_OK;
 }
 
-// (Re)make the stage-packed copies of a layer's PLAIN float16 weights (conv_gemm_wide16.hip; round 3 built the packing for
-// the stacked hi / lo rows only, so a layer without the lo piece fetched half-line weight rows again)
-int pack_plain(dvsg_locnet *net, ConvLayer *L) {
-  if (L->cin % 64 != 0 || L->cout % 128 != 0 || !L->wt16) return DVSG_OK;
+// (Re)make the stage-packed copies of a layer's float16 row matrix `rows` [nrows][k*k*cin] for conv_gemm_wide16.hip: order 0
+// (64-byte activation rows), 1 (128-byte rows), 2 (3x3: a kernel row's taps from one run); a 1x1 layer's K order is the same
+// in 0 and 1: one copy.  A copy that exists already is packed again in place
+int pack_wide16(dvsg_locnet *net, const ConvLayer &L, const _Float16 *rows, int nrows, _Float16 **p0, _Float16 **pa, _Float16 **ph) {
   auto pack = [&](int order, _Float16 **out) -> int {
-    if (!*out) {
-      void *pk = nullptr;
-      DVSG_HIP(hipMalloc(&pk, wide16_packed_bytes(L->cout, L->cin, L->ksize)));
-      net->allocs.push_back(pk);
-      *out = static_cast<_Float16 *>(pk);
-    }
-    return launch_pack_wide16(L->wt16, *out, L->cout, L->cin, L->ksize, order, nullptr);
+    if (!*out)
+      if (int rc = device_alloc(net, wide16_packed_bytes(nrows, L.cin, L.ksize), out)) return rc;
+    return launch_pack_wide16(rows, *out, nrows, L.cin, L.ksize, order, nullptr);
   };
-  if (int rc = pack(0, &L->wt16q)) return rc;
-  if (L->ksize == 1) {
-    L->wt16qa = L->wt16q;
+  if (int rc = pack(0, p0)) return rc;
+  if (L.ksize == 1) {
+    *pa = *p0;
   } else {
-    if (int rc = pack(1, &L->wt16qa)) return rc;
-    if (int rc = pack(2, &L->wt16qh)) return rc;
+    if (int rc = pack(1, pa)) return rc;
+    if (int rc = pack(2, ph)) return rc;
   }
   DVSG_HIP(hipStreamSynchronize(nullptr));
   return DVSG_OK;
+}
+
+// ... of a layer's PLAIN float16 weights (round 3 built the packing for the stacked hi / lo rows only, so a layer without the
+// lo piece fetched half-line weight rows again)
+int pack_plain(dvsg_locnet *net, ConvLayer *L) {
+  if (L->cin % 64 != 0 || L->cout % 128 != 0 || !L->wt16) return DVSG_OK;
+  return pack_wide16(net, *L, L->wt16, L->cout, &L->wt16q, &L->wt16qa, &L->wt16qh);
 }
 
 // Generic conv: HWIO -> [cout][kh][kw][cin] with the BN scale folded in; float32 and float16 copies.
@@ -215,35 +232,14 @@ int make_conv(dvsg_locnet *net, const ArrayMap &m, const std::string &scope, Con
   if (int rc = upload(net, wt, &L->wt)) return rc;
   if (int rc = upload(net, wt16, &L->wt16)) return rc;
   if (int rc = upload(net, wt16s, &L->wt16s)) return rc;
-  if (L->cin % 64 == 0 && L->cout % 64 == 0) {   // the layers conv_gemm_wide16.hip can take
-    // packed copies: order 0 (64-byte activation rows), 1 (128-byte rows), 2 (3x3: a kernel row's taps from one run);
-    // a 1x1 layer's K order is the same in 0 and 1: one copy
-    auto pack = [&](int order, _Float16 **out) -> int {
-      void *pk = nullptr;
-      DVSG_HIP(hipMalloc(&pk, wide16_packed_bytes(2 * L->cout, L->cin, L->ksize)));
-      net->allocs.push_back(pk);
-      if (int rc = launch_pack_wide16(L->wt16s, pk, 2 * L->cout, L->cin, L->ksize, order, nullptr)) return rc;
-      *out = static_cast<_Float16 *>(pk);
-      return DVSG_OK;
-    };
-    if (int rc = pack(0, &L->wt16p)) return rc;
-    if (L->ksize == 1) {
-      L->wt16pa = L->wt16p;
-    } else {
-      if (int rc = pack(1, &L->wt16pa)) return rc;
-      if (int rc = pack(2, &L->wt16ph)) return rc;
-    }
-    DVSG_HIP(hipStreamSynchronize(nullptr));
-  }
+  if (L->cin % 64 == 0 && L->cout % 64 == 0)   // the layers conv_gemm_wide16.hip can take: the stacked pairs, packed
+    if (int rc = pack_wide16(net, *L, L->wt16s, 2 * L->cout, &L->wt16p, &L->wt16pa, &L->wt16ph)) return rc;
   if (int rc = pack_plain(net, L)) return rc;
   if (int rc = upload(net, wt32s, &L->wt32s)) return rc;
   if (K % 32 == 0 && L->cout % 64 == 0) {   // "f32x3": three bfloat16 pieces per weight, packed stage by stage
-    void *pk = nullptr;
-    DVSG_HIP(hipMalloc(&pk, x3_packed_bytes(L->cout, K)));
-    net->allocs.push_back(pk);
-    if (int rc = launch_pack_x3(L->wt, pk, L->cout, K, nullptr)) return rc;
+    if (int rc = device_alloc(net, x3_packed_bytes(L->cout, K), &L->wt3x)) return rc;
+    if (int rc = launch_pack_x3(L->wt, L->wt3x, L->cout, K, nullptr)) return rc;
     DVSG_HIP(hipStreamSynchronize(nullptr));
-    L->wt3x = static_cast<unsigned short *>(pk);
   }
   return upload(net, shift, &L->bias);
 }
@@ -407,33 +403,30 @@ Workspace plan(char *base, int B, int H, int W) {
   return w;
 }
 
-int run_conv(int prec, const ConvLayer &L, bool pairs, const void *x, int B, int H, int W, void *y, int Ho, int Wo,
-             const void *res, int res_H, int res_W, int res_stride, bool relu, const Workspace &ws, int *launch_idx,
-             hipStream_t s, int ldx = 0, int res_ld = 0, int relu_from = -1) {
+// What a layer's launch reads and writes (tensors of storage_of(math), batch B): ld = elements between two pixels where the
+// tensor is a column range of a wider one, 0 = dense
+struct ConvIn { const void *ptr; int H, W, ld = 0; };
+struct ConvRes { const void *ptr = nullptr; int H = 0, W = 0, stride = 1, ld = 0; };   // default-constructed: no residual
+struct ConvOut { void *ptr; int Ho, Wo; };
+// the split-K scratch of a pass and which of its ticket segments the next launch owns
+struct ConvScratch { const Workspace &ws; int launch_idx = 0; };
+constexpr int kNoReluFrom = -1;   // run_conv's relu_from: with relu false, no output channel gets the ReLU (else those from n on)
+
+int run_conv(const ConvLayer &L, ConvMath math, int B, const ConvIn &x, const ConvOut &y, const ConvRes &res, bool relu,
+             int relu_from, ConvScratch *scratch, hipStream_t s) {
   ConvGemm p;
-  p.ldx = ldx; p.res_ld = res_ld; p.relu_from = relu_from;
-  p.splitk_scratch = ws.splitk_slabs;
+  p.math = math;
+  p.splitk_scratch = scratch->ws.splitk_slabs;
   p.splitk_scratch_bytes = kSplitKSlabBytes;
-  p.splitk_counters = ws.splitk_counters + (size_t)((*launch_idx)++ % kMaxConvLaunches) * kSplitKMaxTiles;
-  p.prec = prec == kF32S || prec == kF32X ? kF32 : prec;
-  p.wsplit = prec == kF32S || (prec == kF16 && pairs);
-  p.x3 = prec == kF32X;
-  if (prec == kF32X && !L.wt3x)
+  p.splitk_counters = scratch->ws.splitk_counters + (size_t)(scratch->launch_idx++ % kMaxConvLaunches) * kSplitKMaxTiles;
+  if (math == kMathF32X && !L.wt3x)
     return fail(DVSG_ERR_UNSUPPORTED, "f32x3: layer %d -> %d (k = %d) has no packed bfloat16 pieces (K %% 32, Cout %% 64)", L.cin, L.cout, L.ksize);
-  p.x = x; p.wt = L.weights(prec, p.wsplit != 0); p.bias = L.bias; p.res = res; p.y = y;
-  if (prec == kF16 && pairs) {
-    p.wt_packed = L.wt16p;
-    p.wt_packed_a = L.wt16pa;
-    p.wt_packed_h = L.wt16ph;
-  } else if (prec == kF16) {
-    p.wt_packed = L.wt16q;
-    p.wt_packed_a = L.wt16qa;
-    p.wt_packed_h = L.wt16qh;
-  }
-  p.B = B; p.H = H; p.W = W; p.Cin = L.cin; p.Ho = Ho; p.Wo = Wo; p.Cout = L.cout;
+  p.x = x.ptr; p.w = L.image(math); p.bias = L.bias; p.res = res.ptr; p.y = y.ptr;
+  p.B = B; p.H = x.H; p.W = x.W; p.Cin = L.cin; p.Ho = y.Ho; p.Wo = y.Wo; p.Cout = L.cout;
   p.ksize = L.ksize; p.stride = L.stride; p.pad = L.ksize == 3 ? 1 : 0;
-  p.res_H = res_H; p.res_W = res_W; p.res_stride = res_stride;
-  p.relu = relu;
+  p.ldx = x.ld;
+  p.res_H = res.H; p.res_W = res.W; p.res_stride = res.stride; p.res_ld = res.ld;
+  p.relu = relu; p.relu_from = relu_from;
   return launch_conv_gemm(p, s);
 }
 
@@ -478,10 +471,10 @@ int calib_record(Calib *calib, int slot, const void *x, long M, int C, hipStream
   return check_launch("channel_sum_kernel");
 }
 
-// Runs the network in precision `prec`; stop_stage < 0 runs everything and writes F_t [B,50].  With `calib` (a float32
+// Runs the network in precision `precision`; stop_stage < 0 runs everything and writes F_t [B,50].  With `calib` (a float32
 // pass) the units' convolution inputs are recorded into it, and block 1 runs unfused: its conv2 output only exists in
 // LDS when fused.
-int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind, int B, int H, int W, float *F_t, int stop_stage,
+int forward(const dvsg_locnet *net, const int precision, const Conv1Src &src, int src_kind, int B, int H, int W, float *F_t, int stop_stage,
             float *act_out, size_t act_out_bytes, int *act_dims, void *workspace, size_t workspace_bytes,
             hipStream_t s, Calib *calib) {
   DVSG_REQUIRE(net && src.base && workspace, "locnet forward: NULL pointer");
@@ -492,30 +485,29 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
     return fail(DVSG_ERR_WORKSPACE, "locnet forward: workspace %zu bytes < required %zu", workspace_bytes, ws.total);
   net = base(net);   // a view runs its parent's network; the handle is first read here, behind every check
   const Dims d = root_dims(H, W);
-  // f32x3: float32 tensors throughout; conv1, the pools, block 1's fused kernel and the head are the float32 kernels
-  // themselves, the conv GEMMs multiply bfloat16 pieces (run_conv)
-  const int gprec = prec;
-  if (prec == kF32X) prec = kF32;
+  // the activation tensors' storage format.  (f32x3: float32 tensors throughout; conv1, the pools, block 1's fused kernel and
+  // the head are the float32 kernels themselves, the conv GEMMs multiply bfloat16 pieces)
+  const Precision act = storage_of(math_of(precision, true));
 
   // parity tap: copy (float32 run) or convert (float16 run) the stage's activation to act_out
-  auto tap = [&](int stage, const void *act, int h, int w, int c) -> int {
+  auto tap = [&](int stage, const void *x, int h, int w, int c) -> int {
     if (stage != stop_stage) return 0;
     const size_t n = (size_t)B * h * w * c;
     if (n * sizeof(float) > act_out_bytes)
       return fail(DVSG_ERR_INVALID_ARG, "tap buffer %zu bytes < %zu", act_out_bytes, n * sizeof(float));
-    if (prec == kF16) {
-      if (int rc = launch_f16_to_f32(act, act_out, n, s)) return rc;
-    } else if (prec == kF32S) {
-      if (int rc = launch_p_to_f32(act, act_out, n, s)) return rc;
+    if (act == kF16) {
+      if (int rc = launch_f16_to_f32(x, act_out, n, s)) return rc;
+    } else if (act == kF32S) {
+      if (int rc = launch_p_to_f32(x, act_out, n, s)) return rc;
     } else {
-      DVSG_HIP(hipMemcpyAsync(act_out, act, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+      DVSG_HIP(hipMemcpyAsync(act_out, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     act_dims[0] = h; act_dims[1] = w; act_dims[2] = c;
     return 1;
   };
-#define DVSG_TAP(stage, act, h, w, c)          \
+#define DVSG_TAP(stage, x, h, w, c)            \
   do {                                         \
-    int t_ = tap(stage, act, h, w, c);         \
+    int t_ = tap(stage, x, h, w, c);           \
     if (t_ < 0) return t_;                     \
     if (t_ > 0) return DVSG_OK;                \
   } while (0)
@@ -526,19 +518,19 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
 
   // split-K tickets of every conv launch of this pass (each launch owns its own segment)
   DVSG_RUN(launch_zero_tickets(ws.splitk_counters, (size_t)kMaxConvLaunches * kSplitKMaxTiles, s));
-  int launch_idx = 0;
+  ConvScratch scratch{ws};
   const bool fuse_allowed = g_opt.fuse_conv != 0 && calib == nullptr;   // block 1's conv2 + conv3 in one kernel
   reset_root_kernel();
-  // root: conv1 (+ fused scale_RGB; f32 multiply, output in `prec`) -> bufA, max pool -> bufB
+  // root: conv1 (+ fused scale_RGB; f32 multiply, output in `act`) -> bufA, max pool -> bufB
   {
   MarkerRange mr("dvsg/conv1");
-  DVSG_RUN(launch_conv1(gprec == kF32X && g_opt.x3_conv1 ? kF32X : prec, src, src_kind, net->conv1.wt, net->conv1.wt16, net->conv1.wt32s,
-                        net->conv1.wt3x, net->conv1.bias, ws.bufA, B, H, W, d.H1, d.W1, net->c_in, s));
+  DVSG_RUN(launch_conv1(precision == kF32X && g_opt.x3_conv1 ? kF32X : act, src, src_kind, net->conv1.conv1_images(), ws.bufA, B, H, W,
+                        d.H1, d.W1, net->c_in, s));
   }
   DVSG_TAP(0, ws.bufA, d.H1, d.W1, 64);
   {
   MarkerRange mr("dvsg/pool1");
-  DVSG_RUN(launch_maxpool(prec, ws.bufA, ws.bufB, B, d.H1, d.W1, 64, d.Hp, d.Wp, d.pad_top, d.pad_left, s));
+  DVSG_RUN(launch_maxpool(act, ws.bufA, ws.bufB, B, d.H1, d.W1, 64, d.Hp, d.Wp, d.pad_top, d.pad_left, s));
   }
   DVSG_TAP(1, ws.bufB, d.Hp, d.Wp, 64);
 
@@ -553,72 +545,59 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
     std::snprintf(range_name, sizeof(range_name), "dvsg/block%d/unit_%d", u.block + 1, unit_in_block);
     MarkerRange mr(range_name);
     const int ho = (h - 1) / u.stride + 1, wo = (w - 1) / u.stride + 1;
-    const void *res = X;
-    int res_h = h, res_w = w, res_stride = u.stride;
+    ConvRes res{X, h, w, u.stride};
+    // what this unit's layer of `kind` multiplies: the precision's math, in the float16 mode with or without the lo piece
+    auto math = [&](int kind) { return math_of(precision, f16_pairs(net, u.block, kind)); };
     const int calib_slot = 3 * (stage - 2);
     DVSG_RUN(calib_record(calib, calib_slot, X, (long)B * h * w, u.c1.cin, s));
     // (float16 mode: the fused kernel multiplies against the stacked hi / lo weights only)
     // (f32x3: block 1's units run conv2 + conv3 in the f32x3 fused kernel, conv_fused_x3.hip, the opening unit's shortcut as
     // its own f32x3 GEMM -- x3_fuse = 3; A/B: 0 never fused, 1 the opening unit only and in the exact float32 kernel with
     // its shortcut, 2 all three in the exact float32 kernel)
-    const bool x3_fused = gprec == kF32X && g_opt.x3_fuse == 3;
-    const bool x3_unfused = gprec == kF32X && (g_opt.x3_fuse == 0 || (g_opt.x3_fuse == 1 && !u.has_shortcut));
-    const bool fuse23 = fuse_allowed && !x3_unfused && conv_fusable(prec, u.c2.cin, u.c2.cout, u.c3.cout, u.c2.ksize) &&
-                        (prec != kF16 || (f16_pairs(net, u.block, kKindC2) && f16_pairs(net, u.block, kKindC3) &&
-                                          (!u.has_shortcut || f16_pairs(net, u.block, kKindSc))));
+    const bool x3_fused = precision == kF32X && g_opt.x3_fuse == 3;
+    const bool x3_unfused = precision == kF32X && (g_opt.x3_fuse == 0 || (g_opt.x3_fuse == 1 && !u.has_shortcut));
+    const bool fuse23 = fuse_allowed && !x3_unfused && conv_fusable(act, u.c2.cin, u.c2.cout, u.c3.cout, u.c2.ksize) &&
+                        (act != kF16 || (f16_pairs(net, u.block, kKindC2) && f16_pairs(net, u.block, kKindC3) &&
+                                         (!u.has_shortcut || f16_pairs(net, u.block, kKindSc))));
     // block 1's opening unit: its shortcut conv (64 -> 256) runs inside the fused conv2 + conv3 kernel
     const bool fuse_sc = fuse23 && !x3_fused && u.has_shortcut && u.stride == 1 && u.shortcut.cin == 64 && u.shortcut.cout == 256 &&
                          g_opt.fuse_shortcut;
     // blocks 2-4's opening units, float32 / f32s: shortcut and conv1 as ONE launch over [shortcut | conv1] weight rows; its
     // output [M, depth + base] sits in bufS, the shortcut in columns [0, depth) (conv3's residual, row stride depth + base),
     // conv1's ReLU'd output behind it (conv2's input, same stride).  One launch and one read of the unit's input less.
-    const bool cat = u.has_shortcut && !fuse_sc && u.has_cat && prec != kF16 && g_opt.concat_sc && !calib && u.stride == 1;
-    const void *c2_in = ws.r1;
-    int c2_ldx = 0, res_ld = 0;
+    const bool cat = u.has_shortcut && !fuse_sc && u.has_cat && act != kF16 && g_opt.concat_sc && !calib && u.stride == 1;
+    ConvIn c2_in{ws.r1, h, w};
     if (cat) {
-      DVSG_RUN(run_conv(gprec, u.cat, false, X, B, h, w, ws.bufS, h, w, nullptr, 0, 0, 1, false, ws, &launch_idx, s, 0, 0,
-                        u.shortcut.cout));
-      res = ws.bufS;
-      res_h = ho; res_w = wo; res_stride = 1;
-      res_ld = u.cat.cout;
-      c2_in = ws.bufS + (size_t)u.shortcut.cout * sizeof(float);   // (f32s: 32 values are 128 bytes too)
-      c2_ldx = u.cat.cout;
+      DVSG_RUN(run_conv(u.cat, math_of(precision, false), B, {X, h, w}, {ws.bufS, h, w}, {}, false, u.shortcut.cout, &scratch, s));
+      res = {ws.bufS, ho, wo, 1, u.cat.cout};
+      c2_in = {ws.bufS + (size_t)u.shortcut.cout * sizeof(float), h, w, u.cat.cout};   // (f32s: 32 values are 128 bytes too)
     } else {
     if (u.has_shortcut && !fuse_sc) {  // 1x1 conv + BN, no ReLU (stride is 1 wherever depth changes)
-      DVSG_RUN(run_conv(gprec, u.shortcut, f16_pairs(net, u.block, kKindSc), X, B, h, w, ws.bufS, ho, wo, nullptr, 0, 0, 1, false, ws,
-                        &launch_idx, s));
-      res = ws.bufS;
-      res_h = ho; res_w = wo; res_stride = 1;
+      DVSG_RUN(run_conv(u.shortcut, math(kKindSc), B, {X, h, w}, {ws.bufS, ho, wo}, {}, false, kNoReluFrom, &scratch, s));
+      res = {ws.bufS, ho, wo, 1};
     }
-    DVSG_RUN(run_conv(gprec, u.c1, f16_pairs(net, u.block, kKindC1), X, B, h, w, ws.r1, h, w, nullptr, 0, 0, 1, true, ws, &launch_idx, s));
+    DVSG_RUN(run_conv(u.c1, math(kKindC1), B, {X, h, w}, {ws.r1, h, w}, {}, true, kNoReluFrom, &scratch, s));
     }
     if (fuse23) {  // block 1: conv2 + conv3 in one kernel
       ConvFused f;
-      const bool pcs = prec == kF32S;
-      auto wts_of = [&](const ConvLayer &L) {
-        if (x3_fused) return reinterpret_cast<const float *>(L.wt3x);
-        return pcs ? reinterpret_cast<const float *>(L.wt32s) : prec == kF16 ? reinterpret_cast<const float *>(L.wt16s) : L.wt;
-      };
-      f.pieces = pcs;
-      f.f16 = prec == kF16;
-      f.x3 = x3_fused;
-      f.x = reinterpret_cast<const float *>(ws.r1); f.wt2 = wts_of(u.c2); f.bias2 = u.c2.bias; f.wt3 = wts_of(u.c3); f.bias3 = u.c3.bias;
-      f.res = static_cast<const float *>(res); f.y = reinterpret_cast<float *>(Y);
+      // (float16: fuse23 has checked that all of the unit's layers carry the lo piece; f32x3 through the exact float32
+      // kernel -- x3_fuse 1, 2 -- is the float32 math)
+      f.math = x3_fused ? kMathF32X : math_of(act, true);
+      f.x = ws.r1; f.wt2 = u.c2.image(f.math).rows; f.bias2 = u.c2.bias; f.wt3 = u.c3.image(f.math).rows; f.bias3 = u.c3.bias;
+      f.res = res.ptr; f.y = Y;
       f.B = B; f.H = h; f.W = w; f.Cin = u.c2.cin; f.Ho = ho; f.Wo = wo; f.Cout = u.c3.cout;
-      f.stride = u.c2.stride; f.res_H = res_h; f.res_W = res_w; f.res_stride = res_stride;
+      f.stride = u.c2.stride; f.res_H = res.H; f.res_W = res.W; f.res_stride = res.stride;
       if (fuse_sc) {
         f.res = nullptr;
-        f.sc_x = reinterpret_cast<const float *>(X); f.sc_wt = wts_of(u.shortcut); f.sc_bias = u.shortcut.bias;
+        f.sc_x = X; f.sc_wt = u.shortcut.image(f.math).rows; f.sc_bias = u.shortcut.bias;
         f.sc_cin = u.shortcut.cin;
       }
       DVSG_RUN(launch_conv3x3_1x1(f, s));
     } else {
       DVSG_RUN(calib_record(calib, calib_slot + 1, ws.r1, (long)B * h * w, u.c2.cin, s));
-      DVSG_RUN(run_conv(gprec, u.c2, f16_pairs(net, u.block, kKindC2), c2_in, B, h, w, ws.r2, ho, wo, nullptr, 0, 0, 1, true, ws,
-                        &launch_idx, s, c2_ldx));
+      DVSG_RUN(run_conv(u.c2, math(kKindC2), B, c2_in, {ws.r2, ho, wo}, {}, true, kNoReluFrom, &scratch, s));
       DVSG_RUN(calib_record(calib, calib_slot + 2, ws.r2, (long)B * ho * wo, u.c3.cin, s));
-      DVSG_RUN(run_conv(gprec, u.c3, f16_pairs(net, u.block, kKindC3), ws.r2, B, ho, wo, Y, ho, wo, res, res_h, res_w, res_stride, true,
-                        ws, &launch_idx, s, 0, res_ld));
+      DVSG_RUN(run_conv(u.c3, math(kKindC3), B, {ws.r2, ho, wo}, {Y, ho, wo}, res, true, kNoReluFrom, &scratch, s));
     }
     h = ho; w = wo;
     DVSG_TAP(stage, Y, h, w, u.depth);
@@ -629,7 +608,7 @@ int forward(const dvsg_locnet *net, int prec, const Conv1Src &src, int src_kind,
   // global average pool (float32 partial sums), then the float32 dense head in chunks of <= 16
   // samples; partial layouts are [b][split][k] so a batch chunk is a pointer offset.
   MarkerRange mr_head("dvsg/head");
-  DVSG_RUN(launch_avgpool_partial(prec, X, ws.pool_part, B, h * w, 2048, s));
+  DVSG_RUN(launch_avgpool_partial(act, X, ws.pool_part, B, h * w, 2048, s));
   const float inv_hw = 1.0f / (float)(h * w);
   if (stop_stage == 18) {
     const size_t bytes = (size_t)B * 2048 * sizeof(float);
@@ -716,17 +695,15 @@ int stabilize_ring(const dvsg_locnet *net, int prec, const void *pool, int pool_
                         });
 }
 
-int conv_gemm_op(int prec, int wsplit, const void *x, const void *wt, const float *bias, const void *res, void *y, int B,
+int conv_gemm_op(ConvMath math, const void *x, const void *wt, const float *bias, const void *res, void *y, int B,
                  int H, int W, int Cin, int Cout, int ksize, int stride, int relu, int res_stride, void *scratch,
                  size_t scratch_bytes, void *stream) {
   DVSG_REQUIRE(x && wt && bias && y, "dvsg_conv_gemm: NULL pointer");
   DVSG_REQUIRE(!scratch || ((uintptr_t)scratch & 255) == 0, "dvsg_conv_gemm: scratch must be 256-byte aligned");
   DVSG_REQUIRE(B > 0 && H > 0 && W > 0 && stride >= 1 && res_stride >= 1, "dvsg_conv_gemm: bad shape");
   ConvGemm p;
-  p.prec = prec;
-  p.wsplit = wsplit == 1;
-  p.x3 = wsplit == 2;   // f32x3: packed bfloat16 piece stages
-  p.x = x; p.wt = wt; p.bias = bias; p.res = res; p.y = y;
+  p.math = math;
+  p.x = x; p.w.rows = wt; p.bias = bias; p.res = res; p.y = y;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
   p.Ho = (H - 1) / stride + 1; p.Wo = (W - 1) / stride + 1;
   p.ksize = ksize; p.stride = stride; p.pad = ksize == 3 ? 1 : 0;
@@ -742,24 +719,25 @@ int conv_gemm_op(int prec, int wsplit, const void *x, const void *wt, const floa
     // that may carry the packed weight copies below, which a slab user sizing itself by this field must never reach
     p.splitk_scratch_bytes = std::min(scratch_bytes - cbytes, align256(kSplitKSlabBytes));
   }
-  if (prec == kF16 && Cin % 64 == 0 && Cout % (wsplit ? 64 : 128) == 0 && (ksize == 1 || ksize == 3) && scratch) {
+  const bool pairs = math == kMathF16Pairs;
+  if (storage_of(math) == kF16 && Cin % 64 == 0 && Cout % (pairs ? 64 : 128) == 0 && (ksize == 1 || ksize == 3) && scratch) {
     // the packed weight copies conv_gemm_wide16.hip prefers (what dvsg_locnet_create makes once per layer), made here on
     // every call behind the tickets and the partial-tile slabs when the caller's scratch has room for them; without
     // them the layer runs from the [rows][K] layout
-    const int rows = wsplit ? 2 * Cout : Cout;   // stacked hi / lo rows, or plain ones
+    const int rows = pairs ? 2 * Cout : Cout;   // stacked hi / lo rows, or plain ones
     const size_t need = align256(wide16_packed_bytes(rows, Cin, ksize));
     const size_t base = cbytes + align256(kSplitKSlabBytes);
     if (scratch_bytes >= base + 3 * need) {
       char *pk = static_cast<char *>(scratch) + base;
       if (int rc = launch_pack_wide16(wt, pk, rows, Cin, ksize, 0, as_stream(stream))) return rc;
-      p.wt_packed = pk;
+      p.w.packed = pk;
       if (ksize == 1) {
-        p.wt_packed_a = pk;
+        p.w.packed_a = pk;
       } else {
         if (int rc = launch_pack_wide16(wt, pk + need, rows, Cin, ksize, 1, as_stream(stream))) return rc;
         if (int rc = launch_pack_wide16(wt, pk + 2 * need, rows, Cin, ksize, 2, as_stream(stream))) return rc;
-        p.wt_packed_a = pk + need;
-        p.wt_packed_h = pk + 2 * need;
+        p.w.packed_a = pk + need;
+        p.w.packed_h = pk + 2 * need;
       }
     }
   }
@@ -786,25 +764,22 @@ int forward_tap_entry(const char *fn, int prec, const dvsg_locnet *net, const fl
 // The ConvFused of dvsg_conv3x3_1x1_f32, dvsg_conv3x3_1x1_f32x3 and dvsg_debug_conv3x3_1x1, as forward() fills it for block
 // 1's units (`fn` names the entry point in the messages).  The residual is the tensor `res`, or, with sc_x, the 1x1
 // shortcut conv of sc_x computed in the kernel.
-int fused_op(const char *fn, int prec, const void *x, const void *wt2, const float *bias2, const void *wt3, const float *bias3,
+int fused_op(const char *fn, ConvMath math, const void *x, const void *wt2, const float *bias2, const void *wt3, const float *bias3,
              const void *res, const void *sc_x, const void *sc_wt, const float *sc_bias, int sc_cin, void *y, int B, int H,
              int W, int Cin, int Cout, int stride, int res_stride, void *stream) {
   DVSG_REQUIRE(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && res_stride >= 1,
                "%s: bad shape B=%d H=%d W=%d stride=%d res_stride=%d", fn, B, H, W, stride, res_stride);
   ConvFused f;
-  f.pieces = prec == kF32S;
-  f.f16 = prec == kF16;
-  f.x3 = prec == kF32X;
-  f.x = static_cast<const float *>(x); f.wt2 = static_cast<const float *>(wt2); f.bias2 = bias2;
-  f.wt3 = static_cast<const float *>(wt3); f.bias3 = bias3;
-  f.res = static_cast<const float *>(res); f.y = static_cast<float *>(y);
+  f.math = math;
+  f.x = x; f.wt2 = wt2; f.bias2 = bias2; f.wt3 = wt3; f.bias3 = bias3;
+  f.res = res; f.y = y;
   f.B = B; f.H = H; f.W = W; f.Cin = Cin; f.Cout = Cout;
   f.Ho = (H - 1) / stride + 1; f.Wo = (W - 1) / stride + 1;
   f.stride = stride;
   f.res_H = (f.Ho - 1) * res_stride + 1; f.res_W = (f.Wo - 1) * res_stride + 1; f.res_stride = res_stride;
   if (sc_x) {
     f.res = nullptr;
-    f.sc_x = static_cast<const float *>(sc_x); f.sc_wt = static_cast<const float *>(sc_wt); f.sc_bias = sc_bias;
+    f.sc_x = sc_x; f.sc_wt = sc_wt; f.sc_bias = sc_bias;
     f.sc_cin = sc_cin;
   }
   return launch_conv3x3_1x1(f, as_stream(stream));
@@ -904,25 +879,21 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
         const ConvLayer &a = unit.shortcut, &b = unit.c1;
         unit.cat = ConvLayer{1, a.cin, a.cout + b.cout, 1, false};
         const size_t ka = (size_t)a.cout * a.cin, kb = (size_t)b.cout * b.cin;
-        void *w = nullptr, *ws2 = nullptr, *bi = nullptr, *w3 = nullptr;
-        if (hipMalloc(&w, (ka + kb) * sizeof(float)) != hipSuccess || hipMalloc(&ws2, 2 * (ka + kb) * sizeof(_Float16)) != hipSuccess ||
-            hipMalloc(&bi, (a.cout + b.cout) * sizeof(float)) != hipSuccess || hipMalloc(&w3, 6 * (ka + kb)) != hipSuccess)
-          return bail(fail(DVSG_ERR_HIP, "hipMalloc failed"));
-        net->allocs.push_back(w); net->allocs.push_back(ws2); net->allocs.push_back(bi); net->allocs.push_back(w3);
-        hipError_t e = hipMemcpy(w, a.wt, ka * sizeof(float), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(static_cast<float *>(w) + ka, b.wt, kb * sizeof(float), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(ws2, a.wt32s, 2 * ka * sizeof(_Float16), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(static_cast<_Float16 *>(ws2) + 2 * ka, b.wt32s, 2 * kb * sizeof(_Float16), hipMemcpyDeviceToDevice);
+        ConvLayer &c = unit.cat;
+        if ((rc = device_alloc(net, (ka + kb) * sizeof(float), &c.wt))) return bail(rc);
+        if ((rc = device_alloc(net, 2 * (ka + kb) * sizeof(_Float16), &c.wt32s))) return bail(rc);
+        if ((rc = device_alloc(net, (a.cout + b.cout) * sizeof(float), &c.bias))) return bail(rc);
+        if ((rc = device_alloc(net, 6 * (ka + kb), &c.wt3x))) return bail(rc);
+        hipError_t e = hipMemcpy(c.wt, a.wt, ka * sizeof(float), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(c.wt + ka, b.wt, kb * sizeof(float), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(c.wt32s, a.wt32s, 2 * ka * sizeof(_Float16), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(c.wt32s + 2 * ka, b.wt32s, 2 * kb * sizeof(_Float16), hipMemcpyDeviceToDevice);
         // (the f32x3 packing is by groups of 64 rows: the two layers' packed stages one behind the other)
-        if (e == hipSuccess) e = hipMemcpy(w3, a.wt3x, 6 * ka, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(static_cast<char *>(w3) + 6 * ka, b.wt3x, 6 * kb, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(bi, a.bias, a.cout * sizeof(float), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(static_cast<float *>(bi) + a.cout, b.bias, b.cout * sizeof(float), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(c.wt3x, a.wt3x, 6 * ka, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(c.wt3x + 3 * ka, b.wt3x, 6 * kb, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(c.bias, a.bias, a.cout * sizeof(float), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(c.bias + a.cout, b.bias, b.cout * sizeof(float), hipMemcpyDeviceToDevice);
         if (e != hipSuccess) return bail(fail(DVSG_ERR_HIP, "concatenating shortcut | conv1: %s", hipGetErrorString(e)));
-        unit.cat.wt = static_cast<float *>(w);
-        unit.cat.wt32s = static_cast<_Float16 *>(ws2);
-        unit.cat.wt3x = static_cast<unsigned short *>(w3);
-        unit.cat.bias = static_cast<float *>(bi);
         unit.has_cat = true;
       }
       net->units.push_back(unit);
@@ -946,14 +917,12 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
     }
   if ((rc = upload(net, vs, &net->v_src))) return bail(rc);
   {  // the TPS system of the constant V_src grid is inverted once (float64)
-    void *w = nullptr, *scratch = nullptr;
-    if (hipMalloc(&w, 25 * 28 * sizeof(double)) != hipSuccess) return bail(fail(DVSG_ERR_HIP, "hipMalloc failed"));
-    net->allocs.push_back(w);
+    void *scratch = nullptr;
+    if ((rc = device_alloc(net, 25 * 28 * sizeof(double), &net->winv))) return bail(rc);
     if (hipMalloc(&scratch, 13 * 25 * 2 * sizeof(float)) != hipSuccess) return bail(fail(DVSG_ERR_HIP, "hipMalloc failed"));
-    rc = tps_inverse_columns(net->v_src, 25, static_cast<double *>(w), static_cast<float *>(scratch), nullptr);
+    rc = tps_inverse_columns(net->v_src, 25, net->winv, static_cast<float *>(scratch), nullptr);
     (void)hipFree(scratch);
     if (rc) return bail(rc);
-    net->winv = static_cast<double *>(w);
   }
   *out = net;
   return DVSG_OK;
@@ -1051,28 +1020,28 @@ int dvsg_locnet_forward_tap_f32x3(const dvsg_locnet_t *net, const float *patches
 int dvsg_conv_gemm_f32(const float *x, const float *wt, const float *bias, const float *res, float *y, int B, int H,
                        int W, int Cin, int Cout, int ksize, int stride, int relu, int res_stride, void *scratch,
                        size_t scratch_bytes, void *stream) {
-  return conv_gemm_op(kF32, 0, x, wt, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
+  return conv_gemm_op(kMathF32, x, wt, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
                       scratch_bytes, stream);
 }
 
 int dvsg_conv_gemm_f16(const void *x, const void *wt, const float *bias, const void *res, void *y, int B, int H,
                        int W, int Cin, int Cout, int ksize, int stride, int relu, int res_stride, void *scratch,
                        size_t scratch_bytes, void *stream) {
-  return conv_gemm_op(kF16, 0, x, wt, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
+  return conv_gemm_op(kMathF16Plain, x, wt, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
                       scratch_bytes, stream);
 }
 
 int dvsg_conv_gemm_f32s(const void *x, const void *wt_pieces, const float *bias, const void *res, void *y, int B, int H,
                         int W, int Cin, int Cout, int ksize, int stride, int relu, int res_stride, void *scratch,
                         size_t scratch_bytes, void *stream) {
-  return conv_gemm_op(kF32, 1, x, wt_pieces, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
+  return conv_gemm_op(kMathF32S, x, wt_pieces, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
                       scratch_bytes, stream);
 }
 
 int dvsg_conv_gemm_f32x3(const float *x, const void *wt_packed, const float *bias, const float *res, float *y, int B, int H,
                          int W, int Cin, int Cout, int ksize, int stride, int relu, int res_stride, void *scratch,
                          size_t scratch_bytes, void *stream) {
-  return conv_gemm_op(kF32, 2, x, wt_packed, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
+  return conv_gemm_op(kMathF32X, x, wt_packed, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
                       scratch_bytes, stream);
 }
 
@@ -1093,7 +1062,7 @@ int dvsg_pieces_to_f32(const void *x, float *y, size_t n, void *stream) {
 int dvsg_conv_gemm_f16s(const void *x, const void *wt_split, const float *bias, const void *res, void *y, int B, int H,
                         int W, int Cin, int Cout, int ksize, int stride, int relu, int res_stride, void *scratch,
                         size_t scratch_bytes, void *stream) {
-  return conv_gemm_op(kF16, 1, x, wt_split, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
+  return conv_gemm_op(kMathF16Pairs, x, wt_split, bias, res, y, B, H, W, Cin, Cout, ksize, stride, relu, res_stride, scratch,
                       scratch_bytes, stream);
 }
 
@@ -1101,7 +1070,7 @@ int dvsg_conv3x3_1x1_f32(const float *x, const float *wt2, const float *bias2, c
                          const float *res, float *y, int B, int H, int W, int Cin, int Cout, int stride, int res_stride,
                          void *stream) {
   DVSG_REQUIRE(x && wt2 && bias2 && wt3 && bias3 && res && y, "dvsg_conv3x3_1x1_f32: NULL pointer");
-  return fused_op("dvsg_conv3x3_1x1_f32", kF32, x, wt2, bias2, wt3, bias3, res, nullptr, nullptr, nullptr, 0, y, B, H, W, Cin,
+  return fused_op("dvsg_conv3x3_1x1_f32", kMathF32, x, wt2, bias2, wt3, bias3, res, nullptr, nullptr, nullptr, 0, y, B, H, W, Cin,
                   Cout, stride, res_stride, stream);
 }
 
@@ -1109,7 +1078,7 @@ int dvsg_conv3x3_1x1_f32x3(const float *x, const void *wt2_packed, const float *
                            const float *res, float *y, int B, int H, int W, int Cin, int Cout, int stride, int res_stride,
                            void *stream) {
   DVSG_REQUIRE(x && wt2_packed && bias2 && wt3_packed && bias3 && res && y, "dvsg_conv3x3_1x1_f32x3: NULL pointer");
-  return fused_op("dvsg_conv3x3_1x1_f32x3", kF32X, x, wt2_packed, bias2, wt3_packed, bias3, res, nullptr, nullptr, nullptr, 0,
+  return fused_op("dvsg_conv3x3_1x1_f32x3", kMathF32X, x, wt2_packed, bias2, wt3_packed, bias3, res, nullptr, nullptr, nullptr, 0,
                   y, B, H, W, Cin, Cout, stride, res_stride, stream);
 }
 
@@ -1118,7 +1087,7 @@ int dvsg_debug_conv3x3_1x1(int prec, const void *x, const void *wt2, const float
                            int H, int W, int Cin, int Cout, int stride, int res_stride, void *stream) {
   DVSG_REQUIRE(prec >= kF32 && prec <= kF32X, "dvsg_debug_conv3x3_1x1: unknown precision %d", prec);
   DVSG_REQUIRE(x && wt2 && bias2 && wt3 && bias3 && y, "dvsg_debug_conv3x3_1x1: NULL pointer");
-  return fused_op("dvsg_debug_conv3x3_1x1", prec, x, wt2, bias2, wt3, bias3, res, sc_x, sc_wt, sc_bias, sc_cin, y, B, H, W,
+  return fused_op("dvsg_debug_conv3x3_1x1", math_of(prec, true), x, wt2, bias2, wt3, bias3, res, sc_x, sc_wt, sc_bias, sc_cin, y, B, H, W,
                   Cin, Cout, stride, res_stride, stream);
 }
 
