@@ -251,7 +251,7 @@ def _check_crop(crop):
 
 def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side=False, channel_order="rgb",
                    as_uint8=False, source_res=False, crop=None, crop_margin=None, crop_min=0.5, crop_info=None,
-                   render_filter="bilinear"):
+                   render_filter="bilinear", border="black"):
     """eval.py:76-124 for one clip, entirely on the device.
 
     frames: [N,h0,w0,3], NumPy or torch.
@@ -279,6 +279,11 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     render_filter="bicubic" (source_res only, else ValueError) renders them with the bicubic filter of a view
     (`LocNet.view`: 16 taps, bytes rounded to nearest; include/dvsg_amd.h, "Views and the render filter"); the default
     "bilinear" is sampler A.  F_t, the pool and the crop's zoom do not depend on it.
+    border="replicate" / "mirror" (source_res only, else ValueError) fill the black border of those renders from the
+    source's edge (include/dvsg_amd.h, "Border modes"; `LocNet.view`); with crop they fill whatever the zoom leaves.
+    border="keep" is a ValueError here: it carries each frame's border over from the frame before, and these renders run
+    after the loop in launches of many frames at once, not one frame at a time in order -- `OnlineStabilizer(border="keep")`
+    (or `online.stabilize_clips`) renders frame by frame and takes it.
 
     crop: every stabilised frame has a black border wherever sampler A's taps leave the frame (at F_t = 0 already its last
     row and column).  None (default) returns the frames as the reference does.  "auto" or a zoom z in (0, 1] renders them
@@ -293,8 +298,11 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     crop = _check_crop(crop)
     from . import _lib
     from ._tensor import device, ptr, stream
-    from .networks import check_render_filter
+    from .networks import check_border, check_render_filter
     check_render_filter(render_filter, bool(source_res))
+    if check_border(border, bool(source_res)) == "keep":
+        raise ValueError("border='keep' needs renders that run one frame at a time in order; stabilize_clip renders its "
+                         "frames in batches after the loop: use OnlineStabilizer(border='keep') or online.stabilize_clips")
     if channel_order not in ("rgb", "bgr"):
         raise ValueError("channel_order must be 'rgb' or 'bgr'")
     if model.locnet is None:
@@ -353,7 +361,7 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
         for b0 in range(0, N, batch):
             b1 = min(N, b0 + batch)
             render_source_into(model, fr[b0:b1], F[b0:b1], T, flip, out[b0:b1], side[b0:b1] if side is not None else None,
-                               zoom[b0:b1] if zoom is not None else None, render_filter)
+                               zoom[b0:b1] if zoom is not None else None, render_filter, border)
         if host:
             out = out.cpu().numpy()
             side = side.cpu().numpy() if side is not None else None
@@ -400,16 +408,22 @@ def _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info):
     return zoom, T
 
 
-def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render_filter="bilinear"):
+def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render_filter="bilinear", border="black"):
     """`dvsg_tps_render_u8` for the uint8 frames src [n,H0,W0,3] (device) and their F_t rows F [n,25,2]: the stabilised
     frames at source size into `out` [n,H0,W0,3] (float32, or uint8: np.uint8(x * 255.) in the channel order of src)
     and, if given, `side` [n,H0,2 W0,3] uint8 = (source bytes | uint8 render).  T [n,2,28] receives the TPS
     coefficients.  One render launch; a uint8 `out` is copied into the right half of `side`.  zoom float32 [n] (device):
-    `dvsg_tps_render_zoom_u8`, the render on the grid scaled by zoom[i] about its centre.  render_filter: the filter of the
-    handle the render is given (`LocNet.view`)."""
+    `dvsg_tps_render_zoom_u8`, the render on the grid scaled by zoom[i] about its centre.  render_filter, border: the filter
+    and the border mode of the handle the render is given (`LocNet.view`).  border="keep" is accepted: this is ONE launch,
+    and the samples it leaves unwritten keep what the caller put into `out` (frame i of the launch does not see frame
+    i - 1: a caller that wants the previous output there renders one frame at a time, as OnlineStabilizer does); with
+    `side` it is a ValueError naming border."""
     from . import _lib
     from ._tensor import ptr, stream
-    net = model.locnet.view(render_filter)
+    from .networks import check_border
+    if check_border(border) == "keep" and side is not None:
+        raise ValueError("border='keep' has no side_by_side layout: the unwritten samples are the caller's `out`")
+    net = model.locnet.view(render_filter, border)
     n, H0, W0 = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
     if side is not None:
         side[:, :, :W0] = src   # np.uint8(v / 255. * 255.) == v for every byte: the unstable half is the source

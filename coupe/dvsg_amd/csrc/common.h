@@ -53,7 +53,8 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 // dvsg_tps_render_u8 (winv_cols / coord: the handle's W^-1 columns and V_src)
 int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
                     int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
-                    const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR /* the handle's or view's */);
+                    const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR /* the handle's or view's */,
+                    int render_border = DVSG_BORDER_BLACK /* likewise */);
 // nv12.hip: dvsg_tps_render_nv12 and, with zoom [n] on the device, dvsg_tps_render_zoom_nv12.  The check makes no HIP call
 // and reads no handle (fn: the entry point its messages name); the launch half assumes it passed.
 int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
@@ -62,7 +63,8 @@ int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv,
 int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream,
-                         const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR);
+                         const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR,
+                         int render_border = DVSG_BORDER_BLACK);
 // crop_kernels.hip: the fused coverage scan of dvsg_tps_coverage_f32 (coord_bstride in floats; 0 = broadcast)
 int tps_coverage_impl(const char *fn, const float *coord, long coord_bstride, const float *T, const float *zoom, int B, int P,
                       int src_H, int src_W, int out_h, int out_w, int32_t *n_border, int32_t *key_min, void *workspace,

@@ -95,11 +95,12 @@ struct dvsg_locnet {
   std::vector<double> calib_mu = std::vector<double>((size_t)48 * 2048, 1.0);
   double calib_rows[48] = {0};
   std::vector<void *> allocs;
-  // A VIEW (dvsg_locnet_view_create) is one of these with nothing in it but `parent` and its own render filter: every entry
+  // A VIEW (dvsg_locnet_view_create) is one of these with nothing in it but `parent` and its own render filter and border: every entry
   // point reads the network and the TPS constants through base() at call time, so a later calibration of the parent is seen
   // through its views.  n_views: the live views of a parent, which dvsg_locnet_destroy refuses to pull the network from under.
   const dvsg_locnet *parent = nullptr;
   int render_filter = DVSG_RENDER_BILINEAR;
+  int render_border = DVSG_BORDER_BLACK;
   mutable std::atomic<int> n_views{0};
 };
 
@@ -942,23 +943,37 @@ int dvsg_locnet_destroy(dvsg_locnet_t *net) {
   return DVSG_OK;
 }
 
-int dvsg_locnet_view_create(const dvsg_locnet_t *net, int render_filter, dvsg_locnet_t **view) {
-  DVSG_REQUIRE(net, "dvsg_locnet_view_create: NULL net");
-  DVSG_REQUIRE(view, "dvsg_locnet_view_create: NULL view");
+// both view constructors; fn: the one its messages name.  Everything is decided before the handle is read or anything allocated.
+static int view_create(const char *fn, const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view) {
+  DVSG_REQUIRE(net, "%s: NULL net", fn);
+  DVSG_REQUIRE(view, "%s: NULL view", fn);
   *view = nullptr;
   DVSG_REQUIRE(render_filter == DVSG_RENDER_BILINEAR || render_filter == DVSG_RENDER_BICUBIC,
-               "dvsg_locnet_view_create: render_filter=%d is neither DVSG_RENDER_BILINEAR (0) nor DVSG_RENDER_BICUBIC (1)",
-               render_filter);
+               "%s: render_filter=%d is neither DVSG_RENDER_BILINEAR (0) nor DVSG_RENDER_BICUBIC (1)", fn, render_filter);
+  DVSG_REQUIRE(render_border >= DVSG_BORDER_BLACK && render_border <= DVSG_BORDER_KEEP,
+               "%s: render_border=%d is none of DVSG_BORDER_BLACK (0), _REPLICATE (1), _MIRROR (2), _KEEP (3)", fn,
+               render_border);
   dvsg_locnet *v = new dvsg_locnet();
   v->calib_mu = std::vector<double>();   // (a view keeps no calibration record of its own)
-  v->parent = base(net);                 // a view of a view is a view of the parent
+  v->parent = base(net);                 // a view of a view is a view of the parent: filter and border are the arguments'
   v->render_filter = render_filter;
+  v->render_border = render_border;
   v->parent->n_views.fetch_add(1);
   *view = v;
   return DVSG_OK;
 }
 
+int dvsg_locnet_view_create(const dvsg_locnet_t *net, int render_filter, dvsg_locnet_t **view) {
+  return view_create("dvsg_locnet_view_create", net, render_filter, DVSG_BORDER_BLACK, view);
+}
+
+int dvsg_locnet_view_create_border(const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view) {
+  return view_create("dvsg_locnet_view_create_border", net, render_filter, render_border, view);
+}
+
 int dvsg_locnet_render_filter(const dvsg_locnet_t *net) { return net ? net->render_filter : DVSG_RENDER_BILINEAR; }
+
+int dvsg_locnet_render_border(const dvsg_locnet_t *net) { return net ? net->render_border : DVSG_BORDER_BLACK; }
 
 int dvsg_locnet_in_channels(const dvsg_locnet_t *net) { return net ? base(net)->c_in : 0; }
 
@@ -1317,7 +1332,7 @@ int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t
                        int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_u8: NULL net");
   return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, nullptr, net->render_filter);
+                         u8_W, u8_x0, stream, nullptr, net->render_filter, net->render_border);
 }
 
 // dvsg_tps_render_u8 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_u8 itself)
@@ -1326,7 +1341,7 @@ int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const ui
                             int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_zoom_u8: NULL net");
   return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, zoom, net->render_filter);
+                         u8_W, u8_x0, stream, zoom, net->render_filter, net->render_border);
 }
 
 // dvsg_tps_render_u8 for NV12 frames (nv12.hip): the same T, then both planes warped at their own sizes in one launch.
@@ -1338,7 +1353,7 @@ int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8
   if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride))
     return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
-                              out_pitch, out_frame_stride, stream, nullptr, net->render_filter);
+                              out_pitch, out_frame_stride, stream, nullptr, net->render_filter, net->render_border);
 }
 
 // dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
@@ -1350,7 +1365,7 @@ int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const 
                                      "dvsg_tps_render_zoom_nv12"))
     return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
-                              out_pitch, out_frame_stride, stream, zoom, net->render_filter);
+                              out_pitch, out_frame_stride, stream, zoom, net->render_filter, net->render_border);
 }
 
 // T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)

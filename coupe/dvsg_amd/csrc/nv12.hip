@@ -234,19 +234,23 @@ __device__ __forceinline__ uint8_t chroma_u8(float v) {
 
 // One output column and kTpsRows rows of one plane (ph x pw samples of C bytes), source and output of the same size.
 // kCubic (a bicubic view): the bicubic filter of warp_device.h behind the same map, bytes rounded to nearest.
-template <int C, bool kCubic = false>
+// kBorder (a view with a border mode): what an invalid sample becomes (warp_device.h, "border modes").
+template <int C, bool kCubic = false, int kBorder = DVSG_BORDER_BLACK>
 __device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, size_t pitch, int ph, int pw, int i0, int j,
                                              const float (&xs)[4], const float (&ys)[4], uint8_t *__restrict__ out,
                                              size_t out_pitch) {
   if constexpr (kCubic) {
     CubicTaps<C> ct[4];
-    cubic_load_rows<C>(src, pitch, ph, pw, ph - i0, xs, ys, ct);  // all 16 row loads in flight
+    cubic_load_rows<C, kBorder>(src, pitch, ph, pw, ph - i0, xs, ys, ct);  // all 16 row loads in flight
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = i0 + r;
       if (i >= ph) break;
+      if constexpr (kBorder == DVSG_BORDER_KEEP) {
+        if (!ct[r].valid) continue;   // the caller's bytes stay
+      }
       float v[C];
-      cubic_blend<C, C == 2>(ct[r], v);
+      cubic_blend<C, C == 2, kBorder>(ct[r], v);
       uint8_t *d = out + (size_t)i * out_pitch + (size_t)j * C;
 #pragma unroll
       for (int c = 0; c < C; ++c) d[c] = cubic_u8(v[c], C == 2 ? 128.5 : 0.5);
@@ -254,17 +258,28 @@ __device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, si
     return;
   }
   TapsA<C> taps[4];
+  [[maybe_unused]] bool use[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     if (i0 + r >= ph) break;
-    plane_a_load<C>(src, pitch, ph, pw, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
+    if constexpr (kBorder != DVSG_BORDER_BLACK)
+      border_a_load<C, C == 2, kBorder>(src, pitch, ph, pw, xs[r], ys[r], taps[r], use[r]);
+    else
+      plane_a_load<C>(src, pitch, ph, pw, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = i0 + r;
     if (i >= ph) break;
+    if constexpr (kBorder == DVSG_BORDER_KEEP) {
+      if (!use[r]) continue;   // the caller's bytes stay
+    }
     float v[C];
     sample_a_blend<C>(taps[r], C, v);
+    if constexpr (kBorder != DVSG_BORDER_BLACK) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = use[r] ? v[c] : 0.0f;
+    }
     uint8_t *d = out + (size_t)i * out_pitch + (size_t)j * C;
     if constexpr (C == 1) {
       d[0] = to_u8((double)v[0]);
@@ -387,6 +402,46 @@ __global__ __launch_bounds__(kThreads) void nv12_render_cubic_kernel(Nv12 s, con
     render_plane<1, true>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
 }
 
+// The NV12 render through a view with a border mode (dvsg_locnet_view_create_border; kBorder = DVSG_BORDER_REPLICATE,
+// _MIRROR or _KEEP), for either filter: nv12_render_cubic_kernel's arguments, tiles and map, render_plane's border mode
+// behind the map.  Kernels of their own again: a handle with DVSG_BORDER_BLACK launches the three kernels above.
+template <bool kZoom, bool kCubic, int kBorder>
+__global__ __launch_bounds__(kThreads) void nv12_render_border_kernel(Nv12 s, const float *__restrict__ coord,
+                                                                      const float *__restrict__ T,
+                                                                      const float *__restrict__ zoom, int H, int W, int P,
+                                                                      float sx_l, float sy_l, float sx_c, float sy_c,
+                                                                      int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                                      uint8_t *__restrict__ out_uv, size_t out_pitch,
+                                                                      size_t out_frame_stride) {
+  static_assert(kBorder != DVSG_BORDER_BLACK, "DVSG_BORDER_BLACK is the kernels without a border parameter");
+  __shared__ float4 sp[64];
+  __shared__ float4 sdy[64];
+  __shared__ float sa[6];
+  const int b = blockIdx.y, t = threadIdx.x;
+  int id = blockIdx.x;
+  const bool chroma = id >= n_l;
+  if (chroma) id -= n_l;
+  const int gx = chroma ? gx_c : gx_l;
+  const int i0 = (id / gx) * kTpsRows;
+  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
+  const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
+  float z = 1.0f;
+  if constexpr (kZoom) z = zoom[b];
+  tps_stage<true, kZoom>(coord, 0, T, b, P, t, i0, step_y, sp, sdy, sa, z);
+  __syncthreads();
+  const int j = (id % gx) * kThreads + t;
+  if (j >= pw) return;
+  float x_t = -1.0f + step_x * (float)j;  // tf.linspace: start + step * i (:94)
+  if constexpr (kZoom) x_t = z * x_t;
+  float xs[4], ys[4];
+  tps_map_rows<true, kZoom>(sp, sdy, sa, P, x_t, step_y, i0, xs, ys, z);
+  const size_t in_off = (size_t)b * s.frame_stride, out_off = (size_t)b * out_frame_stride;
+  if (chroma)
+    render_plane<2, kCubic, kBorder>(s.uv + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_uv + out_off, out_pitch);
+  else
+    render_plane<1, kCubic, kBorder>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
+}
+
 inline int grid_for(size_t items, int cap = 1 << 16) {
   const size_t b = (items + kThreads - 1) / kThreads;
   return (int)(b < (size_t)cap ? (b ? b : 1) : (size_t)cap);
@@ -426,7 +481,7 @@ int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv,
 int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream, const float *zoom,
-                         int render_filter) {
+                         int render_filter, int render_border) {
   const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
   const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(H / 2, kTpsRows);
   DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);
@@ -434,6 +489,15 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
   hipStream_t s = as_stream(stream);
   // algorithmic bytes: both planes once in, once out
   ProfScope prof(kClsTpsWarp, s, 0.0, 3.0 * n * H * W);
+  if (render_border != DVSG_BORDER_BLACK) {   // a view with a border mode: the same grid of workgroups for either filter
+    const dim3 grid((unsigned)(n_l + n_c), n);
+    for_render_border(zoom != nullptr, render_filter == DVSG_RENDER_BICUBIC, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {
+      hipLaunchKernelGGL((nv12_render_border_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
+                         Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
+                         lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y, out_uv, out_pitch, out_frame_stride);
+    });
+    return check_launch("nv12_render_border_kernel");
+  }
   if (render_filter == DVSG_RENDER_BICUBIC) {   // a bicubic view: the same grid of workgroups, 16 taps per sample
     const dim3 grid((unsigned)(n_l + n_c), n);
     if (zoom)

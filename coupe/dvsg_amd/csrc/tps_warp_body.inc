@@ -2,7 +2,9 @@
 // declares the parameters documented there, `constexpr bool kZoom` and `constexpr bool kCubic`; names it has no parameter for
 // (zoom; u_index, u_stride, n_pool, out_index) it declares as constants.  kCubic (tps_render_cubic_kernel: uint8 RGB in,
 // the uint8 output form) swaps what follows the map -- sampler A's four taps -- for the bicubic filter of warp_device.h; the
-// map, the thread layout and the output addresses are this one text's.
+// map, the thread layout and the output addresses are this one text's.  `constexpr int kBorder` (tps_render_border_kernel,
+// the same uint8 form): what an invalid sample becomes (warp_device.h, "border modes"); DVSG_BORDER_BLACK drops every
+// border statement.
   constexpr bool kU8Out = std::is_same<TO, uint8_t>::value;
   static_assert(!kU8Out || (C == 3 && std::is_same<TU, uint8_t>::value), "the uint8 output form reads uint8 RGB frames");
   __shared__ float4 sp[64];      // {px, py, T[0][3+k], T[1][3+k]}
@@ -66,13 +68,16 @@
   if constexpr (kCubic) {
     if (!out && !out_rgb) return;
     CubicTaps<3> ct[4];
-    cubic_load_rows<3>(img, (size_t)W * 3, H, W, out_h - i0, xs, ys, ct);  // all 16 row loads in flight
+    cubic_load_rows<3, kBorder>(img, (size_t)W * 3, H, W, out_h - i0, xs, ys, ct);  // all 16 row loads in flight
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = i0 + r;
       if (i >= out_h) break;
+      if constexpr (kBorder == DVSG_BORDER_KEEP) {
+        if (!ct[r].valid) continue;   // the caller's bytes stay
+      }
       float v[3];
-      cubic_blend<3, false>(ct[r], v);
+      cubic_blend<3, false, kBorder>(ct[r], v);
       if (out_rgb) {
         const float rgb[3] = {v[flip ? 2 : 0], v[1], v[flip ? 0 : 2]};
         store_pix<3>(out_rgb, (out_frame * out_h + i) * out_w + j, 3, rgb);
@@ -81,6 +86,38 @@
         uint8_t *d = out + ((out_frame * out_h + i) * out_row + out_x0 + j) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) d[c] = cubic_u8(v[c], 0.5);
+      }
+    }
+    return;
+  }
+  if constexpr (kBorder != DVSG_BORDER_BLACK) {   // sampler A's blend of the taps the border mode picks
+    if (!out && !out_rgb) return;
+    TapsA<3> taps[4];
+    bool use[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (i0 + r >= out_h) break;
+      border_a_load<3, false, kBorder>(img, (size_t)W * 3, H, W, xs[r], ys[r], taps[r], use[r]);  // all 16 tap loads in flight
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = i0 + r;
+      if (i >= out_h) break;
+      if constexpr (kBorder == DVSG_BORDER_KEEP) {
+        if (!use[r]) continue;   // the caller's bytes stay
+      }
+      float v[3];
+      sample_a_blend<3>(taps[r], 3, v);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = use[r] ? v[c] : 0.0f;
+      if (out_rgb) {
+        const float rgb[3] = {v[flip ? 2 : 0], v[1], v[flip ? 0 : 2]};
+        store_pix<3>(out_rgb, (out_frame * out_h + i) * out_w + j, 3, rgb);
+      }
+      if (out) {
+        uint8_t *d = out + ((out_frame * out_h + i) * out_row + out_x0 + j) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = to_u8((double)v[c]);
       }
     }
     return;

@@ -3,6 +3,7 @@
 // reference graph is a chain of separately rounded float32 ops), and a pixel gets the same bits from either.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "common.h"
 
@@ -125,6 +126,56 @@ __device__ __forceinline__ void sample_a_blend(const TapsA<C> &t, int Cn, float 
 }
 
 // ----------------------------------------------------------------------------------------
+// The border modes of the source-size renders (a view of dvsg_locnet_view_create_border; the header's "Border modes").  A
+// mode decides what an INVALID sample becomes and nothing else: DVSG_BORDER_KEEP does not store it, DVSG_BORDER_REPLICATE
+// and DVSG_BORDER_MIRROR evaluate the handle's filter at the coordinate moved into the plane.  The kernels with a border
+// are instantiations of their own (kBorder != 0); DVSG_BORDER_BLACK is the kernels that were there before.
+// ----------------------------------------------------------------------------------------
+// x (sampler A's pixel coordinate, not NaN) moved into [0, m], m = (float)(pw - 1): one reflection about the edge it left
+// by (MIRROR), then the clamp.  A coordinate already inside keeps its value.
+template <int kBorder>
+__device__ __forceinline__ float border_coord(float x, float m) {
+  if constexpr (kBorder == DVSG_BORDER_MIRROR) x = x < 0.0f ? -x : (x > m ? (m + m) - x : x);
+  return fminf(fmaxf(x, 0.0f), m);
+}
+
+// sample_a_load for a plane of bytes (ph x pw samples of C, rows `pitch` bytes apart; kBias: chroma, (b - 128) / 255) under a
+// border mode.  The taps are x0 = floor(xc) and min(x0 + 1, pw - 1), the upper weight from the UNclipped index -- sampler
+// A's clipped weights would cancel on the edge -- so a valid sample (xc == x, no index clipped) gets sampler A's taps and
+// weights, bit for bit, and one set of four loads serves valid and invalid samples without a divergent branch.  `use`: the
+// blend is the sample's value -- KEEP: the sample is valid (else nothing is stored); REPLICATE / MIRROR: the coordinate is
+// no NaN (else the black value).  Every address lies inside the plane's used bytes.
+template <int C, bool kBias, int kBorder>
+__device__ __forceinline__ void border_a_load(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, float xs, float ys,
+                                              TapsA<C> &t, bool &use) {
+  const float x = ((xs + 1.0f) * (float)pw) / 2.0f;  // :48
+  const float y = ((ys + 1.0f) * (float)ph) / 2.0f;  // :49
+  const bool nan = x != x || y != y;
+  use = kBorder == DVSG_BORDER_KEEP ? sample_a_valid(ph, pw, xs, ys) : !nan;
+  const float xc = nan ? 0.0f : border_coord<kBorder>(x, (float)(pw - 1));
+  const float yc = nan ? 0.0f : border_coord<kBorder>(y, (float)(ph - 1));
+  const float x0f = floorf(xc), y0f = floorf(yc);
+  const int x0 = min((int)x0f, pw - 1), y0 = min((int)y0f, ph - 1);   // (in range already wherever (float)(pw - 1) is exact)
+  const int x1 = min(x0 + 1, pw - 1), y1 = min(y0 + 1, ph - 1);
+  const float wx0 = (x0f + 1.0f) - xc, wx1 = xc - x0f, wy0 = (y0f + 1.0f) - yc, wy1 = yc - y0f;
+  t.wa = wx0 * wy0;  // :85-88
+  t.wb = wx0 * wy1;
+  t.wc = wx1 * wy0;
+  t.wd = wx1 * wy1;
+  const uint8_t *pa = img + (size_t)y0 * pitch + (size_t)x0 * C;  // (x0,y0)
+  const uint8_t *pb = img + (size_t)y1 * pitch + (size_t)x0 * C;  // (x0,y1)
+  const uint8_t *pc = img + (size_t)y0 * pitch + (size_t)x1 * C;  // (x1,y0)
+  const uint8_t *pd = img + (size_t)y1 * pitch + (size_t)x1 * C;  // (x1,y1)
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    t.a.v[c] = kBias ? (float)((int)pa[c] - 128) / 255.0f : (float)pa[c] / 255.0f;
+    t.b.v[c] = kBias ? (float)((int)pb[c] - 128) / 255.0f : (float)pb[c] / 255.0f;
+    t.c.v[c] = kBias ? (float)((int)pc[c] - 128) / 255.0f : (float)pc[c] / 255.0f;
+    t.d.v[c] = kBias ? (float)((int)pd[c] - 128) / 255.0f : (float)pd[c] / 255.0f;
+  }
+}
+
+// ----------------------------------------------------------------------------------------
 // The bicubic filter of the source-size renders (a view with DVSG_RENDER_BICUBIC): sampler A's coordinates and validity,
 // OpenCV's INTER_CUBIC weights (A = -0.75), 4 x 4 taps with edge-replicated indices, rows blended first.  Every operation
 // is a separately rounded float32 one in the order the header states; tests/bicubic_ref.py restates it in NumPy.
@@ -143,8 +194,8 @@ template <int C>
 struct CubicTaps {
   uint32_t raw[4][C];   // row r: byte k C + c = component c of window column k
   float wx[4], wy[4];
-  int d;                // taps' first column minus the window's: -1, 0 or 1
-  bool valid;
+  int d;                // taps' first column minus the window's: -1, 0 or 1 (2 too under a border mode: x0 = pw - 1)
+  bool valid;           // the blend is the sample's value (else 0.0f); under a border mode: border_a_load's `use`
 };
 
 // w[k] for the taps at floor(x) - 1 + k, t = x - floor(x)
@@ -173,14 +224,24 @@ __device__ __forceinline__ void load_bytes_x4(const uint8_t *__restrict__ p, uin
 }
 
 // Coordinates, validity, weights, and the 4 row loads (only ISSUED here, like sample_a_load).  kWide: pw >= 4.
-template <int C, bool kWide>
+// kBorder: steps 3-5 at the coordinate moved into the plane (border_coord; a NaN loads from (0, 0) and blends to 0.0f).
+template <int C, bool kWide, int kBorder = DVSG_BORDER_BLACK>
 __device__ __forceinline__ void cubic_load(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, float xs, float ys,
                                            CubicTaps<C> &t) {
-  const float x = ((xs + 1.0f) * (float)pw) / 2.0f;  // sampler A's (:48-49)
-  const float y = ((ys + 1.0f) * (float)ph) / 2.0f;
+  float x = ((xs + 1.0f) * (float)pw) / 2.0f;  // sampler A's (:48-49)
+  float y = ((ys + 1.0f) * (float)ph) / 2.0f;
   t.valid = sample_a_valid(ph, pw, xs, ys);
-  // a valid sample has 0 <= x0 <= pw - 2 and 0 <= y0 <= ph - 2; an invalid one stores 0 and only needs addresses inside the plane
-  const int x0 = t.valid ? f2i(floorf(x)) : 0, y0 = t.valid ? f2i(floorf(y)) : 0;
+  int x0, y0;
+  if constexpr (kBorder == DVSG_BORDER_BLACK) {
+    // a valid sample has 0 <= x0 <= pw - 2 and 0 <= y0 <= ph - 2; an invalid one stores 0 and only needs addresses inside the plane
+    x0 = t.valid ? f2i(floorf(x)) : 0, y0 = t.valid ? f2i(floorf(y)) : 0;
+  } else {
+    const bool nan = x != x || y != y;
+    if constexpr (kBorder != DVSG_BORDER_KEEP) t.valid = !nan;
+    x = nan ? 0.0f : border_coord<kBorder>(x, (float)(pw - 1));
+    y = nan ? 0.0f : border_coord<kBorder>(y, (float)(ph - 1));
+    x0 = min((int)floorf(x), pw - 1), y0 = min((int)floorf(y), ph - 1);   // 0 <= x0 <= pw - 1
+  }
   cubic_weights(x - (float)x0, t.wx);   // x - x0 is exact
   cubic_weights(y - (float)y0, t.wy);
   if constexpr (kWide) {
@@ -207,7 +268,7 @@ __device__ __forceinline__ void cubic_load(const uint8_t *__restrict__ img, size
 
 // cubic_load for the rows i0 .. i0 + n_rows - 1 (n_rows <= 4) of one output column: every load of the thread in flight
 // together.  Which path a plane takes is decided once, outside the rows (a load under a per-row branch is waited for there).
-template <int C>
+template <int C, int kBorder = DVSG_BORDER_BLACK>
 __device__ __forceinline__ void cubic_load_rows(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, int n_rows,
                                                 const float (&xs)[4], const float (&ys)[4], CubicTaps<C> (&ct)[4]) {
 #ifndef DVSG_CUBIC_BYTE_TAPS
@@ -215,7 +276,7 @@ __device__ __forceinline__ void cubic_load_rows(const uint8_t *__restrict__ img,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (r >= n_rows) break;
-      cubic_load<C, true>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
+      cubic_load<C, true, kBorder>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
     }
     return;
   }
@@ -223,12 +284,13 @@ __device__ __forceinline__ void cubic_load_rows(const uint8_t *__restrict__ img,
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     if (r >= n_rows) break;
-    cubic_load<C, false>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
+    cubic_load<C, false, kBorder>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
   }
 }
 
 // v[c] of one pixel; kBias: the chroma plane's samples, (b - 128) / 255.  An invalid pixel is exactly 0.
-template <int C, bool kBias>
+// kBorder: the window may be two columns off the taps (x0 = pw - 1: the taps are columns pw - 2, pw - 1, pw - 1, pw - 1).
+template <int C, bool kBias, int kBorder = DVSG_BORDER_BLACK>
 __device__ __forceinline__ void cubic_blend(const CubicTaps<C> &t, float (&v)[C]) {
   float h[4][C];
 #pragma unroll
@@ -246,8 +308,13 @@ __device__ __forceinline__ void cubic_blend(const CubicTaps<C> &t, float (&v)[C]
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const float a = p[0][c], b = p[1][c], e = p[2][c], f = p[3][c];
-        p[0][c] = t.d < 0 ? a : b;
-        p[1][c] = t.d < 0 ? a : e;
+        if constexpr (kBorder != DVSG_BORDER_BLACK) {
+          p[0][c] = t.d < 0 ? a : (t.d == 2 ? e : b);
+          p[1][c] = t.d < 0 ? a : (t.d == 2 ? f : e);
+        } else {
+          p[0][c] = t.d < 0 ? a : b;
+          p[1][c] = t.d < 0 ? a : e;
+        }
         p[2][c] = t.d < 0 ? b : f;
         p[3][c] = t.d < 0 ? e : f;
       }
@@ -484,6 +551,23 @@ __device__ __forceinline__ void tps_map_rows(const float4 *sp, const float4 *sdy
 }
 
 inline float lin_step(int n) { return n > 1 ? (1.0f - (-1.0f)) / (float)(n - 1) : 0.0f; }
+
+// launch(kZoom, kCubic, kBorder) with the three as compile-time constants: the instantiation of a border render kernel that
+// a handle's filter and border (REPLICATE, MIRROR or KEEP; the entry point has checked it) and the presence of zoom select
+template <typename F>
+inline void for_render_border(bool zoom, bool cubic, int border, F &&launch) {
+  auto with_border = [&](auto kBorder) {
+    if (zoom && cubic) launch(std::true_type(), std::true_type(), kBorder);
+    else if (zoom) launch(std::true_type(), std::false_type(), kBorder);
+    else if (cubic) launch(std::false_type(), std::true_type(), kBorder);
+    else launch(std::false_type(), std::false_type(), kBorder);
+  };
+  switch (border) {
+    case DVSG_BORDER_REPLICATE: with_border(std::integral_constant<int, DVSG_BORDER_REPLICATE>()); break;
+    case DVSG_BORDER_MIRROR: with_border(std::integral_constant<int, DVSG_BORDER_MIRROR>()); break;
+    default: with_border(std::integral_constant<int, DVSG_BORDER_KEEP>()); break;
+  }
+}
 
 }  // namespace
 }  // namespace dvsg

@@ -224,6 +224,7 @@ __global__ __launch_bounds__(kThreads) void tps_warp_kernel(
     int n_pool = 0, const int *__restrict__ out_index = nullptr, int out_row = 0, int out_x0 = 0, int flip = 0,
     float *__restrict__ out_rgb = nullptr) {
   constexpr bool kZoom = false, kCubic = false;
+  constexpr int kBorder = DVSG_BORDER_BLACK;
   const float *const zoom = nullptr;
 #include "tps_warp_body.inc"
 }
@@ -236,6 +237,7 @@ __global__ __launch_bounds__(kThreads) void tps_warp_zoom_kernel(
     float step_x, float step_y, TO *__restrict__ out, float *__restrict__ xs_out, float *__restrict__ ys_out,
     int out_row = 0, int out_x0 = 0, int flip = 0, float *__restrict__ out_rgb = nullptr) {
   constexpr bool kZoom = true, kCubic = false;
+  constexpr int kBorder = DVSG_BORDER_BLACK;
   const int *const u_index = nullptr, *const out_index = nullptr;   // contiguous frames in, contiguous frames out
   constexpr int u_stride = 0, n_pool = 0;
 #include "tps_warp_body.inc"
@@ -251,6 +253,23 @@ __global__ __launch_bounds__(kThreads) void tps_render_cubic_kernel(
     const float *__restrict__ zoom, int H, int W, int P, int out_h, int out_w, float step_x, float step_y,
     TO *__restrict__ out, int out_row, int out_x0, int flip, float *__restrict__ out_rgb) {
   constexpr bool kCubic = true;
+  constexpr int kBorder = DVSG_BORDER_BLACK;
+  constexpr int Cn = 3;
+  const int *const u_index = nullptr, *const out_index = nullptr;
+  constexpr int u_stride = 0, n_pool = 0;
+  float *const xs_out = nullptr, *const ys_out = nullptr;
+#include "tps_warp_body.inc"
+}
+
+// The uint8 render through a view with a border mode (dvsg_locnet_view_create_border; kBorder = DVSG_BORDER_REPLICATE,
+// _MIRROR or _KEEP): tps_render_cubic_kernel's arguments, grid and map for either filter, the border mode of warp_device.h
+// behind the map.  Kernels of their own again: a handle with DVSG_BORDER_BLACK launches the three kernels above.
+template <bool kZoom, bool kCubic, int kBorder, int C = 3, typename TU = uint8_t, typename TO = uint8_t>
+__global__ __launch_bounds__(kThreads) void tps_render_border_kernel(
+    const TU *__restrict__ U, const float *__restrict__ coord, long coord_bstride, const float *__restrict__ T,
+    const float *__restrict__ zoom, int H, int W, int P, int out_h, int out_w, float step_x, float step_y,
+    TO *__restrict__ out, int out_row, int out_x0, int flip, float *__restrict__ out_rgb) {
+  static_assert(kBorder != DVSG_BORDER_BLACK, "DVSG_BORDER_BLACK is the kernels without a border parameter");
   constexpr int Cn = 3;
   const int *const u_index = nullptr, *const out_index = nullptr;
   constexpr int u_stride = 0, n_pool = 0;
@@ -788,7 +807,7 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 // and / or uint8 out_u8 [B,H,u8_W,3] in columns [u8_x0, u8_x0 + W).  Every argument is checked before the first launch.
 int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
                     int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
-                    const float *zoom, int render_filter) {
+                    const float *zoom, int render_filter, int render_border) {
   DVSG_REQUIRE(winv_cols && coord && F_t && src && T, "dvsg_tps_render_u8: NULL pointer");
   DVSG_REQUIRE(out_f32 || out_u8, "dvsg_tps_render_u8: neither out_f32 nor out_u8 given");
   DVSG_REQUIRE(B >= 1 && B <= 65535, "dvsg_tps_render_u8: n=%d outside [1, 65535]", B);
@@ -802,6 +821,13 @@ int tps_render_impl(const double *winv_cols, const float *coord, const float *F_
   hipStream_t s = as_stream(stream);
   // algorithmic bytes: the uint8 frame once, then 3 B (uint8) and / or 12 B (float32) per output pixel
   ProfScope prof(kClsTpsWarp, s, 0.0, (double)B * H * W * (3.0 + (out_u8 ? 3.0 : 0.0) + (out_f32 ? 12.0 : 0.0)));
+  if (render_border != DVSG_BORDER_BLACK) {   // a view with a border mode: the same grid of workgroups for either filter
+    for_render_border(zoom != nullptr, render_filter == DVSG_RENDER_BICUBIC, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {
+      hipLaunchKernelGGL((tps_render_border_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s, src, coord, 0L, T,
+                         zoom, H, W, P, H, W, sx, sy, out_u8, u8_W, u8_x0, channel_flip ? 1 : 0, out_f32);
+    });
+    return check_launch("tps_render_border_kernel");
+  }
   if (render_filter == DVSG_RENDER_BICUBIC) {   // a bicubic view: the same grid of workgroups, 16 taps per pixel
     if (zoom)
       hipLaunchKernelGGL(tps_render_cubic_kernel<true>, grid, dim3(kThreads), 0, s, src, coord, 0L, T, zoom, H, W, P, H, W, sx,

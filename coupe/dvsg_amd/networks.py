@@ -51,6 +51,20 @@ def check_render_filter(render_filter, source_size_render=True):
     return render_filter
 
 
+RENDER_BORDERS = {"black": 0, "replicate": 1, "mirror": 2, "keep": 3}   # DVSG_BORDER_BLACK, _REPLICATE, _MIRROR, _KEEP
+
+
+def check_border(border, source_size_render=True):
+    """border argument -> its name.  Any border but "black" where no source-size render happens (RGB at the model's size,
+    float frames) is a ValueError that names source_res: only the source-size renders have a border mode."""
+    if not isinstance(border, str) or border not in RENDER_BORDERS:
+        raise ValueError("border must be 'black', 'replicate', 'mirror' or 'keep', got %r" % (border,))
+    if border != "black" and not source_size_render:
+        raise ValueError("border=%r fills the border of the source-size render only: it needs source_res=True (uint8 frames) "
+                         "or frame_format='nv12'; frames at the model's size keep sampler A's black border" % (border,))
+    return border
+
+
 class LocNet(object):
     """Owns the device-side network (`dvsg_locnet_t`) and one growable workspace per stream that uses it."""
 
@@ -73,23 +87,25 @@ class LocNet(object):
         _lib.call("dvsg_locnet_create", n, c_names, c_data, c_nd,
                   dims.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(handle))
         self.handle = handle
-        self._views = {}   # render filter -> view handle (dvsg_locnet_view_create), made on first use
+        self._views = {}   # (render filter, border) -> view handle (dvsg_locnet_view_create_border), made on first use
         self._keep = None  # the library copied everything to the device
         self._ws = None
         self.in_channels = _lib.load().dvsg_locnet_in_channels(self.handle)
 
-    def view(self, render_filter="bilinear"):
-        """The handle the source-size renders take for `render_filter`: this network itself for "bilinear", else a view of it
-        (`dvsg_locnet_view_create`: the same network, nothing copied, its own filter), made once per filter and kept until
-        the network goes."""
+    def view(self, render_filter="bilinear", border="black"):
+        """The handle the source-size renders take for `render_filter` and `border`: this network itself for ("bilinear",
+        "black"), else a view of it (`dvsg_locnet_view_create_border`: the same network, nothing copied, its own filter and
+        border mode), made once per pair and kept until the network goes."""
         check_render_filter(render_filter)
-        if render_filter == "bilinear":
+        check_border(border)
+        if render_filter == "bilinear" and border == "black":
             return self.handle
-        v = self._views.get(render_filter)
+        v = self._views.get((render_filter, border))
         if v is None:
             v = ctypes.c_void_p()
-            _lib.call("dvsg_locnet_view_create", self.handle, RENDER_FILTERS[render_filter], ctypes.byref(v))
-            self._views[render_filter] = v
+            _lib.call("dvsg_locnet_view_create_border", self.handle, RENDER_FILTERS[render_filter], RENDER_BORDERS[border],
+                      ctypes.byref(v))
+            self._views[(render_filter, border)] = v
         return v
 
     def __del__(self):

@@ -102,6 +102,19 @@ class OnlineStabilizer(object):
     to nearest, the same black border).  The pool, F_t, the history and the crop's zoom are identical for both.  "bicubic"
     without a source-size render (RGB at the model's size) raises ValueError, as does a float frame pushed into it.
 
+    border: what the source-size render (source_res=True or frame_format="nv12", either filter, with and without crop)
+    makes of a sample whose taps leave the source (include/dvsg_amd.h, "Border modes").  "black" (default): 0, luma 0 /
+    chroma 128.  "replicate" / "mirror": the filter evaluated at the coordinate clamped into / reflected once about the
+    edge of the source; they only select the view the render calls are given (`LocNet.view`).  "keep": such a sample is
+    not written, so it keeps what the stream showed there before.  Each ring owns a persistent output surface at its
+    source size (allocated on first use, again when the stream's source size changes); a step renders into it and returns
+    a fresh copy.  The surface restarts from the source bytes of frame f (float32 outputs: `dvsg_frames_u8_to_f32` of them,
+    in the output's channel order) before f is rendered on the stream's step 0, after `reset(sid)`, and after a device-detected
+    scene cut at f -- the last decided on the device from `dvsg_scene_step_f32`'s `cut` output by a masked copy, nothing
+    synchronised.  The valid samples, the pool, F_t, the history and the crop's zoom are identical for every border; crop
+    composes as it is, the border mode fills whatever the zoom leaves.  A border other than "black" without a
+    source-size render raises ValueError, as does "keep" with side_by_side.
+
     crop: every output frame has a black border (luma 0 / chroma 128 in NV12) wherever sampler A's taps leave the source.
     None (default) returns the frames as they are.  A zoom z in (0, 1] renders every frame of every stream on the output
     grid scaled by z about its centre; nothing is scanned.  "auto" keeps ONE zoom per stream on the device and lowers it
@@ -136,11 +149,15 @@ class OnlineStabilizer(object):
 
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
                  as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None,
-                 crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1, render_filter="bilinear"):
+                 crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1, render_filter="bilinear",
+                 border="black"):
         from . import _lib
         from ._tensor import device
-        from .networks import check_render_filter
+        from .networks import check_border, check_render_filter
         check_render_filter(render_filter, bool(source_res) or frame_format == "nv12")
+        check_border(border, bool(source_res) or frame_format == "nv12")
+        if border == "keep" and side_by_side:
+            raise ValueError("border='keep' has no side_by_side layout: the surface a stream keeps is its output frame")
         crop = _check_crop(crop)
         scene_cut = _check_scene_cut(scene_cut)
         if isinstance(scene_min_len, bool) or not isinstance(scene_min_len, (int, np.integer)) or scene_min_len < 0:
@@ -180,7 +197,10 @@ class OnlineStabilizer(object):
         self.flip = 1 if channel_order == "bgr" else 0
         self.side_by_side, self.as_uint8, self.source_res = bool(side_by_side), bool(as_uint8), bool(source_res)
         self.frame_format, self.yuv_matrix = frame_format, YUV_MATRICES[yuv_matrix]
-        self.render_filter = render_filter
+        self.render_filter, self.border = render_filter, border
+        self._keep = {}           # border="keep": ring -> the stream's persistent output surface, at its source size
+        self._keep_fresh = set()  # rings whose next frame is a step 0: the surface restarts from that frame's source bytes
+        self._cut = None          # int32 [B] on the device: the `cut` output of this step's dvsg_scene_step_f32
         dev = device()
         self.pool = torch.empty((self.max_streams * self.frames_per_stream, self.h, self.w, 3), dtype=torch.float32,
                                 device=dev)
@@ -237,6 +257,8 @@ class OnlineStabilizer(object):
             self._crop_zoom[ring] = self.crop_start
         if self._scene is not None:
             self._scene[ring].zero_()
+        if self.border == "keep":
+            self._keep_fresh.add(ring)
 
     def reset(self, sid):
         """The caller's own cut (a decoder's flag, an edit list): the next frame of the stream is step 0 of eval.py, as if the
@@ -252,6 +274,7 @@ class OnlineStabilizer(object):
         ring, _ = self._stream(sid)
         del self._streams[sid]
         self._crop_last.pop(sid, None)
+        self._keep.pop(ring, None)
         self._free.append(ring)
         self._free.sort()
 
@@ -361,6 +384,34 @@ class OnlineStabilizer(object):
                   self._scene_skip, S, ptr(self._scene), self.max_streams, self._scene_thr, self.scene_min_len,
                   ptr(self._crop_zoom) if self._crop_auto else None, self.crop_start, ptr(table), ptr(out_slots), ptr(cut),
                   ptr(ws), ws.numel() * 4, stream())
+        self._cut = cut
+
+    def _keep_surfaces(self, entries, i, j, first):
+        """border="keep": the output surfaces of batch rows [i, j) as one tensor to render into, and what to do after the
+        render.  first [n, ...]: what a row's surface restarts from (its source frame in the output's form).  A surface is
+        (re)started here on the host's word -- a new ring, reset(), another source size -- or, after a device-detected cut,
+        by a masked copy on this step's `cut` flags.  Returns (out, done): render into out [n, ...], then done() gives the
+        fresh copies to hand out (and stores the rendered rows back into their surfaces)."""
+        surfs = []
+        for b in range(i, j):
+            ring, f = entries[b][4], first[b - i]
+            s = self._keep.get(ring)
+            if s is None or s.shape != f.shape or s.dtype != f.dtype or ring in self._keep_fresh:
+                s = self._keep[ring] = f.clone(memory_format=torch.contiguous_format)
+                self._keep_fresh.discard(ring)
+            elif self._cut is not None:
+                s.copy_(torch.where(self._cut[b] != 0, f, s))
+            surfs.append(s)
+        if len(surfs) == 1:   # the surface itself is the launch's output
+            out = surfs[0].unsqueeze(0)
+            return out, out.clone
+        out = torch.stack(surfs)
+
+        def done():
+            for s, o in zip(surfs, out):
+                s.copy_(o)
+            return out
+        return out, done
 
     def step(self, frames):
         """One step of every stream in `frames` ({sid: frame}); returns {sid: output}."""
@@ -497,13 +548,26 @@ class OnlineStabilizer(object):
     def _render_source(self, entries, groups):
         """Egress of a source_res step: per source size, one `dvsg_tps_render_u8` launch that warps the uint8 frames by
         this step's F_t rows (contiguous: a group is a contiguous batch range) at their own size."""
+        from . import _lib
+        from ._tensor import ptr, stream
         res = {}
         for i, j, src in groups:
             n, H0, W0 = j - i, int(src.shape[1]), int(src.shape[2])
-            out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
+            done = None
+            if self.border == "keep":   # (no side_by_side): the streams' own surfaces, restarted from the source where due
+                first = src
+                if not self.as_uint8:   # the float32 frame the render's own samples are taken from (torch's / is not that)
+                    first = torch.empty((n, H0, W0, 3), dtype=torch.float32, device=src.device)
+                    _lib.call("dvsg_frames_u8_to_f32", ptr(src), n * H0 * W0, self.flip, ptr(first), stream())
+                out, done = self._keep_surfaces(entries, i, j, first)
+            else:
+                out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
             side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
             zoom = self._step_zoom(entries, i, j, [(H0, W0)]) if self.crop is not None else None
-            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, self.render_filter)
+            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, self.render_filter,
+                               self.border)
+            if done is not None:
+                out = done()
             if any(entries[b][2] for b in range(i, j)):
                 out_h = out.cpu().numpy()
                 side_h = side.cpu().numpy() if side is not None else None
@@ -559,10 +623,10 @@ class OnlineStabilizer(object):
         for e in entries:
             self._streams[e[1]][1] += 1
         res = {}
-        net = self.model.locnet.view(self.render_filter)
+        net = self.model.locnet.view(self.render_filter, self.border)
         for i, j, src in groups:
             H0, W0 = entries[i][0]
-            out = torch.empty_like(src)
+            out, done = self._keep_surfaces(entries, i, j, src) if self.border == "keep" else (torch.empty_like(src), None)
             if self.crop is None:
                 _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * W0, W0,
                           3 * H0 // 2 * W0, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * W0, W0,
@@ -572,6 +636,8 @@ class OnlineStabilizer(object):
                 _lib.call("dvsg_tps_render_zoom_nv12", net, ptr(self._F[i:j]), ptr(src),
                           ptr(src) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]), ptr(out),
                           ptr(out) + H0 * W0, W0, 3 * H0 // 2 * W0, stream())
+            if done is not None:
+                out = done()
             out_h = out.cpu().numpy() if any(entries[b][2] for b in range(i, j)) else None
             for b in range(i, j):
                 res[entries[b][1]] = out_h[b - i] if entries[b][2] else out[b - i]

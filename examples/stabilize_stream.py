@@ -77,6 +77,9 @@ def main():
     ap.add_argument("--scene-cut", type=float, default=None, metavar="THR", help="detect scene cuts: a threshold in (0, 1]")
     ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"],
                     help="filter of the source-size render; bicubic with --format rgb turns source_res on")
+    ap.add_argument("--border", default="black", choices=["black", "replicate", "mirror", "keep"],
+                    help="what the source-size render makes of samples outside the source; anything but black with "
+                    "--format rgb turns source_res on, and keep drops the side-by-side frame")
     ap.add_argument("--skip-length", default=None, metavar="A,B,...",
                     help="the window's frame offsets, oldest first (default: the reference's 0,16,24,28,30,31,32)")
     args = ap.parse_args()
@@ -91,12 +94,13 @@ def main():
     nv12 = args.format == "nv12"
     if nv12:
         stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop,
-                                render_filter=args.render_filter, **scene, **window)
+                                render_filter=args.render_filter, border=args.border, **scene, **window)
         make = synthetic_nv12_source
     else:
-        stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=True, as_uint8=True,
-                                crop=crop, source_res=args.render_filter != "bilinear", render_filter=args.render_filter,
-                                **scene, **window)
+        stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=args.border != "keep",
+                                as_uint8=True, crop=crop,
+                                source_res=args.render_filter != "bilinear" or args.border != "black",
+                                render_filter=args.render_filter, border=args.border, **scene, **window)
         make = synthetic_source
     H0, W0 = args.height * 3 // 2, args.width * 3 // 2
     if nv12:
@@ -111,6 +115,9 @@ def main():
         if k == 0 and nv12:
             out = next(iter(outs.values()))
             print("per stream and step: stabilised NV12 surface", out.shape, out.dtype)
+        elif k == 0 and not stab.side_by_side:
+            out = next(iter(outs.values()))
+            print("per stream and step: stabilised", out.shape, out.dtype)
         elif k == 0:
             out, side = next(iter(outs.values()))
             print("per stream and step: stabilised", out.shape, out.dtype, "| side-by-side", side.shape, side.dtype)

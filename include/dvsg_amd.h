@@ -194,6 +194,46 @@ int dvsg_locnet_workspace_bytes(const dvsg_locnet_t *net, int B, int H, int W, s
 int dvsg_locnet_view_create(const dvsg_locnet_t *net, int render_filter, dvsg_locnet_t **view);
 int dvsg_locnet_render_filter(const dvsg_locnet_t *net);
 
+/* Border modes.  What the four source-size renders make of an INVALID sample (step 2 above) is, like the filter, a
+ * property of the handle they are given: a view carries a filter AND a border.  Both functions are host-side: no stream,
+ * no device work, everything decided before anything is allocated.
+ *   dvsg_locnet_view_create_border  dvsg_locnet_view_create with a border mode; dvsg_locnet_view_create(net, f, &v) is
+ *          dvsg_locnet_view_create_border(net, f, DVSG_BORDER_BLACK, &v).  The view rules are the ones above: a view of a
+ *          view is a view of the parent with the filter and border of ITS arguments (nothing inherited), calibrating
+ *          through a view and destroying a parent with live views are refused.  An unknown border is
+ *          DVSG_ERR_INVALID_ARG ("render_border=<n>").
+ *   dvsg_locnet_render_border  the handle's border: 0 for every handle of dvsg_locnet_create, for NULL, and for the
+ *          views of dvsg_locnet_view_create.
+ * A border mode decides what an invalid sample becomes and nothing else: the set of valid samples, T, the TPS map, the
+ * coverage scan (dvsg_tps_coverage_*) and the crop's zoom are the same bits for every mode.  The rule is applied per
+ * plane of ph x pw samples (RGB, NV12 luma, NV12 chroma); x, y and validity are steps 1-2 of the bicubic paragraph, i.e.
+ * sampler A's coordinates, for both filters.  Every float32 operation is rounded on its own.
+ *   Valid samples.  The bits of DVSG_BORDER_BLACK, for every mode and filter.
+ *   Black (DVSG_BORDER_BLACK).  The renders as their own paragraphs and the filter's describe them: an invalid sample is
+ *      byte 0 (RGB, luma) / 128 (chroma).  The launches of a handle with border 0 are the kernels without a border.
+ *   Keep (DVSG_BORDER_KEEP).  An invalid sample, NaN included, is NOT WRITTEN: out_u8 / out_f32, out_y / out_uv keep what
+ *      the caller left there.  Each plane decides on its own validity (a luma sample may be written where the chroma
+ *      sample over it is not).  Row bytes beyond W and columns outside [u8_x0, u8_x0 + W) remain unwritten, as always.
+ *   Replicate (DVSG_BORDER_REPLICATE) and mirror (DVSG_BORDER_MIRROR).  A NaN coordinate (x or y) gives the black value
+ *      (0.0f; byte 0 / 128).  Otherwise, with m = (float)(pw - 1): xr = x (replicate), or
+ *      xr = x < 0 ? -x : (x > m ? (m + m) - x : x) (mirror: ONE reflection); xc = fminf(fmaxf(xr, 0), m); the same for y
+ *      with ph.  The sample is the handle's filter evaluated at (xc, yc):
+ *        bilinear  x0 = (int)floorf(xc); taps x0 and min(x0 + 1, pw - 1); weights (x0f + 1) - xc and xc - x0f -- the upper
+ *                  weight from the UNclipped index (sampler A's clipped weights would cancel on the edge) --; the same
+ *                  for y; wa = wx0 wy0 on (x0, y0), wb = wx0 wy1 on (x0, y1), wc = wx1 wy0 on (x1, y0), wd = wx1 wy1 on
+ *                  (x1, y1); v = ((wa a + wb b) + wc c) + wd d, sampler A's blend; bytes truncate as in the bilinear
+ *                  render (chroma rounds at 128.5 as it does there).  On a valid sample this IS sampler A, bit for bit.
+ *        bicubic   steps 3-6 of the bicubic paragraph at (xc, yc): its taps are edge-replicated already, its bytes round
+ *                  to nearest.
+ *      A plane with pw == 1 or ph == 1 is filled from its single column or row.  No load touches a byte outside the
+ *      pw * C used bytes of the source row it reads. */
+#define DVSG_BORDER_BLACK 0
+#define DVSG_BORDER_REPLICATE 1
+#define DVSG_BORDER_MIRROR 2
+#define DVSG_BORDER_KEEP 3
+int dvsg_locnet_view_create_border(const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view);
+int dvsg_locnet_render_border(const dvsg_locnet_t *net);
+
 /* patches [B,H,W,c_in] in [0,1] -> F_t [B,25,2].  float32 storage, exact-f32 MFMA
  * (v_mfma_f32_32x32x2_f32) accumulation.  c_in != 21: conv1 is the same arithmetic in the root-conv kernel. */
 int dvsg_locnet_forward_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W,

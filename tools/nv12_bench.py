@@ -13,7 +13,12 @@ One JSON line per measurement.
 
 --render-filter bicubic renders through a bicubic view of the network (both renders; every record names the filter).
 
-    python tools/nv12_bench.py [--reps 20] [--render-filter bilinear|bicubic] [--out FILE]
+--border NAME renders through a view with that border mode instead (every record names it); --border all keeps the pairs
+above on "black" and adds, per size and n, both renders through a view of EVERY border mode, alternating inside every
+round, and the copy that OnlineStabilizer(border="keep") adds per frame (a clone of the stream's output surface).
+
+    python tools/nv12_bench.py [--reps 20] [--render-filter bilinear|bicubic] [--border black|replicate|mirror|keep|all]
+                               [--out FILE]
 """
 import argparse
 import json
@@ -31,18 +36,20 @@ def main():
     ap.add_argument("--model-height", type=int, default=288)
     ap.add_argument("--model-width", type=int, default=512)
     ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"])
+    ap.add_argument("--border", default="black", choices=["black", "replicate", "mirror", "keep", "all"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import torch
     import inputs
     import nv12_ref
     from coupe.dvsg_amd import _lib
-    from coupe.dvsg_amd.networks import LocNet
+    from coupe.dvsg_amd.networks import RENDER_BORDERS, LocNet
     from coupe.dvsg_amd.weights import make_synthetic_weights
     if not torch.cuda.is_available():
         raise SystemExit("nv12_bench needs the GPU")
     net = LocNet(make_synthetic_weights(seed=0))
-    handle = net.view(args.render_filter)
+    border = "black" if args.border == "all" else args.border
+    handle = net.view(args.render_filter, border)
     s = lambda: torch.cuda.current_stream().cuda_stream
     h, w, M = args.model_height, args.model_width, 1   # BT.709
     lines = []
@@ -64,7 +71,7 @@ def main():
                 per[name].append(e0.elapsed_time(e1) / args.reps)
         for name, _ in versions:
             v = sorted(per[name])
-            rec = dict(what=what, version=name, render_filter=args.render_filter, frames=n, height=H, width=W, ms_median=round(v[3], 4), ms_min=round(v[0], 4),
+            rec = dict(what=what, version=name, render_filter=args.render_filter, border=name if name in RENDER_BORDERS else border, frames=n, height=H, width=W, ms_median=round(v[3], 4), ms_min=round(v[0], 4),
                        ms_max=round(v[-1], 4), us_per_frame=round(1e3 * v[3] / n, 2))
             print(json.dumps(rec), flush=True)
             lines.append(rec)
@@ -116,6 +123,18 @@ def main():
                                      ("dvsg_frames_nv12_to_rgb_u8 + dvsg_frames_ingest_u8", ingest_rgb)])
             pair("render", n, H, W, [("dvsg_tps_render_nv12", render_nv12), ("dvsg_tps_render_u8 (u8 -> u8)", render_rgb)])
             pair("ingest + render", n, H, W, [("nv12", route_nv12), ("rgb route", route_rgb)])
+            if args.border == "all":
+                def through(call, name):
+                    view = net.view(args.render_filter, name)
+                    if call == "nv12":
+                        return lambda: _lib.call("dvsg_tps_render_nv12", view, F.data_ptr(), y, uv, W, fs, n, H, W, T.data_ptr(),
+                                                 out.data_ptr(), out.data_ptr() + H * W, W, fs, s())
+                    return lambda: _lib.call("dvsg_tps_render_u8", view, F.data_ptr(), rgb.data_ptr(), n, H, W, 0, T.data_ptr(),
+                                             None, out8.data_ptr(), W, 0, s())
+                pair("render borders: dvsg_tps_render_nv12", n, H, W,
+                     [(b, through("nv12", b)) for b in RENDER_BORDERS] + [("keep's copy (clone)", out.clone)])
+                pair("render borders: dvsg_tps_render_u8", n, H, W,
+                     [(b, through("u8", b)) for b in RENDER_BORDERS] + [("keep's copy (clone)", out8.clone)])
             del src, out, rgb, out8
     if args.out:
         with open(args.out, "a") as fh:

@@ -12,8 +12,12 @@ One JSON line per measurement.
 
 --render-filter bicubic measures the renders through a bicubic view of the network (every record names its filter).
 
+--border NAME measures them through a view with that border mode (every record names it); --border all runs part 1 once
+per border mode and part 2's source_res runs once per border mode ("keep" includes its copy of the output surface).
+
     python tools/source_res_bench.py [--steps 30] [--warmup 5] [--sources 1080x1920,2160x3840] [--streams 1,4,16]
-                                     [--render-filter bilinear|bicubic] [--out FILE]
+                                     [--render-filter bilinear|bicubic] [--border black|replicate|mirror|keep|all]
+                                     [--out FILE]
 """
 import argparse
 import ctypes
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--streams", default="1,4,16")
     ap.add_argument("--precision", default="f32")
     ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"])
+    ap.add_argument("--border", default="black", choices=["black", "replicate", "mirror", "keep", "all"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 1 or args.reps < 1:
@@ -56,7 +61,7 @@ def main():
     model = StabNet(h, w).load_weights(make_synthetic_weights(seed=0))
     model.get_evaluation_model(7)
     model.precision = args.precision
-    handle = model.locnet.view(args.render_filter)
+    borders = ["black", "replicate", "mirror", "keep"] if args.border == "all" else [args.border]
     lines = []
 
     def emit(rec):
@@ -97,35 +102,37 @@ def main():
         warp = torch.empty_like(U)
         coord = torch.from_numpy(np.ascontiguousarray(np.tile(V_SRC[None], (n, 1, 1)))).cuda()
 
-        def render():
-            _lib.call("dvsg_tps_render_u8", handle, F.data_ptr(), src.data_ptr(), n, H0, W0, 1, T.data_ptr(), 0,
-                      u8.data_ptr(), W0, 0, s())
-
         def three():
             _lib.call("dvsg_frames_u8_to_f32", src.data_ptr(), n * H0 * W0, 1, U.data_ptr(), s())
             _lib.call("dvsg_tps_warp_f32", U.data_ptr(), coord.data_ptr(), T.data_ptr(), n, H0, W0, 3, 25, H0, W0,
                       warp.data_ptr(), 0, 0, s())
             _lib.call("dvsg_frames_f32_to_u8", warp.data_ptr(), n, H0, W0, 1, u8.data_ptr(), W0, 0, s())
-        t_render, t_three = timed(render), timed(three)
-        # the render's warp kernel alone (class 6), with its algorithmic bytes
-        _lib.check(lib.dvsg_prof_begin(6), "dvsg_prof_begin")
-        for _ in range(args.reps):
-            render()
-        ms, cnt, fl, by = ctypes.c_double(), ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
-        _lib.check(lib.dvsg_prof_end(ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by)),
-                   "dvsg_prof_end")
-        k_ms = ms.value / max(cnt.value, 1)
-        emit({"what": "render_vs_three_launches", "render_filter": args.render_filter, "H0": H0, "W0": W0, "n": n,
-              "render_us_per_frame": 1e3 * t_render / n, "three_launch_us_per_frame": 1e3 * t_three / n,
-              "speedup": t_three / t_render, "render_kernel_us_per_frame": 1e3 * k_ms / n,
-              "render_kernel_GBps": by.value / max(cnt.value, 1) / (k_ms * 1e-3) / 1e9 if k_ms > 0 else None})
+        for border in borders:
+            handle = model.locnet.view(args.render_filter, border)
+
+            def render():
+                _lib.call("dvsg_tps_render_u8", handle, F.data_ptr(), src.data_ptr(), n, H0, W0, 1, T.data_ptr(), 0,
+                          u8.data_ptr(), W0, 0, s())
+            t_render, t_three = timed(render), timed(three)
+            # the render's warp kernel alone (class 6), with its algorithmic bytes
+            _lib.check(lib.dvsg_prof_begin(6), "dvsg_prof_begin")
+            for _ in range(args.reps):
+                render()
+            ms, cnt, fl, by = ctypes.c_double(), ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+            _lib.check(lib.dvsg_prof_end(ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by)),
+                       "dvsg_prof_end")
+            k_ms = ms.value / max(cnt.value, 1)
+            emit({"what": "render_vs_three_launches", "render_filter": args.render_filter, "border": border, "H0": H0, "W0": W0,
+                  "n": n, "render_us_per_frame": 1e3 * t_render / n, "three_launch_us_per_frame": 1e3 * t_three / n,
+                  "speedup": t_three / t_render, "render_kernel_us_per_frame": 1e3 * k_ms / n,
+                  "render_kernel_GBps": by.value / max(cnt.value, 1) / (k_ms * 1e-3) / 1e9 if k_ms > 0 else None})
     # ---- 2. end to end
     for size, bank in banks.items():
         H0, W0 = (int(v) for v in size.split("x"))
         for K in (int(v) for v in args.streams.split(",")):
-            for source_res in (False, True):
+            for source_res, border in [(False, "black")] + [(True, b) for b in borders]:
                 on = OnlineStabilizer(model, max_streams=K, as_uint8=True, source_res=source_res,
-                                      render_filter=args.render_filter if source_res else "bilinear")
+                                      render_filter=args.render_filter if source_res else "bilinear", border=border)
                 sids = [on.open() for _ in range(K)]
 
                 def feed(k):
@@ -138,8 +145,8 @@ def main():
                     on.step(feed(args.warmup + k))
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
-                emit({"what": "online", "render_filter": on.render_filter, "model": [h, w], "H0": H0, "W0": W0, "K": K,
-                      "source_res": source_res,
+                emit({"what": "online", "render_filter": on.render_filter, "border": border, "model": [h, w], "H0": H0,
+                      "W0": W0, "K": K, "source_res": source_res,
                       "precision": args.precision, "steps": args.steps, "frames_per_s": K * args.steps / dt,
                       "ms_per_frame": 1e3 * dt / (K * args.steps)})
                 del on
