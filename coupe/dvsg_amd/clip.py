@@ -168,9 +168,10 @@ def _zoom_tensor(zoom, n, dev):
     return z.contiguous()
 
 
-def _coverage(model, F, src_hw, out_hw, zoom, T=None):
+def _coverage(model, F, src_hw, out_hw, zoom, T=None, net=None):
     """`dvsg_tps_coverage_net_f32` over all rows of F [N,25,2] (device), 65535 at a time -> int32 [2,N] on the device
-    (n_border | key_min); T [N,2,28], if given, receives the TPS coefficients."""
+    (n_border | key_min); T [N,2,28], if given, receives the TPS coefficients.  net: the handle the scan is given (default the
+    network itself); a shaped view (`LocNet.view`) scans the warp its render draws."""
     import ctypes
     from . import _lib
     from ._tensor import ptr, stream
@@ -184,7 +185,7 @@ def _coverage(model, F, src_hw, out_hw, zoom, T=None):
     ws = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=F.device)
     for b0 in range(0, N, 65535):
         b1 = min(N, b0 + 65535)
-        _lib.call("dvsg_tps_coverage_net_f32", model.locnet.handle, ptr(F[b0:b1]), ptr(zoom[b0:b1]) if zoom is not None else None,
+        _lib.call("dvsg_tps_coverage_net_f32", model.locnet.handle if net is None else net, ptr(F[b0:b1]), ptr(zoom[b0:b1]) if zoom is not None else None,
                   b1 - b0, int(sh), int(sw), oh, ow, ptr(T[b0:b1]), ptr(res[0, b0:b1]), ptr(res[1, b0:b1]), ptr(ws),
                   ws.numel() * 8, stream())
     return res
@@ -251,7 +252,7 @@ def _check_crop(crop):
 
 def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side=False, channel_order="rgb",
                    as_uint8=False, source_res=False, crop=None, crop_margin=None, crop_min=0.5, crop_info=None,
-                   render_filter="bilinear", border="black"):
+                   render_filter="bilinear", border="black", strength=1.0, rigidity=0.0, shape_model="affine"):
     """eval.py:76-124 for one clip, entirely on the device.
 
     frames: [N,h0,w0,3], NumPy or torch.
@@ -284,6 +285,10 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     border="keep" is a ValueError here: it carries each frame's border over from the frame before, and these renders run
     after the loop in launches of many frames at once, not one frame at a time in order -- `OnlineStabilizer(border="keep")`
     (or `online.stabilize_clips`) renders frame by frame and takes it.
+    strength, rigidity, shape_model (source_res only, else ValueError): how much of each frame's warp those renders apply
+    (include/dvsg_amd.h, "Warp shaping"; `OnlineStabilizer` describes them).  They select the view the renders AND the
+    scans of crop are given, so the clip's one zoom of crop="auto" is the zoom of the shaped warps.  The loop, F_t and the
+    pool do not depend on them.
 
     crop: every stabilised frame has a black border wherever sampler A's taps leave the frame (at F_t = 0 already its last
     row and column).  None (default) returns the frames as the reference does.  "auto" or a zoom z in (0, 1] renders them
@@ -298,8 +303,9 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     crop = _check_crop(crop)
     from . import _lib
     from ._tensor import device, ptr, stream
-    from .networks import check_border, check_render_filter
+    from .networks import check_border, check_render_filter, check_shape
     check_render_filter(render_filter, bool(source_res))
+    strength, rigidity, shape_model = check_shape(strength, rigidity, shape_model, bool(source_res))
     if check_border(border, bool(source_res)) == "keep":
         raise ValueError("border='keep' needs renders that run one frame at a time in order; stabilize_clip renders its "
                          "frames in batches after the loop: use OnlineStabilizer(border='keep') or online.stabilize_clips")
@@ -351,7 +357,9 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     zoom = None
     if crop is not None:
         out_hw = (int(fr.shape[1]), int(fr.shape[2])) if source_res else (h, w)
-        zoom, T_all = _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info)
+        shaped = strength != 1.0 or rigidity != 0.0   # the scans take the view the renders take
+        zoom, T_all = _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info,
+                                   model.locnet.view(render_filter, border, strength, rigidity, shape_model) if shaped else None)
     if source_res:   # eval.py:112-113 at the frames' own size, in launches of at most RENDER_BATCH_BYTES of output
         H0, W0 = int(fr.shape[1]), int(fr.shape[2])
         out = torch.empty((N, H0, W0, 3), dtype=torch.uint8 if as_uint8 else torch.float32, device=dev)
@@ -361,7 +369,8 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
         for b0 in range(0, N, batch):
             b1 = min(N, b0 + batch)
             render_source_into(model, fr[b0:b1], F[b0:b1], T, flip, out[b0:b1], side[b0:b1] if side is not None else None,
-                               zoom[b0:b1] if zoom is not None else None, render_filter, border)
+                               zoom[b0:b1] if zoom is not None else None, render_filter, border, strength, rigidity,
+                               shape_model)
         if host:
             out = out.cpu().numpy()
             side = side.cpu().numpy() if side is not None else None
@@ -390,25 +399,27 @@ def stabilize_clip(model, session, frames, skip_length=SKIP_LENGTH, side_by_side
     return (out, side) if side_by_side else out
 
 
-def _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info):
+def _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info, net=None):
     """The crop of stabilize_clip: scan every frame's F_t on the plain grid, pick the clip's zoom ("auto") or take the
-    caller's, scan again at that zoom for the report.  Returns (zoom float32 [N] on the device, T [N,2,28])."""
+    caller's, scan again at that zoom for the report.  net: the handle the scans are given (`_coverage`).  Returns (zoom
+    float32 [N] on the device, T [N,2,28])."""
     N = int(F.shape[0])
     D = _check_crop_grid(*out_hw)
     margin = 2.0 / (min(out_hw) - 1) if crop_margin is None else float(crop_margin)
     T = torch.empty((N, 2, model.param_dim + 3), dtype=torch.float32, device=F.device)
-    key = _coverage(model, F, out_hw, out_hw, None, T)[1].cpu().numpy().astype(np.int64)
+    key = _coverage(model, F, out_hw, out_hw, None, T, net)[1].cpu().numpy().astype(np.int64)
     free = np.minimum(key, D).astype(np.float64) / D
     z = crop_zoom(free, margin, crop_min) if isinstance(crop, str) else crop
     zoom = torch.full((N,), float(z), dtype=torch.float32, device=F.device)
     if isinstance(crop_info, dict):
-        left = _coverage(model, F, out_hw, out_hw, zoom)[0].cpu().numpy().astype(np.int64)
+        left = _coverage(model, F, out_hw, out_hw, zoom, None, net)[0].cpu().numpy().astype(np.int64)
         crop_info.update(zoom=float(z), cropping_ratio=float(z), free=free, border_pixels=left,
                          limited=np.nonzero(free - margin < float(crop_min))[0])
     return zoom, T
 
 
-def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render_filter="bilinear", border="black"):
+def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render_filter="bilinear", border="black",
+                       strength=1.0, rigidity=0.0, shape_model="affine"):
     """`dvsg_tps_render_u8` for the uint8 frames src [n,H0,W0,3] (device) and their F_t rows F [n,25,2]: the stabilised
     frames at source size into `out` [n,H0,W0,3] (float32, or uint8: np.uint8(x * 255.) in the channel order of src)
     and, if given, `side` [n,H0,2 W0,3] uint8 = (source bytes | uint8 render).  T [n,2,28] receives the TPS
@@ -417,13 +428,14 @@ def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render
     and the border mode of the handle the render is given (`LocNet.view`).  border="keep" is accepted: this is ONE launch,
     and the samples it leaves unwritten keep what the caller put into `out` (frame i of the launch does not see frame
     i - 1: a caller that wants the previous output there renders one frame at a time, as OnlineStabilizer does); with
-    `side` it is a ValueError naming border."""
+    `side` it is a ValueError naming border.  strength, rigidity, shape_model: the warp shape of that handle -- the render
+    applies F' of include/dvsg_amd.h, "Warp shaping", and T receives its coefficients."""
     from . import _lib
     from ._tensor import ptr, stream
     from .networks import check_border
     if check_border(border) == "keep" and side is not None:
         raise ValueError("border='keep' has no side_by_side layout: the unwritten samples are the caller's `out`")
-    net = model.locnet.view(render_filter, border)
+    net = model.locnet.view(render_filter, border, strength, rigidity, shape_model)
     n, H0, W0 = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
     if side is not None:
         side[:, :, :W0] = src   # np.uint8(v / 255. * 255.) == v for every byte: the unstable half is the source

@@ -40,8 +40,16 @@ int tps_solve_impl(const float *coord, long coord_bstride, const float *rhs, int
                    int P, float *T, int *n_singular, void *stream);
 // constant control points (the evaluation graph's V_src): W^-1 once, then a matrix-vector product per frame
 int tps_inverse_columns(const float *coord, int P, double *winv_cols, float *scratch, void *stream);
+// A handle's warp shape (dvsg_locnet_view_create_shaped; include/dvsg_amd.h, "Warp shaping").  The default is every other
+// handle's: unshaped.
+struct RenderShape {
+  int model = DVSG_SHAPE_AFFINE;
+  float strength = 1.0f, rigidity = 0.0f;
+  bool shaped() const { return !(strength == 1.0f && rigidity == 0.0f); }
+};
+// shape.shaped() (rhs = F_t, rhs_is_vector, P == 25 only): tps_shape_apply_kernel in tps_apply_kernel's place, T of F'
 int tps_apply_impl(const double *winv_cols, const float *coord, const float *rhs, int rhs_is_vector, int B, int P,
-                   float *T, void *stream);
+                   float *T, void *stream, RenderShape shape = RenderShape());
 int tps_warp_impl(const float *U, const float *coord, long coord_bstride, const float *T, int B, int H,
                   int W, int C, int P, int out_h, int out_w, float *out, float *x_s, float *y_s,
                   void *stream, const float *zoom = nullptr /* [B] device: the zoomed grid of tps_warp_zoom_kernel */);
@@ -54,7 +62,8 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
                     int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
                     const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR /* the handle's or view's */,
-                    int render_border = DVSG_BORDER_BLACK /* likewise */);
+                    int render_border = DVSG_BORDER_BLACK /* likewise */,
+                    RenderShape shape = RenderShape() /* likewise */);
 // nv12.hip: dvsg_tps_render_nv12 and, with zoom [n] on the device, dvsg_tps_render_zoom_nv12.  The check makes no HIP call
 // and reads no handle (fn: the entry point its messages name); the launch half assumes it passed.
 int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
@@ -64,7 +73,7 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream,
                          const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR,
-                         int render_border = DVSG_BORDER_BLACK);
+                         int render_border = DVSG_BORDER_BLACK, RenderShape shape = RenderShape());
 // crop_kernels.hip: the fused coverage scan of dvsg_tps_coverage_f32 (coord_bstride in floats; 0 = broadcast)
 int tps_coverage_impl(const char *fn, const float *coord, long coord_bstride, const float *T, const float *zoom, int B, int P,
                       int src_H, int src_W, int out_h, int out_w, int32_t *n_border, int32_t *key_min, void *workspace,

@@ -95,12 +95,13 @@ struct dvsg_locnet {
   std::vector<double> calib_mu = std::vector<double>((size_t)48 * 2048, 1.0);
   double calib_rows[48] = {0};
   std::vector<void *> allocs;
-  // A VIEW (dvsg_locnet_view_create) is one of these with nothing in it but `parent` and its own render filter and border: every entry
+  // A VIEW (dvsg_locnet_view_create) is one of these with nothing in it but `parent` and its own render filter, border and shape: every entry
   // point reads the network and the TPS constants through base() at call time, so a later calibration of the parent is seen
   // through its views.  n_views: the live views of a parent, which dvsg_locnet_destroy refuses to pull the network from under.
   const dvsg_locnet *parent = nullptr;
   int render_filter = DVSG_RENDER_BILINEAR;
   int render_border = DVSG_BORDER_BLACK;
+  RenderShape render_shape;
   mutable std::atomic<int> n_views{0};
 };
 
@@ -943,8 +944,9 @@ int dvsg_locnet_destroy(dvsg_locnet_t *net) {
   return DVSG_OK;
 }
 
-// both view constructors; fn: the one its messages name.  Everything is decided before the handle is read or anything allocated.
-static int view_create(const char *fn, const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view) {
+// the view constructors; fn: the one its messages name.  Everything is decided before the handle is read or anything allocated.
+static int view_create(const char *fn, const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view,
+                       RenderShape shape = RenderShape()) {
   DVSG_REQUIRE(net, "%s: NULL net", fn);
   DVSG_REQUIRE(view, "%s: NULL view", fn);
   *view = nullptr;
@@ -953,11 +955,16 @@ static int view_create(const char *fn, const dvsg_locnet_t *net, int render_filt
   DVSG_REQUIRE(render_border >= DVSG_BORDER_BLACK && render_border <= DVSG_BORDER_KEEP,
                "%s: render_border=%d is none of DVSG_BORDER_BLACK (0), _REPLICATE (1), _MIRROR (2), _KEEP (3)", fn,
                render_border);
+  DVSG_REQUIRE(shape.model >= DVSG_SHAPE_AFFINE && shape.model <= DVSG_SHAPE_TRANSLATION,
+               "%s: shape_model=%d is none of DVSG_SHAPE_AFFINE (0), _SIMILARITY (1), _TRANSLATION (2)", fn, shape.model);
+  DVSG_REQUIRE(shape.strength >= 0.0f && shape.strength <= 1.0f, "%s: strength=%g outside [0, 1]", fn, (double)shape.strength);
+  DVSG_REQUIRE(shape.rigidity >= 0.0f && shape.rigidity <= 1.0f, "%s: rigidity=%g outside [0, 1]", fn, (double)shape.rigidity);
   dvsg_locnet *v = new dvsg_locnet();
   v->calib_mu = std::vector<double>();   // (a view keeps no calibration record of its own)
-  v->parent = base(net);                 // a view of a view is a view of the parent: filter and border are the arguments'
+  v->parent = base(net);                 // a view of a view is a view of the parent: filter, border and shape are the arguments'
   v->render_filter = render_filter;
   v->render_border = render_border;
+  v->render_shape = shape;
   v->parent->n_views.fetch_add(1);
   *view = v;
   return DVSG_OK;
@@ -969,6 +976,23 @@ int dvsg_locnet_view_create(const dvsg_locnet_t *net, int render_filter, dvsg_lo
 
 int dvsg_locnet_view_create_border(const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view) {
   return view_create("dvsg_locnet_view_create_border", net, render_filter, render_border, view);
+}
+
+int dvsg_locnet_view_create_shaped(const dvsg_locnet_t *net, int render_filter, int render_border, int shape_model,
+                                   float strength, float rigidity, dvsg_locnet_t **view) {
+  RenderShape shape;
+  shape.model = shape_model;
+  shape.strength = strength;
+  shape.rigidity = rigidity;
+  return view_create("dvsg_locnet_view_create_shaped", net, render_filter, render_border, view, shape);
+}
+
+int dvsg_locnet_render_shape(const dvsg_locnet_t *net, int *shape_model, float *strength, float *rigidity) {
+  const RenderShape shape = net ? net->render_shape : RenderShape();
+  if (shape_model) *shape_model = shape.model;
+  if (strength) *strength = shape.strength;
+  if (rigidity) *rigidity = shape.rigidity;
+  return DVSG_OK;
 }
 
 int dvsg_locnet_render_filter(const dvsg_locnet_t *net) { return net ? net->render_filter : DVSG_RENDER_BILINEAR; }
@@ -1332,7 +1356,7 @@ int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t
                        int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_u8: NULL net");
   return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, nullptr, net->render_filter, net->render_border);
+                         u8_W, u8_x0, stream, nullptr, net->render_filter, net->render_border, net->render_shape);
 }
 
 // dvsg_tps_render_u8 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_u8 itself)
@@ -1341,7 +1365,7 @@ int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const ui
                             int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_zoom_u8: NULL net");
   return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, zoom, net->render_filter, net->render_border);
+                         u8_W, u8_x0, stream, zoom, net->render_filter, net->render_border, net->render_shape);
 }
 
 // dvsg_tps_render_u8 for NV12 frames (nv12.hip): the same T, then both planes warped at their own sizes in one launch.
@@ -1353,7 +1377,8 @@ int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8
   if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride))
     return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
-                              out_pitch, out_frame_stride, stream, nullptr, net->render_filter, net->render_border);
+                              out_pitch, out_frame_stride, stream, nullptr, net->render_filter, net->render_border,
+                              net->render_shape);
 }
 
 // dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
@@ -1365,15 +1390,17 @@ int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const 
                                      "dvsg_tps_render_zoom_nv12"))
     return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
-                              out_pitch, out_frame_stride, stream, zoom, net->render_filter, net->render_border);
+                              out_pitch, out_frame_stride, stream, zoom, net->render_filter, net->render_border,
+                              net->render_shape);
 }
 
 // T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)
 int dvsg_tps_coefficients_f32(const dvsg_locnet_t *net, const float *F_t, int n, float *T, void *stream) {
   DVSG_REQUIRE(net && F_t && T, "dvsg_tps_coefficients_f32: NULL pointer");
   DVSG_REQUIRE(n >= 1, "dvsg_tps_coefficients_f32: n=%d must be >= 1", n);
+  const RenderShape shape = net->render_shape;   // the handle's own; the network is the parent's
   net = base(net);
-  return tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream);
+  return tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream, shape);
 }
 
 // The coverage scan of a clip's F_t rows: the T of dvsg_stabilize_* / dvsg_tps_render_u8 for F_t (written), then
@@ -1390,8 +1417,9 @@ int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const 
   if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || workspace_bytes < need)
     return fail(DVSG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed, 8-byte aligned (dvsg_tps_coverage_workspace_bytes)",
                 fn, workspace_bytes, need);
+  const RenderShape shape = net->render_shape;   // the scan counts the border the shaped render draws
   net = base(net);
-  if (int rc = tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream)) return rc;
+  if (int rc = tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream, shape)) return rc;
   return tps_coverage_impl(fn, net->v_src, 0, T, zoom, n, 25, src_H, src_W, out_h, out_w, n_border, key_min, workspace,
                            workspace_bytes, stream);
 }

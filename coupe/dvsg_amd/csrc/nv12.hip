@@ -481,11 +481,11 @@ int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv,
 int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream, const float *zoom,
-                         int render_filter, int render_border) {
+                         int render_filter, int render_border, RenderShape shape) {
   const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
   const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(H / 2, kTpsRows);
   DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);
-  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream)) return rc;
+  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, shape)) return rc;
   hipStream_t s = as_stream(stream);
   // algorithmic bytes: both planes once in, once out
   ProfScope prof(kClsTpsWarp, s, 0.0, 3.0 * n * H * W);

@@ -173,6 +173,87 @@ __global__ __launch_bounds__(64) void tps_apply_kernel(const double *__restrict_
   }
 }
 
+// tps_apply_kernel for a SHAPED view (dvsg_locnet_view_create_shaped; the rule is include/dvsg_amd.h, "Warp shaping"): the
+// frame's F_t is staged in LDS, every lane reads its 25 rows by broadcast and forms the same float64 sums in the order
+// i = 0..24 (so every lane holds the same fit; no tree reduction, which would be another rounding order), lane i < 25
+// forms F'_i and keeps it in LDS as coord + F' in float32 -- and from there on this IS tps_apply_kernel with
+// rhs_is_vector: the same 56 dot products in the same order.  F' never reaches memory.  A kernel of its own, so
+// tps_apply_kernel keeps its instructions; the file is compiled with -ffp-contract=off, which the rule needs (every
+// product and sum below rounded on its own).  s = (double)strength, k = 1.0 - (double)rigidity, formed on the host: both
+// are exact in float64 arithmetic, the same bits as formed here.
+constexpr int kShapePts = 25;
+__global__ __launch_bounds__(64) void tps_shape_apply_kernel(const double *__restrict__ winv_cols,
+                                                             const float *__restrict__ coord,
+                                                             const float *__restrict__ F, int model, double s, double k,
+                                                             float *__restrict__ T) {
+  constexpr int P = kShapePts, n = P + 3;
+  __shared__ double px[P], py[P], dx[P], dy[P];
+  __shared__ double yx[P], yy[P];
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (t < P) {
+    px[t] = (double)coord[t * 2 + 0];
+    py[t] = (double)coord[t * 2 + 1];
+    dx[t] = (double)F[((size_t)b * P + t) * 2 + 0];
+    dy[t] = (double)F[((size_t)b * P + t) * 2 + 1];
+  }
+  __syncthreads();
+  double sx = 0.0, sy = 0.0;
+  for (int i = 0; i < P; ++i) {
+    sx += dx[i];
+    sy += dy[i];
+  }
+  const double mx = sx / 25.0, my = sy / 25.0;
+  // the linear part of the fit as L_x = (mx + cxx px) + cxy py, L_y = (my + cyx px) + cyy py
+  double cxx = 0.0, cxy = 0.0, cyx = 0.0, cyy = 0.0;
+  if (model == DVSG_SHAPE_SIMILARITY) {
+    double sa = 0.0, sb = 0.0;
+    for (int i = 0; i < P; ++i) {
+      sa += px[i] * dx[i] + py[i] * dy[i];
+      sb += px[i] * dy[i] - py[i] * dx[i];
+    }
+    cxx = cyy = sa / 25.0;   // a
+    cyx = sb / 25.0;         // b; L_x subtracts b py
+  } else if (model == DVSG_SHAPE_AFFINE) {
+    for (int i = 0; i < P; ++i) {
+      cxx += px[i] * dx[i];
+      cxy += py[i] * dx[i];
+      cyx += px[i] * dy[i];
+      cyy += py[i] * dy[i];
+    }
+    cxx /= 12.5;
+    cxy /= 12.5;
+    cyx /= 12.5;
+    cyy /= 12.5;
+  }
+  if (t < P) {
+    double Lx, Ly;
+    if (model == DVSG_SHAPE_TRANSLATION) {
+      Lx = mx;
+      Ly = my;
+    } else if (model == DVSG_SHAPE_SIMILARITY) {
+      Lx = (mx + cxx * px[t]) - cyx * py[t];
+      Ly = (my + cyx * px[t]) + cyy * py[t];
+    } else {
+      Lx = (mx + cxx * px[t]) + cxy * py[t];
+      Ly = (my + cyx * px[t]) + cyy * py[t];
+    }
+    const float fx = (float)(s * (Lx + k * (dx[t] - Lx)));   // F'
+    const float fy = (float)(s * (Ly + k * (dy[t] - Ly)));
+    yx[t] = (double)(coord[t * 2 + 0] + fx);   // coord + vector in float32, as tps_apply_kernel
+    yy[t] = (double)(coord[t * 2 + 1] + fy);
+  }
+  __syncthreads();
+  if (t < n) {
+    double ax = 0.0, ay = 0.0;
+    for (int j = 0; j < P; ++j) {
+      const double w = winv_cols[(size_t)j * n + t];
+      ax += w * yx[j];
+      ay += w * yy[j];
+    }
+    T[((size_t)b * 2 + 0) * n + t] = (float)ax;
+    T[((size_t)b * 2 + 1) * n + t] = (float)ay;
+  }
+}
 
 // ----------------------------------------------------------------------------------------
 // Fused TPS grid generation + sampler A (ThinPlateSpline.py:92-141).
@@ -730,10 +811,16 @@ int tps_inverse_columns(const float *coord, int P, double *winv_cols, float *scr
 }
 
 int tps_apply_impl(const double *winv_cols, const float *coord, const float *rhs, int rhs_is_vector, int B, int P,
-                   float *T, void *stream) {
+                   float *T, void *stream, RenderShape shape) {
   DVSG_REQUIRE(winv_cols && coord && rhs && T, "tps_apply: NULL pointer");
   DVSG_REQUIRE(B > 0 && P >= 3 && P <= kMaxPts, "tps_apply: bad shape B=%d P=%d", B, P);
   ProfScope prof(kClsTpsSolve, as_stream(stream), 0.0, (double)B * (4.0 * P + 2.0 * (P + 3)) * 4.0);
+  if (shape.shaped()) {   // a shaped view: one launch in tps_apply_kernel's place, one workgroup per frame as there
+    DVSG_REQUIRE(rhs_is_vector && P == kShapePts, "tps_apply: a shape needs F_t on the %d-point grid", kShapePts);
+    hipLaunchKernelGGL(tps_shape_apply_kernel, dim3(B), dim3(64), 0, as_stream(stream), winv_cols, coord, rhs, shape.model,
+                       (double)shape.strength, 1.0 - (double)shape.rigidity, T);
+    return check_launch("tps_shape_apply_kernel");
+  }
   hipLaunchKernelGGL(tps_apply_kernel, dim3(B), dim3(64), 0, as_stream(stream), winv_cols, coord, rhs, rhs_is_vector, P, T);
   return check_launch("tps_apply_kernel");
 }
@@ -807,7 +894,7 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 // and / or uint8 out_u8 [B,H,u8_W,3] in columns [u8_x0, u8_x0 + W).  Every argument is checked before the first launch.
 int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
                     int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
-                    const float *zoom, int render_filter, int render_border) {
+                    const float *zoom, int render_filter, int render_border, RenderShape shape) {
   DVSG_REQUIRE(winv_cols && coord && F_t && src && T, "dvsg_tps_render_u8: NULL pointer");
   DVSG_REQUIRE(out_f32 || out_u8, "dvsg_tps_render_u8: neither out_f32 nor out_u8 given");
   DVSG_REQUIRE(B >= 1 && B <= 65535, "dvsg_tps_render_u8: n=%d outside [1, 65535]", B);
@@ -815,7 +902,7 @@ int tps_render_impl(const double *winv_cols, const float *coord, const float *F_
   DVSG_REQUIRE(!out_u8 || (u8_x0 >= 0 && (long)u8_W >= (long)u8_x0 + W),
                "dvsg_tps_render_u8: columns [%d, %ld) do not fit a row of %d pixels", u8_x0, (long)u8_x0 + W, u8_W);
   DVSG_REQUIRE(!out_u8 || (long)H * u8_W < (1L << 31), "dvsg_tps_render_u8: uint8 image too large");
-  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream)) return rc;
+  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream, shape)) return rc;
   dim3 grid(ceil_div(W, kThreads), ceil_div(H, kTpsRows), B);
   const float sx = lin_step(W), sy = lin_step(H);
   hipStream_t s = as_stream(stream);

@@ -65,6 +65,31 @@ def check_border(border, source_size_render=True):
     return border
 
 
+SHAPE_MODELS = {"affine": 0, "similarity": 1, "translation": 2}   # DVSG_SHAPE_AFFINE, _SIMILARITY, _TRANSLATION
+
+
+def check_shape(strength=1.0, rigidity=0.0, shape_model="affine", source_size_render=True):
+    """strength, rigidity and shape_model arguments -> (strength, rigidity, shape_model) with the two numbers as the float32
+    values the library receives.  Each number must lie in [0, 1] (NaN is refused).  Any shape but the unshaped
+    (strength 1, rigidity 0) where no source-size render happens (RGB at the model's size, float frames) is a ValueError that
+    names source_res: only what is rendered at source size is shaped, the recurrence never is."""
+    if not isinstance(shape_model, str) or shape_model not in SHAPE_MODELS:
+        raise ValueError("shape_model must be 'affine', 'similarity' or 'translation', got %r" % (shape_model,))
+    out = []
+    for name, v in (("strength", strength), ("rigidity", rigidity)):
+        if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number in [0, 1], got %r" % (name, v))
+        f = float(np.float32(v))
+        if not 0.0 <= f <= 1.0:   # (NaN fails both comparisons)
+            raise ValueError("%s must be a number in [0, 1], got %r" % (name, v))
+        out.append(f)
+    if (out[0] != 1.0 or out[1] != 0.0) and not source_size_render:
+        raise ValueError("strength=%r, rigidity=%r shape the source-size render only: they need source_res=True (uint8 frames) "
+                         "or frame_format='nv12'; frames at the model's size feed the recurrence and stay unshaped"
+                         % (strength, rigidity))
+    return out[0], out[1], shape_model
+
+
 class LocNet(object):
     """Owns the device-side network (`dvsg_locnet_t`) and one growable workspace per stream that uses it."""
 
@@ -87,25 +112,36 @@ class LocNet(object):
         _lib.call("dvsg_locnet_create", n, c_names, c_data, c_nd,
                   dims.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(handle))
         self.handle = handle
-        self._views = {}   # (render filter, border) -> view handle (dvsg_locnet_view_create_border), made on first use
+        self._views = {}   # (render filter, border, strength, rigidity, shape model) -> view handle, made on first use
         self._keep = None  # the library copied everything to the device
         self._ws = None
         self.in_channels = _lib.load().dvsg_locnet_in_channels(self.handle)
 
-    def view(self, render_filter="bilinear", border="black"):
-        """The handle the source-size renders take for `render_filter` and `border`: this network itself for ("bilinear",
-        "black"), else a view of it (`dvsg_locnet_view_create_border`: the same network, nothing copied, its own filter and
-        border mode), made once per pair and kept until the network goes."""
+    def view(self, render_filter="bilinear", border="black", strength=1.0, rigidity=0.0, shape_model="affine"):
+        """The handle the source-size renders, the coverage scan and `dvsg_tps_coefficients_f32` take for `render_filter`,
+        `border` and the warp shape: this network itself for ("bilinear", "black") unshaped, else a view of it
+        (`dvsg_locnet_view_create_border`, or `dvsg_locnet_view_create_shaped` when strength != 1 or rigidity != 0: the same
+        network, nothing copied, its own filter, border mode and shape), made once per set of five values and kept until the
+        network goes.  An unshaped view is the same whatever its shape_model."""
         check_render_filter(render_filter)
         check_border(border)
-        if render_filter == "bilinear" and border == "black":
-            return self.handle
-        v = self._views.get((render_filter, border))
+        strength, rigidity, shape_model = check_shape(strength, rigidity, shape_model)
+        shaped = strength != 1.0 or rigidity != 0.0
+        if not shaped:
+            shape_model = "affine"
+            if render_filter == "bilinear" and border == "black":
+                return self.handle
+        key = (render_filter, border, strength, rigidity, shape_model)
+        v = self._views.get(key)
         if v is None:
             v = ctypes.c_void_p()
-            _lib.call("dvsg_locnet_view_create_border", self.handle, RENDER_FILTERS[render_filter], RENDER_BORDERS[border],
-                      ctypes.byref(v))
-            self._views[(render_filter, border)] = v
+            if shaped:
+                _lib.call("dvsg_locnet_view_create_shaped", self.handle, RENDER_FILTERS[render_filter], RENDER_BORDERS[border],
+                          SHAPE_MODELS[shape_model], strength, rigidity, ctypes.byref(v))
+            else:
+                _lib.call("dvsg_locnet_view_create_border", self.handle, RENDER_FILTERS[render_filter],
+                          RENDER_BORDERS[border], ctypes.byref(v))
+            self._views[key] = v
         return v
 
     def __del__(self):

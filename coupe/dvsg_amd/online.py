@@ -115,6 +115,16 @@ class OnlineStabilizer(object):
     composes as it is, the border mode fills whatever the zoom leaves.  A border other than "black" without a
     source-size render raises ValueError, as does "keep" with side_by_side.
 
+    strength, rigidity, shape_model: how much of the network's warp the source-size render applies (source_res=True or
+    frame_format="nv12"; every filter and border, with and without crop and scene_cut; include/dvsg_amd.h, "Warp shaping").
+    strength in [0, 1] scales the correction (0: the source as it is, for A/B viewing; 1, the default: all of it);
+    rigidity in [0, 1] pulls the 25 control points' displacements towards their least-squares fit by shape_model --
+    "affine" (default), "similarity" or "translation" -- so that rigidity=1 renders a warp that cannot wobble.  They only
+    select the view (`LocNet.view`) that the render, the coverage scan of crop="auto" and the coefficient call are given, so
+    the zoom is that of the border the shaped render draws, and they cost no launch.  The recurrence is untouched: the
+    network was trained on its own full-strength history, so the pool, F_t and the model-size history are those of a run
+    without shaping.  Anything but (1, 0) without a source-size render raises ValueError.
+
     crop: every output frame has a black border (luma 0 / chroma 128 in NV12) wherever sampler A's taps leave the source.
     None (default) returns the frames as they are.  A zoom z in (0, 1] renders every frame of every stream on the output
     grid scaled by z about its centre; nothing is scanned.  "auto" keeps ONE zoom per stream on the device and lowers it
@@ -150,12 +160,13 @@ class OnlineStabilizer(object):
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
                  as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None,
                  crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1, render_filter="bilinear",
-                 border="black"):
+                 border="black", strength=1.0, rigidity=0.0, shape_model="affine"):
         from . import _lib
         from ._tensor import device
-        from .networks import check_border, check_render_filter
+        from .networks import check_border, check_render_filter, check_shape
         check_render_filter(render_filter, bool(source_res) or frame_format == "nv12")
         check_border(border, bool(source_res) or frame_format == "nv12")
+        shape = check_shape(strength, rigidity, shape_model, bool(source_res) or frame_format == "nv12")
         if border == "keep" and side_by_side:
             raise ValueError("border='keep' has no side_by_side layout: the surface a stream keeps is its output frame")
         crop = _check_crop(crop)
@@ -198,6 +209,7 @@ class OnlineStabilizer(object):
         self.side_by_side, self.as_uint8, self.source_res = bool(side_by_side), bool(as_uint8), bool(source_res)
         self.frame_format, self.yuv_matrix = frame_format, YUV_MATRICES[yuv_matrix]
         self.render_filter, self.border = render_filter, border
+        self.strength, self.rigidity, self.shape_model = shape
         self._keep = {}           # border="keep": ring -> the stream's persistent output surface, at its source size
         self._keep_fresh = set()  # rings whose next frame is a step 0: the surface restarts from that frame's source bytes
         self._cut = None          # int32 [B] on the device: the `cut` output of this step's dvsg_scene_step_f32
@@ -286,6 +298,13 @@ class OnlineStabilizer(object):
             raise ValueError("stream %d is closed" % sid)
         raise ValueError("stream %r was never opened" % (sid,))
 
+    def _net(self):
+        """The handle every call that turns F_t into T is given: the view the render uses, so that scan, crop and render see
+        one warp; the network itself when nothing is shaped (the scan does not read a filter or a border)."""
+        if self.strength == 1.0 and self.rigidity == 0.0:
+            return self.model.locnet.handle
+        return self.model.locnet.view(self.render_filter, self.border, self.strength, self.rigidity, self.shape_model)
+
     def push(self, sid, frame):
         """`step` for a single stream: its output for `frame`."""
         return self.step({sid: frame})[sid]
@@ -329,7 +348,7 @@ class OnlineStabilizer(object):
             need = ctypes.c_size_t()
             _lib.call("dvsg_tps_coverage_workspace_bytes", n, gh, gw, ctypes.byref(need))
             ws = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=dev)
-            _lib.call("dvsg_tps_coverage_net_f32", self.model.locnet.handle, ptr(self._F[i:j]), None, n, gh, gw, gh, gw,
+            _lib.call("dvsg_tps_coverage_net_f32", self._net(), ptr(self._F[i:j]), None, n, gh, gw, gh, gw,
                       ptr(self._T[i:j]), ptr(keys[g, 0]), ptr(keys[g, 1]), ptr(ws), ws.numel() * 8, stream())
         slots = torch.from_numpy(rings).pin_memory().to(dev, non_blocking=True)
         zoom = torch.empty((n,), dtype=torch.float32, device=dev)
@@ -526,7 +545,7 @@ class OnlineStabilizer(object):
         B, h, w, flip = len(entries), self.h, self.w, self.flip
         zoom = self._step_zoom(entries, 0, B, [(h, w)])
         if not self._crop_auto:   # no scan has written T
-            _lib.call("dvsg_tps_coefficients_f32", self.model.locnet.handle, ptr(self._F[:B]), B, ptr(self._T[:B]), stream())
+            _lib.call("dvsg_tps_coefficients_f32", self._net(), ptr(self._F[:B]), B, ptr(self._T[:B]), stream())
         u = self.pool.index_select(0, in_slots)
         out = torch.empty_like(u)
         _lib.call("dvsg_tps_warp_zoom_f32", ptr(u), ptr(self._V[:B]), ptr(self._T[:B]), ptr(zoom), B, h, w, 3,
@@ -565,7 +584,7 @@ class OnlineStabilizer(object):
             side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
             zoom = self._step_zoom(entries, i, j, [(H0, W0)]) if self.crop is not None else None
             render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, self.render_filter,
-                               self.border)
+                               self.border, self.strength, self.rigidity, self.shape_model)
             if done is not None:
                 out = done()
             if any(entries[b][2] for b in range(i, j)):
@@ -623,7 +642,7 @@ class OnlineStabilizer(object):
         for e in entries:
             self._streams[e[1]][1] += 1
         res = {}
-        net = self.model.locnet.view(self.render_filter, self.border)
+        net = self.model.locnet.view(self.render_filter, self.border, self.strength, self.rigidity, self.shape_model)
         for i, j, src in groups:
             H0, W0 = entries[i][0]
             out, done = self._keep_surfaces(entries, i, j, src) if self.border == "keep" else (torch.empty_like(src), None)
@@ -648,7 +667,8 @@ def stabilize_clips(model, clips, batch=None, **kw):
     """eval.py:76-124 for K whole clips at once: the clips run through one `OnlineStabilizer` of `batch` streams
     (default K) in lockstep, so each step is one batched call and every clip keeps its own recurrence exactly.  Clips
     may differ in length (a finished clip's ring goes to the next waiting clip).  `kw` are OnlineStabilizer's options,
-    scene_cut and scene_min_len among them: every clip then restarts its own history at its own cuts.
+    scene_cut and scene_min_len among them: every clip then restarts its own history at its own cuts; strength, rigidity
+    and shape_model shape every clip's source-size render alike.
     Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips).  With
     frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result.  crop=... is OnlineStabilizer's: frame k of a
     clip is rendered with the zoom the ratchet has reached at frame k, NOT with `stabilize_clip`'s one clip-wide zoom

@@ -306,8 +306,8 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
             `flush()`, `width` and `height` (which must then be the source's).
         Sources may differ in size, layout and length; a sink may have another layout than its source.
     batch: streams per step (default: all sources).  depth: frames in flight per source, >= 1.
-    online_kw: OnlineStabilizer's crop, crop_*, scene_cut, scene_min_len, skip_length, render_filter, border and yuv_matrix, passed
-        through.
+    online_kw: OnlineStabilizer's crop, crop_*, scene_cut, scene_min_len, skip_length, render_filter, border, strength, rigidity,
+        shape_model and yuv_matrix, passed through.
         yuv_matrix defaults to "auto" here: `y4m.default_yuv_matrix` of the first source's height, resolved per call.
 
     One `OnlineStabilizer(model, max_streams=batch, frame_format="nv12")` serves all sources on `stabilize_clips`' own
@@ -447,6 +447,13 @@ def _parser():
     ap.add_argument("--border", default=None, choices=["black", "replicate", "mirror", "keep"],
                     help="what the render makes of samples outside the source: black (default), the source's edge "
                     "replicated or mirrored, or keep what the stream showed there before")
+    ap.add_argument("--strength", type=float, default=None, metavar="S",
+                    help="fraction of the network's warp that is rendered, in [0, 1] (default 1; 0 shows the source)")
+    ap.add_argument("--rigidity", type=float, default=None, metavar="R",
+                    help="pull of the rendered warp towards its --shape-model fit, in [0, 1] (default 0: the free spline; "
+                    "1 cannot wobble)")
+    ap.add_argument("--shape-model", default=None, choices=["affine", "similarity", "translation"],
+                    help="the rigid motion --rigidity pulls towards (default: affine)")
     ap.add_argument("--scene-cut", type=float, default=None, metavar="THR")
     ap.add_argument("--scene-min-len", type=int, default=None, metavar="N")
     ap.add_argument("--yuv-matrix", default="auto", choices=["auto", "bt709", "bt601"])
@@ -526,7 +533,8 @@ def _run(args, note):
         model.get_evaluation_model(S)
         model.precision = args.precision
         kw = dict(skip_length=skip, yuv_matrix=args.yuv_matrix)
-        for key in ("crop", "crop_min", "crop_margin", "crop_recover", "scene_cut", "scene_min_len", "render_filter", "border"):
+        for key in ("crop", "crop_min", "crop_margin", "crop_recover", "scene_cut", "scene_min_len", "render_filter", "border",
+                    "strength", "rigidity", "shape_model"):
             if getattr(args, key) is not None:
                 kw[key] = getattr(args, key)
         sinks = []

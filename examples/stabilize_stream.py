@@ -80,6 +80,12 @@ def main():
     ap.add_argument("--border", default="black", choices=["black", "replicate", "mirror", "keep"],
                     help="what the source-size render makes of samples outside the source; anything but black with "
                     "--format rgb turns source_res on, and keep drops the side-by-side frame")
+    ap.add_argument("--strength", type=float, default=1.0,
+                    help="fraction of the network's warp the source-size render applies, in [0, 1]; anything but 1 with "
+                    "--format rgb turns source_res on (as --rigidity does)")
+    ap.add_argument("--rigidity", type=float, default=0.0,
+                    help="pull of the rendered warp towards its --shape-model fit, in [0, 1]: 1 renders a warp that cannot wobble")
+    ap.add_argument("--shape-model", default="affine", choices=["affine", "similarity", "translation"])
     ap.add_argument("--skip-length", default=None, metavar="A,B,...",
                     help="the window's frame offsets, oldest first (default: the reference's 0,16,24,28,30,31,32)")
     args = ap.parse_args()
@@ -92,15 +98,17 @@ def main():
     net.get_evaluation_model(S)
     net.precision = args.precision
     nv12 = args.format == "nv12"
+    shape = dict(strength=args.strength, rigidity=args.rigidity, shape_model=args.shape_model)
+    shaped = args.strength != 1.0 or args.rigidity != 0.0
     if nv12:
         stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop,
-                                render_filter=args.render_filter, border=args.border, **scene, **window)
+                                render_filter=args.render_filter, border=args.border, **shape, **scene, **window)
         make = synthetic_nv12_source
     else:
         stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=args.border != "keep",
                                 as_uint8=True, crop=crop,
-                                source_res=args.render_filter != "bilinear" or args.border != "black",
-                                render_filter=args.render_filter, border=args.border, **scene, **window)
+                                source_res=args.render_filter != "bilinear" or args.border != "black" or shaped,
+                                render_filter=args.render_filter, border=args.border, **shape, **scene, **window)
         make = synthetic_source
     H0, W0 = args.height * 3 // 2, args.width * 3 // 2
     if nv12:

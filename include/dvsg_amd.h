@@ -159,7 +159,9 @@ int dvsg_locnet_workspace_bytes(const dvsg_locnet_t *net, int B, int H, int W, s
  * filter of the handle each call passes.  Both functions are host-side: no stream, no device work.
  *   dvsg_locnet_view_create  a VIEW of `net`: the same network and TPS constants, nothing copied, with its own render
  *          filter (DVSG_RENDER_BILINEAR or DVSG_RENDER_BICUBIC).  Every entry point that takes a dvsg_locnet_t accepts a
- *          view, and everything but the four renders behaves exactly as on the parent, bit for bit.  A view resolves to
+ *          view, and everything but the four renders -- and, for a SHAPED view ("Warp shaping" below), the two other
+ *          entry points that turn F_t into T through a handle, dvsg_tps_coverage_net_f32 and dvsg_tps_coefficients_f32 --
+ *          behaves exactly as on the parent, bit for bit.  A view resolves to
  *          its parent at call time (it copies no pointers), so a later dvsg_locnet_calibrate_f16 of the parent is seen
  *          through its views; calibrating THROUGH a view is DVSG_ERR_INVALID_ARG.  A view of a view is a view of the
  *          parent.  dvsg_locnet_destroy(view) frees the view only; destroying a parent that still has views is
@@ -233,6 +235,51 @@ int dvsg_locnet_render_filter(const dvsg_locnet_t *net);
 #define DVSG_BORDER_KEEP 3
 int dvsg_locnet_view_create_border(const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view);
 int dvsg_locnet_render_border(const dvsg_locnet_t *net);
+
+/* Warp shaping: strength and rigidity.  How much of the network's F_t a render applies is, like the filter and the border,
+ * a property of the handle: a view carries a filter, a border AND a shape (model, strength, rigidity).  Both functions are
+ * host-side: no stream, no device work, everything decided before anything is allocated.
+ *   dvsg_locnet_view_create_shaped  dvsg_locnet_view_create_border with a shape.  shape_model is DVSG_SHAPE_AFFINE,
+ *          _SIMILARITY or _TRANSLATION; strength and rigidity lie in [0, 1] (NaN is refused).  An unknown model, filter or
+ *          border, a value outside [0, 1] or a NULL pointer is DVSG_ERR_INVALID_ARG; the message names the argument and its
+ *          value ("shape_model=<n>", "strength=<x>", "rigidity=<x>").  The view rules are the ones above: a view of a view is
+ *          a view of the parent with the filter, border and shape of ITS arguments (nothing inherited), calibrating through
+ *          a view and destroying a parent with live views are refused.
+ *   dvsg_locnet_render_shape  the handle's shape into the three pointers (each may be NULL); always DVSG_OK.  It is
+ *          (DVSG_SHAPE_AFFINE, 1.0f, 0.0f) for NULL, for every handle of dvsg_locnet_create and for every view of
+ *          dvsg_locnet_view_create and dvsg_locnet_view_create_border.
+ * A view with strength == 1.0f && rigidity == 0.0f is UNSHAPED whatever its model: its launches and its bits are exactly
+ * those of dvsg_locnet_view_create_border(net, render_filter, render_border).
+ *
+ * The rule, per frame.  d_i = F_t[i] (float32, i = 0..24), p_i = V_src[i], the constant 5 x 5 grid with coordinates 0,
+ * +-0.5 and +-1: sum p = 0, sum px py = 0, sum px^2 = sum py^2 = 12.5, sum |p|^2 = 25.  Everything is float64, every
+ * operation rounded on its own (no contraction), every sum runs sequentially over i = 0..24 from 0.0.
+ *   Means.        mx = (sum dx_i) / 25.0, my = (sum dy_i) / 25.0.
+ *   Translation.  L_i = (mx, my).
+ *   Similarity.   a = (sum (px_i dx_i + py_i dy_i)) / 25.0, b = (sum (px_i dy_i - py_i dx_i)) / 25.0;
+ *                 L_ix = (mx + a px_i) - b py_i, L_iy = (my + b px_i) + a py_i.
+ *   Affine.       axx = (sum px_i dx_i) / 12.5, axy = (sum py_i dx_i) / 12.5, ayx = (sum px_i dy_i) / 12.5,
+ *                 ayy = (sum py_i dy_i) / 12.5; L_ix = (mx + axx px_i) + axy py_i, L_iy = (my + ayx px_i) + ayy py_i.
+ *   Shaped displacement.  s = (double)strength, k = 1.0 - (double)rigidity;
+ *                 F'_i = (float)(s * (L_i + k * (d_i - L_i))), one rounding to nearest per component.
+ * L is the least-squares fit of the model to the 25 displacements (the grid's moments above make the normal equations
+ * diagonal).  A NaN in a frame's F_t makes that frame's F' NaN at all 25 points, in the component it stands in (it enters
+ * that component's mean) and, with DVSG_SHAPE_SIMILARITY, in the other as well (a and b sum both); other frames are unaffected.
+ *
+ * The contract.  An entry point given a shaped view v and F_t writes and uses exactly what it would if given the unshaped
+ * view with v's filter and border and F', bit for bit: T and every output.  The entry points that read the shape are the
+ * ones that turn F_t into T through a handle: dvsg_tps_render_u8, dvsg_tps_render_zoom_u8, dvsg_tps_render_nv12,
+ * dvsg_tps_render_zoom_nv12, dvsg_tps_coverage_net_f32 and dvsg_tps_coefficients_f32 -- so the coverage scan of a shaped
+ * view counts the border its render draws.  Every other entry point (dvsg_locnet_forward_*, dvsg_stabilize_*, the ring
+ * and the masked entry points) behaves on a shaped view exactly as on the parent: the recurrence never sees the shape.
+ * A shaped view launches one kernel in the place of the one that forms T (F' stays in shared memory; F_t is not written):
+ * the count of launches is that of the unshaped view. */
+#define DVSG_SHAPE_AFFINE 0
+#define DVSG_SHAPE_SIMILARITY 1
+#define DVSG_SHAPE_TRANSLATION 2
+int dvsg_locnet_view_create_shaped(const dvsg_locnet_t *net, int render_filter, int render_border, int shape_model,
+                                   float strength, float rigidity, dvsg_locnet_t **view);
+int dvsg_locnet_render_shape(const dvsg_locnet_t *net, int *shape_model, float *strength, float *rigidity);
 
 /* patches [B,H,W,c_in] in [0,1] -> F_t [B,25,2].  float32 storage, exact-f32 MFMA
  * (v_mfma_f32_32x32x2_f32) accumulation.  c_in != 21: conv1 is the same arithmetic in the root-conv kernel. */

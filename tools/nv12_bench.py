@@ -17,8 +17,11 @@ One JSON line per measurement.
 above on "black" and adds, per size and n, both renders through a view of EVERY border mode, alternating inside every
 round, and the copy that OnlineStabilizer(border="keep") adds per frame (a clone of the stream's output surface).
 
+--strength S, --rigidity R, --shape-model NAME render through a SHAPED view (include/dvsg_amd.h, "Warp shaping": one kernel
+in the place of the one that forms T, no launch added); every record names the three values.
+
     python tools/nv12_bench.py [--reps 20] [--render-filter bilinear|bicubic] [--border black|replicate|mirror|keep|all]
-                               [--out FILE]
+                               [--strength S] [--rigidity R] [--shape-model affine|similarity|translation] [--out FILE]
 """
 import argparse
 import json
@@ -37,6 +40,9 @@ def main():
     ap.add_argument("--model-width", type=int, default=512)
     ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"])
     ap.add_argument("--border", default="black", choices=["black", "replicate", "mirror", "keep", "all"])
+    ap.add_argument("--strength", type=float, default=1.0)
+    ap.add_argument("--rigidity", type=float, default=0.0)
+    ap.add_argument("--shape-model", default="affine", choices=["affine", "similarity", "translation"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import torch
@@ -49,7 +55,8 @@ def main():
         raise SystemExit("nv12_bench needs the GPU")
     net = LocNet(make_synthetic_weights(seed=0))
     border = "black" if args.border == "all" else args.border
-    handle = net.view(args.render_filter, border)
+    shape = (args.strength, args.rigidity, args.shape_model)
+    handle = net.view(args.render_filter, border, *shape)
     s = lambda: torch.cuda.current_stream().cuda_stream
     h, w, M = args.model_height, args.model_width, 1   # BT.709
     lines = []
@@ -71,7 +78,8 @@ def main():
                 per[name].append(e0.elapsed_time(e1) / args.reps)
         for name, _ in versions:
             v = sorted(per[name])
-            rec = dict(what=what, version=name, render_filter=args.render_filter, border=name if name in RENDER_BORDERS else border, frames=n, height=H, width=W, ms_median=round(v[3], 4), ms_min=round(v[0], 4),
+            rec = dict(what=what, version=name, render_filter=args.render_filter, border=name if name in RENDER_BORDERS else border,
+                       strength=args.strength, rigidity=args.rigidity, shape_model=args.shape_model, frames=n, height=H, width=W, ms_median=round(v[3], 4), ms_min=round(v[0], 4),
                        ms_max=round(v[-1], 4), us_per_frame=round(1e3 * v[3] / n, 2))
             print(json.dumps(rec), flush=True)
             lines.append(rec)
@@ -125,7 +133,7 @@ def main():
             pair("ingest + render", n, H, W, [("nv12", route_nv12), ("rgb route", route_rgb)])
             if args.border == "all":
                 def through(call, name):
-                    view = net.view(args.render_filter, name)
+                    view = net.view(args.render_filter, name, *shape)
                     if call == "nv12":
                         return lambda: _lib.call("dvsg_tps_render_nv12", view, F.data_ptr(), y, uv, W, fs, n, H, W, T.data_ptr(),
                                                  out.data_ptr(), out.data_ptr() + H * W, W, fs, s())

@@ -15,9 +15,12 @@ One JSON line per measurement.
 --border NAME measures them through a view with that border mode (every record names it); --border all runs part 1 once
 per border mode and part 2's source_res runs once per border mode ("keep" includes its copy of the output surface).
 
+--strength S, --rigidity R, --shape-model NAME measure them through a SHAPED view (include/dvsg_amd.h, "Warp shaping": one
+kernel in the place of the one that forms T, no launch added); every record names the three values.
+
     python tools/source_res_bench.py [--steps 30] [--warmup 5] [--sources 1080x1920,2160x3840] [--streams 1,4,16]
                                      [--render-filter bilinear|bicubic] [--border black|replicate|mirror|keep|all]
-                                     [--out FILE]
+                                     [--strength S] [--rigidity R] [--shape-model affine|similarity|translation] [--out FILE]
 """
 import argparse
 import ctypes
@@ -43,6 +46,9 @@ def main():
     ap.add_argument("--precision", default="f32")
     ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"])
     ap.add_argument("--border", default="black", choices=["black", "replicate", "mirror", "keep", "all"])
+    ap.add_argument("--strength", type=float, default=1.0)
+    ap.add_argument("--rigidity", type=float, default=0.0)
+    ap.add_argument("--shape-model", default="affine", choices=["affine", "similarity", "translation"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 1 or args.reps < 1:
@@ -62,9 +68,11 @@ def main():
     model.get_evaluation_model(7)
     model.precision = args.precision
     borders = ["black", "replicate", "mirror", "keep"] if args.border == "all" else [args.border]
+    shape = dict(strength=args.strength, rigidity=args.rigidity, shape_model=args.shape_model)
     lines = []
 
     def emit(rec):
+        rec.update(shape)
         print(json.dumps(rec), flush=True)
         lines.append(rec)
 
@@ -108,7 +116,7 @@ def main():
                       warp.data_ptr(), 0, 0, s())
             _lib.call("dvsg_frames_f32_to_u8", warp.data_ptr(), n, H0, W0, 1, u8.data_ptr(), W0, 0, s())
         for border in borders:
-            handle = model.locnet.view(args.render_filter, border)
+            handle = model.locnet.view(args.render_filter, border, **shape)
 
             def render():
                 _lib.call("dvsg_tps_render_u8", handle, F.data_ptr(), src.data_ptr(), n, H0, W0, 1, T.data_ptr(), 0,
@@ -132,7 +140,8 @@ def main():
         for K in (int(v) for v in args.streams.split(",")):
             for source_res, border in [(False, "black")] + [(True, b) for b in borders]:
                 on = OnlineStabilizer(model, max_streams=K, as_uint8=True, source_res=source_res,
-                                      render_filter=args.render_filter if source_res else "bilinear", border=border)
+                                      render_filter=args.render_filter if source_res else "bilinear", border=border,
+                                      **(shape if source_res else {}))
                 sids = [on.open() for _ in range(K)]
 
                 def feed(k):
