@@ -102,6 +102,7 @@ struct dvsg_locnet {
   int render_filter = DVSG_RENDER_BILINEAR;
   int render_border = DVSG_BORDER_BLACK;
   RenderShape render_shape;
+  int surface_format = DVSG_SURFACE_NV12;   // read by dvsg_tps_render_nv12 / _zoom_nv12 alone
   mutable std::atomic<int> n_views{0};
 };
 
@@ -987,6 +988,22 @@ int dvsg_locnet_view_create_shaped(const dvsg_locnet_t *net, int render_filter, 
   return view_create("dvsg_locnet_view_create_shaped", net, render_filter, render_border, view, shape);
 }
 
+// a view of net's parent with net's OWN filter, border and shape (inherited, unlike the three constructors above) and the
+// given surface format
+int dvsg_locnet_view_create_surface(const dvsg_locnet_t *net, int surface_format, dvsg_locnet_t **view) {
+  const char *fn = "dvsg_locnet_view_create_surface";
+  DVSG_REQUIRE(net, "%s: NULL net", fn);
+  DVSG_REQUIRE(view, "%s: NULL view", fn);
+  *view = nullptr;
+  DVSG_REQUIRE(surface_format == DVSG_SURFACE_NV12 || surface_format == DVSG_SURFACE_P010,
+               "%s: surface_format=%d is neither DVSG_SURFACE_NV12 (0) nor DVSG_SURFACE_P010 (1)", fn, surface_format);
+  if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
+  (*view)->surface_format = surface_format;
+  return DVSG_OK;
+}
+
+int dvsg_locnet_render_surface(const dvsg_locnet_t *net) { return net ? net->surface_format : DVSG_SURFACE_NV12; }
+
 int dvsg_locnet_render_shape(const dvsg_locnet_t *net, int *shape_model, float *strength, float *rigidity) {
   const RenderShape shape = net ? net->render_shape : RenderShape();
   if (shape_model) *shape_model = shape.model;
@@ -1369,16 +1386,21 @@ int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const ui
 }
 
 // dvsg_tps_render_u8 for NV12 frames (nv12.hip): the same T, then both planes warped at their own sizes in one launch.
-// Every argument is checked before the handle is read.
+// Every argument is checked before the handle is read; a P010 view's further checks follow, before any device work.
 int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
                          size_t frame_stride, int n, int H, int W, float *T, uint8_t *out_y, uint8_t *out_uv, size_t out_pitch,
                          size_t out_frame_stride, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_nv12: NULL net");
-  if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride))
+  if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
+                                     "dvsg_tps_render_nv12"))
     return rc;
+  if (net->surface_format == DVSG_SURFACE_P010)   // the first read of the handle
+    if (int rc = tps_render_p010_check(y, uv, pitch, frame_stride, n, W, out_y, out_uv, out_pitch, out_frame_stride,
+                                       "dvsg_tps_render_nv12"))
+      return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
                               out_pitch, out_frame_stride, stream, nullptr, net->render_filter, net->render_border,
-                              net->render_shape);
+                              net->render_shape, net->surface_format);
 }
 
 // dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
@@ -1389,9 +1411,13 @@ int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const 
   if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
                                      "dvsg_tps_render_zoom_nv12"))
     return rc;
+  if (net->surface_format == DVSG_SURFACE_P010)   // the first read of the handle
+    if (int rc = tps_render_p010_check(y, uv, pitch, frame_stride, n, W, out_y, out_uv, out_pitch, out_frame_stride,
+                                       "dvsg_tps_render_zoom_nv12"))
+      return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
                               out_pitch, out_frame_stride, stream, zoom, net->render_filter, net->render_border,
-                              net->render_shape);
+                              net->render_shape, net->surface_format);
 }
 
 // T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)

@@ -188,21 +188,18 @@ __global__ __launch_bounds__(kThreads) void ingest_nv12_resize_kernel(Nv12 s, in
 // A plane's sample as the float32 image dvsg_tps_warp_f32 would be given.  Luma: (float)((double)Y / 255.0); chroma:
 // (float)(((double)c - 128.0) / 255.0).  One correctly rounded float32 division of the exact integer gives the same value
 // for every byte (exhaustive on the host: tests/test_nv12_cpu.py; the luma case is load_pix<C>(const uint8_t *)'s).
-template <int C>
-__device__ __forceinline__ Pix<C> load_plane(const uint8_t *__restrict__ p) {
+// S = uint16_t: a P010 plane, the 10-bit rule of warp_device.h's sample_f32.
+template <int C, typename S = uint8_t>
+__device__ __forceinline__ Pix<C> load_plane(const S *__restrict__ p) {
   Pix<C> r;
-  if constexpr (C == 1) {
-    r.v[0] = (float)p[0] / 255.0f;
-  } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) r.v[c] = (float)((int)p[c] - 128) / 255.0f;
-  }
+  for (int c = 0; c < C; ++c) r.v[c] = load_sample<S, C == 2>(p + c);
   return r;
 }
 
 // sample_a_load on a plane whose rows are `pitch` bytes apart: its coordinate, index and weight expressions in its order,
-// C bytes per sample.  The indices are clipped into the plane, so every tap address lies inside it.
-template <int C>
+// C samples of type S per pixel.  The indices are clipped into the plane, so every tap address lies inside it.
+template <int C, typename S = uint8_t>
 __device__ __forceinline__ void plane_a_load(const uint8_t *__restrict__ img, size_t pitch, int H, int W, float xs, float ys,
                                              TapsA<C> &t) {
   const float x = ((xs + 1.0f) * (float)W) / 2.0f;  // :48
@@ -220,10 +217,11 @@ __device__ __forceinline__ void plane_a_load(const uint8_t *__restrict__ img, si
   t.wb = (x1f - x) * (y - y0f);
   t.wc = (x - x0f) * (y1f - y);
   t.wd = (x - x0f) * (y - y0f);
-  t.a = load_plane<C>(img + (size_t)y0 * pitch + x0 * C);  // (x0,y0)
-  t.b = load_plane<C>(img + (size_t)y1 * pitch + x0 * C);  // (x0,y1)
-  t.c = load_plane<C>(img + (size_t)y0 * pitch + x1 * C);  // (x1,y0)
-  t.d = load_plane<C>(img + (size_t)y1 * pitch + x1 * C);  // (x1,y1)
+  constexpr int kStep = C * kSampleBytes<S>;   // bytes from one sample to the next
+  t.a = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y0 * pitch + x0 * kStep));  // (x0,y0)
+  t.b = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y1 * pitch + x0 * kStep));  // (x0,y1)
+  t.c = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y0 * pitch + x1 * kStep));  // (x1,y0)
+  t.d = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y1 * pitch + x1 * kStep));  // (x1,y1)
 }
 
 // chroma back to a byte: clamp(floor((double)v * 255.0 + 128.5), 0, 255); NaN gives 0 like to_u8
@@ -232,16 +230,34 @@ __device__ __forceinline__ uint8_t chroma_u8(float v) {
   return d >= 255.0 ? (uint8_t)255 : (d > 0.0 ? (uint8_t)(int)d : (uint8_t)0);
 }
 
-// One output column and kTpsRows rows of one plane (ph x pw samples of C bytes), source and output of the same size.
+// The C P010 words of one output pixel at d (2-byte aligned): luma one 16-bit store, chroma one dword store where d allows.
+template <int C>
+__device__ __forceinline__ void store_words(uint8_t *__restrict__ d, const float (&v)[C]) {
+  if constexpr (C == 1) {
+    *reinterpret_cast<uint16_t *>(d) = p010_word(v[0], 0.5);
+  } else {
+    const uint16_t u = p010_word(v[0], 512.5), w = p010_word(v[1], 512.5);
+    if ((reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+      *reinterpret_cast<uint32_t *>(d) = (uint32_t)u | ((uint32_t)w << 16);
+    } else {
+      reinterpret_cast<uint16_t *>(d)[0] = u;
+      reinterpret_cast<uint16_t *>(d)[1] = w;
+    }
+  }
+}
+
+// One output column and kTpsRows rows of one plane (ph x pw pixels of C samples of type S), source and output of the same size.
 // kCubic (a bicubic view): the bicubic filter of warp_device.h behind the same map, bytes rounded to nearest.
 // kBorder (a view with a border mode): what an invalid sample becomes (warp_device.h, "border modes").
-template <int C, bool kCubic = false, int kBorder = DVSG_BORDER_BLACK>
+// S = uint16_t (a P010 view): the samples and the words of warp_device.h's sample_f32 / p010_word in both filters; the
+// planes' addresses are 2-byte aligned (tps_render_nv12_check).
+template <int C, bool kCubic = false, int kBorder = DVSG_BORDER_BLACK, typename S = uint8_t>
 __device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, size_t pitch, int ph, int pw, int i0, int j,
                                              const float (&xs)[4], const float (&ys)[4], uint8_t *__restrict__ out,
                                              size_t out_pitch) {
   if constexpr (kCubic) {
-    CubicTaps<C> ct[4];
-    cubic_load_rows<C, kBorder>(src, pitch, ph, pw, ph - i0, xs, ys, ct);  // all 16 row loads in flight
+    CubicTaps<C, S> ct[4];
+    cubic_load_rows<C, kBorder, S>(src, pitch, ph, pw, ph - i0, xs, ys, ct);  // all 16 row loads in flight
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = i0 + r;
@@ -250,10 +266,14 @@ __device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, si
         if (!ct[r].valid) continue;   // the caller's bytes stay
       }
       float v[C];
-      cubic_blend<C, C == 2, kBorder>(ct[r], v);
-      uint8_t *d = out + (size_t)i * out_pitch + (size_t)j * C;
+      cubic_blend<C, C == 2, kBorder, S>(ct[r], v);
+      uint8_t *d = out + (size_t)i * out_pitch + (size_t)j * (C * kSampleBytes<S>);
+      if constexpr (kSampleBytes<S> == 2) {
+        store_words<C>(d, v);
+      } else {
 #pragma unroll
-      for (int c = 0; c < C; ++c) d[c] = cubic_u8(v[c], C == 2 ? 128.5 : 0.5);
+        for (int c = 0; c < C; ++c) d[c] = cubic_u8(v[c], C == 2 ? 128.5 : 0.5);
+      }
     }
     return;
   }
@@ -263,9 +283,9 @@ __device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, si
   for (int r = 0; r < 4; ++r) {
     if (i0 + r >= ph) break;
     if constexpr (kBorder != DVSG_BORDER_BLACK)
-      border_a_load<C, C == 2, kBorder>(src, pitch, ph, pw, xs[r], ys[r], taps[r], use[r]);
+      border_a_load<C, C == 2, kBorder, S>(src, pitch, ph, pw, xs[r], ys[r], taps[r], use[r]);
     else
-      plane_a_load<C>(src, pitch, ph, pw, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
+      plane_a_load<C, S>(src, pitch, ph, pw, xs[r], ys[r], taps[r]);  // all 16 tap loads in flight
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -280,8 +300,10 @@ __device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, si
 #pragma unroll
       for (int c = 0; c < C; ++c) v[c] = use[r] ? v[c] : 0.0f;
     }
-    uint8_t *d = out + (size_t)i * out_pitch + (size_t)j * C;
-    if constexpr (C == 1) {
+    uint8_t *d = out + (size_t)i * out_pitch + (size_t)j * (C * kSampleBytes<S>);
+    if constexpr (kSampleBytes<S> == 2) {
+      store_words<C>(d, v);
+    } else if constexpr (C == 1) {
       d[0] = to_u8((double)v[0]);
     } else {
       const uint8_t u = chroma_u8(v[0]), w = chroma_u8(v[1]);
@@ -363,17 +385,13 @@ __global__ __launch_bounds__(kThreads) void nv12_render_zoom_kernel(Nv12 s, cons
     render_plane<1>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
 }
 
-// The NV12 render through a bicubic view: the tiles and the map of nv12_render_kernel (kZoom: of nv12_render_zoom_kernel; zoom
-// is read by that form only), render_plane's bicubic filter behind the map.  A kernel of its own: the two above stay the
-// instructions they were.
-template <bool kZoom>
-__global__ __launch_bounds__(kThreads) void nv12_render_cubic_kernel(Nv12 s, const float *__restrict__ coord,
-                                                                     const float *__restrict__ T,
-                                                                     const float *__restrict__ zoom, int H, int W, int P,
-                                                                     float sx_l, float sy_l, float sx_c, float sy_c,
-                                                                     int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
-                                                                     uint8_t *__restrict__ out_uv, size_t out_pitch,
-                                                                     size_t out_frame_stride) {
+// One tile of one plane of a frame for the kernels that are templates: nv12_render_kernel's tiles and map (kZoom: those of
+// nv12_render_zoom_kernel; zoom is read by that form only), render_plane<C, kCubic, kBorder, S> behind the map.
+template <typename S, bool kZoom, bool kCubic, int kBorder>
+__device__ __forceinline__ void render_tile(const Nv12 &s, const float *__restrict__ coord, const float *__restrict__ T,
+                                            const float *__restrict__ zoom, int H, int W, int P, float sx_l, float sy_l,
+                                            float sx_c, float sy_c, int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                            uint8_t *__restrict__ out_uv, size_t out_pitch, size_t out_frame_stride) {
   __shared__ float4 sp[64];
   __shared__ float4 sdy[64];
   __shared__ float sa[6];
@@ -397,14 +415,28 @@ __global__ __launch_bounds__(kThreads) void nv12_render_cubic_kernel(Nv12 s, con
   tps_map_rows<true, kZoom>(sp, sdy, sa, P, x_t, step_y, i0, xs, ys, z);
   const size_t in_off = (size_t)b * s.frame_stride, out_off = (size_t)b * out_frame_stride;
   if (chroma)
-    render_plane<2, true>(s.uv + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_uv + out_off, out_pitch);
+    render_plane<2, kCubic, kBorder, S>(s.uv + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_uv + out_off, out_pitch);
   else
-    render_plane<1, true>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
+    render_plane<1, kCubic, kBorder, S>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
+}
+
+// The NV12 render through a bicubic view: render_tile with the bicubic filter.  A kernel of its own: the two above stay
+// the instructions they were.
+template <bool kZoom>
+__global__ __launch_bounds__(kThreads) void nv12_render_cubic_kernel(Nv12 s, const float *__restrict__ coord,
+                                                                     const float *__restrict__ T,
+                                                                     const float *__restrict__ zoom, int H, int W, int P,
+                                                                     float sx_l, float sy_l, float sx_c, float sy_c,
+                                                                     int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                                     uint8_t *__restrict__ out_uv, size_t out_pitch,
+                                                                     size_t out_frame_stride) {
+  render_tile<uint8_t, kZoom, true, DVSG_BORDER_BLACK>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, out_y,
+                                                       out_uv, out_pitch, out_frame_stride);
 }
 
 // The NV12 render through a view with a border mode (dvsg_locnet_view_create_border; kBorder = DVSG_BORDER_REPLICATE,
-// _MIRROR or _KEEP), for either filter: nv12_render_cubic_kernel's arguments, tiles and map, render_plane's border mode
-// behind the map.  Kernels of their own again: a handle with DVSG_BORDER_BLACK launches the three kernels above.
+// _MIRROR or _KEEP), for either filter: render_tile with the border mode.  Kernels of their own again: a handle with
+// DVSG_BORDER_BLACK launches the three kernels above.
 template <bool kZoom, bool kCubic, int kBorder>
 __global__ __launch_bounds__(kThreads) void nv12_render_border_kernel(Nv12 s, const float *__restrict__ coord,
                                                                       const float *__restrict__ T,
@@ -414,32 +446,22 @@ __global__ __launch_bounds__(kThreads) void nv12_render_border_kernel(Nv12 s, co
                                                                       uint8_t *__restrict__ out_uv, size_t out_pitch,
                                                                       size_t out_frame_stride) {
   static_assert(kBorder != DVSG_BORDER_BLACK, "DVSG_BORDER_BLACK is the kernels without a border parameter");
-  __shared__ float4 sp[64];
-  __shared__ float4 sdy[64];
-  __shared__ float sa[6];
-  const int b = blockIdx.y, t = threadIdx.x;
-  int id = blockIdx.x;
-  const bool chroma = id >= n_l;
-  if (chroma) id -= n_l;
-  const int gx = chroma ? gx_c : gx_l;
-  const int i0 = (id / gx) * kTpsRows;
-  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
-  const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
-  float z = 1.0f;
-  if constexpr (kZoom) z = zoom[b];
-  tps_stage<true, kZoom>(coord, 0, T, b, P, t, i0, step_y, sp, sdy, sa, z);
-  __syncthreads();
-  const int j = (id % gx) * kThreads + t;
-  if (j >= pw) return;
-  float x_t = -1.0f + step_x * (float)j;  // tf.linspace: start + step * i (:94)
-  if constexpr (kZoom) x_t = z * x_t;
-  float xs[4], ys[4];
-  tps_map_rows<true, kZoom>(sp, sdy, sa, P, x_t, step_y, i0, xs, ys, z);
-  const size_t in_off = (size_t)b * s.frame_stride, out_off = (size_t)b * out_frame_stride;
-  if (chroma)
-    render_plane<2, kCubic, kBorder>(s.uv + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_uv + out_off, out_pitch);
-  else
-    render_plane<1, kCubic, kBorder>(s.y + in_off, s.pitch, ph, pw, i0, j, xs, ys, out_y + out_off, out_pitch);
+  render_tile<uint8_t, kZoom, kCubic, kBorder>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, out_y, out_uv,
+                                               out_pitch, out_frame_stride);
+}
+
+// The render through a P010 view (dvsg_locnet_view_create_surface): the planes are 16-bit words (include/dvsg_amd.h, "P010
+// frames"), pitch and frame strides still in bytes, for every filter, border and zoom: render_tile with S = uint16_t.
+// Kernels of their own: a handle without the property launches the 8-bit kernels above, whose instructions stay.
+template <bool kZoom, bool kCubic, int kBorder>
+__global__ __launch_bounds__(kThreads) void p010_render_kernel(Nv12 s, const float *__restrict__ coord,
+                                                               const float *__restrict__ T, const float *__restrict__ zoom,
+                                                               int H, int W, int P, float sx_l, float sy_l, float sx_c,
+                                                               float sy_c, int gx_l, int n_l, int gx_c,
+                                                               uint8_t *__restrict__ out_y, uint8_t *__restrict__ out_uv,
+                                                               size_t out_pitch, size_t out_frame_stride) {
+  render_tile<uint16_t, kZoom, kCubic, kBorder>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, out_y, out_uv,
+                                                out_pitch, out_frame_stride);
 }
 
 inline int grid_for(size_t items, int cap = 1 << 16) {
@@ -461,6 +483,17 @@ int check_nv12(const char *fn, const char *what, const void *y, const void *uv, 
   return DVSG_OK;
 }
 
+// what P010 frames ask on top of check_nv12: W samples are 2 W bytes of a row, and every address is a word's
+int check_p010(const char *fn, const char *what, const void *y, const void *uv, size_t pitch, size_t frame_stride, int n, int W) {
+  DVSG_REQUIRE(pitch >= 2 * (size_t)W, "%s: %s pitch=%zu < 2 W = %zu (P010: 2 bytes per sample)", fn, what, pitch, 2 * (size_t)W);
+  DVSG_REQUIRE(pitch % 2 == 0, "%s: %s pitch=%zu is odd (P010 words are 2-byte aligned)", fn, what, pitch);
+  DVSG_REQUIRE(n == 1 || frame_stride % 2 == 0, "%s: %s frame_stride=%zu is odd (P010 words are 2-byte aligned)", fn, what,
+               frame_stride);
+  DVSG_REQUIRE(reinterpret_cast<uintptr_t>(y) % 2 == 0, "%s: %s y plane pointer is not 2-byte aligned", fn, what);
+  DVSG_REQUIRE(reinterpret_cast<uintptr_t>(uv) % 2 == 0, "%s: %s uv plane pointer is not 2-byte aligned", fn, what);
+  return DVSG_OK;
+}
+
 int check_matrix(const char *fn, int matrix) {
   DVSG_REQUIRE(matrix == DVSG_YUV_BT601_LIMITED || matrix == DVSG_YUV_BT709_LIMITED,
                "%s: matrix=%d is neither DVSG_YUV_BT601_LIMITED (0) nor DVSG_YUV_BT709_LIMITED (1)", fn, matrix);
@@ -477,18 +510,43 @@ int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv,
   return check_nv12(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, H, W);
 }
 
-// the arguments have passed tps_render_nv12_check
+int tps_render_p010_check(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int W,
+                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, const char *fn) {
+  if (int rc = check_p010(fn, "source", y, uv, pitch, frame_stride, n, W)) return rc;
+  return check_p010(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, W);
+}
+
+// the arguments have passed tps_render_nv12_check (and, for DVSG_SURFACE_P010, tps_render_p010_check)
 int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream, const float *zoom,
-                         int render_filter, int render_border, RenderShape shape) {
+                         int render_filter, int render_border, RenderShape shape, int surface_format) {
   const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
   const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(H / 2, kTpsRows);
   DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);
   if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, shape)) return rc;
   hipStream_t s = as_stream(stream);
-  // algorithmic bytes: both planes once in, once out
-  ProfScope prof(kClsTpsWarp, s, 0.0, 3.0 * n * H * W);
+  // algorithmic bytes: both planes once in, once out (P010: two bytes per sample)
+  ProfScope prof(kClsTpsWarp, s, 0.0, (surface_format == DVSG_SURFACE_P010 ? 6.0 : 3.0) * n * H * W);
+  if (surface_format == DVSG_SURFACE_P010) {   // a P010 view: the same grid of workgroups for every filter, border and zoom
+    const dim3 grid((unsigned)(n_l + n_c), n);
+    auto launch = [&](auto kZoom, auto kCubic, auto kBorder) {
+      hipLaunchKernelGGL((p010_render_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
+                         Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
+                         lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y, out_uv, out_pitch, out_frame_stride);
+    };
+    const bool cubic = render_filter == DVSG_RENDER_BICUBIC;
+    if (render_border != DVSG_BORDER_BLACK) {
+      for_render_border(zoom != nullptr, cubic, render_border, launch);
+    } else {
+      const std::integral_constant<int, DVSG_BORDER_BLACK> black;
+      if (zoom && cubic) launch(std::true_type(), std::true_type(), black);
+      else if (zoom) launch(std::true_type(), std::false_type(), black);
+      else if (cubic) launch(std::false_type(), std::true_type(), black);
+      else launch(std::false_type(), std::false_type(), black);
+    }
+    return check_launch("p010_render_kernel");
+  }
   if (render_border != DVSG_BORDER_BLACK) {   // a view with a border mode: the same grid of workgroups for either filter
     const dim3 grid((unsigned)(n_l + n_c), n);
     for_render_border(zoom != nullptr, render_filter == DVSG_RENDER_BICUBIC, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {

@@ -126,6 +126,37 @@ __device__ __forceinline__ void sample_a_blend(const TapsA<C> &t, int Cn, float 
 }
 
 // ----------------------------------------------------------------------------------------
+// The sample type S of a plane of the source-size renders: uint8_t (RGB, NV12) or uint16_t (P010: a little-endian word whose
+// high 10 bits are the sample, s = word >> 6; the low 6 bits are ignored on input and written as 0).  kBias: a chroma plane,
+// centred on the neutral value.  One correctly rounded float32 division of the exact integer, as for the bytes; for all
+// 1024 values it equals (float)((double)s / 1023.0) (exhaustive on the host: tests/test_p010_cpu.py).
+// ----------------------------------------------------------------------------------------
+template <typename S>
+constexpr int kSampleBytes = (int)sizeof(S);
+
+// the sample `s` (a byte, or a word already shifted down) as the float32 image the filters blend
+template <typename S, bool kBias>
+__device__ __forceinline__ float sample_f32(int s) {
+  if constexpr (kSampleBytes<S> == 1) return kBias ? (float)(s - 128) / 255.0f : (float)s / 255.0f;
+  else return kBias ? (float)(s - 512) / 1023.0f : (float)s / 1023.0f;
+}
+
+// the same from the plane's memory
+template <typename S, bool kBias>
+__device__ __forceinline__ float load_sample(const S *__restrict__ p) {
+  if constexpr (kSampleBytes<S> == 1) return kBias ? (float)((int)p[0] - 128) / 255.0f : (float)p[0] / 255.0f;
+  else return sample_f32<S, kBias>((int)(p[0] >> 6));
+}
+
+// a P010 word from a blended value: clamp(floor((double)v * 1023.0 + half), 0, 1023) << 6, half = 0.5 (luma) or 512.5
+// (chroma), in both filters; NaN gives 0.  Luma rounds to NEAREST here where the NV12 bilinear render truncates: at 10 bits
+// truncation is no round trip (include/dvsg_amd.h, "P010 frames").
+__device__ __forceinline__ uint16_t p010_word(float v, double half) {
+  const double d = (double)v * 1023.0 + half;
+  return (uint16_t)((d >= 1023.0 ? 1023 : (d > 0.0 ? (int)d : 0)) << 6);
+}
+
+// ----------------------------------------------------------------------------------------
 // The border modes of the source-size renders (a view of dvsg_locnet_view_create_border; the header's "Border modes").  A
 // mode decides what an INVALID sample becomes and nothing else: DVSG_BORDER_KEEP does not store it, DVSG_BORDER_REPLICATE
 // and DVSG_BORDER_MIRROR evaluate the handle's filter at the coordinate moved into the plane.  The kernels with a border
@@ -139,13 +170,13 @@ __device__ __forceinline__ float border_coord(float x, float m) {
   return fminf(fmaxf(x, 0.0f), m);
 }
 
-// sample_a_load for a plane of bytes (ph x pw samples of C, rows `pitch` bytes apart; kBias: chroma, (b - 128) / 255) under a
+// sample_a_load for a plane of samples S (ph x pw samples of C, rows `pitch` bytes apart; kBias: chroma, sample_f32's) under a
 // border mode.  The taps are x0 = floor(xc) and min(x0 + 1, pw - 1), the upper weight from the UNclipped index -- sampler
 // A's clipped weights would cancel on the edge -- so a valid sample (xc == x, no index clipped) gets sampler A's taps and
 // weights, bit for bit, and one set of four loads serves valid and invalid samples without a divergent branch.  `use`: the
 // blend is the sample's value -- KEEP: the sample is valid (else nothing is stored); REPLICATE / MIRROR: the coordinate is
 // no NaN (else the black value).  Every address lies inside the plane's used bytes.
-template <int C, bool kBias, int kBorder>
+template <int C, bool kBias, int kBorder, typename S = uint8_t>
 __device__ __forceinline__ void border_a_load(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, float xs, float ys,
                                               TapsA<C> &t, bool &use) {
   const float x = ((xs + 1.0f) * (float)pw) / 2.0f;  // :48
@@ -162,16 +193,17 @@ __device__ __forceinline__ void border_a_load(const uint8_t *__restrict__ img, s
   t.wb = wx0 * wy1;
   t.wc = wx1 * wy0;
   t.wd = wx1 * wy1;
-  const uint8_t *pa = img + (size_t)y0 * pitch + (size_t)x0 * C;  // (x0,y0)
-  const uint8_t *pb = img + (size_t)y1 * pitch + (size_t)x0 * C;  // (x0,y1)
-  const uint8_t *pc = img + (size_t)y0 * pitch + (size_t)x1 * C;  // (x1,y0)
-  const uint8_t *pd = img + (size_t)y1 * pitch + (size_t)x1 * C;  // (x1,y1)
+  constexpr size_t kStep = (size_t)C * kSampleBytes<S>;   // bytes from one sample to the next
+  const S *pa = reinterpret_cast<const S *>(img + (size_t)y0 * pitch + (size_t)x0 * kStep);  // (x0,y0)
+  const S *pb = reinterpret_cast<const S *>(img + (size_t)y1 * pitch + (size_t)x0 * kStep);  // (x0,y1)
+  const S *pc = reinterpret_cast<const S *>(img + (size_t)y0 * pitch + (size_t)x1 * kStep);  // (x1,y0)
+  const S *pd = reinterpret_cast<const S *>(img + (size_t)y1 * pitch + (size_t)x1 * kStep);  // (x1,y1)
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    t.a.v[c] = kBias ? (float)((int)pa[c] - 128) / 255.0f : (float)pa[c] / 255.0f;
-    t.b.v[c] = kBias ? (float)((int)pb[c] - 128) / 255.0f : (float)pb[c] / 255.0f;
-    t.c.v[c] = kBias ? (float)((int)pc[c] - 128) / 255.0f : (float)pc[c] / 255.0f;
-    t.d.v[c] = kBias ? (float)((int)pd[c] - 128) / 255.0f : (float)pd[c] / 255.0f;
+    t.a.v[c] = load_sample<S, kBias>(pa + c);
+    t.b.v[c] = load_sample<S, kBias>(pb + c);
+    t.c.v[c] = load_sample<S, kBias>(pc + c);
+    t.d.v[c] = load_sample<S, kBias>(pd + c);
   }
 }
 
@@ -187,12 +219,13 @@ __device__ __forceinline__ void border_a_load(const uint8_t *__restrict__ img, s
 // lies wholly inside the row's pw C used bytes wherever the row has 4 samples; at the two edges (x0 = 0, x0 = pw - 2: the
 // window is one column off the taps) the replicated taps are picked out of it in registers (CubicTaps::d).  A plane with
 // pw < 4 has no such window and takes one byte load per tap component, column indices clamped: the same packed layout.
-// No load touches a byte outside the row's pw C used bytes.  DVSG_CUBIC_BYTE_TAPS (a build switch for the A/B of DESIGN
+// No load touches a byte outside the row's pw C used bytes.  A plane of 16-bit samples (S = uint16_t) is the same with
+// words for bytes: a row of the window is 8 C contiguous bytes, one load of 2 C dwords, two samples to a register.  DVSG_CUBIC_BYTE_TAPS (a build switch for the A/B of DESIGN
 // 5.bicubic, never set in the product) sends every plane down the byte path.
 // ----------------------------------------------------------------------------------------
-template <int C>
+template <int C, typename S = uint8_t>
 struct CubicTaps {
-  uint32_t raw[4][C];   // row r: byte k C + c = component c of window column k
+  uint32_t raw[4][C * kSampleBytes<S>];   // row r: sample k C + c (a byte or a 16-bit word) = component c of window column k
   float wx[4], wy[4];
   int d;                // taps' first column minus the window's: -1, 0 or 1 (2 too under a border mode: x0 = pw - 1)
   bool valid;           // the blend is the sample's value (else 0.0f); under a border mode: border_a_load's `use`
@@ -208,7 +241,7 @@ __device__ __forceinline__ void cubic_weights(float t, float (&w)[4]) {
   w[3] = ((1.0f - w[0]) - w[1]) - w[2];
 }
 
-// C dwords from any byte address
+// C dwords from any byte address (C <= 4)
 template <int C>
 __device__ __forceinline__ void load_bytes_x4(const uint8_t *__restrict__ p, uint32_t (&raw)[C]) {
   if constexpr (C == 1) {
@@ -225,9 +258,10 @@ __device__ __forceinline__ void load_bytes_x4(const uint8_t *__restrict__ p, uin
 
 // Coordinates, validity, weights, and the 4 row loads (only ISSUED here, like sample_a_load).  kWide: pw >= 4.
 // kBorder: steps 3-5 at the coordinate moved into the plane (border_coord; a NaN loads from (0, 0) and blends to 0.0f).
-template <int C, bool kWide, int kBorder = DVSG_BORDER_BLACK>
+template <int C, bool kWide, int kBorder = DVSG_BORDER_BLACK, typename S = uint8_t>
 __device__ __forceinline__ void cubic_load(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, float xs, float ys,
-                                           CubicTaps<C> &t) {
+                                           CubicTaps<C, S> &t) {
+  constexpr int kB = kSampleBytes<S>, kPer = 4 / kB;   // bytes of a sample, samples to a dword
   float x = ((xs + 1.0f) * (float)pw) / 2.0f;  // sampler A's (:48-49)
   float y = ((ys + 1.0f) * (float)ph) / 2.0f;
   t.valid = sample_a_valid(ph, pw, xs, ys);
@@ -248,7 +282,8 @@ __device__ __forceinline__ void cubic_load(const uint8_t *__restrict__ img, size
     const int xw = clampi(x0 - 1, 0, pw - 4);
     t.d = x0 - 1 - xw;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) load_bytes_x4<C>(img + (size_t)clampi(y0 - 1 + r, 0, ph - 1) * pitch + (size_t)xw * C, t.raw[r]);
+    for (int r = 0; r < 4; ++r)
+      load_bytes_x4<C * kB>(img + (size_t)clampi(y0 - 1 + r, 0, ph - 1) * pitch + (size_t)xw * (C * kB), t.raw[r]);
     return;
   }
   t.d = 0;
@@ -256,27 +291,27 @@ __device__ __forceinline__ void cubic_load(const uint8_t *__restrict__ img, size
   for (int r = 0; r < 4; ++r) {
     const uint8_t *row = img + (size_t)clampi(y0 - 1 + r, 0, ph - 1) * pitch;
 #pragma unroll
-    for (int c = 0; c < C; ++c) t.raw[r][c] = 0;
+    for (int c = 0; c < C * kB; ++c) t.raw[r][c] = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const uint8_t *p = row + (size_t)clampi(x0 - 1 + k, 0, pw - 1) * C;
+      const S *p = reinterpret_cast<const S *>(row + (size_t)clampi(x0 - 1 + k, 0, pw - 1) * (C * kB));
 #pragma unroll
-      for (int c = 0; c < C; ++c) t.raw[r][(k * C + c) / 4] |= (uint32_t)p[c] << (8 * ((k * C + c) % 4));
+      for (int c = 0; c < C; ++c) t.raw[r][(k * C + c) / kPer] |= (uint32_t)p[c] << (8 * kB * ((k * C + c) % kPer));
     }
   }
 }
 
 // cubic_load for the rows i0 .. i0 + n_rows - 1 (n_rows <= 4) of one output column: every load of the thread in flight
 // together.  Which path a plane takes is decided once, outside the rows (a load under a per-row branch is waited for there).
-template <int C, int kBorder = DVSG_BORDER_BLACK>
+template <int C, int kBorder = DVSG_BORDER_BLACK, typename S = uint8_t>
 __device__ __forceinline__ void cubic_load_rows(const uint8_t *__restrict__ img, size_t pitch, int ph, int pw, int n_rows,
-                                                const float (&xs)[4], const float (&ys)[4], CubicTaps<C> (&ct)[4]) {
+                                                const float (&xs)[4], const float (&ys)[4], CubicTaps<C, S> (&ct)[4]) {
 #ifndef DVSG_CUBIC_BYTE_TAPS
   if (pw >= 4) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (r >= n_rows) break;
-      cubic_load<C, true, kBorder>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
+      cubic_load<C, true, kBorder, S>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
     }
     return;
   }
@@ -284,14 +319,15 @@ __device__ __forceinline__ void cubic_load_rows(const uint8_t *__restrict__ img,
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     if (r >= n_rows) break;
-    cubic_load<C, false, kBorder>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
+    cubic_load<C, false, kBorder, S>(img, pitch, ph, pw, xs[r], ys[r], ct[r]);
   }
 }
 
-// v[c] of one pixel; kBias: the chroma plane's samples, (b - 128) / 255.  An invalid pixel is exactly 0.
+// v[c] of one pixel; kBias: the chroma plane's samples (sample_f32).  An invalid pixel is exactly 0.
 // kBorder: the window may be two columns off the taps (x0 = pw - 1: the taps are columns pw - 2, pw - 1, pw - 1, pw - 1).
-template <int C, bool kBias, int kBorder = DVSG_BORDER_BLACK>
-__device__ __forceinline__ void cubic_blend(const CubicTaps<C> &t, float (&v)[C]) {
+template <int C, bool kBias, int kBorder = DVSG_BORDER_BLACK, typename S = uint8_t>
+__device__ __forceinline__ void cubic_blend(const CubicTaps<C, S> &t, float (&v)[C]) {
+  constexpr int kB = kSampleBytes<S>, kPer = 4 / kB;
   float h[4][C];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -300,8 +336,8 @@ __device__ __forceinline__ void cubic_blend(const CubicTaps<C> &t, float (&v)[C]
     for (int k = 0; k < 4; ++k) {
 #pragma unroll
       for (int c = 0; c < C; ++c) {
-        const int byte = (int)((t.raw[r][(k * C + c) / 4] >> (8 * ((k * C + c) % 4))) & 0xffu);
-        p[k][c] = kBias ? (float)(byte - 128) / 255.0f : (float)byte / 255.0f;
+        const uint32_t raw = t.raw[r][(k * C + c) / kPer] >> (8 * kB * ((k * C + c) % kPer));
+        p[k][c] = sample_f32<S, kBias>(kB == 1 ? (int)(raw & 0xffu) : (int)((raw & 0xffffu) >> 6));
       }
     }
     if (t.d != 0) {   // the window is one column off the taps: edge replicate

@@ -90,6 +90,15 @@ def check_shape(strength=1.0, rigidity=0.0, shape_model="affine", source_size_re
     return out[0], out[1], shape_model
 
 
+SURFACES = {"nv12": 0, "p010": 1}   # DVSG_SURFACE_NV12, DVSG_SURFACE_P010
+
+
+def check_surface(surface):
+    if not isinstance(surface, str) or surface not in SURFACES:
+        raise ValueError("surface must be 'nv12' or 'p010', got %r" % (surface,))
+    return surface
+
+
 class LocNet(object):
     """Owns the device-side network (`dvsg_locnet_t`) and one growable workspace per stream that uses it."""
 
@@ -112,17 +121,29 @@ class LocNet(object):
         _lib.call("dvsg_locnet_create", n, c_names, c_data, c_nd,
                   dims.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(handle))
         self.handle = handle
-        self._views = {}   # (render filter, border, strength, rigidity, shape model) -> view handle, made on first use
+        self._views = {}   # (render filter, border, strength, rigidity, shape model, surface) -> view handle, made on first use
         self._keep = None  # the library copied everything to the device
         self._ws = None
         self.in_channels = _lib.load().dvsg_locnet_in_channels(self.handle)
 
-    def view(self, render_filter="bilinear", border="black", strength=1.0, rigidity=0.0, shape_model="affine"):
+    def view(self, render_filter="bilinear", border="black", strength=1.0, rigidity=0.0, shape_model="affine", surface="nv12"):
         """The handle the source-size renders, the coverage scan and `dvsg_tps_coefficients_f32` take for `render_filter`,
         `border` and the warp shape: this network itself for ("bilinear", "black") unshaped, else a view of it
         (`dvsg_locnet_view_create_border`, or `dvsg_locnet_view_create_shaped` when strength != 1 or rigidity != 0: the same
         network, nothing copied, its own filter, border mode and shape), made once per set of five values and kept until the
-        network goes.  An unshaped view is the same whatever its shape_model."""
+        network goes.  An unshaped view is the same whatever its shape_model.  surface="p010": the view of that handle
+        whose NV12 renders read and write P010 surfaces (`dvsg_locnet_view_create_surface`: filter, border and shape
+        inherited); no other entry point reads it."""
+        check_surface(surface)
+        if surface != "nv12":
+            key = (render_filter, border, strength, rigidity, shape_model, surface)
+            v = self._views.get(key)
+            if v is None:
+                inner = self.view(render_filter, border, strength, rigidity, shape_model)
+                v = ctypes.c_void_p()
+                _lib.call("dvsg_locnet_view_create_surface", inner, SURFACES[surface], ctypes.byref(v))
+                self._views[key] = v
+            return v
         check_render_filter(render_filter)
         check_border(border)
         strength, rigidity, shape_model = check_shape(strength, rigidity, shape_model)
@@ -131,7 +152,7 @@ class LocNet(object):
             shape_model = "affine"
             if render_filter == "bilinear" and border == "black":
                 return self.handle
-        key = (render_filter, border, strength, rigidity, shape_model)
+        key = (render_filter, border, strength, rigidity, shape_model, surface)
         v = self._views.get(key)
         if v is None:
             v = ctypes.c_void_p()

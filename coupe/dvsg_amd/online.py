@@ -24,6 +24,7 @@ from .clip import SKIP_LENGTH, _check_crop, _check_crop_grid, _check_window, che
 
 
 YUV_MATRICES = {"bt601": 0, "bt709": 1}   # DVSG_YUV_BT601_LIMITED, DVSG_YUV_BT709_LIMITED
+SURFACE_FORMATS = ("nv12", "p010")         # frame formats that are decoder surfaces: two planes, a source-size render
 SCENE_STATE_INTS = 68                     # DVSG_SCENE_STATE_INTS: k, cuts, S, 0, the previous histogram [64]
 
 
@@ -96,6 +97,17 @@ class OnlineStabilizer(object):
     itself is still the one `dvsg_stabilize_ring_inplace_f32` call, on the same pool of model-size float RGB frames.
     side_by_side, as_uint8, channel_order="bgr", float frames and odd sizes raise ValueError.
 
+    frame_format="p010": the same for 10-bit surfaces (include/dvsg_amd.h, "P010 frames"): a Y plane and an interleaved UV
+    plane of 16-bit little-endian words, the sample in the high 10 bits.  A frame is a 2-D array or device tensor in one of
+    two forms and comes back in the form it was given: uint8 [3 H0 / 2, 2 W0] (the words' bytes, low byte first), or uint16
+    [3 H0 / 2, W0] (NumPy uint16, or torch.uint16 where this torch has it); internally it is the uint8 form.  The options,
+    checks and results are those of "nv12" (even H0, W0 >= 4; no side_by_side, as_uint8 or channel_order; crop, scene_cut,
+    border="keep" surfaces, strength and rigidity as there; the coverage scan's grids stay (H0, W0) and (H0 / 2, W0 / 2)).
+    What the network sees is DEFINED as the NV12 surface made of each word's HIGH BYTE (word >> 8, the sample's top 8
+    bits): one strided copy per source-size group, `src[..., 1::2]`, into a buffer this object owns, then the same
+    `dvsg_frames_ingest_nv12`.  The pool, F_t and the crop state are therefore those of an "nv12" run fed those bytes.  The
+    render goes through `LocNet.view(..., surface="p010")` with pitch = 2 W0 and warps the 10-bit planes themselves.
+
     render_filter: the filter of the source-size render (source_res=True or frame_format="nv12", with and without crop).
     "bilinear" (default) is sampler A; "bicubic" gives the render calls a view of the network with that filter
     (`LocNet.view`, include/dvsg_amd.h "Views and the render filter": 16 taps, OpenCV's INTER_CUBIC weights, bytes rounded
@@ -164,9 +176,10 @@ class OnlineStabilizer(object):
         from . import _lib
         from ._tensor import device
         from .networks import check_border, check_render_filter, check_shape
-        check_render_filter(render_filter, bool(source_res) or frame_format == "nv12")
-        check_border(border, bool(source_res) or frame_format == "nv12")
-        shape = check_shape(strength, rigidity, shape_model, bool(source_res) or frame_format == "nv12")
+        surface = frame_format in SURFACE_FORMATS
+        check_render_filter(render_filter, bool(source_res) or surface)
+        check_border(border, bool(source_res) or surface)
+        shape = check_shape(strength, rigidity, shape_model, bool(source_res) or surface)
         if border == "keep" and side_by_side:
             raise ValueError("border='keep' has no side_by_side layout: the surface a stream keeps is its output frame")
         crop = _check_crop(crop)
@@ -181,17 +194,18 @@ class OnlineStabilizer(object):
             raise ValueError("crop_recover must be >= 0, got %r" % (crop_recover,))
         if channel_order not in ("rgb", "bgr"):
             raise ValueError("channel_order must be 'rgb' or 'bgr'")
-        if frame_format not in ("rgb", "nv12"):
-            raise ValueError("frame_format must be 'rgb' or 'nv12', got %r" % (frame_format,))
+        if frame_format not in ("rgb",) + SURFACE_FORMATS:
+            raise ValueError("frame_format must be 'rgb', 'nv12' or 'p010', got %r" % (frame_format,))
         if yuv_matrix not in YUV_MATRICES:
             raise ValueError("yuv_matrix must be 'bt709' or 'bt601', got %r" % (yuv_matrix,))
-        if frame_format == "nv12":
+        if surface:
             if side_by_side:
-                raise ValueError("frame_format='nv12' has no side_by_side layout: an NV12 frame has two planes")
+                raise ValueError("frame_format=%r has no side_by_side layout: such a frame has two planes" % (frame_format,))
             if as_uint8:
-                raise ValueError("frame_format='nv12' always returns uint8 NV12 frames: as_uint8 does not apply")
+                raise ValueError("frame_format=%r always returns frames in the layout it is given: as_uint8 does not apply"
+                                 % (frame_format,))
             if channel_order != "rgb":
-                raise ValueError("frame_format='nv12' has no channel_order: the pool is RGB, got %r" % (channel_order,))
+                raise ValueError("frame_format=%r has no channel_order: the pool is RGB, got %r" % (frame_format, channel_order))
             source_res = True
         if model.locnet is None:
             raise _lib.DvsgError("StabNet has no weights: call load_weights()/load_ckpt() first")
@@ -212,6 +226,7 @@ class OnlineStabilizer(object):
         self.strength, self.rigidity, self.shape_model = shape
         self._keep = {}           # border="keep": ring -> the stream's persistent output surface, at its source size
         self._keep_fresh = set()  # rings whose next frame is a step 0: the surface restarts from that frame's source bytes
+        self._hi = {}             # frame_format="p010": (H0, W0) -> uint8 [max_streams, 3 H0 / 2, W0], the words' high bytes
         self._cut = None          # int32 [B] on the device: the `cut` output of this step's dvsg_scene_step_f32
         dev = device()
         self.pool = torch.empty((self.max_streams * self.frames_per_stream, self.h, self.w, 3), dtype=torch.float32,
@@ -438,7 +453,7 @@ class OnlineStabilizer(object):
         from ._tensor import device, ptr, stream
         if not frames:
             return {}
-        if self.frame_format == "nv12":
+        if self.frame_format in SURFACE_FORMATS:
             return self._step_nv12(frames)
         dev = device()
         h, w, flip = self.h, self.w, self.flip
@@ -598,68 +613,100 @@ class OnlineStabilizer(object):
         return res
 
     def _step_nv12(self, frames):
-        """`step` for frame_format="nv12": ingest per source size, the one stabilise call, render per source size."""
+        """`step` for frame_format="nv12" and "p010": ingest per source size, the one stabilise call, render per source size.
+        bps: the bytes of a sample; a P010 frame is handled as its bytes, uint8 [3 H0 / 2, 2 W0]."""
         from . import _lib
         from ._tensor import device, ptr, stream
         dev = device()
         h, w = self.h, self.w
+        name, bps = self.frame_format, 2 if self.frame_format == "p010" else 1
+        u16 = getattr(torch, "uint16", None)
+        words = set()   # streams whose frame came as 16-bit words and leaves as such
         # ---- check everything before the first launch: a bad frame leaves every stream as it was
         entries = []
         for sid, fr in frames.items():
             ring, k = self._stream(sid)
             host = not isinstance(fr, torch.Tensor)
+            if bps == 2 and host and np.asarray(fr).dtype == np.uint16:   # the words' bytes as they lie in memory
+                if not np.little_endian:
+                    raise ValueError("stream %r: P010 words are little-endian; pass the uint8 form on this host" % (sid,))
+                fr = np.ascontiguousarray(fr).view(np.uint8)
+                words.add(sid)
             t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
+            if bps == 2 and u16 is not None and t.dtype == u16:
+                t = t.contiguous().view(torch.uint8)
+                words.add(sid)
             if t.dtype.is_floating_point:
-                raise ValueError("stream %r: frame_format='nv12' takes uint8 surfaces, not float frames (%s)" % (sid, t.dtype))
+                raise ValueError("stream %r: frame_format=%r takes uint8 surfaces, not float frames (%s)" % (sid, name, t.dtype))
             if t.dtype != torch.uint8:
-                raise TypeError("stream %r: NV12 frames must be uint8, got %s" % (sid, t.dtype))
+                raise TypeError("stream %r: %s frames must be uint8%s, got %s"
+                                % (sid, name.upper(), " or uint16" if bps == 2 else "", t.dtype))
             if t.dim() != 2:
-                raise ValueError("stream %r: an NV12 frame must be [3*H0/2, W0], got %s" % (sid, tuple(t.shape)))
-            R, W0 = int(t.shape[0]), int(t.shape[1])
+                raise ValueError("stream %r: %s frame must be [3*H0/2, %sW0], got %s"
+                                 % (sid, "an NV12" if bps == 1 else "a P010", "2*" if bps == 2 else "", tuple(t.shape)))
+            R, W0 = int(t.shape[0]), int(t.shape[1]) // bps
             H0 = 2 * R // 3
-            if R % 3 or H0 % 2 or W0 % 2 or H0 < 4 or W0 < 4:
-                raise ValueError("stream %r: an NV12 frame [3*H0/2, W0] needs even H0, W0 >= 4 (odd sizes have no chroma "
-                                 "layout), got %s" % (sid, tuple(t.shape)))
+            if R % 3 or H0 % 2 or W0 % 2 or H0 < 4 or W0 < 4 or int(t.shape[1]) % bps:
+                raise ValueError("stream %r: %s frame [3*H0/2, %sW0] needs even H0, W0 >= 4 (odd sizes have no chroma "
+                                 "layout), got %s" % (sid, "an NV12" if bps == 1 else "a P010 uint8", "2*" if bps == 2 else "",
+                                                      tuple(t.shape)))
             entries.append(((H0, W0), sid, host, t, ring, k))
         entries.sort(key=lambda e: e[0])   # one contiguous batch range per source size
         B = len(entries)
         _, table, out_slots, in_slots, rings = self._slot_tables(entries)
         n_pool = int(self.pool.shape[0])
-        groups = []   # (i, j, device frames [j-i, 3 H0 / 2, W0])
+        groups = []   # (i, j, device frames [j-i, 3 H0 / 2, bps W0])
+        hi_used = set()
         i = 0
         while i < B:
             (H0, W0), j = entries[i][0], i
             while j < B and entries[j][0] == (H0, W0):
                 j += 1
             src = torch.stack([e[3].to(dev) for e in entries[i:j]]).contiguous()
-            _lib.call("dvsg_frames_ingest_nv12", ptr(src), ptr(src) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0,
+            seen = src
+            if bps == 2:   # the network sees the words' high bytes: one strided copy into a buffer of this object's
+                buf = self._hi.get((H0, W0))
+                if buf is None:
+                    buf = self._hi[(H0, W0)] = torch.empty((self.max_streams, 3 * H0 // 2, W0), dtype=torch.uint8, device=dev)
+                hi_used.add((H0, W0))
+                seen = buf[:j - i]
+                seen.copy_(src[..., 1::2])
+            _lib.call("dvsg_frames_ingest_nv12", ptr(seen), ptr(seen) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0,
                       self.yuv_matrix, ptr(self.pool), n_pool, ptr(in_slots[i:j]), h, w, stream())
             groups.append((i, j, src))
             i = j
+        for key in [k for k in self._hi if k not in hi_used]:   # a source size no stream of this step has
+            del self._hi[key]
         if rings is not None:
             self._scene_step(rings, table, out_slots)
         self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
         for e in entries:
             self._streams[e[1]][1] += 1
         res = {}
-        net = self.model.locnet.view(self.render_filter, self.border, self.strength, self.rigidity, self.shape_model)
+        net = self.model.locnet.view(self.render_filter, self.border, self.strength, self.rigidity, self.shape_model,
+                                     surface=name)
         for i, j, src in groups:
             H0, W0 = entries[i][0]
+            pitch = bps * W0   # rows are packed; the UV plane follows the Y plane
             out, done = self._keep_surfaces(entries, i, j, src) if self.border == "keep" else (torch.empty_like(src), None)
             if self.crop is None:
-                _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * W0, W0,
-                          3 * H0 // 2 * W0, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * W0, W0,
-                          3 * H0 // 2 * W0, stream())
+                _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * pitch, pitch,
+                          3 * H0 // 2 * pitch, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * pitch, pitch,
+                          3 * H0 // 2 * pitch, stream())
             else:   # chroma leaves the source first: both planes are scanned, each on its own grid
                 zoom = self._step_zoom(entries, i, j, [(H0, W0), (H0 // 2, W0 // 2)])
                 _lib.call("dvsg_tps_render_zoom_nv12", net, ptr(self._F[i:j]), ptr(src),
-                          ptr(src) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]), ptr(out),
-                          ptr(out) + H0 * W0, W0, 3 * H0 // 2 * W0, stream())
+                          ptr(src) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]),
+                          ptr(out), ptr(out) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, stream())
             if done is not None:
                 out = done()
             out_h = out.cpu().numpy() if any(entries[b][2] for b in range(i, j)) else None
             for b in range(i, j):
-                res[entries[b][1]] = out_h[b - i] if entries[b][2] else out[b - i]
+                sid = entries[b][1]
+                o = out_h[b - i] if entries[b][2] else out[b - i]
+                if sid in words:   # back in the form it came in
+                    o = o.view(np.uint16) if entries[b][2] else o.view(u16)
+                res[sid] = o
         return {sid: res[sid] for sid in frames}
 
 
@@ -670,7 +717,8 @@ def stabilize_clips(model, clips, batch=None, **kw):
     scene_cut and scene_min_len among them: every clip then restarts its own history at its own cuts; strength, rigidity
     and shape_model shape every clip's source-size render alike.
     Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips).  With
-    frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result.  crop=... is OnlineStabilizer's: frame k of a
+    frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result; with "p010" [N,3*H0/2,2*W0] uint8 or
+    [N,3*H0/2,W0] uint16, likewise.  crop=... is OnlineStabilizer's: frame k of a
     clip is rendered with the zoom the ratchet has reached at frame k, NOT with `stabilize_clip`'s one clip-wide zoom
     (the two agree from the frame on that sets the clip's minimum)."""
     from ._tensor import device
@@ -680,12 +728,22 @@ def stabilize_clips(model, clips, batch=None, **kw):
     batch = K if batch is None else max(1, min(int(batch), K))
     dev = device()
     host = [not isinstance(c, torch.Tensor) for c in clips]
-    dclips = []
+    dclips, words = [], set()
     for c, hst in zip(clips, host):
+        fmt = kw.get("frame_format", "rgb")
+        if fmt == "p010":   # uint16 clips run in the uint8 form and come back as words
+            u16 = getattr(torch, "uint16", None)
+            if hst and np.asarray(c).dtype == np.uint16:
+                c = np.ascontiguousarray(c).view(np.uint8)
+                words.add(len(dclips))
+            elif not hst and u16 is not None and c.dtype == u16:
+                c = c.contiguous().view(torch.uint8)
+                words.add(len(dclips))
         t = (torch.as_tensor(np.ascontiguousarray(c)) if hst else c).to(dev).contiguous()
-        if kw.get("frame_format", "rgb") == "nv12":
+        if fmt in SURFACE_FORMATS:
             if t.dim() != 3 or t.shape[0] < 1:
-                raise ValueError("every NV12 clip must be [N,3*H0/2,W0] with N >= 1, got %s" % (tuple(t.shape),))
+                raise ValueError("every %s clip must be [N,3*H0/2,%sW0] with N >= 1, got %s"
+                                 % (fmt.upper(), "2*" if fmt == "p010" else "", tuple(t.shape)))
         elif t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
             raise ValueError("every clip must be [N,h,w,3] with N >= 1, got %s" % (tuple(t.shape),))
         dclips.append(t)
@@ -712,5 +770,7 @@ def stabilize_clips(model, clips, batch=None, **kw):
         else:
             o = torch.stack(outs[c])
             o = o.cpu().numpy() if host[c] else o
+            if c in words:
+                o = o.view(np.uint16) if host[c] else o.view(torch.uint16)
         result.append(o)
     return result

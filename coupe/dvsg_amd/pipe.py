@@ -21,6 +21,10 @@ device buffers for the two repacks where the source or the sink is Y4M).  A slot
   (c) the source's writer thread waits on that event -- the only host-side wait on the device -- writes the frame and hands
       the slot back to the reader.
 
+Ten-bit runs (`C420p10` Y4M or raw P010 at every end) are the same loop around one `OnlineStabilizer(frame_format="p010")`:
+frames are uint8 [3 H / 2, 2 W], the repacks are `y4m.i420p10_to_p010` and `y4m.p010_to_i420p10`.  All ends of one call share
+a bit depth.
+
 A slot is not refilled before its frame is written, so a source never has more than `depth` frames between `readinto` and
 `write` (back-pressure: a slow sink stalls its reader, memory does not grow), and every reuse hazard is covered by the order
 of the stations: when a slot returns to (a) its download has finished, hence the step that read its device input, hence its
@@ -115,6 +119,10 @@ class _Staging(object):
             src.record_stream(self.copy_out)    # the step's own output tensor: its memory is not reused before the copy
 
 
+# the planar layouts and their repacks to and from what OnlineStabilizer takes
+_PLANAR = {"i420": (y4m.i420_to_nv12, y4m.nv12_to_i420), "i420p10": (y4m.i420p10_to_p010, y4m.p010_to_i420p10)}
+
+
 class _Lane(object):
     """One source, its sink, its slots and its two threads."""
 
@@ -137,8 +145,8 @@ class _Lane(object):
         for _ in range(depth):
             s = _Slot()
             s.host_in, s.dev_in = staging.host(shape), staging.dev(shape)
-            s.nv12_in = staging.dev(shape) if source.layout == "i420" else None
-            s.dev_out = staging.dev(shape) if sink.layout == "i420" else None
+            s.nv12_in = staging.dev(shape) if source.layout in _PLANAR else None
+            s.dev_out = staging.dev(shape) if sink.layout in _PLANAR else None
             s.host_out = staging.host(shape)
             s.e_up, s.e_step, s.e_down = staging.event(), staging.event(), staging.event()
             self.free.put(s)
@@ -189,18 +197,18 @@ class _Lane(object):
 
     # ---- (b)
     def upload(self, slot):
-        """The slot's frame on the device as NV12 [3 H / 2, W], ordered on the compute stream."""
+        """The slot's frame on the device as NV12 [3 H / 2, W] (10-bit: P010 [3 H / 2, 2 W]), ordered on the compute stream."""
         self.staging.upload(slot)
         if slot.nv12_in is None:
             return slot.dev_in
-        return y4m.i420_to_nv12(slot.dev_in, out=slot.nv12_in)
+        return _PLANAR[self.source.layout][0](slot.dev_in, out=slot.nv12_in)
 
     def submit(self, slot, out):
         """The stabilised NV12 frame `out` (device) on its way to the sink."""
         if tuple(out.shape) != tuple(slot.host_out.shape):
             raise ValueError("source %d: the step returned %s for a frame of %s" % (self.index, tuple(out.shape),
                                                                                   tuple(slot.host_out.shape)))
-        src = out if slot.dev_out is None else y4m.nv12_to_i420(out, out=slot.dev_out)
+        src = out if slot.dev_out is None else _PLANAR[self.sink.layout][1](out, out=slot.dev_out)
         self.staging.download(slot, src)
         self.towrite.put(slot)
 
@@ -279,20 +287,28 @@ def _snapshot(on, sid):
 
 
 def _check_ends(sources, sinks):
+    """Everything that can be said of the ends before a frame is read; returns the run's bit depth (8 without sources)."""
     if len(sources) != len(sinks):
         raise ValueError("stabilize_pipes needs one sink per source, got %d sources and %d sinks" % (len(sources), len(sinks)))
+    bits = None
     for i, (src, snk) in enumerate(zip(sources, sinks)):
         for end, what in ((src, "source"), (snk, "sink")):
-            if getattr(end, "layout", None) not in ("i420", "nv12"):
-                raise ValueError("%s %d: layout must be 'i420' or 'nv12', got %r" % (what, i, getattr(end, "layout", None)))
+            layout = getattr(end, "layout", None)
+            if layout not in y4m.LAYOUT_BITS:
+                raise ValueError("%s %d: layout must be 'i420' or 'nv12' (10-bit: 'i420p10' or 'p010'), got %r" % (what, i, layout))
+            bits = y4m.LAYOUT_BITS[layout] if bits is None else bits
+            if y4m.LAYOUT_BITS[layout] != bits:
+                raise ValueError("%s %d is %d-bit (%s) in a %d-bit run: all sources and sinks of one call share a bit depth"
+                                 % (what, i, y4m.LAYOUT_BITS[layout], layout, bits))
         y4m.check_size(int(src.width), int(src.height))
-        if tuple(src.frame_shape) != (3 * int(src.height) // 2, int(src.width)):
-            raise ValueError("source %d: frame_shape %s is not [3 H / 2, W] of %d x %d"
-                             % (i, tuple(src.frame_shape), src.width, src.height))
+        if tuple(src.frame_shape) != (3 * int(src.height) // 2, (2 if bits == 10 else 1) * int(src.width)):
+            raise ValueError("source %d: frame_shape %s is not [3 H / 2, %sW] of %d x %d"
+                             % (i, tuple(src.frame_shape), "2 " if bits == 10 else "", src.width, src.height))
         size = (getattr(snk, "width", src.width), getattr(snk, "height", src.height))
         if size != (src.width, src.height):
             raise ValueError("sink %d is %d x %d but its source is %d x %d: the output has the size of the input"
                              % ((i,) + size + (src.width, src.height)))
+    return bits or 8
 
 
 def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, **online_kw):
@@ -305,6 +321,10 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
         a sink: `layout`, `write(frame)` for a uint8 array [3 H / 2, W] that is only valid during the call, and optionally
             `flush()`, `width` and `height` (which must then be the source's).
         Sources may differ in size, layout and length; a sink may have another layout than its source.
+        Ten bits: layouts "i420p10" (Y4M C420p10: planar, value in the low 10 bits of a little-endian word) and "p010"
+        (semi-planar, value in the high 10 bits), frames uint8 [3 H / 2, 2 W].  All sources and sinks of one call share a
+        bit depth; a mix raises ValueError before any frame is read.  A 10-bit run goes through one
+        `OnlineStabilizer(frame_format="p010")`; an 8-bit run is what it was.
     batch: streams per step (default: all sources).  depth: frames in flight per source, >= 1.
     online_kw: OnlineStabilizer's crop, crop_*, scene_cut, scene_min_len, skip_length, render_filter, border, strength, rigidity,
         shape_model and yuv_matrix, passed through.
@@ -326,7 +346,7 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
     Returns a list with, per source, dict(frames written, high_water: the most frames it ever had between readinto and
     write (<= depth), seconds from its opening to its last write, zoom with crop and cuts with scene_cut, else None)."""
     sources, sinks = list(sources), list(sinks)
-    _check_ends(sources, sinks)
+    bits = _check_ends(sources, sinks)
     K = len(sources)
     if isinstance(depth, bool) or int(depth) != depth or depth < 1:
         raise ValueError("depth must be an integer >= 1, got %r" % (depth,))
@@ -339,7 +359,7 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
         kw = dict(online_kw)
         if kw.get("yuv_matrix", "auto") == "auto":
             kw["yuv_matrix"] = y4m.default_yuv_matrix(sources[0].height)
-        on = OnlineStabilizer(model, max_streams=batch, frame_format="nv12", **kw)
+        on = OnlineStabilizer(model, max_streams=batch, frame_format="p010" if bits == 10 else "nv12", **kw)
         step, staging = on.step, _Staging(True)
     else:
         import torch
@@ -423,12 +443,14 @@ def _parser():
         def error(self, message):     # one line and status 1, not argparse's usage block and status 2
             raise _UsageError(message)
 
-    ap = Parser(prog=PROG, description="Stabilise uncompressed video from files or pipes (Y4M or raw NV12).")
+    ap = Parser(prog=PROG, description="Stabilise uncompressed video from files or pipes (Y4M, raw NV12 or raw P010).")
     ap.add_argument("--input", action="append", metavar="PATH|-", help="repeatable; default: stdin")
     ap.add_argument("--output", action="append", metavar="PATH|-", help="repeatable, one per input; default: stdout")
-    ap.add_argument("--format", default="y4m", choices=["y4m", "nv12"], help="of the inputs (nv12: header-less, needs --size)")
-    ap.add_argument("--output-format", default=None, choices=["y4m", "nv12"], help="of the outputs (default: --format)")
-    ap.add_argument("--size", default=None, metavar="WxH", help="frame size of raw NV12 inputs")
+    ap.add_argument("--format", default="y4m", choices=["y4m", "nv12", "p010"],
+                    help="of the inputs (nv12, p010: header-less, need --size; y4m: 8-bit, or 10-bit C420p10)")
+    ap.add_argument("--output-format", default=None, choices=["y4m", "nv12", "p010"],
+                    help="of the outputs (default: --format); of the inputs' bit depth")
+    ap.add_argument("--size", default=None, metavar="WxH", help="frame size of raw NV12 / P010 inputs")
     ap.add_argument("--fps", default="25", metavar="N[/D]", help="frame rate written to a Y4M output of a raw NV12 input")
     w = ap.add_mutually_exclusive_group(required=True)
     w.add_argument("--ckpt", metavar="DIR", help="reference checkpoint directory (with its `checkpoints` index)")
@@ -484,8 +506,8 @@ def _arguments(argv):
         raise _UsageError("stdin and stdout can serve one stream each")
     args.output_format = args.output_format or args.format
     args.size = _size(args.size, "--size") if args.size is not None else None
-    if args.format == "nv12" and args.size is None:
-        raise _UsageError("--format nv12 has no header: --size WxH is required")
+    if args.format in ("nv12", "p010") and args.size is None:
+        raise _UsageError("--format %s has no header: --size WxH is required" % args.format)
     args.model_size = _size(args.model_size, "--model-size")
     try:
         args.fps = y4m._as_ratio(args.fps, "--fps")
@@ -515,7 +537,8 @@ def _run(args, note):
         for path in args.input:
             f = sys.stdin.buffer if path == "-" else open(path, "rb")
             files.append(f)
-            sources.append(y4m.Y4MReader(f) if args.format == "y4m" else y4m.RawNV12Reader(f, *args.size))
+            sources.append(y4m.Y4MReader(f, depths=(8, 10)) if args.format == "y4m" else
+                           y4m.RawP010Reader(f, *args.size) if args.format == "p010" else y4m.RawNV12Reader(f, *args.size))
         for path, src in zip(args.input, sources):
             if any(t.upper() == "XCOLORRANGE=FULL" for t in src.tags):
                 note("%s: full-range video goes through unchanged; the CNN sees it through a limited-range matrix" % path)
@@ -547,9 +570,12 @@ def _run(args, note):
             files.append(f)
             if args.output_format == "nv12":
                 sinks.append(y4m.RawNV12Writer(f, src.width, src.height))
-            else:
+            elif args.output_format == "p010":
+                sinks.append(y4m.RawP010Writer(f, src.width, src.height))
+            else:   # a Y4M header repeats the source's C tag (C420p10 for a raw P010 source) and its X tags
                 sinks.append(y4m.Y4MWriter(f, src.width, src.height, src.fps or args.fps, aspect=src.aspect,
-                                           colorspace=src.colorspace, tags=src.tags, interlace=src.interlace))
+                                           colorspace="420p10" if src.layout == "p010" else src.colorspace, tags=src.tags,
+                                           interlace=src.interlace))
         stats = stabilize_pipes(model, sources, sinks, batch=args.batch, depth=args.depth, **kw)
         if args.stats:
             for path, st in zip(args.input, stats):

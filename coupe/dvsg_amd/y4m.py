@@ -22,12 +22,21 @@ at both ends); its effect on F_t has not been measured.
 Readers and writers share one small interface, which `pipe.stabilize_pipes` relies on: `width`, `height`, `layout` ("i420"
 or "nv12"), `frame_shape` ([3 H / 2, W]), `frame_bytes`; a reader has `readinto(buf) -> bool` (False at a clean end of the
 stream) and iterates over fresh arrays; a writer has `write(frame)` and `flush()`.
+
+Ten bits.  `Y4MReader(f, depths=(8, 10))` also takes `C420p10` (`ffmpeg -pix_fmt yuv420p10le -strict -1 -f yuv4mpegpipe`): the
+same three planes with 2 bytes per sample, little-endian, the value in the LOW 10 bits; `layout` is then "i420p10" and a frame
+is the stream's bytes, uint8 [3 H / 2, 2 W] (3 W H bytes).  `Y4MWriter(colorspace="420p10")` writes it.  `RawP010Reader` and
+`RawP010Writer` are header-less P010 (`-f rawvideo -pix_fmt p010le`, `layout` "p010"): Y and interleaved U V as 16-bit
+little-endian words with the value in the HIGH 10 bits -- what `OnlineStabilizer(frame_format="p010")` takes.
+`i420p10_to_p010` and `p010_to_i420p10` repack between the two on the device.  The default `depths=(8,)` refuses `C420p10`.
 """
 import numpy as np
 
 MAGIC = b"YUV4MPEG2"
 FRAME_MAGIC = b"FRAME"
 CHROMA_420 = ("420", "420jpeg", "420mpeg2", "420paldv")   # 8-bit 4:2:0; they differ in chroma siting only
+CHROMA_420_P10 = ("420p10",)                               # 10-bit 4:2:0, 2 bytes per sample
+LAYOUT_BITS = {"i420": 8, "nv12": 8, "i420p10": 10, "p010": 10}   # the layouts of this module and their bit depth
 MAX_HEADER = 4096                                          # bytes of one header line, the newline included
 
 
@@ -124,10 +133,10 @@ def _frame_view(buf, nbytes):
 class _Reader(object):
     layout = None
 
-    def _init_frames(self, fileobj, width, height):
+    def _init_frames(self, fileobj, width, height, sample_bytes=1):
         self.fileobj, self.width, self.height = fileobj, int(width), int(height)
-        self.frame_shape = (3 * self.height // 2, self.width)
-        self.frame_bytes = self.frame_shape[0] * self.width
+        self.frame_shape = (3 * self.height // 2, sample_bytes * self.width)
+        self.frame_bytes = self.frame_shape[0] * self.frame_shape[1]
         self.frames_read = 0
 
     def _payload(self, view):
@@ -136,7 +145,7 @@ class _Reader(object):
             raise Y4MError("frame %d is truncated: %d of %d bytes received" % (self.frames_read, got, len(view)))
 
     def read(self):
-        """The next frame as a fresh uint8 array [3 H / 2, W], or None at the end of the stream."""
+        """The next frame as a fresh uint8 array of `frame_shape`, or None at the end of the stream."""
         frame = np.empty(self.frame_shape, dtype=np.uint8)
         return frame if self.readinto(frame) else None
 
@@ -161,10 +170,19 @@ class Y4MReader(_Reader):
     Accepted: C420, C420jpeg, C420mpeg2, C420paldv or no C tag; Ip, I? or no I tag.  Everything else -- another chroma
     format or bit depth, interlaced material, an odd or tiny or missing W / H, a wrong magic -- raises Y4MError naming the
     tag, before any frame is read.  A stream that ends inside a frame raises Y4MError with the frame's index and the bytes
-    received; one that ends after the header yields no frames."""
+    received; one that ends after the header yields no frames.
+
+    depths: the bit depths the caller is ready for, a subset of (8, 10).  With 10 among them C420p10 is accepted as well:
+    `layout` is "i420p10", `colorspace` "420p10", and a frame is uint8 [3 H / 2, 2 W], every sample 2 bytes little-endian
+    with its value in the low 10 bits.  The default (8,) refuses it like any other format."""
     layout = "i420"
 
-    def __init__(self, fileobj):
+    def __init__(self, fileobj, depths=(8,)):
+        depths = tuple(depths)
+        if not depths or any(d not in (8, 10) for d in depths):
+            raise ValueError("depths must be a non-empty subset of (8, 10), got %r" % (depths,))
+        accepted = (CHROMA_420 if 8 in depths else ()) + (CHROMA_420_P10 if 10 in depths else ())
+        sample_bytes = 1 if 8 in depths else 2   # without a C tag a stream is 8-bit 4:2:0
         line = _read_line(fileobj)
         if line is None:
             raise Y4MError("an empty stream: no YUV4MPEG2 header")
@@ -193,16 +211,22 @@ class Y4MReader(_Reader):
                     raise Y4MError("tag %s: interlaced material is not supported (progressive Ip or I? only)" % tag)
                 self.interlace = tag[1:]
             elif key == "C":
-                if tag[1:] not in CHROMA_420:
-                    raise Y4MError("tag %s: only 8-bit 4:2:0 is supported (%s)" % (tag, ", ".join("C" + c for c in CHROMA_420)))
+                if tag[1:] not in accepted:
+                    raise Y4MError("tag %s: only %s 4:2:0 is supported (%s)" % (tag, " and ".join("%d-bit" % d for d in sorted(depths)),
+                                                                                ", ".join("C" + c for c in accepted)))
                 self.colorspace = tag[1:]
+                sample_bytes = 2 if tag[1:] in CHROMA_420_P10 else 1
             elif key not in "WH":
                 tags.append(tag)
         if width is None or height is None:
             raise Y4MError("the Y4M header has no %s tag: %r" % ("W" if width is None else "H", line[:80]))
         check_size(width, height, "W", "H")
+        if self.colorspace is None and 8 not in depths:
+            raise Y4MError("the Y4M header has no C tag, which means 8-bit 4:2:0, and depths=%r does not take it" % (depths,))
         self.tags = tuple(tags)
-        self._init_frames(fileobj, width, height)
+        if sample_bytes == 2:
+            self.layout = "i420p10"
+        self._init_frames(fileobj, width, height, sample_bytes)
 
     def readinto(self, buf):
         view = _frame_view(buf, self.frame_bytes)
@@ -244,14 +268,25 @@ class RawNV12Reader(_Reader):
         return True
 
 
+class RawP010Reader(RawNV12Reader):
+    """Header-less P010 (`-f rawvideo -pix_fmt p010le`): frames of 3 W H bytes, uint8 [3 H / 2, 2 W] -- H rows of Y and H / 2
+    rows of interleaved U V, every sample a 16-bit little-endian word with its value in the high 10 bits.  RawNV12Reader's
+    interface."""
+    layout = "p010"
+
+    def __init__(self, fileobj, width, height):
+        check_size(int(width), int(height))
+        self._init_frames(fileobj, width, height, 2)
+
+
 class _Writer(object):
     layout = None
 
-    def _init_frames(self, fileobj, width, height):
+    def _init_frames(self, fileobj, width, height, sample_bytes=1):
         self.fileobj, self.width, self.height = fileobj, int(width), int(height)
         check_size(self.width, self.height)
-        self.frame_shape = (3 * self.height // 2, self.width)
-        self.frame_bytes = self.frame_shape[0] * self.width
+        self.frame_shape = (3 * self.height // 2, sample_bytes * self.width)
+        self.frame_bytes = self.frame_shape[0] * self.frame_shape[1]
         self.frames_written = 0
 
     def _write_all(self, data):
@@ -271,15 +306,19 @@ class _Writer(object):
 class Y4MWriter(_Writer):
     """Writes the stream header once, then `FRAME\\n` and the I420 bytes per `write(frame)`.  fps and aspect are a
     Fraction, (num, den), an int or "N/D"; aspect, interlace and colorspace of None leave their tag out; `tags` are appended
-    verbatim (a reader's `tags`, to carry XCOLORRANGE and the like through)."""
+    verbatim (a reader's `tags`, to carry XCOLORRANGE and the like through).  colorspace="420p10": 10-bit frames, uint8
+    [3 H / 2, 2 W] as Y4MReader hands them over; `layout` is then "i420p10"."""
     layout = "i420"
 
     def __init__(self, fileobj, width, height, fps, aspect=None, colorspace="420jpeg", tags=(), interlace="p"):
-        self._init_frames(fileobj, width, height)
+        if colorspace is not None and colorspace not in CHROMA_420 + CHROMA_420_P10:
+            raise Y4MError("colorspace %r: only 8-bit and 10-bit 4:2:0 is written (%s)"
+                           % (colorspace, ", ".join(CHROMA_420 + CHROMA_420_P10)))
+        if colorspace in CHROMA_420_P10:
+            self.layout = "i420p10"
+        self._init_frames(fileobj, width, height, 2 if colorspace in CHROMA_420_P10 else 1)
         self.fps = _as_ratio(fps, "fps")
         self.aspect = None if aspect is None else _as_ratio(aspect, "aspect")
-        if colorspace is not None and colorspace not in CHROMA_420:
-            raise Y4MError("colorspace %r: only 8-bit 4:2:0 is written (%s)" % (colorspace, ", ".join(CHROMA_420)))
         if interlace not in (None, "p", "?"):
             raise Y4MError("interlace %r: progressive only ('p', '?' or None)" % (interlace,))
         self.colorspace, self.interlace, self.tags = colorspace, interlace, tuple(tags)
@@ -314,6 +353,18 @@ class RawNV12Writer(_Writer):
         self.frames_written += 1
 
 
+class RawP010Writer(_Writer):
+    """Header-less P010: `write(frame)` writes the 3 W H bytes of a P010 frame, uint8 [3 H / 2, 2 W]."""
+    layout = "p010"
+
+    def __init__(self, fileobj, width, height):
+        self._init_frames(fileobj, width, height, 2)
+
+    def write(self, frame):
+        self._write_all(_frame_view(frame, self.frame_bytes))
+        self.frames_written += 1
+
+
 def _planes(t):
     """A frame [3 H / 2, W] or a batch [n, 3 H / 2, W] as views: (y [n, H W], chroma [n, H W / 2], H, W)."""
     if t.dim() == 2:
@@ -330,7 +381,7 @@ def _planes(t):
     return flat[:, :H * W], flat[:, H * W:], H, W
 
 
-def _repack(src, out, to_nv12):
+def _repack_out(src, out):
     import torch
     if out is None:
         out = torch.empty(src.shape, dtype=src.dtype, device=src.device)
@@ -339,6 +390,12 @@ def _repack(src, out, to_nv12):
                          % (tuple(out.shape), out.dtype, out.device, tuple(src.shape), src.dtype, src.device))
     if out.data_ptr() == src.data_ptr() and src.numel():
         raise ValueError("out must not be src: the repack is not done in place")
+    return out
+
+
+def _repack(src, out, to_nv12, given=None):
+    """The two strided copies; given: the caller's own `out` (already checked) in the place of the check here."""
+    out = _repack_out(src, out) if given is None else out
     sy, sc, H, W = _planes(src)
     oy, oc, _, _ = _planes(out)
     n, q = int(sy.shape[0]), H * W // 4
@@ -360,6 +417,40 @@ def i420_to_nv12(src, out=None):
 def nv12_to_i420(src, out=None):
     """The inverse of `i420_to_nv12`, with the same contract."""
     return _repack(src, out, False)
+
+
+def _words(t, what):
+    """A 10-bit frame or batch, uint8 [..., 3 H / 2, 2 W], as int16 words [..., 3 H / 2, W] over the same memory (int16: the
+    16-bit type every torch has; the bits are what matters)."""
+    import torch
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3) or int(t.shape[-1]) % 4:
+        raise ValueError("%s: a 10-bit 4:2:0 frame is uint8 [3 H / 2, 2 W] with even W (a batch [n, 3 H / 2, 2 W]), got %s %s"
+                         % (what, t.dtype, tuple(t.shape)))
+    if t.numel() and (t.stride(-1) != 1 or any(s % 2 for s in t.stride()[:-1]) or t.data_ptr() % 2):
+        raise ValueError("%s: the rows of a frame must be contiguous and 2-byte aligned (strides %s)" % (what, tuple(t.stride())))
+    return t.view(torch.int16)
+
+
+def i420p10_to_p010(src, out=None):
+    """C420p10 frames as Y4MReader(depths=(8, 10)) yields them (uint8 [3 H / 2, 2 W] or a batch: Y, the U plane, the V plane,
+    16-bit little-endian, value in the low 10 bits) -> P010 (Y, interleaved U V, value in the HIGH 10 bits):
+    word_out = (word_in << 6) mod 2^16, so the upper 6 bits of a C420p10 sample are dropped.  Two strided copies and one
+    in-place shift on the current stream, no synchronise, no allocation when `out` is given.  Returns out."""
+    out = _repack_out(src, out)
+    o16 = _words(out, "out")
+    _repack(_words(src, "src"), o16, True, given=out)
+    o16.bitwise_left_shift_(6)   # int16: the bits of a word with the top bit set survive (no arithmetic is done on them)
+    return out
+
+
+def p010_to_i420p10(src, out=None):
+    """The inverse for P010 words: word_out = word_in >> 6 as an UNSIGNED shift (int16's >> is arithmetic, so the sign
+    copies are masked off), then U and V split into planes.  The low 6 bits of a P010 word are dropped."""
+    out = _repack_out(src, out)
+    o16 = _words(out, "out")
+    _repack(_words(src, "src"), o16, False, given=out)
+    o16.bitwise_right_shift_(6).bitwise_and_(0x03FF)
+    return out
 
 
 def default_yuv_matrix(height):

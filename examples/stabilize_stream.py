@@ -10,6 +10,9 @@ an encoder that speak uncompressed Y4M or raw NV12 over pipes (coupe/dvsg_amd/pi
 --format nv12: the source hands over NV12 surfaces [3 H0 / 2, W0] as a hardware decoder does (built on the host here) and
 each step returns the stabilised surfaces at source size in the same layout, ready for an encoder.
 
+--format p010: the same for 10-bit surfaces (HEVC Main10 from a hardware decoder): uint16 [3 H0 / 2, W0], the sample in
+each word's high 10 bits; all ten bits come back warped, the network looks at the words' high bytes.
+
 --crop auto|Z: the frames come back without sampler A's black border.  Z in (0, 1] is a fixed zoom; "auto" keeps one zoom
 per stream on the device and only ever lowers it (OnlineStabilizer(crop="auto")); the zoom each stream has reached is
 printed at the end.
@@ -65,6 +68,16 @@ def synthetic_nv12_source(seed, n, h, w, cut_at=None):
         yield np.ascontiguousarray(np.concatenate([yk, c[k % 8]], axis=0).astype(np.uint8))
 
 
+def synthetic_p010_source(seed, n, h, w, cut_at=None):
+    """Yields n P010 frames [3h/2, w] uint16 (the sample in the high 10 bits, limited range 64 .. 940 / 960), one at a time."""
+    import inputs
+    y = inputs.smooth_frames(seed, 8, h, w, C=1)[..., 0]
+    c = (64 + inputs.smooth_frames(seed + 100, 8, h // 2, w // 2, C=2) * 896).reshape(8, h // 2, w)
+    for k in range(n):
+        yk = 64 + _scene(y[k % 8], k, cut_at) * 876
+        yield np.ascontiguousarray(np.concatenate([yk, c[k % 8]], axis=0).astype(np.uint16) << 6)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=2)
@@ -72,7 +85,7 @@ def main():
     ap.add_argument("--height", type=int, default=288)    # config.py:12-13
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--precision", default="f32", choices=["f32", "f32x3", "f32s", "f16"])
-    ap.add_argument("--format", default="rgb", choices=["rgb", "nv12"])
+    ap.add_argument("--format", default="rgb", choices=["rgb", "nv12", "p010"])
     ap.add_argument("--crop", default=None, help="'auto' or a zoom in (0, 1]")
     ap.add_argument("--scene-cut", type=float, default=None, metavar="THR", help="detect scene cuts: a threshold in (0, 1]")
     ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"],
@@ -97,13 +110,13 @@ def main():
     net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0, c_in=3 * S))
     net.get_evaluation_model(S)
     net.precision = args.precision
-    nv12 = args.format == "nv12"
+    nv12 = args.format in ("nv12", "p010")   # a decoder's surfaces: two planes, rendered at source size
     shape = dict(strength=args.strength, rigidity=args.rigidity, shape_model=args.shape_model)
     shaped = args.strength != 1.0 or args.rigidity != 0.0
     if nv12:
-        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format="nv12", yuv_matrix="bt709", crop=crop,
+        stab = OnlineStabilizer(net, max_streams=args.streams, frame_format=args.format, yuv_matrix="bt709", crop=crop,
                                 render_filter=args.render_filter, border=args.border, **shape, **scene, **window)
-        make = synthetic_nv12_source
+        make = synthetic_nv12_source if args.format == "nv12" else synthetic_p010_source
     else:
         stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=args.border != "keep",
                                 as_uint8=True, crop=crop,
@@ -122,7 +135,7 @@ def main():
         lat.append(time.perf_counter() - t0)
         if k == 0 and nv12:
             out = next(iter(outs.values()))
-            print("per stream and step: stabilised NV12 surface", out.shape, out.dtype)
+            print("per stream and step: stabilised %s surface" % args.format.upper(), out.shape, out.dtype)
         elif k == 0 and not stab.side_by_side:
             out = next(iter(outs.values()))
             print("per stream and step: stabilised", out.shape, out.dtype)

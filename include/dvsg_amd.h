@@ -281,6 +281,51 @@ int dvsg_locnet_view_create_shaped(const dvsg_locnet_t *net, int render_filter, 
                                    float strength, float rigidity, dvsg_locnet_t **view);
 int dvsg_locnet_render_shape(const dvsg_locnet_t *net, int *shape_model, float *strength, float *rigidity);
 
+/* P010 frames: the surface format.  Whether the planes that dvsg_tps_render_nv12 and dvsg_tps_render_zoom_nv12 read and
+ * write hold 8-bit samples (NV12) or 10-bit samples in 16-bit words (P010: what a hardware decoder hands over for HEVC
+ * Main10) is, like the filter, the border and the shape, a property of the handle: no entry point is added for it.  Both
+ * functions are host-side: no stream, no device work, everything decided before anything is allocated.
+ *   dvsg_locnet_view_create_surface  a view of `net`'s parent that carries `net`'s OWN filter, border and shape -- these
+ *          are INHERITED here, unlike in the three constructors above, whose views have what their arguments say and
+ *          nothing else (and so DVSG_SURFACE_NV12) -- and the given surface format.  The view rules are the ones above: a
+ *          view of a view is a view of the parent, calibrating through a view and destroying a parent with live views are
+ *          refused.  An unknown format or a NULL pointer is DVSG_ERR_INVALID_ARG ("surface_format=<n>").
+ *   dvsg_locnet_render_surface  the handle's format: 0 for NULL, for every handle of dvsg_locnet_create and for every view
+ *          of dvsg_locnet_view_create, _border and _shaped.
+ * ONLY dvsg_tps_render_nv12 and dvsg_tps_render_zoom_nv12 read the format.  Every other entry point -- dvsg_tps_render_u8,
+ * dvsg_tps_render_zoom_u8, dvsg_tps_coverage_net_f32, dvsg_tps_coefficients_f32 and all the rest -- behaves on a P010 view
+ * exactly as on the same view without the property, bit for bit.  dvsg_frames_nv12_to_rgb_u8 and dvsg_frames_ingest_nv12 take
+ * no handle and are 8-bit only: the network sees 10-bit footage through the NV12 surface made of each word's high byte.
+ *
+ * Given a DVSG_SURFACE_P010 view, the two renders take P010 surfaces through their existing arguments:
+ *   Layout.  A Y plane and an interleaved UV plane (U0 V0 U1 V1 ...) of 16-bit LITTLE-ENDIAN words, placed by y, uv, pitch
+ *          and frame_stride as for NV12.  W and H count samples; pitch and frame_stride count BYTES.  A sample is
+ *          s = word >> 6, in [0, 1023]; the low 6 bits are ignored on input and written as 0.
+ *   Checks, before any device work.  The NV12 rules with pitch >= 2 W in the place of pitch >= W; pitch, frame_stride (where
+ *          n > 1) and the four plane pointers are 2-byte aligned.  DVSG_ERR_INVALID_ARG; the message names the argument.
+ *   Per plane.  Each plane is an image of its own size under the same normalised TPS map, as for NV12; T is written as
+ *          dvsg_tps_render_u8 writes it.  Every float32 operation is rounded on its own, in both filters; NaN gives word 0.
+ *            luma    C = 1, (H, W):          in (float)s / 1023.0f,
+ *                                            out clamp(floor((double)v * 1023.0 + 0.5), 0, 1023) << 6;
+ *            chroma  C = 2, (H / 2, W / 2):  in (float)((int)s - 512) / 1023.0f,
+ *                                            out clamp(floor((double)v * 1023.0 + 512.5), 0, 1023) << 6.
+ *          The bilinear render is dvsg_tps_warp_f32 / dvsg_tps_warp_zoom_f32 on those float images, bit for bit.  An
+ *          invalid sample under DVSG_BORDER_BLACK is luma word 0 and chroma word 512 << 6, the neutral value.
+ *   Luma rounds to NEAREST in the bilinear render too, where NV12 luma truncates.  Truncation is no round trip at 10 bits:
+ *          floor((double)((float)s / 1023.0f) * 1023.0) comes back one low for 519 of the 1024 values (the float32 quotient
+ *          lies below s / 1023 for those), so an identity warp would darken half the codes.  Rounding to nearest and the
+ *          chroma rule are exact for all 1024 values, and (float)s / 1023.0f equals (float)((double)s / 1023.0) for all of
+ *          them (tests/test_p010_cpu.py holds the three counts).
+ *   Bicubic, the three border modes, zoom and shaping apply as their paragraphs above state, with the sample rule of step 4
+ *          and the output rule of step 6 replaced by the two lines above (the bilinear evaluation under REPLICATE / MIRROR
+ *          rounds like every P010 output).  "No load touches a byte outside the used bytes of the source row" means the
+ *          2 pw C bytes of a row.  Bytes beyond 2 W of an output row and bytes between frames are never written.
+ *   A handle without the property launches the kernels it launched before; the P010 kernels are instantiations of their own. */
+#define DVSG_SURFACE_NV12 0
+#define DVSG_SURFACE_P010 1
+int dvsg_locnet_view_create_surface(const dvsg_locnet_t *net, int surface_format, dvsg_locnet_t **view);
+int dvsg_locnet_render_surface(const dvsg_locnet_t *net);
+
 /* patches [B,H,W,c_in] in [0,1] -> F_t [B,25,2].  float32 storage, exact-f32 MFMA
  * (v_mfma_f32_32x32x2_f32) accumulation.  c_in != 21: conv1 is the same arithmetic in the root-conv kernel. */
 int dvsg_locnet_forward_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W,
@@ -632,6 +677,8 @@ int dvsg_scene_step_f32(const float *pool, int n_pool, int H, int W, const int32
  *          dvsg_tps_render_nv12; T is written as dvsg_tps_render_u8 writes it.  zoom[i] == 1.0f gives dvsg_tps_render_nv12's
  *          bytes; zoom NULL: dvsg_tps_render_nv12 itself.
  * Every argument is checked before the first launch.
+ * dvsg_frames_nv12_to_rgb_u8 and dvsg_frames_ingest_nv12 take no handle and are 8-bit only.  The two renders read and write
+ * P010 surfaces (10-bit samples in 16-bit words) when the handle they are given is a DVSG_SURFACE_P010 view: "P010 frames" above.
  * ------------------------------------------------------------------------------------- */
 #define DVSG_YUV_BT601_LIMITED 0
 #define DVSG_YUV_BT709_LIMITED 1
