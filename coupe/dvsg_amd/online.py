@@ -17,9 +17,14 @@ frame k - span - 1, which no window of step k reads (they read frames k - span .
 of those streams), whose warp stores each result straight into its stream's history slot: independent streams keep
 their own lag-1 recurrence and still share batched CNN launches.  The pool never grows with the length of a stream.
 """
+import ctypes
+from collections import namedtuple
+
 import numpy as np
 import torch
 
+from . import _lib   # binds the library on the first call, not here: importing this module needs neither it nor a device
+from ._tensor import device, ptr, stream
 from .clip import SKIP_LENGTH, _check_crop, _check_crop_grid, _check_window, check_skip_length, render_source_into
 
 
@@ -61,6 +66,100 @@ def stream_window_row(k, base, skip_length=SKIP_LENGTH):
         row = (base + np.maximum(k + skip - span, 0) % hist).astype(np.int32)
         row[-1] = base + hist                                           # the unstable frame k (eval.py:103)
     return row, base + k % hist
+
+
+# One frame of a step.  key: what rows of one ingest and render launch share (`_rgb_key`, `_surface_key`); host: the frame
+# came from NumPy; t: the frame as a tensor, surfaces in the uint8 form; ring, k: the stream's ring and step count; words: the
+# output goes back as 16-bit words.
+Row = namedtuple("Row", "key sid host t ring k words")
+
+# The slot rows of a step on the device: table int32 [B,S], out_slots and in_slots int32 [B]; rings int32 [B] with
+# scene_cut (table and out_slots are then written by `dvsg_scene_step_f32`), else None.
+SlotTables = namedtuple("SlotTables", "table out_slots in_slots rings")
+
+
+def _words_to_bytes(x, what):
+    """P010 given as 16-bit words -- host uint16, or torch.uint16 where this torch has it -- as the uint8 form, the words'
+    bytes as they lie in memory: (x, whether it was words).  Anything else comes back as it is."""
+    if isinstance(x, torch.Tensor):
+        u16 = getattr(torch, "uint16", None)
+        return (x.contiguous().view(torch.uint8), True) if u16 is not None and x.dtype == u16 else (x, False)
+    if np.asarray(x).dtype != np.uint16:
+        return x, False
+    if not np.little_endian:
+        raise ValueError("%s: P010 words are little-endian; pass the uint8 form on this host" % (what,))
+    return np.ascontiguousarray(x).view(np.uint8), True
+
+
+def _bytes_to_words(x):
+    """A result in the uint8 form back as 16-bit words, NumPy or device tensor."""
+    return x.view(np.uint16) if isinstance(x, np.ndarray) else x.view(torch.uint16)
+
+
+def _rgb_key(sid, t, h, w, source_res, crop):
+    """Check an RGB frame; its sort key: resized uint8 (0, H0, W0), same-size uint8 (1,), float32 (2,), float64 (3,)."""
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError("stream %r: a frame must be [h,w,3], got %s" % (sid, tuple(t.shape)))
+    if t.dtype == torch.uint8:
+        if crop and source_res:
+            _check_crop_grid(int(t.shape[0]), int(t.shape[1]))
+        return (0, int(t.shape[0]), int(t.shape[1])) if tuple(t.shape[:2]) != (h, w) else (1,)
+    if not t.dtype.is_floating_point:
+        raise TypeError("stream %r: frames must be uint8 or floating point, got %s" % (sid, t.dtype))
+    if source_res:
+        raise ValueError("stream %r: source_res renders the uint8 source frame; a float frame has no source "
+                         "beyond the model's size" % (sid,))
+    if tuple(t.shape[:2]) != (h, w):
+        raise ValueError("stream %r: float frames must already be [%d,%d,3] (StabNet(h, w) fixes the STN "
+                         "out_size), got %s" % (sid, h, w, tuple(t.shape)))
+    return (3,) if t.dtype == torch.float64 else (2,)
+
+
+def _surface_key(sid, t, name):
+    """Check an NV12 or P010 surface in the uint8 form; its sort key (H0, W0)."""
+    bps = 2 if name == "p010" else 1   # the bytes of a sample
+    if t.dtype.is_floating_point:
+        raise ValueError("stream %r: frame_format=%r takes uint8 surfaces, not float frames (%s)" % (sid, name, t.dtype))
+    if t.dtype != torch.uint8:
+        raise TypeError("stream %r: %s frames must be uint8%s, got %s"
+                        % (sid, name.upper(), " or uint16" if bps == 2 else "", t.dtype))
+    if t.dim() != 2:
+        raise ValueError("stream %r: %s frame must be [3*H0/2, %sW0], got %s"
+                         % (sid, "an NV12" if bps == 1 else "a P010", "2*" if bps == 2 else "", tuple(t.shape)))
+    R, W0 = int(t.shape[0]), int(t.shape[1]) // bps
+    H0 = 2 * R // 3
+    if R % 3 or H0 % 2 or W0 % 2 or H0 < 4 or W0 < 4 or int(t.shape[1]) % bps:
+        raise ValueError("stream %r: %s frame [3*H0/2, %sW0] needs even H0, W0 >= 4 (odd sizes have no chroma "
+                         "layout), got %s" % (sid, "an NV12" if bps == 1 else "a P010 uint8", "2*" if bps == 2 else "",
+                                              tuple(t.shape)))
+    return (H0, W0)
+
+
+def plan_step(frames, stream_of, h, w, frame_format="rgb", source_res=False, crop=False):
+    """What a step of `frames` ({sid: frame}) will do, decided without a device: (rows, runs).  rows: one `Row` per frame in
+    BATCH ORDER -- resized uint8 by source size, same-size uint8, float32, float64; surfaces by source size; equal keys in
+    feed order -- and runs: the maximal ranges (i, j) of rows of one key, each one ingest and one render launch.
+    stream_of(sid) -> (ring, count) of an open stream; h, w: the model's size; crop: whether the step crops.  Every frame is
+    checked here, before the first launch: a bad frame raises and leaves every stream as it was."""
+    rows = []
+    for sid, fr in frames.items():
+        ring, k = stream_of(sid)
+        host, words = not isinstance(fr, torch.Tensor), False
+        if frame_format == "p010":
+            fr, words = _words_to_bytes(fr, "stream %r" % (sid,))
+        t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
+        key = _surface_key(sid, t, frame_format) if frame_format in SURFACE_FORMATS else \
+            _rgb_key(sid, t, h, w, source_res, crop)
+        rows.append(Row(key, sid, host, t, ring, k, words))
+    rows.sort(key=lambda r: r.key)   # stable
+    runs, i = [], 0
+    while i < len(rows):
+        j = i + 1
+        while j < len(rows) and rows[j].key == rows[i].key:
+            j += 1
+        runs.append((i, j))
+        i = j
+    return rows, runs
 
 
 class OnlineStabilizer(object):
@@ -173,8 +272,6 @@ class OnlineStabilizer(object):
                  as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None,
                  crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1, render_filter="bilinear",
                  border="black", strength=1.0, rigidity=0.0, shape_model="affine"):
-        from . import _lib
-        from ._tensor import device
         from .networks import check_border, check_render_filter, check_shape
         surface = frame_format in SURFACE_FORMATS
         check_render_filter(render_filter, bool(source_res) or surface)
@@ -251,7 +348,6 @@ class OnlineStabilizer(object):
         self.scene_cut, self.scene_min_len = scene_cut, int(scene_min_len)
         self._scene = None        # int32 [max_streams, 68]: the scene state of the stream that owns ring r (dvsg_scene_step_f32)
         if scene_cut is not None:
-            import ctypes
             if 2 * self.h * self.w > 2 ** 31 - 1:
                 raise ValueError("scene_cut: a frame of %d x %d is too large (2 h w must stay below 2^31)" % (self.h, self.w))
             self._scene_thr = scene_threshold_count(scene_cut, self.h, self.w)
@@ -313,12 +409,22 @@ class OnlineStabilizer(object):
             raise ValueError("stream %d is closed" % sid)
         raise ValueError("stream %r was never opened" % (sid,))
 
-    def _net(self):
-        """The handle every call that turns F_t into T is given: the view the render uses, so that scan, crop and render see
-        one warp; the network itself when nothing is shaped (the scan does not read a filter or a border)."""
+    @property
+    def _render_options(self):
+        """The five options that select the view of a source-size render, by the names `LocNet.view` gives them."""
+        return dict(render_filter=self.render_filter, border=self.border, strength=self.strength, rigidity=self.rigidity,
+                    shape_model=self.shape_model)
+
+    def _view(self, scan=False):
+        """The handle a surface render is given, `LocNet.view(..., surface=frame_format)`, asked for at call time: the cache
+        is LocNet's.  scan=True: the handle every call that only turns F_t into T is given (the coverage scan,
+        `dvsg_tps_coefficients_f32`): the view the render uses without the surface, so that scan, crop and render see one
+        warp; the network itself when nothing is shaped (the scan does not read a filter or a border)."""
+        if not scan:
+            return self.model.locnet.view(surface=self.frame_format, **self._render_options)
         if self.strength == 1.0 and self.rigidity == 0.0:
             return self.model.locnet.handle
-        return self.model.locnet.view(self.render_filter, self.border, self.strength, self.rigidity, self.shape_model)
+        return self.model.locnet.view(**self._render_options)
 
     def push(self, sid, frame):
         """`step` for a single stream: its output for `frame`."""
@@ -344,18 +450,15 @@ class OnlineStabilizer(object):
         k, cuts, S = (int(v) for v in self._scene[ring, :3].tolist())
         return dict(frames_since_cut=k, cuts=cuts, score=S / float(2 * self.h * self.w))
 
-    def _step_zoom(self, entries, i, j, grids):
+    def _step_zoom(self, rows, i, j, grids):
         """The zoom of batch rows [i, j) -> float32 [j - i] on the device.  crop=z: the constant.  "auto": one coverage
         scan of the rows' F_t per grid of `grids` (one (H, W), or the luma and the chroma plane's), each with the source
         and the output of that size, then the ratchet on the rows' streams; T rows [i, j) are written."""
-        import ctypes
-        from . import _lib
-        from ._tensor import device, ptr, stream
         n = j - i
         if not self._crop_auto:
             return self._crop_zoom[:n]
         dev = device()
-        rings = np.array([e[4] for e in entries[i:j]], dtype=np.int32)
+        rings = np.array([r.ring for r in rows[i:j]], dtype=np.int32)
         if np.unique(rings).size != n:
             raise ValueError("two frames of one step share a crop state slot")
         keys = torch.empty((len(grids), 2, n), dtype=torch.int32, device=dev)   # per grid: n_border | key_min
@@ -363,7 +466,7 @@ class OnlineStabilizer(object):
             need = ctypes.c_size_t()
             _lib.call("dvsg_tps_coverage_workspace_bytes", n, gh, gw, ctypes.byref(need))
             ws = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=dev)
-            _lib.call("dvsg_tps_coverage_net_f32", self._net(), ptr(self._F[i:j]), None, n, gh, gw, gh, gw,
+            _lib.call("dvsg_tps_coverage_net_f32", self._view(scan=True), ptr(self._F[i:j]), None, n, gh, gw, gh, gw,
                       ptr(self._T[i:j]), ptr(keys[g, 0]), ptr(keys[g, 1]), ptr(ws), ws.numel() * 8, stream())
         slots = torch.from_numpy(rings).pin_memory().to(dev, non_blocking=True)
         zoom = torch.empty((n,), dtype=torch.float32, device=dev)
@@ -374,41 +477,37 @@ class OnlineStabilizer(object):
                   D[1] if len(grids) > 1 else 0, ptr(slots), n, ptr(self._crop_zoom), self.max_streams, margin, self.crop_min,
                   self.crop_recover, ptr(zoom), ptr(free), stream())
         for b in range(i, j):
-            self._crop_last[entries[b][1]] = (free, b - i)
+            self._crop_last[rows[b].sid] = (free, b - i)
         return zoom
 
-    def _slot_tables(self, entries):
-        """The step's slot rows for `entries` (ring at [4], step count at [5]) in batch order: the host array
-        [table B*S | out slots B | input slots B], its three parts on the device, and None.  With scene_cut the step count is
-        the device's: the upload is [rings B | input slots B], table and out slots are device buffers that `_scene_step`
-        fills after ingest (their part of the host array is -1), and the last value is the rings on the device."""
-        from ._tensor import device
-        B, S = len(entries), len(self.skip_length)
+    def _input_slot(self, ring):
+        """The pool frame that holds the unstable frame of the step of the stream on `ring`."""
+        return ring * self.frames_per_stream + self.span + 1
+
+    def _slot_tables(self, rows):
+        """The step's `SlotTables` for `rows` in batch order.  Without scene_cut one upload [table B*S | out slots B | input
+        slots B] from the host's step counts.  With it the step count is the device's: the upload is [rings B | input slots B],
+        and table and out slots are device buffers that `_scene_step` fills after ingest."""
+        B, S = len(rows), len(self.skip_length)
         if self._scene is not None:
-            rings = np.array([e[4] for e in entries], dtype=np.int32)
+            rings = np.array([r.ring for r in rows], dtype=np.int32)
             if np.unique(rings).size != B:
                 raise ValueError("two frames of one step share a ring")
-            rows = np.full(B * S + 2 * B, -1, dtype=np.int32)
-            rows[B * S + B:] = rings * self.frames_per_stream + self.span + 1
-            up = torch.from_numpy(np.concatenate([rings, rows[B * S + B:]])).pin_memory().to(device(), non_blocking=True)
-            return rows, torch.empty((B, S), dtype=torch.int32, device=device()), \
-                torch.empty((B,), dtype=torch.int32, device=device()), up[B:], up[:B]
-        rows = np.empty(B * S + 2 * B, dtype=np.int32)     # [table B*S | out slots B | input slots B]
-        for i, (_, _, _, _, ring, k) in enumerate(entries):
-            base = ring * self.frames_per_stream
-            rows[i * S:(i + 1) * S], rows[B * S + i] = stream_window_row(k, base, self.skip_length)
-            rows[B * S + B + i] = base + self.span + 1
+            up = torch.from_numpy(np.concatenate([rings, self._input_slot(rings)])).pin_memory().to(device(), non_blocking=True)
+            return SlotTables(torch.empty((B, S), dtype=torch.int32, device=device()),
+                              torch.empty((B,), dtype=torch.int32, device=device()), up[B:], up[:B])
+        host = np.empty(B * S + 2 * B, dtype=np.int32)     # [table B*S | out slots B | input slots B]
+        for i, r in enumerate(rows):
+            host[i * S:(i + 1) * S], host[B * S + i] = stream_window_row(r.k, r.ring * self.frames_per_stream, self.skip_length)
+            host[B * S + B + i] = self._input_slot(r.ring)
         # a fresh pinned buffer per step: the caching host allocator does not hand it out again before this copy is done
-        idx = torch.from_numpy(rows).pin_memory().to(device(), non_blocking=True)
-        return rows, idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:], None
+        idx = torch.from_numpy(host).pin_memory().to(device(), non_blocking=True)
+        return SlotTables(idx[:B * S].view(B, S), idx[B * S:B * S + B], idx[B * S + B:], None)
 
     def _scene_step(self, rings, table, out_slots):
         """scene_cut: the one `dvsg_scene_step_f32` call of a step, between ingest and the stabilise call.  It reads the step's
         input slots, decides every stream's cut and writes `table` and `out_slots`; only crop="auto" hands it the zoom
         state to restart."""
-        import ctypes
-        from . import _lib
-        from ._tensor import device, ptr, stream
         B, S = int(table.shape[0]), len(self.skip_length)
         need = ctypes.c_size_t()
         _lib.call("dvsg_scene_workspace_bytes", B, ctypes.byref(need))
@@ -420,7 +519,7 @@ class OnlineStabilizer(object):
                   ptr(ws), ws.numel() * 4, stream())
         self._cut = cut
 
-    def _keep_surfaces(self, entries, i, j, first):
+    def _keep_surfaces(self, rows, i, j, first):
         """border="keep": the output surfaces of batch rows [i, j) as one tensor to render into, and what to do after the
         render.  first [n, ...]: what a row's surface restarts from (its source frame in the output's form).  A surface is
         (re)started here on the host's word -- a new ring, reset(), another source size -- or, after a device-detected cut,
@@ -428,7 +527,7 @@ class OnlineStabilizer(object):
         fresh copies to hand out (and stores the rendered rows back into their surfaces)."""
         surfs = []
         for b in range(i, j):
-            ring, f = entries[b][4], first[b - i]
+            ring, f = rows[b].ring, first[b - i]
             s = self._keep.get(ring)
             if s is None or s.shape != f.shape or s.dtype != f.dtype or ring in self._keep_fresh:
                 s = self._keep[ring] = f.clone(memory_format=torch.contiguous_format)
@@ -448,120 +547,105 @@ class OnlineStabilizer(object):
         return out, done
 
     def step(self, frames):
-        """One step of every stream in `frames` ({sid: frame}); returns {sid: output}."""
-        from . import _lib
-        from ._tensor import device, ptr, stream
+        """One step of every stream in `frames` ({sid: frame}); returns {sid: output}.  What depends on the frame format is
+        the check (`_rgb_key`, `_surface_key` under `plan_step`), the ingest of a run and its render."""
         if not frames:
             return {}
+        rows, runs = plan_step(frames, self._stream, self.h, self.w, self.frame_format, self.source_res, self.crop is not None)
+        B = len(rows)
         if self.frame_format in SURFACE_FORMATS:
-            return self._step_nv12(frames)
-        dev = device()
-        h, w, flip = self.h, self.w, self.flip
-        # ---- check everything before the first launch: a bad frame leaves every stream as it was
-        entries = []
-        for sid, fr in frames.items():
-            ring, k = self._stream(sid)
-            host = not isinstance(fr, torch.Tensor)
-            t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
-            if t.dim() != 3 or t.shape[2] != 3:
-                raise ValueError("stream %r: a frame must be [h,w,3], got %s" % (sid, tuple(t.shape)))
-            if t.dtype == torch.uint8:
-                kind = (0, int(t.shape[0]), int(t.shape[1])) if tuple(t.shape[:2]) != (h, w) else (1,)
-                if self.crop is not None and self.source_res:
-                    _check_crop_grid(int(t.shape[0]), int(t.shape[1]))
-            elif t.dtype.is_floating_point:
-                if self.source_res:
-                    raise ValueError("stream %r: source_res renders the uint8 source frame; a float frame has no source "
-                                     "beyond the model's size" % (sid,))
-                if tuple(t.shape[:2]) != (h, w):
-                    raise ValueError("stream %r: float frames must already be [%d,%d,3] (StabNet(h, w) fixes the STN "
-                                     "out_size), got %s" % (sid, h, w, tuple(t.shape)))
-                kind = (3,) if t.dtype == torch.float64 else (2,)
-            else:
-                raise TypeError("stream %r: frames must be uint8 or floating point, got %s" % (sid, t.dtype))
-            entries.append((kind, sid, host, t, ring, k))
-        # batch order: resized uint8 by source size, same-size uint8, float, float64 -- each group is a contiguous
-        # range of the step's slot rows
-        entries.sort(key=lambda e: e[0])
-        B = len(entries)
-        rows, table, out_slots, in_slots, rings = self._slot_tables(entries)
-        S = len(self.skip_length)
-        n_pool = int(self.pool.shape[0])
-        side = torch.empty((B, h, 2 * w, 3), dtype=torch.uint8, device=dev) \
-            if self.side_by_side and not self.source_res else None
-        groups = []           # uint8 batch ranges (i, j, device frames [j-i,H0,W0,3]): one source size each
-        # ---- ingest: the unstable frames into their input slots (eval.py:79-80)
-        left_from_pool = []   # batch positions whose unstable half is rendered from the float32 input slot
-        i = 0
-        while i < B:
-            kind = entries[i][0]
-            j = i
-            while j < B and entries[j][0] == kind:
-                j += 1
-            if kind[0] <= 1:
-                ts = [e[3].to(dev) for e in entries[i:j]]
-                src = ts[0].contiguous() if j - i == 1 else torch.stack(ts)
-                u8 = side[i:j] if side is not None and kind[0] == 0 else None
-                _lib.call("dvsg_frames_ingest_u8", ptr(src), j - i, int(src.shape[-3]), int(src.shape[-2]), flip,
-                          ptr(self.pool), n_pool, ptr(in_slots[i:j]), h, w, ptr(u8), 2 * w, 0, stream())
-                groups.append((i, j, src.view(j - i, *src.shape[-3:])))
-                if kind[0] == 1:
-                    left_from_pool.extend(range(i, j))
-            else:
-                for b in range(i, j):
-                    t = entries[b][3].to(dev)
-                    self.pool[int(rows[B * S + B + b])].copy_(t)   # one rounding to float32 (the feed cast)
-                    if side is not None and kind[0] == 3:
-                        t = t.contiguous()
-                        _lib.call("dvsg_frames_f64_to_u8", ptr(t), 1, h, w, flip, ptr(side[b]), 2 * w, 0, stream())
-                    elif kind[0] == 2:
-                        left_from_pool.append(b)
-            i = j
-        if side is not None and left_from_pool:   # one contiguous range: same-size uint8 and float32 frames
-            a, b = left_from_pool[0], left_from_pool[-1] + 1
-            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(in_slots[a:b]), b - a, h, w, flip,
-                      ptr(side[a:b]), 2 * w, 0, stream())
-        # ---- the step: every stream's window from its ring, every result into its history slot (eval.py:101-120)
-        if rings is not None:
-            self._scene_step(rings, table, out_slots)
-        self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
-        for e in entries:
-            self._streams[e[1]][1] += 1
-        if self.source_res:
-            res = self._render_source(entries, groups)
-            return {sid: res[sid] for sid in frames}
-        if self.crop is not None:
-            return self._egress_cropped(frames, entries, in_slots, side)
-        # ---- egress (eval.py:112-113)
-        if side is not None:
-            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(out_slots), B, h, w, flip, ptr(side),
-                      2 * w, w, stream())
-        if self.as_uint8:
-            out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev)
-            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(out_slots), B, h, w, flip, ptr(out),
-                      w, 0, stream())
+            ingest, render = self._ingest_surface, self._render_surface
         else:
-            out = self.pool.index_select(0, out_slots)   # the ring slot is overwritten span + 1 steps later
-        if any(e[2] for e in entries):
-            out_h = out.cpu().numpy()
-            side_h = side.cpu().numpy() if side is not None else None
+            ingest = self._ingest_rgb
+            render = self._render_source if self.source_res else self._egress_plain if self.crop is None else self._egress_cropped
+        slots = self._slot_tables(rows)
+        side = torch.empty((B, self.h, 2 * self.w, 3), dtype=torch.uint8, device=device()) \
+            if self.side_by_side and not self.source_res else None
+        # ---- ingest: the unstable frames into their input slots (eval.py:79-80); what a run's render reads, per run
+        srcs = [ingest(rows, i, j, slots.in_slots, side) for i, j in runs]
+        if side is not None:
+            self._side_from_slots(rows, slots.in_slots, side)
+        for size in set(self._hi).difference(r.key for r in rows):   # P010: a source size no stream of this step has
+            del self._hi[size]
+        # ---- the step: every stream's window from its ring, every result into its history slot (eval.py:101-120)
+        if slots.rings is not None:
+            self._scene_step(slots.rings, slots.table, slots.out_slots)
+        self.model.locnet.stabilize_ring_inplace(self.pool, slots.table, slots.out_slots, self._F[:B],
+                                                 precision=self.model.precision)
+        for r in rows:
+            self._streams[r.sid][1] += 1
+        # ---- egress (eval.py:112-113): per run at source size, else the whole batch as one range; every range is handed
+        # out before the next is rendered
         res = {}
-        for b, e in enumerate(entries):
-            o, sd = (out_h[b], side_h[b] if side is not None else None) if e[2] else (out[b], side[b] if side is not None else None)
-            res[e[1]] = (o, sd) if self.side_by_side else o
+        for (i, j), src in zip(runs, srcs) if self.source_res else [((0, B), None)]:
+            out, sd = render(rows, i, j, src, slots, side)
+            self._hand_out(res, rows[i:j], out, sd)
         return {sid: res[sid] for sid in frames}
 
-    def _egress_cropped(self, frames, entries, in_slots, side):
-        """Egress of a model-size step with crop: the step's unstable frames (a gathered copy of the input slots) warped
-        once more by the step's own T on the zoomed grid (`dvsg_tps_warp_zoom_f32`); the history slots keep the uncropped
-        frames.  `side` arrives with its unstable half written."""
-        from . import _lib
-        from ._tensor import ptr, stream
-        B, h, w, flip = len(entries), self.h, self.w, self.flip
-        zoom = self._step_zoom(entries, 0, B, [(h, w)])
+    def _hand_out(self, res, rows, out, side=None):
+        """res[sid] for `rows`, whose outputs are out[0], out[1], ... (and side[...], with side_by_side): NumPy for a row that
+        came from the host -- one `.cpu()` per tensor, only if there is such a row -- else views of the device tensors; a
+        row that came as 16-bit words leaves as such."""
+        dev = (out,) if side is None else (out, side)
+        cpu = tuple(t.cpu().numpy() for t in dev) if any(r.host for r in rows) else None
+        for b, r in enumerate(rows):
+            ts = cpu if r.host else dev
+            o = _bytes_to_words(ts[0][b]) if r.words else ts[0][b]
+            res[r.sid] = o if side is None else (o, ts[1][b])
+
+    def _ingest_rgb(self, rows, i, j, in_slots, side):
+        """Ingest of an RGB run: uint8 frames by one `dvsg_frames_ingest_u8` launch, which also writes the unstable half of
+        `side` for resized frames; returns them on the device, [j-i,H0,W0,3].  Float frames are copied into their input slots
+        (None); a float64 frame's half of `side` is rendered from the float64."""
+        dev, h, w, kind = device(), self.h, self.w, rows[i].key[0]
+        if kind <= 1:
+            ts = [r.t.to(dev) for r in rows[i:j]]
+            src = ts[0].contiguous() if j - i == 1 else torch.stack(ts)
+            u8 = side[i:j] if side is not None and kind == 0 else None
+            _lib.call("dvsg_frames_ingest_u8", ptr(src), j - i, int(src.shape[-3]), int(src.shape[-2]), self.flip,
+                      ptr(self.pool), int(self.pool.shape[0]), ptr(in_slots[i:j]), h, w, ptr(u8), 2 * w, 0, stream())
+            return src.view(j - i, *src.shape[-3:])
+        for b in range(i, j):
+            t = rows[b].t.to(dev)
+            self.pool[self._input_slot(rows[b].ring)].copy_(t)   # one rounding to float32 (the feed cast)
+            if side is not None and kind == 3:
+                t = t.contiguous()
+                _lib.call("dvsg_frames_f64_to_u8", ptr(t), 1, h, w, self.flip, ptr(side[b]), 2 * w, 0, stream())
+        return None
+
+    def _side_from_slots(self, rows, in_slots, side):
+        """The unstable halves of `side` that ingest left: same-size uint8 and float32 rows, rendered from their float32
+        input slots -- one contiguous range of the batch order."""
+        left = [b for b, r in enumerate(rows) if r.key in ((1,), (2,))]
+        if left:
+            a, b = left[0], left[-1] + 1
+            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), int(self.pool.shape[0]), ptr(in_slots[a:b]), b - a,
+                      self.h, self.w, self.flip, ptr(side[a:b]), 2 * self.w, 0, stream())
+
+    def _egress_plain(self, rows, i, j, src, slots, side):
+        """Egress of a model-size step without crop, the whole batch: the history slots the step wrote.  `side` arrives with
+        its unstable half written."""
+        B, h, w, flip, n_pool = len(rows), self.h, self.w, self.flip, int(self.pool.shape[0])
+        if side is not None:
+            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(slots.out_slots), B, h, w, flip, ptr(side),
+                      2 * w, w, stream())
+        if self.as_uint8:
+            out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=self.pool.device)
+            _lib.call("dvsg_frames_f32_to_u8_slots", ptr(self.pool), n_pool, ptr(slots.out_slots), B, h, w, flip, ptr(out),
+                      w, 0, stream())
+        else:
+            out = self.pool.index_select(0, slots.out_slots)   # the ring slot is overwritten span + 1 steps later
+        return out, side
+
+    def _egress_cropped(self, rows, i, j, src, slots, side):
+        """Egress of a model-size step with crop, the whole batch: the step's unstable frames (a gathered copy of the input
+        slots) warped once more by the step's own T on the zoomed grid (`dvsg_tps_warp_zoom_f32`); the history slots keep
+        the uncropped frames.  `side` arrives with its unstable half written."""
+        B, h, w, flip = len(rows), self.h, self.w, self.flip
+        zoom = self._step_zoom(rows, 0, B, [(h, w)])
         if not self._crop_auto:   # no scan has written T
-            _lib.call("dvsg_tps_coefficients_f32", self._net(), ptr(self._F[:B]), B, ptr(self._T[:B]), stream())
-        u = self.pool.index_select(0, in_slots)
+            _lib.call("dvsg_tps_coefficients_f32", self._view(scan=True), ptr(self._F[:B]), B, ptr(self._T[:B]), stream())
+        u = self.pool.index_select(0, slots.in_slots)
         out = torch.empty_like(u)
         _lib.call("dvsg_tps_warp_zoom_f32", ptr(u), ptr(self._V[:B]), ptr(self._T[:B]), ptr(zoom), B, h, w, 3,
                   self.model.param_dim, h, w, ptr(out), None, None, stream())
@@ -570,144 +654,57 @@ class OnlineStabilizer(object):
         if self.as_uint8:
             f32, out = out, torch.empty((B, h, w, 3), dtype=torch.uint8, device=out.device)
             _lib.call("dvsg_frames_f32_to_u8", ptr(f32), B, h, w, flip, ptr(out), w, 0, stream())
-        if any(e[2] for e in entries):
-            out_h = out.cpu().numpy()
-            side_h = side.cpu().numpy() if side is not None else None
-        res = {}
-        for b, e in enumerate(entries):
-            o, sd = (out_h[b], side_h[b] if side is not None else None) if e[2] else (out[b], side[b] if side is not None else None)
-            res[e[1]] = (o, sd) if self.side_by_side else o
-        return {sid: res[sid] for sid in frames}
+        return out, side
 
-    def _render_source(self, entries, groups):
-        """Egress of a source_res step: per source size, one `dvsg_tps_render_u8` launch that warps the uint8 frames by
-        this step's F_t rows (contiguous: a group is a contiguous batch range) at their own size."""
-        from . import _lib
-        from ._tensor import ptr, stream
-        res = {}
-        for i, j, src in groups:
-            n, H0, W0 = j - i, int(src.shape[1]), int(src.shape[2])
-            done = None
-            if self.border == "keep":   # (no side_by_side): the streams' own surfaces, restarted from the source where due
-                first = src
-                if not self.as_uint8:   # the float32 frame the render's own samples are taken from (torch's / is not that)
-                    first = torch.empty((n, H0, W0, 3), dtype=torch.float32, device=src.device)
-                    _lib.call("dvsg_frames_u8_to_f32", ptr(src), n * H0 * W0, self.flip, ptr(first), stream())
-                out, done = self._keep_surfaces(entries, i, j, first)
-            else:
-                out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
-            side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
-            zoom = self._step_zoom(entries, i, j, [(H0, W0)]) if self.crop is not None else None
-            render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, self.render_filter,
-                               self.border, self.strength, self.rigidity, self.shape_model)
-            if done is not None:
-                out = done()
-            if any(entries[b][2] for b in range(i, j)):
-                out_h = out.cpu().numpy()
-                side_h = side.cpu().numpy() if side is not None else None
-            for b in range(i, j):
-                e = entries[b]
-                o, sd = (out_h[b - i], side_h[b - i] if side is not None else None) if e[2] else \
-                    (out[b - i], side[b - i] if side is not None else None)
-                res[e[1]] = (o, sd) if self.side_by_side else o
-        return res
+    def _render_source(self, rows, i, j, src, slots, side):
+        """Egress of a source_res run: one `dvsg_tps_render_u8` launch that warps the uint8 frames `src` by this step's F_t
+        rows [i, j) at their own size."""
+        n, H0, W0 = j - i, int(src.shape[1]), int(src.shape[2])
+        done = None
+        if self.border == "keep":   # (no side_by_side): the streams' own surfaces, restarted from the source where due
+            first = src
+            if not self.as_uint8:   # the float32 frame the render's own samples are taken from (torch's / is not that)
+                first = torch.empty((n, H0, W0, 3), dtype=torch.float32, device=src.device)
+                _lib.call("dvsg_frames_u8_to_f32", ptr(src), n * H0 * W0, self.flip, ptr(first), stream())
+            out, done = self._keep_surfaces(rows, i, j, first)
+        else:
+            out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
+        side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
+        zoom = self._step_zoom(rows, i, j, [(H0, W0)]) if self.crop is not None else None
+        render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, **self._render_options)
+        return (out if done is None else done()), side
 
-    def _step_nv12(self, frames):
-        """`step` for frame_format="nv12" and "p010": ingest per source size, the one stabilise call, render per source size.
-        bps: the bytes of a sample; a P010 frame is handled as its bytes, uint8 [3 H0 / 2, 2 W0]."""
-        from . import _lib
-        from ._tensor import device, ptr, stream
-        dev = device()
-        h, w = self.h, self.w
-        name, bps = self.frame_format, 2 if self.frame_format == "p010" else 1
-        u16 = getattr(torch, "uint16", None)
-        words = set()   # streams whose frame came as 16-bit words and leaves as such
-        # ---- check everything before the first launch: a bad frame leaves every stream as it was
-        entries = []
-        for sid, fr in frames.items():
-            ring, k = self._stream(sid)
-            host = not isinstance(fr, torch.Tensor)
-            if bps == 2 and host and np.asarray(fr).dtype == np.uint16:   # the words' bytes as they lie in memory
-                if not np.little_endian:
-                    raise ValueError("stream %r: P010 words are little-endian; pass the uint8 form on this host" % (sid,))
-                fr = np.ascontiguousarray(fr).view(np.uint8)
-                words.add(sid)
-            t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
-            if bps == 2 and u16 is not None and t.dtype == u16:
-                t = t.contiguous().view(torch.uint8)
-                words.add(sid)
-            if t.dtype.is_floating_point:
-                raise ValueError("stream %r: frame_format=%r takes uint8 surfaces, not float frames (%s)" % (sid, name, t.dtype))
-            if t.dtype != torch.uint8:
-                raise TypeError("stream %r: %s frames must be uint8%s, got %s"
-                                % (sid, name.upper(), " or uint16" if bps == 2 else "", t.dtype))
-            if t.dim() != 2:
-                raise ValueError("stream %r: %s frame must be [3*H0/2, %sW0], got %s"
-                                 % (sid, "an NV12" if bps == 1 else "a P010", "2*" if bps == 2 else "", tuple(t.shape)))
-            R, W0 = int(t.shape[0]), int(t.shape[1]) // bps
-            H0 = 2 * R // 3
-            if R % 3 or H0 % 2 or W0 % 2 or H0 < 4 or W0 < 4 or int(t.shape[1]) % bps:
-                raise ValueError("stream %r: %s frame [3*H0/2, %sW0] needs even H0, W0 >= 4 (odd sizes have no chroma "
-                                 "layout), got %s" % (sid, "an NV12" if bps == 1 else "a P010 uint8", "2*" if bps == 2 else "",
-                                                      tuple(t.shape)))
-            entries.append(((H0, W0), sid, host, t, ring, k))
-        entries.sort(key=lambda e: e[0])   # one contiguous batch range per source size
-        B = len(entries)
-        _, table, out_slots, in_slots, rings = self._slot_tables(entries)
-        n_pool = int(self.pool.shape[0])
-        groups = []   # (i, j, device frames [j-i, 3 H0 / 2, bps W0])
-        hi_used = set()
-        i = 0
-        while i < B:
-            (H0, W0), j = entries[i][0], i
-            while j < B and entries[j][0] == (H0, W0):
-                j += 1
-            src = torch.stack([e[3].to(dev) for e in entries[i:j]]).contiguous()
-            seen = src
-            if bps == 2:   # the network sees the words' high bytes: one strided copy into a buffer of this object's
-                buf = self._hi.get((H0, W0))
-                if buf is None:
-                    buf = self._hi[(H0, W0)] = torch.empty((self.max_streams, 3 * H0 // 2, W0), dtype=torch.uint8, device=dev)
-                hi_used.add((H0, W0))
-                seen = buf[:j - i]
-                seen.copy_(src[..., 1::2])
-            _lib.call("dvsg_frames_ingest_nv12", ptr(seen), ptr(seen) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0,
-                      self.yuv_matrix, ptr(self.pool), n_pool, ptr(in_slots[i:j]), h, w, stream())
-            groups.append((i, j, src))
-            i = j
-        for key in [k for k in self._hi if k not in hi_used]:   # a source size no stream of this step has
-            del self._hi[key]
-        if rings is not None:
-            self._scene_step(rings, table, out_slots)
-        self.model.locnet.stabilize_ring_inplace(self.pool, table, out_slots, self._F[:B], precision=self.model.precision)
-        for e in entries:
-            self._streams[e[1]][1] += 1
-        res = {}
-        net = self.model.locnet.view(self.render_filter, self.border, self.strength, self.rigidity, self.shape_model,
-                                     surface=name)
-        for i, j, src in groups:
-            H0, W0 = entries[i][0]
-            pitch = bps * W0   # rows are packed; the UV plane follows the Y plane
-            out, done = self._keep_surfaces(entries, i, j, src) if self.border == "keep" else (torch.empty_like(src), None)
-            if self.crop is None:
-                _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * pitch, pitch,
-                          3 * H0 // 2 * pitch, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * pitch, pitch,
-                          3 * H0 // 2 * pitch, stream())
-            else:   # chroma leaves the source first: both planes are scanned, each on its own grid
-                zoom = self._step_zoom(entries, i, j, [(H0, W0), (H0 // 2, W0 // 2)])
-                _lib.call("dvsg_tps_render_zoom_nv12", net, ptr(self._F[i:j]), ptr(src),
-                          ptr(src) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]),
-                          ptr(out), ptr(out) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, stream())
-            if done is not None:
-                out = done()
-            out_h = out.cpu().numpy() if any(entries[b][2] for b in range(i, j)) else None
-            for b in range(i, j):
-                sid = entries[b][1]
-                o = out_h[b - i] if entries[b][2] else out[b - i]
-                if sid in words:   # back in the form it came in
-                    o = o.view(np.uint16) if entries[b][2] else o.view(u16)
-                res[sid] = o
-        return {sid: res[sid] for sid in frames}
+    def _ingest_surface(self, rows, i, j, in_slots, side):
+        """Ingest of a run of NV12 or P010 surfaces of one size: one `dvsg_frames_ingest_nv12` launch; returns the frames on
+        the device, [j-i, 3 H0 / 2, bps W0] (bps: the bytes of a sample; a P010 frame is handled as its bytes)."""
+        dev, (H0, W0) = device(), rows[i].key
+        src = torch.stack([r.t.to(dev) for r in rows[i:j]]).contiguous()
+        seen = src
+        if self.frame_format == "p010":   # the network sees the words' high bytes: one strided copy into a buffer this object owns
+            buf = self._hi.get((H0, W0))
+            if buf is None:
+                buf = self._hi[(H0, W0)] = torch.empty((self.max_streams, 3 * H0 // 2, W0), dtype=torch.uint8, device=dev)
+            seen = buf[:j - i]
+            seen.copy_(src[..., 1::2])
+        _lib.call("dvsg_frames_ingest_nv12", ptr(seen), ptr(seen) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0,
+                  self.yuv_matrix, ptr(self.pool), int(self.pool.shape[0]), ptr(in_slots[i:j]), self.h, self.w, stream())
+        return src
+
+    def _render_surface(self, rows, i, j, src, slots, side):
+        """Egress of a run of surfaces: one `dvsg_tps_render_nv12` (or `_zoom_nv12`) launch that warps both planes of `src`."""
+        (H0, W0), net = rows[i].key, self._view()
+        pitch = int(src.shape[2])   # bps W0: rows are packed; the UV plane follows the Y plane
+        out, done = self._keep_surfaces(rows, i, j, src) if self.border == "keep" else (torch.empty_like(src), None)
+        if self.crop is None:
+            _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * pitch, pitch,
+                      3 * H0 // 2 * pitch, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * pitch, pitch,
+                      3 * H0 // 2 * pitch, stream())
+        else:   # chroma leaves the source first: both planes are scanned, each on its own grid
+            zoom = self._step_zoom(rows, i, j, [(H0, W0), (H0 // 2, W0 // 2)])
+            _lib.call("dvsg_tps_render_zoom_nv12", net, ptr(self._F[i:j]), ptr(src),
+                      ptr(src) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]),
+                      ptr(out), ptr(out) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, stream())
+        return (out if done is None else done()), None
 
 
 def stabilize_clips(model, clips, batch=None, **kw):
@@ -721,24 +718,18 @@ def stabilize_clips(model, clips, batch=None, **kw):
     [N,3*H0/2,W0] uint16, likewise.  crop=... is OnlineStabilizer's: frame k of a
     clip is rendered with the zoom the ratchet has reached at frame k, NOT with `stabilize_clip`'s one clip-wide zoom
     (the two agree from the frame on that sets the clip's minimum)."""
-    from ._tensor import device
     K = len(clips)
     if K == 0:
         return []
     batch = K if batch is None else max(1, min(int(batch), K))
     dev = device()
     host = [not isinstance(c, torch.Tensor) for c in clips]
-    dclips, words = [], set()
+    dclips, words = [], []
     for c, hst in zip(clips, host):
         fmt = kw.get("frame_format", "rgb")
+        words.append(False)
         if fmt == "p010":   # uint16 clips run in the uint8 form and come back as words
-            u16 = getattr(torch, "uint16", None)
-            if hst and np.asarray(c).dtype == np.uint16:
-                c = np.ascontiguousarray(c).view(np.uint8)
-                words.add(len(dclips))
-            elif not hst and u16 is not None and c.dtype == u16:
-                c = c.contiguous().view(torch.uint8)
-                words.add(len(dclips))
+            c, words[-1] = _words_to_bytes(c, "clip %d" % len(dclips))
         t = (torch.as_tensor(np.ascontiguousarray(c)) if hst else c).to(dev).contiguous()
         if fmt in SURFACE_FORMATS:
             if t.dim() != 3 or t.shape[0] < 1:
@@ -770,7 +761,7 @@ def stabilize_clips(model, clips, batch=None, **kw):
         else:
             o = torch.stack(outs[c])
             o = o.cpu().numpy() if host[c] else o
-            if c in words:
-                o = o.view(np.uint16) if host[c] else o.view(torch.uint16)
+            if words[c]:
+                o = _bytes_to_words(o)
         result.append(o)
     return result
