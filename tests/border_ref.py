@@ -31,21 +31,25 @@ def move(x, n, border, dtype=f32):
     return np.minimum(np.maximum(x, dtype(0)), m).astype(dtype)
 
 
-def bilinear_at(plane, xc, yc, chroma=False, dtype=f32):
-    """the bilinear filter at (xc, yc) inside the plane: taps x0 and min(x0 + 1, pw - 1), the upper weight from the unclipped
-    index, sampler A's blend"""
-    plane = np.asarray(plane)
-    ph, pw = plane.shape[:2]
+def bilinear_taps(s, xc, yc, dtype=f32):
+    """the bilinear filter at (xc, yc) inside the image s [ph, pw, C] of samples of `dtype`: taps x0 and min(x0 + 1, pw - 1),
+    the upper weight from the unclipped index, sampler A's blend"""
+    ph, pw = s.shape[:2]
+    assert s.dtype == dtype
     x0f, y0f = np.floor(xc), np.floor(yc)
     x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
     x1, y1 = np.minimum(x0 + 1, pw - 1), np.minimum(y0 + 1, ph - 1)
     one = dtype(1)
     wx0, wx1, wy0, wy1 = (x0f + one) - xc, xc - x0f, (y0f + one) - yc, yc - y0f
     wa, wb, wc, wd = ((wx0 * wy0)[..., None], (wx0 * wy1)[..., None], (wx1 * wy0)[..., None], (wx1 * wy1)[..., None])
-    s = R.samples(plane, chroma, dtype)
     v = ((wa * s[y0, x0] + wb * s[y1, x0]) + wc * s[y0, x1]) + wd * s[y1, x1]
     assert v.dtype == dtype
     return v
+
+
+def bilinear_at(plane, xc, yc, chroma=False, dtype=f32):
+    """bilinear_taps on the samples of a plane of bytes"""
+    return bilinear_taps(R.samples(np.asarray(plane), chroma, dtype), xc, yc, dtype)
 
 
 def bicubic_at(plane, xc, yc, chroma=False, dtype=f32):

@@ -12,7 +12,9 @@ What differs between the two is the bookkeeping, which is the subject.
 
 Nothing here imports `coupe.dvsg_amd.online`: no `stream_window_row`, no slot, count or state rule of the product.  Ingest
 and egress go through the plain C entry points the fused ones are pinned against (tests/test_gpu_online.py,
-tests/test_gpu_nv12.py), one row (n = 1) at a time.
+tests/test_gpu_nv12.py), one row (n = 1) at a time.  frame_format="p010": the network sees the NV12 surface of word >> 8,
+computed on the words, through the NV12 ingest; the render is one n = 1 call through `LocNet.view(..., surface="p010")` at
+pitch 2 W0; a frame that came as 16-bit words leaves as such.
 
 `make_schedule(name)` / `coverage(schedule)`: deterministic schedules of open / close / reset / feed events with a content
 of its own for every stream, and the facts tests/test_online_model_cpu.py asserts about them so that a later edit cannot
@@ -117,14 +119,15 @@ class UnboundedStreams(object):
                  source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None, crop_min=0.5,
                  crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1, render_filter="bilinear", border="black",
                  strength=1.0, rigidity=0.0, shape_model="affine"):
-        assert channel_order in ("rgb", "bgr") and frame_format in ("rgb", "nv12")
+        assert channel_order in ("rgb", "bgr") and frame_format in ("rgb", "nv12", "p010")
         assert render_filter in FILTERS and border in BORDERS
         self.model, self.net = model, model.locnet
         self.h, self.w = model.h, model.w
         self.max_streams = int(max_streams)
         self.skip = tuple(int(s) for s in skip_length)
         self.flip = 1 if channel_order == "bgr" else 0
-        self.nv12 = frame_format == "nv12"
+        self.p010 = frame_format == "p010"              # 10-bit surfaces: the network sees the NV12 surface of word >> 8
+        self.nv12 = frame_format in ("nv12", "p010")    # two planes, a source-size render
         self.matrix = YUV_MATRICES[yuv_matrix]
         self.side_by_side, self.as_uint8 = bool(side_by_side), bool(as_uint8)
         self.source_res = bool(source_res) or self.nv12
@@ -206,6 +209,9 @@ class UnboundedStreams(object):
             r = _Row()
             r.sid, r.st = sid, self._streams[sid]
             r.host = not isinstance(fr, torch.Tensor)
+            r.words = False
+            if self.p010:
+                fr = self._p010(r, fr)
             r.t = (torch.as_tensor(np.ascontiguousarray(fr)) if r.host else fr).cuda().contiguous()
             if self.nv12:
                 assert r.t.dtype == torch.uint8 and r.t.dim() == 2
@@ -243,8 +249,23 @@ class UnboundedStreams(object):
             o = self._egress(r, out[b:b + 1], F[b:b + 1].contiguous())
             if r.host:
                 o = tuple(p.cpu().numpy() for p in o) if isinstance(o, tuple) else o.cpu().numpy()
+            if r.words:                                           # a frame that came as 16-bit words leaves as such
+                o = o.view(np.uint16) if r.host else o.view(torch.uint16)
             res[r.sid] = o
         return {sid: res[sid] for sid in frames}
+
+    def _p010(self, r, fr):
+        """A P010 frame -- uint8 [3 H0 / 2, 2 W0], the words' bytes, or uint16 [3 H0 / 2, W0], host or device: r.p010 keeps its
+        bytes on the device for the render, r.words whether it came as words; returns the NV12 surface the network sees,
+        uint8 [3 H0 / 2, W0] = word >> 8, computed on the words."""
+        import torch
+        a = fr.cpu().numpy() if isinstance(fr, torch.Tensor) else np.ascontiguousarray(fr)
+        r.words = a.dtype == np.uint16
+        assert a.dtype in (np.uint8, np.uint16) and a.ndim == 2 and np.little_endian
+        words = a if r.words else a.view("<u2")
+        r.p010 = torch.from_numpy(words.view(np.uint8).copy()).cuda()
+        hi = (words >> np.uint16(8)).astype(np.uint8)
+        return hi if r.host else torch.from_numpy(hi).cuda()
 
     def _ingest(self, r):
         """r.u: the unstable frame at the model's size, float32 [h,w,3] RGB; r.src: the uint8 source [1,H0,W0,3] (NV12:
@@ -259,9 +280,10 @@ class UnboundedStreams(object):
         left = torch.empty((1, h, 2 * w, 3), dtype=torch.uint8, device=dev) if want_left else None
         if self.nv12:
             H0, W0 = r.key
-            r.src = t.unsqueeze(0)
+            nv = t.unsqueeze(0)
+            r.src = r.p010.unsqueeze(0) if self.p010 else nv    # what the render warps
             rgb = torch.empty((1, H0, W0, 3), dtype=torch.uint8, device=dev)
-            _lib.call("dvsg_frames_nv12_to_rgb_u8", r.src.data_ptr(), r.src.data_ptr() + H0 * W0, W0, 3 * H0 // 2 * W0, 1, H0, W0,
+            _lib.call("dvsg_frames_nv12_to_rgb_u8", nv.data_ptr(), nv.data_ptr() + H0 * W0, W0, 3 * H0 // 2 * W0, 1, H0, W0,
                       self.matrix, 0, rgb.data_ptr(), _stream())
             t, flip = rgb[0], 0                                   # convert, then the RGB path
         if t.dtype == torch.uint8:
@@ -335,8 +357,12 @@ class UnboundedStreams(object):
             src = r.src
             zoom = self._zoom(r, F, T, [(H0, W0), (H0 // 2, W0 // 2)])
             out = self._surface(r, src)
-            args = (r.src.data_ptr(), r.src.data_ptr() + H0 * W0, W0, 3 * H0 // 2 * W0, 1, H0, W0)
-            tail = (T.data_ptr(), out.data_ptr(), out.data_ptr() + H0 * W0, W0, 3 * H0 // 2 * W0, _stream())
+            pitch = 2 * W0 if self.p010 else W0                   # rows are packed; P010: one n = 1 call through a P010 view
+            if self.p010:
+                assert tuple(src.shape) == (1, 3 * H0 // 2, pitch) and src.dtype == torch.uint8
+                view = self.net.view(*self.view_args, surface="p010")
+            args = (r.src.data_ptr(), r.src.data_ptr() + H0 * pitch, pitch, 3 * H0 // 2 * pitch, 1, H0, W0)
+            tail = (T.data_ptr(), out.data_ptr(), out.data_ptr() + H0 * pitch, pitch, 3 * H0 // 2 * pitch, _stream())
             if zoom is None:
                 _lib.call("dvsg_tps_render_nv12", view, F.data_ptr(), *(args + tail))
             else:
@@ -424,7 +450,8 @@ def run_clips(streams, clips, batch):
 # ---------------------------------------------------------------------------------------------------------------------
 N_STEPS = 90
 MAX_STREAMS = 3
-SIZES = {"u8a": (45, 70), "u8b": (40, 64), "u8s": (MODEL_H, MODEL_W), "nva": (40, 48), "nvb": (36, 64)}
+SIZES = {"u8a": (45, 70), "u8b": (40, 64), "u8s": (MODEL_H, MODEL_W), "nva": (40, 48), "nvb": (36, 64), "pa": (40, 48),
+         "pb": (36, 64)}
 
 # name -> (opened before step, closed before step or None, steps it is open in but NOT fed, resets before steps,
 #          planted scene changes at these frame numbers of the stream)
@@ -443,9 +470,22 @@ _KINDS = {
     "source_res": {"a": "u8a", "b": "u8b", "c": "u8a", "d": "u8b", "e": "u8a", "f": "u8b", "g": "u8b"},
     "nv12": {"a": "nva", "b": "nvb", "c": "nvb", "d": "nva", "e": "nvb", "f": "nvb", "g": "nva"},
     "model_size": {"b": "f32", "a": "f32", "c": "f32", "d": "f64", "e": "f32", "f": "f64", "g": "f32"},
+    # a is left out of step 50 while b and e (one size) are fed: the other size is gone for a step and comes back
+    "p010": {"a": "pa", "b": "pb", "c": "pb", "d": "pa", "e": "pb", "f": "pb", "g": "pa"},
 }
-_FEED_ORDER = {"rgb": "fgbadce", "source_res": "abcdefg", "nv12": "abcdefg", "model_size": "gfbadce"}
-_HOST = {"rgb": "acdfg", "source_res": "bdf", "nv12": "a", "model_size": "adg"}   # NumPy in; the others device tensors
+_FEED_ORDER = {"rgb": "fgbadce", "source_res": "abcdefg", "nv12": "abcdefg", "model_size": "gfbadce", "p010": "abcdefg"}
+_HOST = {"rgb": "acdfg", "source_res": "bdf", "nv12": "a", "model_size": "adg", "p010": "ad"}   # NumPy in; the others device tensors
+# the form a P010 stream's frames arrive in: 16-bit words or their bytes, from the host or on the device ("dev_u16" only
+# where the installed torch has torch.uint16; the other streams are "dev_u8")
+_P010_FORMS = {"a": "host_u16", "d": "host_u8", "b": "dev_u16"}
+
+
+def _has_torch_uint16():
+    try:
+        import torch
+    except ImportError:
+        return False
+    return hasattr(torch, "uint16")
 _SEED = {n: 5100 + 7 * i for i, n in enumerate("abcdefg")}
 
 
@@ -479,6 +519,12 @@ def make_schedule(name):
             cur ^= int(j in planted)
             scenes.append(cur)
         sched.streams[n] = dict(kind=_KINDS[name][n], seed=_SEED[n], n=len(fed), scenes=scenes, host=n in _HOST[name])
+        if name == "p010":
+            form = _P010_FORMS.get(n, "dev_u8")
+            if form == "dev_u16" and not _has_torch_uint16():
+                form = "dev_u8"
+            assert form.startswith("host") == (n in _HOST[name])
+            sched.streams[n]["form"] = form
     return sched
 
 
@@ -502,6 +548,16 @@ def stream_frames(spec):
         H, W = SIZES[kind]
         return np.round(_levels(seed, n, H, W, scenes) * 255).astype(np.uint8)
     H, W = SIZES[kind]
+    if kind in ("pa", "pb"):
+        # 10-bit codes: luma 64 + 876 level (its high byte is the NV12 schedule's 16 + 219 level, so the two scenes keep
+        # disjoint high-byte histograms), chroma around 512; seeded NON-ZERO bits in the low 6 of every word.  uint16 words
+        # [n, 3 H / 2, W], or their bytes [n, 3 H / 2, 2 W] for a stream fed in the uint8 form.
+        y = np.round(64 + 876 * _levels(seed, n, H, W, scenes, C=1)[..., 0]).astype(np.uint16)
+        uv = np.round(512 + 48 * (inputs.smooth_frames(seed + 500, n, H // 2, W // 2, C=2) - 0.5)).astype(np.uint16)
+        code = np.concatenate([y, uv.reshape(n, H // 2, W)], axis=1)
+        low = np.random.default_rng(seed + 900).integers(1, 64, code.shape, dtype=np.uint16)
+        words = ((code << 6) | low).astype("<u2")
+        return words.view(np.uint16) if spec.get("form", "host_u16").endswith("u16") else words.view(np.uint8)
     y = np.round(16 + 219 * _levels(seed, n, H, W, scenes, C=1)[..., 0]).astype(np.uint8)
     uv = np.round(128 + 12 * (inputs.smooth_frames(seed + 500, n, H // 2, W // 2, C=2) - 0.5)).astype(np.uint8)
     return np.concatenate([y, uv.reshape(n, H // 2, W)], axis=1)
@@ -516,7 +572,8 @@ def coverage(sched):
     facts = dict(longest=0, reuse_after_long=False, reuse_after_one_frame=False, close_and_open_before_one_step=False,
                  left_out=set(), streams=set(), opened_not_fed=False, empty_step=False, batch_sizes=set(), reset_k=[],
                  max_groups=0, max_sizes=0, cut_alone=False, two_cuts=False, suppressed=0, cut_k=[], planted_after_reset=0,
-                 max_open=0, cuts=[])
+                 max_open=0, cuts=[], forms=set(), shared_launch=False, size_returns=False)
+    before, gone = set(), False      # the source sizes of the last step that fed something; a size it had is missing now
     freed = []                       # frames of the closed streams whose place nobody has taken yet, oldest first
     for t, events in enumerate(sched):
         fed, opened, closed_now = [], [], False
@@ -551,7 +608,14 @@ def coverage(sched):
             facts["opened_not_fed"] |= bool(set(opened) - set(fed))
             kinds = [sched.streams[n]["kind"] for n in fed]
             facts["max_groups"] = max(facts["max_groups"], len(set(kinds)))
-            facts["max_sizes"] = max(facts["max_sizes"], len(set(SIZES[c] for c in kinds if c in SIZES and c != "u8s")))
+            sized = [SIZES[c] for c in kinds if c in SIZES and c != "u8s"]
+            facts["max_sizes"] = max(facts["max_sizes"], len(set(sized)))
+            facts["forms"] |= set(sched.streams[n].get("form") for n in fed)
+            facts["shared_launch"] |= len(sized) > len(set(sized))        # two rows of one key: one run, one launch
+            now = set(sized)
+            facts["size_returns"] |= gone and len(now) >= 2                # ... and a later step feeds both again
+            gone |= len(before) >= 2 and len(now) == 1 and now < before    # one of two sizes after a step that fed both ...
+            before = now
         cuts = []
         for n in fed:
             j, sc = frames[n], sched.streams[n]["scenes"]

@@ -96,10 +96,11 @@ def render_u8(handle, F, src, flip, zoom, want_f32, want_u8, u8_W, u8_x0):
 
 
 @pytest.mark.parametrize("zoomed", [False, True])
-@pytest.mark.parametrize("H,W", [(7, 9), (12, 21)])
+@pytest.mark.parametrize("H,W", [(7, 9), (12, 21), (5, 515)])
 def test_rgb_render_is_the_reference(net, H, W, zoomed):
     """dvsg_tps_render_u8 / dvsg_tps_render_zoom_u8 through a bicubic view.  7 x 9 and 12 x 21: x0 = 0 and x0 = pw - 2 occur,
-    a row of 3 W bytes starts at every byte alignment, and neither width is a multiple of any vector."""
+    a row of 3 W bytes starts at every byte alignment, and neither width is a multiple of any vector.  5 x 515: three column
+    tiles of 256 with a partial last one (blockIdx.x > 0), one partial 4-row tile, rows of 1545 bytes."""
     n = 3
     view = net.view("bicubic")
     src_h = np.random.default_rng(H * W).integers(0, 256, (n, H, W, 3), dtype=np.uint8)
@@ -153,10 +154,11 @@ def nv12_reference(b, T, zoom):
 
 
 @pytest.mark.parametrize("zoomed", [False, True])
-@pytest.mark.parametrize("H,W,pitch", [(8, 12, 16), (10, 36, 48)])
+@pytest.mark.parametrize("H,W,pitch", [(8, 12, 16), (10, 36, 48), (10, 520, 528)])
 def test_nv12_render_is_the_reference(net, H, W, pitch, zoomed):
     """dvsg_tps_render_nv12 / dvsg_tps_render_zoom_nv12 through a bicubic view, pitch > W and a padded frame_stride (the UV
-    plane starts two rows behind the luma).  The 8 x 12 chroma plane is 4 x 6: nearly every tap row clamps."""
+    plane starts two rows behind the luma).  The 8 x 12 chroma plane is 4 x 6: nearly every tap row clamps.  10 x 520: luma
+    over three 256-column tiles, chroma over two, both planes end in a partial 4-row tile."""
     n = 3
     view = net.view("bicubic")
     b = nv12_ref.Batch(H + W, n, H, W, pitch, H + 2)

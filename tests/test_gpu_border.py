@@ -4,8 +4,9 @@ for byte and -- out_f32 -- bit for bit, no sample masked or left out.  x_s, y_s 
 dvsg_tps_warp_zoom_f32 at each plane's size, as the header defines them.  Every render writes into PRE-FILLED outputs (seeded
 bytes, floats in [2, 3)), so what "keep" leaves and what no mode may touch are both visible.  Synthetic weights, f32.
 
-Shapes: RGB 7 x 10, 16 x 24 and 1 x 5; NV12 8 x 12, 4 x 4 (a 2 x 2 chroma plane: the byte-tap path) and 16 x 20 (pitch 32, the UV
-plane three rows behind the luma, out_pitch > W).  Each test asserts about its own inputs that every side of every plane has a
+Shapes: RGB 7 x 10, 16 x 24, 1 x 5 and 5 x 515 (three 256-column tiles, the last one partial); NV12 8 x 12, 4 x 4 (a 2 x 2 chroma
+plane: the byte-tap path), 16 x 20 (pitch 32, the UV plane three rows behind the luma, out_pitch > W) and 10 x 520 (pitch 528:
+luma over three column tiles, chroma over two, both planes end in a partial 4-row tile).  Each test asserts about its own inputs that every side of every plane has a
 full row or column of invalid samples in some frame, and that at least a quarter of all its samples (all shapes, planes and
 frames of the launch) are valid.  The quarter is taken over the test's inputs as a whole: a plane with ph == 1 (RGB 1 x 5) has no
 valid sample by the header's rule and the 2 x 2 chroma plane has at most one per frame, so neither can hold it alone."""
@@ -23,8 +24,8 @@ import test_gpu_bicubic as B
 
 pytestmark = pytest.mark.gpu
 
-RGB_SHAPES = ((7, 10), (16, 24), (1, 5))
-NV12_SHAPES = ((8, 12, 12, 8, 12), (4, 4, 4, 4, 4), (16, 20, 32, 19, 28))    # H, W, pitch, uv_row, out_pitch
+RGB_SHAPES = ((7, 10), (16, 24), (1, 5), (5, 515))
+NV12_SHAPES = ((8, 12, 12, 8, 12), (4, 4, 4, 4, 4), (16, 20, 32, 19, 28), (10, 520, 528, 11, 524))    # H, W, pitch, uv_row, out_pitch
 ZOOM = (1.0, 0.8, 0.6)
 BORDERS = ("replicate", "mirror", "keep")
 FILTERS = ("bilinear", "bicubic")

@@ -8,6 +8,10 @@ streams at once, suppressed by scene_min_len, after the ring is full and on the 
 output must be `array_equal` (uint8, float32 and NV12 bytes, both halves of a side_by_side pair); after the last step
 `crop_state` and `scene_state` of every open stream must match, and the cuts the model saw must be the planted ones.
 
+`test_p010_all_options` drives the "p010" schedule (10-bit surfaces of two sizes, fed as host and device words and bytes; a size
+that disappears for a step and comes back) in two forms, `test_stabilize_clips_p010` holds stabilize_clips(frame_format="p010"),
+the expected value of tests/test_gpu_p010.py::test_pipes_ten_bit, to the model.
+
 The model runs ONE `LocNet.stabilize` call per step at the product's B and batch order, so no tolerance is needed; the
 premise (a ring call at B is gather + stabilise at B; the n = 1 renders are the batched ones) is pinned by
 tests/test_gpu_ring.py and tests/test_gpu_online.py and was not measured for these schedules before this file ran.
@@ -137,6 +141,18 @@ def test_nv12_all_options(synthetic_weights):
     _run(om.make_schedule("nv12"), *_both(synthetic_weights, dict(frame_format="nv12", crop="auto", border="keep", **SCENE)))
 
 
+@pytest.mark.parametrize("form", ["keep_bilinear", "mirror_bicubic_shaped"])
+def test_p010_all_options(synthetic_weights, form):
+    """P010 of two sizes; the streams arrive as host uint16, host uint8, device uint16 (where torch has it) and device uint8
+    and leave in the form they came in.  One of the two sizes is fed alone for a step and comes back (the per-size high-byte
+    buffers are dropped and made again); two streams of one size share a launch; keep_bilinear is the render form
+    tests/test_gpu_p010.py::test_bilinear_borders_are_the_reference pins."""
+    kw = dict(frame_format="p010", crop="auto", **SCENE)
+    kw.update(dict(border="keep") if form == "keep_bilinear" else
+              dict(render_filter="bicubic", border="mirror", strength=0.8, rigidity=0.5, shape_model="similarity"))
+    _run(om.make_schedule("p010"), *_both(synthetic_weights, kw))
+
+
 def test_model_size_crop_and_cuts(synthetic_weights):
     _run(om.make_schedule("model_size"), *_both(synthetic_weights, dict(crop="auto", crop_recover=0.01, **SCENE)))
 
@@ -152,6 +168,26 @@ def test_stabilize_clips(synthetic_weights):
         assert g.shape == (len(w_), H, W, 3)
         for k in range(len(w_)):
             assert np.array_equal(g[k], w_[k]), "clip %d, frame %d: %d values differ" % (c, k, int((g[k] != w_[k]).sum()))
+
+
+def test_stabilize_clips_p010(synthetic_weights):
+    """Three P010 clips of 1, 9 and 40 frames (two sizes) through two rings, one given as uint16 words and two as uint8
+    bytes, against the model fed clip by clip in the same lockstep: frame by frame, dtype by dtype."""
+    from coupe.dvsg_amd.online import stabilize_clips
+    model = _model(synthetic_weights)
+    specs = [dict(kind=k, seed=5500 + i, n=n, scenes=[0] * n, form=f)
+             for i, (k, n, f) in enumerate((("pa", 1, "host_u8"), ("pb", 9, "host_u16"), ("pa", 40, "host_u8")))]
+    clips = [om.stream_frames(s) for s in specs]
+    assert [c.dtype for c in clips] == [np.uint8, np.uint16, np.uint8]
+    kw = dict(frame_format="p010", crop="auto", border="keep")
+    got = stabilize_clips(model, clips, batch=2, **kw)
+    want = om.run_clips(om.UnboundedStreams(model, max_streams=2, **kw), clips, 2)
+    for c, (g, w_) in enumerate(zip(got, want)):
+        assert isinstance(g, np.ndarray) and g.dtype == clips[c].dtype and g.shape == clips[c].shape, "clip %d" % c
+        assert not np.array_equal(g, clips[c])
+        for k in range(len(w_)):
+            assert w_[k].dtype == g.dtype and np.array_equal(g[k], w_[k]), "clip %d, frame %d: %d values differ" % (
+                c, k, int((g[k] != w_[k]).sum()))
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16", "f32s", "f32x3"])

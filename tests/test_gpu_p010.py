@@ -4,7 +4,9 @@ surfaces, OnlineStabilizer(frame_format="p010") and 10-bit pipes.  Everything co
 
 Shapes: (4, 4) -- chroma 2 x 2, the bicubic pw < 4 path; (6, 8) -- chroma pw = 4, the packed window fills the row; (10, 520) --
 luma over three 256-column tiles, chroma over two, both planes end in a partial 4-row tile.  n = 2, frame_stride larger than
-the frame, input pitch 2 W + 6 (even, no multiple of 4: words off the dword grid), another output pitch."""
+the frame, input pitch 2 W + 6 (even, no multiple of 4: words off the dword grid), another output pitch.  The border tests
+also run the three-frame launches of tests/test_gpu_border.py ("launch", "far", "nan") with its zoom.  COVERED names a test
+for each of the sixteen p010_render_kernel<kZoom, kCubic, kBorder> instantiations."""
 import ctypes
 import io
 import threading
@@ -13,11 +15,13 @@ import numpy as np
 import pytest
 
 import bicubic_ref as R
+import border_ref
 import inputs
 import nv12_ref
 import p010_ref
 import shape_ref
 import test_gpu_bicubic as B
+import test_gpu_border as GB
 
 pytestmark = pytest.mark.gpu
 
@@ -48,12 +52,12 @@ def vectors():
     return (np.float32(2.0) * inputs.control_vectors(905, 2)).astype(np.float32)
 
 
-def source(H, W, uv_row, low):
-    return p010_ref.P010Batch(100 * H + W, 2, H, W, 2 * W + 6, uv_row, tail=1, low=low)
+def source(H, W, uv_row, low, n=2):
+    return p010_ref.P010Batch(100 * H + W, n, H, W, 2 * W + 6, uv_row, tail=1, low=low)
 
 
-def prefill(H, W, uv_row, out_pitch):
-    b = p010_ref.P010Batch(0, 2, H, W, out_pitch, uv_row + 1, tail=2, fill=POISON)
+def prefill(H, W, uv_row, out_pitch, n=2):
+    b = p010_ref.P010Batch(0, n, H, W, out_pitch, uv_row + 1, tail=2, fill=POISON)
     b.buf[:] = np.random.default_rng(7 * H + W).integers(0, 256, b.buf.shape, dtype=np.uint8)
     return b
 
@@ -88,6 +92,51 @@ def grids(T, zoom, H, W):
         assert ok.any() and not ok.all(), "plane %d x %d: %d of %d samples valid" % (ph, pw, ok.sum(), ok.size)
         out.append((xs, ys, ok))
     return out
+
+
+# The three-frame launches of tests/test_gpu_border.py -- "launch" (every side of every plane fully invalid in some frame),
+# "far" (the clamp behind the one reflection is reached) and "nan" (one NaN component in frame 1) -- with its zoom.
+KINDS = ("launch", "far", "nan")
+
+
+def launch(kind, shape, zoomed):
+    """(source, pre-filled output, F_t, zoom) of a three-frame launch of `kind` at a row of SHAPES"""
+    H, W, uv_row, low, out_pitch = shape
+    return (source(H, W, uv_row, low, 3), prefill(H, W, uv_row, out_pitch, 3), GB.vectors(kind),
+            _dev(np.float32(GB.ZOOM)) if zoomed else None)
+
+
+def plane_grids(T, zoom, n, H, W):
+    """per plane: (x_s, y_s, valid) [n, ph, pw] of the grid-only dvsg_tps_warp_zoom_f32"""
+    out = []
+    for ph, pw in ((H, W), (H // 2, W // 2)):
+        xs, ys = grid(T, zoom, n, ph, pw)
+        out.append((xs, ys, np.stack([R.valid(ph, pw, xs[i], ys[i]) for i in range(n)])))
+    return out
+
+
+def black_and_grids(net, filt, kind, shape, zoomed):
+    """(the two planes' words of the black-border P010 render of the launch, its plane_grids), once per launch"""
+    key = ("black", filt, kind, shape, zoomed)
+    if key not in _CACHE:
+        b, pre, F, zoom = launch(kind, shape, zoomed)
+        T, out = render(net.view(filt, "black", surface="p010"), F, b, zoom, pre)
+        _CACHE[key] = (pre.words(out), plane_grids(T, zoom, 3, shape[0], shape[1]))
+    return _CACHE[key]
+
+
+def check_launch_inputs(net, zoomed):
+    """tests/test_gpu_border.py's two assertions about the "launch" kind's masks, over all SHAPES and both planes"""
+    if ("masks", zoomed) not in _CACHE:
+        GB.check_inputs([ok for shape in SHAPES for _, _, ok in black_and_grids(net, "bilinear", "launch", shape, zoomed)[1]])
+        _CACHE[("masks", zoomed)] = True
+
+
+def check_kind(kind, xs, ys, ok, what):
+    if kind == "far":
+        assert not ok.any(), what
+    elif kind == "nan":
+        assert (np.isnan(xs[1]) | np.isnan(ys[1])).all() and not ok[1].any() and ok[0].any(), what
 
 
 def warp_plane(s, T, zoom):
@@ -161,6 +210,123 @@ def test_bicubic_borders_are_the_reference(net, H, W, uv_row, low, out_pitch, bo
         if border == "keep":
             assert np.array_equal(got[p][~ok], before[p][~ok]), "%s: keep wrote an invalid sample" % name
     assert np.array_equal(pre.outside(out), pre.outside()), "bytes beyond 2 W, between the planes or the frames were written"
+    # the far launch and the launch with a NaN (three frames): every sample is the restatement's; in the frame with the NaN
+    # coordinate every written luma word is 0 and every chroma word 512 << 6, and keep writes nothing
+    shape = (H, W, uv_row, low, out_pitch)
+    for kind in KINDS[1:]:
+        b, pre, F, zoom = launch(kind, shape, zoomed)
+        T, out = render(view, F, b, zoom, pre)
+        key = (H, W, zoomed, kind)
+        if key not in _CACHE:
+            _CACHE[key] = plane_grids(T, zoom, 3, H, W)
+        got, before, src = pre.words(out), pre.words(), b.words()
+        for p, (name, (xs, ys, ok)) in enumerate(zip(("luma", "chroma"), _CACHE[key])):
+            what = "%s %s %s %dx%d zoom=%d" % (kind, border, name, H, W, zoomed)
+            check_kind(kind, xs, ys, ok, what)
+            want = np.empty_like(got[p])
+            for i in range(3):
+                v, written = p010_ref.render_bicubic(src[p][i], xs[i], ys[i], border, p == 1)
+                want[i] = np.where(written[..., None], p010_ref.to_word(v, p == 1), before[p][i])
+                assert np.array_equal(written, ok[i] if border == "keep" else np.ones_like(ok[i]))
+            same_bits(got[p], want, what)
+            if kind == "nan":
+                blank = before[p][1] if border == "keep" else np.full_like(before[p][1], NEUTRAL if p else 0)
+                same_bits(got[p][1], blank, what + ": the frame with a NaN coordinate")
+        assert np.array_equal(pre.outside(out), pre.outside()), "%s: bytes outside the planes were written" % kind
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2b. bilinear x replicate, mirror, keep x zoom: render_plane<C, false, kBorder, uint16_t> against p010_ref.render_bilinear
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("zoomed", [False, True])
+@pytest.mark.parametrize("border", ["replicate", "mirror", "keep"])
+@pytest.mark.parametrize("H,W,uv_row,low,out_pitch", SHAPES)
+def test_bilinear_borders_are_the_reference(net, H, W, uv_row, low, out_pitch, border, zoomed, kind):
+    """Valid samples are the bits of the black-border P010 render of the same launch; invalid ones are
+    to_word(p010_ref.render_bilinear), word for word; keep leaves the pre-filled words.  (4, 4): in the 2 x 2 chroma plane
+    x1 = min(x0 + 1, pw - 1) clips at once."""
+    shape = (H, W, uv_row, low, out_pitch)
+    b, pre, F, zoom = launch(kind, shape, zoomed)
+    T, out = render(net.view("bilinear", border, surface="p010"), F, b, zoom, pre)
+    black, g = black_and_grids(net, "bilinear", kind, shape, zoomed)
+    if kind == "launch":
+        check_launch_inputs(net, zoomed)
+    got, before, src = pre.words(out), pre.words(), b.words()
+    for p, (name, (xs, ys, ok)) in enumerate(zip(("luma", "chroma"), g)):
+        what = "%s %s %s %dx%d zoom=%d" % (kind, border, name, H, W, zoomed)
+        check_kind(kind, xs, ys, ok, what)
+        want, wrote = np.empty_like(got[p]), np.empty_like(ok)
+        for i in range(3):
+            v, wrote[i] = p010_ref.render_bilinear(src[p][i], xs[i], ys[i], border, p == 1)
+            want[i] = np.where(wrote[i][..., None], p010_ref.to_word(v, p == 1), before[p][i])
+        assert np.array_equal(wrote, ok if border == "keep" else np.ones_like(ok))
+        same_bits(got[p][ok], black[p][ok], what + ", valid samples against the black border")
+        same_bits(got[p][~ok], want[~ok], what + ", invalid samples against p010_ref.render_bilinear")
+        assert ((got[p][wrote] & 0x3F) == 0).all(), what + ": low bits were written"
+        if border == "keep":
+            assert np.array_equal(got[p][~ok], before[p][~ok]) and (before[p][~ok] & 0x3F).any(), what + ": keep wrote an invalid sample"
+        elif kind == "nan":
+            assert (got[p][1] == (NEUTRAL if p else 0)).all(), what + ": a NaN coordinate gives the black value"
+    assert np.array_equal(pre.outside(out), pre.outside()), "bytes beyond 2 W, between the planes or the frames were written"
+
+
+@pytest.mark.parametrize("zoomed", [False, True])
+@pytest.mark.parametrize("filt", ["bilinear", "bicubic"])
+@pytest.mark.parametrize("border", ["replicate", "mirror"])
+def test_far_launch_writes_one_corner_sample(net, border, filt, zoomed):
+    """A known answer that no restatement enters.  F_t = (-2.5, +2.5) at all 25 points moves every coordinate of every plane
+    out through the left side (x < 0) and the bottom side (y > ph - 1).  Replicate clamps each to (0, ph - 1): every word of
+    a frame's plane is that plane's BOTTOM-LEFT sample with the low bits cleared.  Mirror reflects once (x -> -x, y -> 2 (ph - 1)
+    - y) and clamps what is still outside, so wherever the coordinate lies beyond the one reflection on both axes --
+    x <= -(pw - 1) and y >= 2 (ph - 1), read off the grid alone -- the word is the TOP-RIGHT sample; samples within one
+    reflection on an axis are blends and are left to the restatement tests.  On the clamped coordinate the bilinear weights
+    are 1, 0, 0, 0 and the bicubic ones 0, 1, 0, 0 on each axis, exactly (t = 0; tests/test_p010_cpu.py checks both
+    restatements), so both filters are held exactly."""
+    F = GB.vectors("far")
+    assert (F[..., 0] < 0).all() and (F[..., 1] > 0).all()
+    for shape in SHAPES:
+        H, W = shape[:2]
+        b, pre, F, zoom = launch("far", shape, zoomed)
+        T, out = render(net.view(filt, border, surface="p010"), F, b, zoom, pre)
+        got, src = pre.words(out), b.words()
+        for p, (xs, ys, ok) in enumerate(plane_grids(T, zoom, 3, H, W)):
+            ph, pw = ok.shape[1:]
+            x, y = border_ref.coords(ph, pw, xs, ys, np.float64)
+            assert (x < 0).all() and (y > ph - 1).all()
+            sel = np.ones_like(ok) if border == "replicate" else (x <= -(pw - 1)) & (y >= 2 * (ph - 1))
+            for i in range(3):
+                assert sel[i].any(), "no sample of frame %d of the %d x %d plane lies beyond the reflection" % (i, ph, pw)
+                corner = src[p][i, ph - 1, 0] if border == "replicate" else src[p][i, 0, pw - 1]
+                bad = (got[p][i][sel[i]] != (corner & 0xFFC0)).any(axis=-1)
+                assert not bad.any(), "%s %s %dx%d plane %d frame %d zoom=%d: %d of %d words are not the corner sample" % (
+                    border, filt, H, W, p, i, zoomed, bad.sum(), bad.size)
+
+
+# (kZoom, kCubic, kBorder) of p010_render_kernel -> the test that launches it, from the parametrisations above
+COVERED = {}
+for _z in (False, True):
+    COVERED[(_z, False, "black")] = "test_bilinear_render_is_the_composition"
+    for _b in ("replicate", "mirror", "keep"):
+        COVERED[(_z, False, _b)] = "test_bilinear_borders_are_the_reference"
+    for _b in ("black", "replicate", "mirror", "keep"):
+        COVERED[(_z, True, _b)] = "test_bicubic_borders_are_the_reference"
+
+
+def _parametrised(test):
+    """the set of (zoomed, border or None) over the parametrize marks of a test function"""
+    values = {m.args[0]: m.args[1] for m in test.pytestmark if m.name == "parametrize"}
+    return {(z, bd) for z in values["zoomed"] for bd in values.get("border", [None])}
+
+
+def test_every_p010_render_instantiation_has_a_test():
+    """2 x 2 x 4 instantiations of p010_render_kernel<kZoom, kCubic, kBorder>, each named with a test whose parameters reach it"""
+    assert len(COVERED) == 16 and set(COVERED) == {(z, c, bd) for z in (False, True) for c in (False, True)
+                                                   for bd in border_ref.BORDERS}
+    for (z, cubic, bd), name in COVERED.items():
+        cases = _parametrised(globals()[name])
+        assert (z, bd) in cases or (z, None) in cases and bd == "black", (z, cubic, bd, name)
+        assert ("bicubic" in name) == cubic
 
 
 def test_bicubic_tiny_plane(net):

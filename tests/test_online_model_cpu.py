@@ -11,7 +11,7 @@ import pytest
 import online_model as om
 import scene_ref
 
-SCHEDULES = ["rgb", "source_res", "nv12", "model_size"]
+SCHEDULES = ["rgb", "source_res", "nv12", "model_size", "p010"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -52,6 +52,14 @@ def test_schedule_covers_its_cases(name):
         rank = {"u8a": 1, "u8b": 0, "u8s": 2, "f32": 3, "f64": 4}
         assert any([rank[sched.streams[n]["kind"]] for w, n in ev if w == "feed"] !=
                    sorted(rank[sched.streams[n]["kind"]] for w, n in ev if w == "feed") for ev in sched)
+    if name == "p010":
+        want = {"host_u16", "host_u8", "dev_u8"} | ({"dev_u16"} if om._has_torch_uint16() else set())
+        assert f["forms"] == want, "words and bytes, from the host and on the device: %s" % f["forms"]
+        assert set(s["kind"] for s in sched.streams.values()) == {"pa", "pb"} and om.SIZES["pa"] != om.SIZES["pb"]
+        assert f["size_returns"], "one of the two sizes is fed alone after a step that fed both, and both are fed again later"
+        assert f["shared_launch"], "a run of two streams of one size"
+        # tests/test_gpu_online_model.py runs this schedule under border="keep": a reset() and a planted cut on such a stream
+        assert f["reset_k"] and f["cuts"]
     if name == "rgb":
         # the unstable half of a float64 frame between two rows rendered from the float32 slot (feed order 1, 3, 2)
         assert any([sched.streams[n]["kind"] for w, n in ev if w == "feed"] == ["u8s", "f64", "f32"] for ev in sched)
@@ -70,6 +78,32 @@ def test_stream_content_is_its_own():
     nv = om.make_schedule("nv12")
     fr = om.stream_frames(nv.streams["a"])
     assert fr.dtype == np.uint8 and fr.shape[1:] == (60, 48)
+
+
+def test_p010_content_uses_all_sixteen_bits():
+    """10-bit codes whose two bits below the high byte vary, seeded non-zero low 6 bits in every word, chroma around 512,
+    and scenes whose high bytes (what the network and the cut statistic see) share no luma value; the uint8 form is the
+    same words' bytes."""
+    sched = om.make_schedule("p010")
+    for n, spec in sched.streams.items():
+        fr = om.stream_frames(spec)
+        H, W = om.SIZES[spec["kind"]]
+        u16 = spec["form"].endswith("u16")
+        assert fr.dtype == (np.uint16 if u16 else np.uint8) and fr.shape == (spec["n"], 3 * H // 2, W if u16 else 2 * W), n
+        words = fr if u16 else fr.view("<u2")
+        assert np.array_equal(om.stream_frames(dict(spec, form="host_u16")), words)
+        assert ((words & 0x3F) != 0).all()
+        code = words >> 6
+        assert len(np.unique(code[:, :H] & 3)) == 4 and len(np.unique(code[:, H:] & 3)) == 4
+        y, uv = code[:, :H].astype(int), code[:, H:].astype(int)
+        assert 64 <= y.min() and y.max() <= 940 and 480 <= uv.min() and uv.max() <= 544 and uv.min() < 512 < uv.max()
+        sc = np.asarray(spec["scenes"])
+        hi = words[:, :H] >> 8
+        if (sc == 0).any() and (sc == 1).any():
+            assert hi[sc == 0].max() < hi[sc == 1].min()
+    nv = om.stream_frames(om.make_schedule("nv12").streams["a"])
+    pa = om.stream_frames(sched.streams["a"])
+    assert np.abs((pa[:, :40] >> 8).astype(int) - nv[:, :40]).max() <= 1, "the high byte is the NV12 schedule's luma"
 
 
 def test_planted_cuts_are_the_only_cuts_of_the_float_content():
