@@ -184,9 +184,10 @@ constexpr int rootconv_ld(int cin) { return rootconv_kpad(cin) + 2; }           
 // the P format: rootconv_kernel only), SRC (-1 where the family has none; rootconv_kernel records NW = 4, root_band_kernel
 // NW = 8 and TO = 0), the marching kernel's bands and quads_per_band or the band kernel's bands and (longest band's) row
 // pairs per band (else -1), the max pool kernel (0 maxpool_kernel<float>, 1 maxpool_kernel<_Float16>, 2
-// maxpool_h8_kernel, 3 maxpool_p_kernel), the average pool kernel (0 avgpool_partial_kernel<float>, 1 <_Float16>, 2
+// maxpool_h8_kernel, 3 maxpool_p_kernel, 4 root_pool_seams_kernel: family 7 then was root_band_pool_kernel, the pool in
+// conv1's epilogue), the average pool kernel (0 avgpool_partial_kernel<float>, 1 <_Float16>, 2
 // avgpool_partial_p_kernel) and the number of dense batch chunks.  Reset to -1 by forward(), written where launch_conv1,
-// launch_maxpool, launch_avgpool_partial and forward() issue the launches.  Host-only
+// launch_maxpool, launch_root_pool_seams, launch_avgpool_partial and forward() issue the launches.  Host-only
 constexpr int kRootKernelFields = 9;
 enum RootKernelField { kRootConv1 = 0, kRootNW, kRootTO, kRootSRC, kRootBands, kRootQuads, kRootMaxpool, kRootAvgpool,
                        kRootDenseChunks };
@@ -221,13 +222,25 @@ struct Conv1Weights {
   const unsigned short *x3;    // wt1x
   const float *bias;           // [64]
 };
+// The root max pool inside conv1: where `pool` is given (the caller has checked: float32, no pad on the pool's top and left,
+// nobody reads conv1's output) and launch_conv1 takes the band kernel, it may run root_band_pool_kernel instead (debug
+// option root_pool) -- the pooled tensor goes to `pooled`, whole but for the elements on a tile or band seam, and of `y` only
+// the conv values those elements still miss are written.  `fused` then is set and launch_root_pool_seams must follow on the
+// same stream in place of launch_maxpool; otherwise conv1 ran as without `pool`.
+struct RootPool {
+  void *pooled;                     // [B, Ho / 2, Wo / 2, 64] float32
+  bool fused = false;               // out
+  int bands = 0, ppb = 0, nbig = 0; // out: the launch's band split, which decides the row seams
+};
 int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const Conv1Weights &wt, void *y, int B, int H, int W, int Ho,
-                 int Wo, int cin, hipStream_t s);
+                 int Wo, int cin, hipStream_t s, RootPool *pool = nullptr);
+// finishes the seam elements of a fused launch from the conv values in `conv_taps` (launch_conv1's y); records max pool kernel 4
+int launch_root_pool_seams(const RootPool &pool, const void *conv_taps, int B, int Ho, int Wo, hipStream_t s);
 // rootconv_kernel declares its LDS per launch (up to 140 KB at cin = 48): raises every instantiation's dynamic LDS limit.
 // Called once per handle by dvsg_locnet_create for cin != 21, outside any stream operation
 int prepare_rootconv();
-// root_band_kernel (float32, cin = 21, big unmasked launches) declares 142 656 bytes of LDS: raises its instantiations'
-// dynamic LDS limit.  Called once per handle by dvsg_locnet_create for cin == 21, outside any stream operation
+// root_band_kernel (float32, cin = 21, big unmasked launches) declares 142 656 bytes of LDS, root_band_pool_kernel 159 040:
+// raises their instantiations' dynamic LDS limits.  Called once per handle by dvsg_locnet_create for cin == 21, outside any stream operation
 int prepare_root_band();
 
 // 3x3 stride-2 TF-SAME max pool (slim resnet root), C % 8 == 0.

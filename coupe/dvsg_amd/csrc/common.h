@@ -93,6 +93,8 @@ struct DebugOptions {
   int conv1_variant = 0;       // 0 = auto; 1 = float32 kernel with 8 waves; 2 = float16 output from the float32 multiply;
                                // 3 = float16, one output row per workgroup; 4 = never the marching kernel; 5 = always;
                                // float32: 6 = always the band kernel (unmasked sources), 7 = always the one-row kernel
+  int root_pool = 0;           // float32 root max pool in the band kernel's epilogue (root_band_pool_kernel + seam kernel): 0 = where
+                               // the band kernel is the library's own choice, 1 = never, 2 = wherever the band kernel runs
   int wide16_min_tiles = 128;  // float16 mode: 256 x 128 tiles from this many of them (a quarter of a round of 512 workgroups).
                                // Round 2 measured 256 (128 and below lost at batch 1-2 with the kernels of then); with packed
                                // weight stages, 128-byte activation rows and the 3x3 row reuse 128 is -0.5 % at batch 16, -4.5 %

@@ -607,210 +607,100 @@ constexpr int RB_SLOTS = 3;
 constexpr size_t RB_LDS = sizeof(float) * (size_t)(2 * C1_WELEMS + RB_SLOTS * C1_SEG_PAD);   // 142 656 bytes
 static_assert(RB_LDS <= 160 * 1024, "the band kernel's LDS must fit a CU");
 
-template <int SRC>
-__global__ __launch_bounds__(RB_NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void root_band_kernel(const Conv1Src src, const float *__restrict__ wt1, const float *__restrict__ bias,
-                      float *__restrict__ y, int H, int W, int Ho, int Wo, int wtiles, int bands, int ppb, int nbig) {
-  constexpr int NT = RB_NT, MI = 2;
-  static_assert(C1_TILE * C1_LDC <= C1_WELEMS, "epilogue tile must fit in a weight buffer");
-  extern __shared__ __attribute__((aligned(16))) float rb_lds[];
-  float *const w_s = rb_lds;                      // [2][C1_WELEMS]
-  float *const in_s = rb_lds + 2 * C1_WELEMS;     // [RB_SLOTS][C1_SEG_PAD]
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
+// root_band_pool_kernel (root_band_kernel.inc with RB_POOL, the same text otherwise): the root's 3x3 / stride 2 max pool in the pair's epilogue, for Ho and Wo even (TF 'SAME' then
+// pads nothing on the top and the left: pooled element (r, c) is the max of conv rows 2r .. 2r + 2 x columns 2c .. 2c + 2
+// that exist).  Pooled row r is pair r and the upper row of pair r + 1, and a column tile's 128 conv columns are its 64
+// pooled columns plus, for the last of them, column 0 of the tile to the right.  At a pair's epilogue both rows sit in the
+// transpose tiles; thread (pooled column lc, channels 4 col4 .. + 3) forms, after conv1_tile_out's own bias and ReLU per
+// tap, the 3-wide maxima `hu` and `hl` of the upper and the lower row over the tile's own columns, finishes pooled row
+// p - 1 as max(carry, hu) and leaves carry = max(hu, hl) for the pair after this one.  The carry, 64 pooled columns x 64
+// channels, lives in 16 KB of LDS behind the input slots (159 040 bytes in all) and every entry is read and written by
+// one thread only: no barrier.  In registers it would be 8 VGPRs alive through the MFMA loops, where the frame ring's
+// instantiations stand at 252 and 253 of 256 registers already, and through the pooled tensor it would be a second store and a
+// load per element (profiles/r26_root_pool_resources.txt).
+// What another workgroup owns is never waited for.  The pooled elements that need it are stored as the max over the taps
+// this workgroup owns -- column 64 j + 63 of tile j where conv column 128 (j + 1) exists, and a band's last pooled row
+// where the next band's first conv row exists -- and the conv values a neighbour misses go to their ordinary places in
+// the conv1 output tensor `y`, of which nothing else is written: conv column 128 j of every row for j >= 1, and the first
+// conv row of every band but the first.  root_pool_seams_kernel finishes those elements on the same stream.
+// The max of values that are never NaN (ReLU: fmaxf(NaN, 0) = 0) with -0 < +0 (v_max_f32) does not depend on the order
+// of the taps: every pooled element is maxpool_kernel's, bit for bit (tests/test_root_pool_fused.py).
+constexpr int RB_CARRY = 64 * 64;                                // floats: one horizontally pooled row of a tile
+constexpr size_t RB_POOL_LDS = RB_LDS + sizeof(float) * RB_CARRY;   // 159 040 bytes
+static_assert(RB_POOL_LDS <= 160 * 1024, "the pooling band kernel's LDS must fit a CU");
 
-  const Conv1Tile tile = conv1_tile(wtiles, bands);
-  const int b = tile.b, band = tile.ho, wo0 = tile.wo0;
-  const int pairs = (Ho + 1) / 2;
-  const int p0 = band * ppb - (band > nbig ? band - nbig : 0);
-  const int p1 = min(p0 + (band < nbig ? ppb : ppb - 1), pairs);
-  if (p0 >= p1) return;
+#define RB_KERNEL root_band_kernel
+#define RB_POOL 0
+#include "root_band_kernel.inc"
+#undef RB_KERNEL
+#undef RB_POOL
+#define RB_KERNEL root_band_pool_kernel
+#define RB_POOL 1
+#include "root_band_kernel.inc"
+#undef RB_KERNEL
+#undef RB_POOL
 
-#ifdef DVSG_STAMPS
-  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long t_begin = C1_STAMP(), r_begin = __builtin_amdgcn_s_memrealtime();
-#endif
-  typedef typename Conv1RowSel<NT, RB_IN4, SRC>::type Row;
-  Row row;
-  row.init(src, tid, b, wo0, H, W, C1_SEG_PAD);
-  if constexpr (Row::kRing) {   // elements the scatter never writes (the zero tap's slot, the tail) must be finite
-    for (int e = tid; e < RB_SLOTS * C1_SEG_PAD; e += NT) in_s[e] = 0.f;
-    __syncthreads();
+// The pooled elements root_band_pool_kernel left as partial maxima, finished from the conv values it stored for them (`a`,
+// the conv1 output tensor's addresses).  One thread = one pooled pixel x 4 channels, in two ranges:
+//   [0, n_col): the column seams -- (b, r, s) with pooled column c = 64 s + 63, s < ncs = the column tiles but the last.  The
+//     taps missing are conv column 2c + 2 = 128 (s + 1) of rows 2r, 2r + 1 and 2r + 2; if r is also the last row of a band
+//     but the last, conv row 2r + 2 at columns 2c and 2c + 1 too;
+//   [n_col, total): the row seams -- (b, k, c) with pooled row r = (first pair of band k + 1) - 1, k < bands - 1, every c but
+//     the column seams: conv row 2r + 2 at columns 2c, 2c + 1 and, inside the row, 2c + 2.
+// Band i starts at pair i ppb - max(i - nbig, 0), as in the band kernel.  In place: each element is read and written by its
+// own thread.
+__global__ __launch_bounds__(256) void root_pool_seams_kernel(const float *__restrict__ a, float *__restrict__ y, int Ho, int Wo,
+                                                             int ncs, int bands, int ppb, int nbig, size_t n_col,
+                                                             size_t total) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int Hp = Ho >> 1, Wp = Wo >> 1;
+  const int c4 = (int)(e & 15);
+  auto band_start = [&](int i) { return i * ppb - (i > nbig ? i - nbig : 0); };
+  int r, c;
+  size_t b;
+  bool col_seam, row_seam;
+  if (e < n_col) {
+    size_t t = e >> 4;
+    c = 64 * (int)(t % ncs) + 63;
+    t /= ncs;
+    r = (int)(t % Hp);
+    b = t / Hp;
+    const int p = r + 1, full = nbig * ppb;   // is pair p the first of a band?
+    const int i = p < full ? p / ppb : nbig + (p - full) / (ppb > 1 ? ppb - 1 : 1);
+    col_seam = true;
+    row_seam = p < Hp && i < bands && band_start(i) == p;
+  } else {
+    size_t t = (e - n_col) >> 4;
+    c = (int)(t % Wp);
+    t /= Wp;
+    r = band_start((int)(t % (bands - 1)) + 1) - 1;
+    b = t / (bands - 1);
+    if (r < 0 || r + 1 >= Hp) return;              // (no band starts there: launch_conv1's bands never do)
+    if ((c & 63) == 63 && 2 * c + 2 < Wo) return;  // the first range's
+    col_seam = false;
+    row_seam = true;
   }
-  typename Row::Data rd[3];
-  floatx4 w_reg[RB_WLOADS];
-  auto load_w = [&](int kh) __attribute__((always_inline)) {
-    const floatx4 *wsrc = reinterpret_cast<const floatx4 *>(wt1 + (size_t)kh * C1_WELEMS);
-#pragma unroll
-    for (int i = 0; i < RB_WLOADS; ++i) {
-      const int q = tid + NT * i;
-      w_reg[i] = wsrc[q < C1_WELEMS / 4 ? q : 0];
-    }
+  float *const out = y + ((b * Hp + r) * Wp + c) * 64 + 4 * c4;
+  float4 m = load4(out);
+  auto take = [&](int hi, int wi) {
+    const float4 v = load4(a + ((b * Ho + hi) * Wo + wi) * 64 + 4 * c4);
+    m.x = fmaxf(m.x, v.x);
+    m.y = fmaxf(m.y, v.y);
+    m.z = fmaxf(m.z, v.z);
+    m.w = fmaxf(m.w, v.w);
   };
-  auto put_w = [&](int i, float *dst) __attribute__((always_inline)) {
-    const int q = tid + NT * i;
-    if (q < C1_WELEMS / 4) reinterpret_cast<floatx4 *>(dst)[q] = w_reg[i];
-  };
-  auto put_row = [&](const typename Row::Data &d, float *slot) __attribute__((always_inline)) {
-    if constexpr (Row::kRing) {
-      row.scatter(d, [&](int e, float v) __attribute__((always_inline)) { slot[e] = v; });
-    } else {
+  if (col_seam) {
 #pragma unroll
-      for (int i = 0; i < RB_IN4; ++i) {
-        const int q = tid + NT * i;
-        const floatx4 v = row.scaled(d, i);
-        if (q < C1_SEG_PAD / 4) reinterpret_cast<floatx4 *>(slot)[q] = v;
-      }
-    }
-  };
-  // the first three input rows and the first weight row of the pair whose upper row is ho_
-  auto load_first = [&](int ho_) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) row.load(rd[i], 2 * ho_ - 3 + i);
-    load_w(0);
-  };
-#ifdef DVSG_STAMPS
-  st[0] = C1_STAMP() - t_begin;
-#endif
-  load_first(2 * p0);
-
-  for (int p = p0; p < p1; ++p) {
-    const int ho = 2 * p;
-#ifdef DVSG_STAMPS
-    const unsigned long long f0 = C1_STAMP();
-#endif
-    // (the barrier that ends the pair before this one freed every slot and both weight buffers)
-#pragma unroll
-    for (int i = 0; i < RB_WLOADS; ++i) put_w(i, w_s);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      __builtin_amdgcn_sched_barrier(0);   // one row's scatter at a time: interleaved, a frame ring's three run out of registers
-      put_row(rd[i], in_s + i * C1_SEG_PAD);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    floatx16 acc[MI], acc2[MI];   // even and odd taps: see conv1_kernel
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[mi][q] = acc2[mi][q] = 0.f;
-#ifdef DVSG_STAMPS
-    const unsigned long long f1 = C1_STAMP();
-    __syncthreads();
-    st[2] += f1 - f0;
-    st[3] += C1_STAMP() - f1;
-#else
-    __syncthreads();
-#endif
-
-    int s_up = 0;   // slot of the upper row's operand: t mod 3
-    for (int t = 0; t < 7; ++t) {
-#ifdef DVSG_STAMPS
-      const unsigned long long s3 = C1_STAMP();
-#endif
-      if (t < 6) {
-        row.load(rd[0], 2 * ho + t);   // input row i = t + 3 of the pair
-        load_w(t + 1);
-      }
-#ifdef DVSG_STAMPS
-      st[4] += C1_STAMP() - s3;
-#endif
-      __builtin_amdgcn_sched_barrier(0);  // prefetch stays ahead of the MFMA loop
-      const int s_lo = s_up == 0 ? 2 : s_up - 1;   // (t + 2) mod 3
-      const float *a0 = in_s + (wr ? s_lo : s_up) * C1_SEG_PAD + 2 * kConv1Cin * (wm * 32 * MI + r) + 2 * h;
-      const float *bp = w_s + (t & 1) * C1_WELEMS + (wn * 32 + r) * kConv1Ld + 2 * h;
-      // kernel row t + 1 into the idle buffer, one store per request from the middle of the loop on.  (At t = 6 the
-      // registers still hold kernel row 6 and the idle buffer nothing anyone reads: the stores stay unconditional.)
-      float *w_next = w_s + ((t + 1) & 1) * C1_WELEMS;
-      // conv1_kernel's loop: the operands of step u + 1 are requested before the MFMAs of step u are issued
-      constexpr int STEPS = kConv1Kpad / 4, PAIRS = (STEPS + 1) / 2;   // two steps per request: one ds_read2_b64 per operand
-      constexpr int WPUT0 = PAIRS / 2;
-      float2 va[2][2][MI], vb[2][2];
-      auto read_pair = [&](int slot, int g) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (2 * g + j >= STEPS) break;
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-            va[slot][j][mi] = *reinterpret_cast<const float2 *>(a0 + mi * (2 * kConv1Cin * 32) + 4 * (2 * g + j));
-          vb[slot][j] = *reinterpret_cast<const float2 *>(bp + 4 * (2 * g + j));
-        }
-      };
-      read_pair(0, 0);
-#pragma unroll
-      for (int g = 0; g < PAIRS; ++g) {
-        if (g + 1 < PAIRS) read_pair((g + 1) & 1, g + 1);
-        if (g >= WPUT0 && g < WPUT0 + RB_WLOADS) put_w(g - WPUT0, w_next);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (2 * g + j >= STEPS) break;
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) acc[mi] = mfma32(va[g & 1][j][mi].x, vb[g & 1][j].x, acc[mi]);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) acc2[mi] = mfma32(va[g & 1][j][mi].y, vb[g & 1][j].y, acc2[mi]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (t < 6) {
-#ifdef DVSG_STAMPS  // (each stamp drains lgkmcnt: the phase times are upper bounds)
-        const unsigned long long s0 = C1_STAMP();
-        __syncthreads();
-        const unsigned long long s1 = C1_STAMP();
-        put_row(rd[0], in_s + s_up * C1_SEG_PAD);
-        const unsigned long long s2 = C1_STAMP();
-        __syncthreads();
-        st[1] += s1 - s0;
-        st[2] += s2 - s1;
-        st[3] += C1_STAMP() - s2;
-#else
-        __syncthreads();   // everyone is done with input row t
-        put_row(rd[0], in_s + s_up * C1_SEG_PAD);
-        __syncthreads();
-#endif
-      }
-      s_up = s_up == 2 ? 0 : s_up + 1;
-    }
-
-    // ---- epilogue: the next pair's first loads fly under it; one transpose tile per row in the (idle) weight buffers
-#ifdef DVSG_STAMPS
-    const unsigned long long e0 = C1_STAMP();
-#endif
-    __syncthreads();
-    float *Cs = w_s + wr * C1_WELEMS;
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-      C1_TILE_PUT(Cs, wm * 32 * MI + mi * 32, wn * 32, acc[mi][q] + acc2[mi][q]);
-    __builtin_amdgcn_sched_barrier(0);   // (the accumulators are dead: their registers take the rows in flight)
-    if (p + 1 < p1) load_first(ho + 2);
-    // (the thread's place in the epilogue is derived here, per pair: held in registers across the band, the addresses and
-    // the bias that follow from it push the frame ring's instantiations past 256 registers)
-    int tid_e = tid;
-    asm volatile("" : "+v"(tid_e));
-    const float4 b4 = conv1_tile_bias(bias, tid_e);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (ho + j >= Ho) break;   // a last pair of one row
-      float *yrow = y + (((size_t)b * Ho + ho + j) * Wo + wo0) * 64 + 4 * (tid_e & 15);
-      conv1_tile_out<NT / 16>(w_s + j * C1_WELEMS, b4, tid_e, wo0, Wo,
-                              [&](int row_, float4 v) __attribute__((always_inline)) { store4(yrow + (size_t)row_ * 64, v); });
-    }
-    __syncthreads();
-#ifdef DVSG_STAMPS
-    st[5] += C1_STAMP() - e0;
-#endif
+    for (int i = 0; i < 3; ++i)
+      if (2 * r + i < Ho) take(2 * r + i, 2 * c + 2);
   }
-#ifdef DVSG_STAMPS
-  if (tid == 0 && blockIdx.x < 65536) {
-    unsigned long long *o = g_c1_stamps + (size_t)blockIdx.x * 8;
-    o[0] = st[0]; o[1] = st[1]; o[2] = st[2]; o[3] = st[3]; o[4] = st[4]; o[5] = st[5];
-    o[6] = C1_STAMP() - t_begin;
-    o[7] = __builtin_amdgcn_s_memrealtime() - r_begin;
+  if (row_seam) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (2 * c + j < Wo && !(col_seam && j == 2)) take(2 * r + 2, 2 * c + j);
   }
-#endif
+  store4(out, m);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2149,7 +2039,8 @@ bool with_conv1_src(int src, F &&f) {
 int g_last_root_kernel[kRootKernelFields] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
 
 int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const Conv1Weights &wt, void *y, int B, int H, int W, int Ho,
-                 int Wo, int cin, hipStream_t s) {
+                 int Wo, int cin, hipStream_t s, RootPool *pool) {
+  if (pool) pool->fused = false;
   const float *const wt1 = wt.f32, *const bias = wt.bias;
   const _Float16 *const wt1h = wt.f16, *const wt1s = wt.pieces;
   const unsigned short *const wt1x = wt.x3;
@@ -2255,11 +2146,24 @@ int launch_conv1(int out_prec, const Conv1Src &src, int src_kind, const Conv1Wei
       bands = nbig = ((Ho + 1) / 2 + ppb - 1) / ppb;
     }
     const dim3 bgrid((unsigned)((long)wtiles * bands * B));
+    // the root max pool in the pairs' epilogues (root_band_pool_kernel), where the caller offers it: root_pool 0 fuses where
+    // the band kernel is the library's own choice, 2 wherever it runs, 1 never
+    const bool fuse = pool && Ho % 2 == 0 && Wo % 2 == 0 && (g_opt.root_pool == 2 || (g_opt.root_pool == 0 && variant == 0));
+    if (fuse) {
+      pool->fused = true;
+      pool->bands = bands;
+      pool->ppb = ppb;
+      pool->nbig = nbig;
+    }
     legal = with_conv1_src<false>(SRC, [&](auto src_c) {
       constexpr int S = decltype(src_c)::value;
       record_conv1_kernel(7, 8, 0, S, bands, ppb);
-      hipLaunchKernelGGL((root_band_kernel<S>), bgrid, dim3(RB_NT), RB_LDS, s, src, wt1, bias, static_cast<float *>(y), H, W, Ho,
-                         Wo, wtiles, bands, ppb, nbig);
+      if (fuse)
+        hipLaunchKernelGGL((root_band_pool_kernel<S>), bgrid, dim3(RB_NT), RB_POOL_LDS, s, src, wt1, bias, static_cast<float *>(y),
+                           static_cast<float *>(pool->pooled), H, W, Ho, Wo, wtiles, bands, ppb, nbig);
+      else
+        hipLaunchKernelGGL((root_band_kernel<S>), bgrid, dim3(RB_NT), RB_LDS, s, src, wt1, bias, static_cast<float *>(y), H, W, Ho,
+                           Wo, wtiles, bands, ppb, nbig);
     });
   } else if (variant != 0 && variant != 7 && src_kind == kSrcWindow && !src.mask) {
     record_conv1_kernel(0, 8, 0, 0);
@@ -2303,6 +2207,9 @@ int prepare_root_band() {
       const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&root_band_kernel<S>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)RB_LDS);
       if (err == hipSuccess) err = e;
+      const hipError_t ep = hipFuncSetAttribute(reinterpret_cast<const void *>(&root_band_pool_kernel<S>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)RB_POOL_LDS);
+      if (err == hipSuccess) err = ep;
     });
   DVSG_HIP(err);
   return DVSG_OK;
@@ -2336,6 +2243,20 @@ int launch_maxpool(int prec, const void *x, void *y, int B, int H, int W, int C,
     hipLaunchKernelGGL(maxpool_kernel<float>, dim3(blocks), dim3(256), 0, s, static_cast<const float *>(x),
                        static_cast<float *>(y), H, W, C / 4, Ho, Wo, pad_top, pad_left, total);
   return check_launch("maxpool_kernel");
+}
+
+int launch_root_pool_seams(const RootPool &pool, const void *conv_taps, int B, int Ho, int Wo, hipStream_t s) {
+  DVSG_REQUIRE(pool.fused && Ho % 2 == 0 && Wo % 2 == 0 && pool.bands >= 1, "root pool seams: no fused root launch to finish");
+  const int Hp = Ho / 2, Wp = Wo / 2, ncs = ceil_div(Wo, C1_TILE) - 1;
+  const size_t n_col = (size_t)B * Hp * ncs * 16, total = n_col + (size_t)B * (pool.bands - 1) * Wp * 16;
+  g_last_root_kernel[kRootMaxpool] = 4;
+  if (total == 0) return DVSG_OK;   // one column tile, one band: the band kernel's pooled rows are whole
+  const size_t want = (total + 255) / 256;
+  DVSG_REQUIRE(want < (1u << 31), "root pool seams: %zu blocks do not fit a grid", want);
+  ProfScope prof(kClsMaxpool, s, 0.0, 4.0 * 4.0 * (double)total * 5.0);   // (about: a partial and ~3 taps in, one element out)
+  hipLaunchKernelGGL(root_pool_seams_kernel, dim3((unsigned)want), dim3(256), 0, s, static_cast<const float *>(conv_taps),
+                     static_cast<float *>(pool.pooled), Ho, Wo, ncs, pool.bands, pool.ppb, pool.nbig, n_col, total);
+  return check_launch("root_pool_seams_kernel");
 }
 
 }  // namespace dvsg

@@ -524,16 +524,24 @@ int forward(const dvsg_locnet *net, const int precision, const Conv1Src &src, in
   ConvScratch scratch{ws};
   const bool fuse_allowed = g_opt.fuse_conv != 0 && calib == nullptr;   // block 1's conv2 + conv3 in one kernel
   reset_root_kernel();
-  // root: conv1 (+ fused scale_RGB; f32 multiply, output in `act`) -> bufA, max pool -> bufB
+  // root: conv1 (+ fused scale_RGB; f32 multiply, output in `act`) -> bufA, max pool -> bufB.  Float32, where the pool pads
+  // nothing on the top and the left (H1 and W1 even) and conv1's output is not tapped: the band kernel may pool in its
+  // epilogue (launch_conv1), and bufA then holds the seam elements' missing conv values only
+  RootPool root_pool{ws.bufB};
+  const bool pool_in_conv1 = precision == kF32 && stop_stage != 0 && d.pad_top == 0 && d.pad_left == 0 && d.H1 % 2 == 0 &&
+                             d.W1 % 2 == 0 && g_opt.root_pool != 1;
   {
   MarkerRange mr("dvsg/conv1");
   DVSG_RUN(launch_conv1(precision == kF32X && g_opt.x3_conv1 ? kF32X : act, src, src_kind, net->conv1.conv1_images(), ws.bufA, B, H, W,
-                        d.H1, d.W1, net->c_in, s));
+                        d.H1, d.W1, net->c_in, s, pool_in_conv1 ? &root_pool : nullptr));
   }
   DVSG_TAP(0, ws.bufA, d.H1, d.W1, 64);
   {
   MarkerRange mr("dvsg/pool1");
-  DVSG_RUN(launch_maxpool(act, ws.bufA, ws.bufB, B, d.H1, d.W1, 64, d.Hp, d.Wp, d.pad_top, d.pad_left, s));
+  if (root_pool.fused)
+    DVSG_RUN(launch_root_pool_seams(root_pool, ws.bufA, B, d.H1, d.W1, s));
+  else
+    DVSG_RUN(launch_maxpool(act, ws.bufA, ws.bufB, B, d.H1, d.W1, 64, d.Hp, d.Wp, d.pad_top, d.pad_left, s));
   }
   DVSG_TAP(1, ws.bufB, d.Hp, d.Wp, 64);
 
@@ -800,6 +808,7 @@ constexpr struct {
 } kDebugOptions[] = {
     {"conv_variant", &DebugOptions::conv_variant, opt_any},
     {"conv1_variant", &DebugOptions::conv1_variant, opt_any},
+    {"root_pool", &DebugOptions::root_pool, opt_any},
     {"wide16_min_tiles", &DebugOptions::wide16_min_tiles, opt_any},
     {"wide16_packed", &DebugOptions::wide16_packed, opt_any},
     {"wide16_arows", &DebugOptions::wide16_arows, opt_any},

@@ -798,10 +798,13 @@ int dvsg_conv3x3_1x1_f32(const float *x, const float *wt2, const float *bias2, c
                          const float *res, float *y, int B, int H, int W, int Cin, int Cout, int stride, int res_stride,
                          void *stream);
 
-/* Diagnostic A/B switches for kernel experiments, process-global; an unknown name is DVSG_ERR_INVALID_ARG.  The 17
+/* Diagnostic A/B switches for kernel experiments, process-global; an unknown name is DVSG_ERR_INVALID_ARG.  The 18
  * names and their defaults: "conv_variant" 0, "conv1_variant" 0 (0 = the launch policy's own choice of kernel; in
  * float32, 6 = root_band_kernel -- row pairs in bands, one workgroup per CU -- at any size for unmasked sources, in bands of at
- * most 3 pairs, and 7 = the one-row conv1_kernel at any size: the two are equal bit for bit), "fuse_conv" 1,
+ * most 3 pairs, and 7 = the one-row conv1_kernel at any size: the two are equal bit for bit), "root_pool" 0 (float32, conv1's
+ * output of even height and width and not tapped: the root max pool in the band kernel's epilogue, root_band_pool_kernel +
+ * root_pool_seams_kernel, 0 = where the band kernel is the policy's own choice, 1 = never, 2 = wherever the band kernel
+ * runs; equal to the separate max pool bit for bit), "fuse_conv" 1,
  * "fuse_shortcut" 1, "concat_sc" 1 (block 1's conv2 + conv3 in one kernel, its shortcut conv in that kernel too, the
  * shortcut + conv1 of blocks 2-4's opening units as one launch; 0 selects the separate launches), "x3_conv1" 1, "x3_fuse" 3
  * (the f32x3 precision's own conv1 kernel and block-1 fusion; 0 the float32 kernel / never fused), "f16_split" 1,

@@ -2,7 +2,9 @@
 """Per-workgroup phase times of the float32 conv1 kernels from a -DDVSG_STAMPS build (see tools/README.md):
    DVSG_AMD_LIB=build/lib_stamps.so [PROBE_REP=20] [PROBE_VARIANT=7] python tools/stamp_probe_conv1.py [B H W]
 The stamps are those of the last of PROBE_REP launches (default 3).  PROBE_VARIANT sets conv1_variant: the library's own
-choice (0) is root_band_kernel at big launches and conv1_kernel otherwise; 6 / 7 force the one or the other."""
+choice (0) is root_band_kernel at big launches and conv1_kernel otherwise; 6 / 7 force the one or the other.
+PROBE_STAGE=1 taps the root max pool instead of conv1: the band kernel then is root_band_pool_kernel (the pool in its
+epilogue) and root_pool_seams_kernel follows it; the stamps are the band kernel's either way."""
 import ctypes, os, sys
 import numpy as np
 import torch
@@ -20,8 +22,9 @@ x = bench.gpu_windows(B, H, W, 1, dev)
 lib = _lib.load()
 if os.environ.get("PROBE_VARIANT"):
     _lib.call("dvsg_debug_set_option", b"conv1_variant", int(os.environ["PROBE_VARIANT"]))
+stage = int(os.environ.get("PROBE_STAGE", "0"))
 for _ in range(int(os.environ.get("PROBE_REP", "3"))):
-    net.tap(x, 0)       # stops after conv1
+    net.tap(x, stage)   # stops after conv1 (0) or the root max pool (1)
 torch.cuda.synchronize()
 rec = (ctypes.c_int * 9)()
 _lib.call("dvsg_debug_last_root_kernel", rec, 9)
@@ -36,8 +39,8 @@ clk = np.median(life / real)
 q = lambda a: "med %8.0f  p10 %8.0f  p90 %8.0f  share of lifetime %.3f" % (
     np.median(a), np.percentile(a, 10), np.percentile(a, 90), np.median(a / life))
 if band:
-    print("root_band_kernel B=%d %dx%d: %d bands of <= %d row pairs, %d workgroups sampled, in-kernel clock %.0f MHz" %
-          (B, W, H, rec[4], rec[5], n, clk))
+    print("%s B=%d %dx%d: %d bands of <= %d row pairs, %d workgroups sampled, in-kernel clock %.0f MHz" %
+          ("root_band_pool_kernel" if rec[6] == 4 else "root_band_kernel", B, W, H, rec[4], rec[5], n, clk))
     names = ["band prologue (index setup)", "barrier 1 (per step: everyone's MFMAs + own loads landed)",
              "scale + LDS stores of the input rows", "barrier 2 (per step and pair)", "load issue", "epilogues (both rows' transposes + stores)",
              "lifetime"]
