@@ -1,4 +1,4 @@
-// Launch interface of the localizationNet kernels (conv_gemm.hip, conv1_pool.hip, head.hip),
+// Launch interface of the localizationNet kernels (conv_gemm.hip, conv1.hip and the conv1_*.hip kernel files, root_pool.hip, head.hip),
 // used by locnet.hip.
 //
 // `Precision` is the network's notion: what an entry point was asked for, and the storage of the activations between layers.

@@ -84,6 +84,18 @@ int tps_coverage_impl(const char *fn, const float *coord, long coord_bstride, co
                       int src_H, int src_W, int out_h, int out_w, int32_t *n_border, int32_t *key_min, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+// The values of the debug option conv1_variant (DebugOptions below; read by choose_conv1, conv1.hip)
+enum Conv1Variant {
+  kConv1VarAuto = 0,
+  kConv1VarEightWaves = 1,   // float32 kernel with 8 waves
+  kConv1VarF32ToF16 = 2,     // float16 output from the float32 multiply
+  kConv1VarF16OneRow = 3,    // float16, one output row per workgroup
+  kConv1VarNoMarch = 4,      // float16: never the marching kernel
+  kConv1VarMarch = 5,        // float16: always the marching kernel
+  kConv1VarBand = 6,         // float32: always the band kernel (unmasked sources)
+  kConv1VarOneRow = 7        // float32: always the one-row kernel
+};
+
 // The diagnostic A/B switches of dvsg_debug_set_option, one member per option name, at their defaults.  One instance,
 // g_opt (api_common.cpp); the launch policies read its members.  Host-only, not synchronised: tests and tools set a
 // switch between calls, never during one.

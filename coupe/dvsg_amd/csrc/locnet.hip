@@ -1,6 +1,6 @@
 // Host side of localizationNet (networks.py:30-46) and of the fused evaluation graph
 // (model.py:98-123): checkpoint ingestion (BatchNorm folding, weight re-layout for the MFMA
-// fragment scheme of conv_gemm.hip / conv1_pool.hip, float16 copies), workspace planning and the
+// fragment scheme of conv_gemm.hip / the conv1_*.hip kernels, float16 copies), workspace planning and the
 // launch sequence for both storage precisions.
 #include <atomic>
 #include <cmath>
@@ -525,11 +525,10 @@ int forward(const dvsg_locnet *net, const int precision, const Conv1Src &src, in
   const bool fuse_allowed = g_opt.fuse_conv != 0 && calib == nullptr;   // block 1's conv2 + conv3 in one kernel
   reset_root_kernel();
   // root: conv1 (+ fused scale_RGB; f32 multiply, output in `act`) -> bufA, max pool -> bufB.  Float32, where the pool pads
-  // nothing on the top and the left (H1 and W1 even) and conv1's output is not tapped: the band kernel may pool in its
-  // epilogue (launch_conv1), and bufA then holds the seam elements' missing conv values only
+  // nothing on the top and the left and conv1's output is not tapped: the band kernel may pool in its epilogue (whether it
+  // does is launch_conv1's choice), and bufA then holds the seam elements' missing conv values only
   RootPool root_pool{ws.bufB};
-  const bool pool_in_conv1 = precision == kF32 && stop_stage != 0 && d.pad_top == 0 && d.pad_left == 0 && d.H1 % 2 == 0 &&
-                             d.W1 % 2 == 0 && g_opt.root_pool != 1;
+  const bool pool_in_conv1 = precision == kF32 && stop_stage != 0 && d.pad_top == 0 && d.pad_left == 0;
   {
   MarkerRange mr("dvsg/conv1");
   DVSG_RUN(launch_conv1(precision == kF32X && g_opt.x3_conv1 ? kF32X : act, src, src_kind, net->conv1.conv1_images(), ws.bufA, B, H, W,

@@ -1,4 +1,4 @@
-// The text of root_band_kernel and root_band_pool_kernel (conv1_pool.hip includes it once for each, and describes both).
+// The text of root_band_kernel and root_band_pool_kernel (conv1_f32.hip includes it once for each, and describes both).
 // RB_KERNEL is the kernel's name, RB_POOL 0 or 1: with 1 the pair's epilogue forms the root max pool's row instead of storing
 // the two conv rows, and the kernel takes the pooled tensor behind `y`.  One text, not a function the two kernels call:
 // inlined from a shared __device__ function the plain kernel's register allocation moved in four of its six instantiations,

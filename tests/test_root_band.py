@@ -2,7 +2,7 @@
 conv1_kernel<4, float, SRC>, bit for bit.
 
 The band kernel feeds the same operands, in the same order, through the same instruction into the same two chains per
-output element as the one-row kernel (conv1_pool.hip), so its output must EQUAL that kernel's: no tolerance, the tensors
+output element as the one-row kernel (conv1_f32.hip), so its output must EQUAL that kernel's: no tolerance, the tensors
 are compared as int32.  The one-row kernel is held to float64 element by element in test_root_head_f64.py, and equality
 carries that bound over.  conv1_variant 6 forces the band kernel at any size (bands of at most 3 pairs), 7 the one-row
 kernel; 0 is the library's own choice, restated here as `root_bands`.

@@ -1,6 +1,6 @@
 """conv1, the root max pool and the head pinned to float64, element by element.
 
-Every conv1 instantiation of conv1_pool.hip that a public path can launch is launched on purpose by a case of CASES, which
+Every conv1 instantiation of conv1_f32.hip, conv1_f16.hip and conv1_x3.hip that a public path can launch is launched on purpose by a case of CASES, which
 names the launch record it expects (dvsg_debug_last_root_kernel: family, NW, TO, SRC, bands, quads per band, max pool,
 average pool, dense chunks); the record must match exactly, and a CPU test checks the table against the mangled names of
 the built library.  tau, bound, excess, Guarded and TINY are test_conv_gemm_f64.py's, the float16 interval check is

@@ -4,6 +4,11 @@
     tools/isa_table.py OBJ_DIR               symbol | instructions | sha1
     tools/isa_table.py PARENT_DIR NOW_DIR    symbol | instructions parent | instructions now | sha1 parent | sha1 now | same
     tools/isa_table.py --resources PARENT_DIR NOW_DIR    the same, then one line per differing symbol (below)
+    tools/isa_table.py --by-symbol [--resources] PARENT_DIR NOW_DIR
+        the two directories compared by kernel symbol across all their objects, for a change that moves kernels between
+        files: symbol | object parent | object now | instructions | sha1 | same, with one line for each object whose symbols
+        all stayed in it unchanged.  A symbol found in two objects of one side is reported and fails the comparison like a
+        differing one.
 
 For every .o: the fat binary section is dumped with llvm-objcopy, its gfx950 member unbundled with clang-offload-bundler
 and disassembled with llvm-objdump -d; addresses and encodings are stripped and the remaining instruction text is hashed
@@ -113,9 +118,65 @@ def verdict(ia, ib, ra, rb):
                                                     100.0 * (ib - ia) / ia, " | ".join(cells))
 
 
+def by_symbol(a_dir, b_dir, resources):
+    """Parent against now by kernel symbol, whichever object holds it: for a change that moves kernels between files."""
+    sides, dup = [], []
+    for d in (a_dir, b_dir):
+        k, res, where = {}, {}, {}
+        for o in objects(d):
+            r = {} if resources else None
+            for s, v in kernels(os.path.join(d, o), r).items():
+                if s in k:
+                    dup.append("%s | twice in %s: %s and %s" % (s, d, where[s], o))
+                k[s], where[s] = v, o
+                if resources:
+                    res[s] = r[s]
+        sides.append((k, res, where))
+    (a, ra, wa), (b, rb, wb) = sides
+    # an object whose symbols stayed where they were, every one identical, gets one line instead of a row per symbol
+    names = set(wa.values()) | set(wb.values())
+    quiet = {o for o in names if {s for s in a if wa[s] == o} == {s for s in b if wb[s] == o} and
+             all(a[s] == b[s] for s in a if wa[s] == o)}
+    rows, differing, detail = [], 0, []
+    for o in sorted(quiet):
+        rows.append("(%s: %d symbols, all in the same object on both sides and identical)" % (o, sum(1 for s in a if wa[s] == o)))
+    for s in sorted(set(a) | set(b)):
+        ia, ha = a.get(s, ("-", "-"))
+        ib, hb = b.get(s, ("-", "-"))
+        same = s in a and s in b and a[s] == b[s]
+        differing += not same
+        if wa.get(s) in quiet and wb.get(s) in quiet:
+            continue
+        rows.append("%s | %s | %s | %s | %s | %s | %s | %s" % (s, wa.get(s, "-"), wb.get(s, "-"), ia, ib, ha, hb, "yes" if same else "NO"))
+        if resources and not same:
+            one = ra.get(s) or rb.get(s) or {}
+            detail.append("%s | %s" % (s, verdict(ia, ib, ra[s], rb[s]) if s in a and s in b else
+                                       "DIFFERENT | on one side only (%s) | %s" % (
+                                           "parent" if s in a else "now", " | ".join("%s %s" % kv for kv in one.items()))))
+    print("%d objects parent, %d now, %d kernel symbols parent, %d now, %s%s" % (
+        len(objects(a_dir)), len(objects(b_dir)), len(a), len(b),
+        "every one identical" if not differing else "%d DIFFERING or on one side only" % differing,
+        ", %d in two objects of one side" % len(dup) if dup else ""))
+    print("symbol | object parent | object now | instructions parent | instructions now | sha1 parent | sha1 now | same")
+    print("\n".join(rows))
+    if dup:
+        print("\nsymbols in two objects of one side:")
+        print("\n".join(dup))
+    if resources:
+        print("\nresources of the %d differing symbols: verdict | instructions now - parent | metadata and instruction classes"
+              % len(detail))
+        print("\n".join(detail))
+    return 1 if differing or dup else 0
+
+
 def main(argv):
     resources = "--resources" in argv
-    argv = [a for a in argv if a != "--resources"]
+    symbols = "--by-symbol" in argv
+    argv = [a for a in argv if a not in ("--resources", "--by-symbol")]
+    if symbols:
+        if len(argv) != 3:
+            sys.exit(__doc__)
+        return by_symbol(argv[1], argv[2], resources)
     if len(argv) == 2:
         for o in objects(argv[1]):
             k = kernels(os.path.join(argv[1], o))

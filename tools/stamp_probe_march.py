@@ -20,7 +20,7 @@ for _ in range(4):
 torch.cuda.synchronize()
 lib = _lib.load()
 buf = np.zeros((65536, 8), dtype=np.uint64)
-assert lib.dvsg_debug_read_conv1_stamps(ctypes.c_void_p(buf.ctypes.data), ctypes.c_size_t(buf.nbytes)) == 0
+assert lib.dvsg_debug_read_march_stamps(ctypes.c_void_p(buf.ctypes.data), ctypes.c_size_t(buf.nbytes)) == 0
 st = buf[buf[:, 3] > 0].astype(np.float64)
 steps = st[:, 3]
 print("conv1_f16_march_kernel B=%d %dx%d: %d workgroups sampled, %.0f steps each (s_memtime ticks: shader-clock cycles on this part)"
