@@ -419,7 +419,7 @@ def _choose_zoom(model, F, out_hw, crop, crop_margin, crop_min, crop_info, net=N
 
 
 def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render_filter="bilinear", border="black",
-                       strength=1.0, rigidity=0.0, shape_model="affine"):
+                       strength=1.0, rigidity=0.0, shape_model="affine", out_size=None):
     """`dvsg_tps_render_u8` for the uint8 frames src [n,H0,W0,3] (device) and their F_t rows F [n,25,2]: the stabilised
     frames at source size into `out` [n,H0,W0,3] (float32, or uint8: np.uint8(x * 255.) in the channel order of src)
     and, if given, `side` [n,H0,2 W0,3] uint8 = (source bytes | uint8 render).  T [n,2,28] receives the TPS
@@ -429,18 +429,22 @@ def render_source_into(model, src, F, T, flip, out, side=None, zoom=None, render
     and the samples it leaves unwritten keep what the caller put into `out` (frame i of the launch does not see frame
     i - 1: a caller that wants the previous output there renders one frame at a time, as OnlineStabilizer does); with
     `side` it is a ValueError naming border.  strength, rigidity, shape_model: the warp shape of that handle -- the render
-    applies F' of include/dvsg_amd.h, "Warp shaping", and T receives its coefficients."""
+    applies F' of include/dvsg_amd.h, "Warp shaping", and T receives its coefficients.  out_size=(H, W): the render goes
+    through the scaled view of that handle and `out` is [n,H,W,3] (include/dvsg_amd.h, "Output size"); with `side` it is a
+    ValueError naming out_size."""
     from . import _lib
     from ._tensor import ptr, stream
     from .networks import check_border
     if check_border(border) == "keep" and side is not None:
         raise ValueError("border='keep' has no side_by_side layout: the unwritten samples are the caller's `out`")
-    net = model.locnet.view(render_filter, border, strength, rigidity, shape_model)
+    if out_size is not None and side is not None:
+        raise ValueError("out_size has no side_by_side layout: the source half keeps the source's size")
+    net = model.locnet.view(render_filter, border, strength, rigidity, shape_model, out_size=out_size)
     n, H0, W0 = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
     if side is not None:
         side[:, :, :W0] = src   # np.uint8(v / 255. * 255.) == v for every byte: the unstable half is the source
     if out.dtype == torch.uint8:
-        f32, u8, u8_W, u8_x0 = None, out, W0, 0
+        f32, u8, u8_W, u8_x0 = None, out, int(out.shape[2]), 0
     else:                       # one launch writes the float32 render and the right half of side
         f32, u8, u8_W, u8_x0 = out, side, 2 * W0, W0
     if zoom is not None:

@@ -63,22 +63,29 @@ int tps_render_impl(const double *winv_cols, const float *coord, const float *F_
                     int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
                     const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR /* the handle's or view's */,
                     int render_border = DVSG_BORDER_BLACK /* likewise */,
-                    RenderShape shape = RenderShape() /* likewise */);
+                    RenderShape shape = RenderShape() /* likewise */,
+                    int out_H = 0, int out_W = 0 /* a scaled view's output size; (0, 0): the source's */);
 // nv12.hip: dvsg_tps_render_nv12 and, with zoom [n] on the device, dvsg_tps_render_zoom_nv12.  The check makes no HIP call
 // and reads no handle (fn: the entry point its messages name); the launch half assumes it passed.  tps_render_p010_check:
 // what a P010 view (dvsg_locnet_view_create_surface) asks on top of it, once the handle may be read -- planes of 16-bit
 // words, pitch >= 2 W, pitches, frame strides and plane pointers 2-byte aligned; no HIP call either.
 int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
                           int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
-                          size_t out_frame_stride, const char *fn = "dvsg_tps_render_nv12");
+                          size_t out_frame_stride, const char *fn = "dvsg_tps_render_nv12",
+                          int out_H = 0, int out_W = 0 /* a scaled view's output size; (0, 0): the source's */);
 int tps_render_p010_check(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int W,
-                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, const char *fn);
+                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, const char *fn,
+                          int out_W = 0 /* a scaled view's output width; 0: W */);
 int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream,
                          const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR,
                          int render_border = DVSG_BORDER_BLACK, RenderShape shape = RenderShape(),
-                         int surface_format = DVSG_SURFACE_NV12);
+                         int surface_format = DVSG_SURFACE_NV12, int out_H = 0, int out_W = 0 /* a scaled view's size */,
+                         const char *fn = "dvsg_tps_render_nv12");
+// nv12.hip: what a scaled view (dvsg_locnet_view_create_scaled) asks of a render of (H, W) frames at another size
+// (out_H, out_W): at most 4 virtual samples per axis, no DVSG_BORDER_KEEP.  No HIP call.
+int render_scaled_check(const char *fn, int H, int W, int out_H, int out_W, int render_border);
 // crop_kernels.hip: the fused coverage scan of dvsg_tps_coverage_f32 (coord_bstride in floats; 0 = broadcast)
 int tps_coverage_impl(const char *fn, const float *coord, long coord_bstride, const float *T, const float *zoom, int B, int P,
                       int src_H, int src_W, int out_h, int out_w, int32_t *n_border, int32_t *key_min, void *workspace,

@@ -6,7 +6,10 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <string>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "cnn_kernels.h"
@@ -103,6 +106,7 @@ struct dvsg_locnet {
   int render_border = DVSG_BORDER_BLACK;
   RenderShape render_shape;
   int surface_format = DVSG_SURFACE_NV12;   // read by dvsg_tps_render_nv12 / _zoom_nv12 alone
+  int out_h = 0, out_w = 0;                 // read by the four source-size renders alone; (0, 0): the source's size
   mutable std::atomic<int> n_views{0};
 };
 
@@ -939,10 +943,48 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
   return DVSG_OK;
 }
 
+// The views that carry an output size other than (0, 0), by address.  dvsg_tps_render_nv12 / _zoom_nv12 check every argument
+// before they read the handle (a caller's garbage pointer with a bad pitch is refused, not followed), and what the output
+// planes must hold depends on the view's size: looking the POINTER up here tells them without reading through it.  Any
+// other pointer has (0, 0), the source's size.
+// INVARIANT: the table and the handles' out_h / out_w always agree.  set_view_size is the one place that writes either, once
+// per view and before the constructor hands the view out; a view's fields never change afterwards; dvsg_locnet_destroy
+// erases the entry before it frees the view.  So a live view v has g_scaled_views[v] == (v->out_h, v->out_w) if that is not
+// (0, 0) and no entry otherwise, and the RGB renders (which read the fields) and the NV12 renders (which read the table) see
+// one size.  g_n_scaled counts the entries: while no scaled view exists a render takes no lock.
+static std::mutex g_scaled_mutex;
+static std::unordered_map<const dvsg_locnet *, std::pair<int, int>> g_scaled_views;
+static std::atomic<int> g_n_scaled{0};
+
+static void scaled_view_size(const dvsg_locnet *net, int *out_h, int *out_w) {
+  *out_h = *out_w = 0;
+  if (g_n_scaled.load(std::memory_order_acquire) == 0) return;
+  std::lock_guard<std::mutex> lock(g_scaled_mutex);
+  const auto it = g_scaled_views.find(net);
+  *out_h = it == g_scaled_views.end() ? 0 : it->second.first;
+  *out_w = it == g_scaled_views.end() ? 0 : it->second.second;
+}
+
+// the view's size is set once, here, before the constructor hands the view out
+static void set_view_size(dvsg_locnet *v, int out_h, int out_w) {
+  v->out_h = out_h;
+  v->out_w = out_w;
+  if (out_h || out_w) {
+    std::lock_guard<std::mutex> lock(g_scaled_mutex);
+    g_scaled_views[v] = std::make_pair(out_h, out_w);
+    g_n_scaled.store((int)g_scaled_views.size(), std::memory_order_release);
+  }
+}
+
 int dvsg_locnet_destroy(dvsg_locnet_t *net) {
   if (!net) return DVSG_OK;
   if (net->parent) {   // a view owns nothing
     net->parent->n_views.fetch_sub(1);
+    if (net->out_h || net->out_w) {
+      std::lock_guard<std::mutex> lock(g_scaled_mutex);
+      g_scaled_views.erase(net);
+      g_n_scaled.store((int)g_scaled_views.size(), std::memory_order_release);
+    }
     delete net;
     return DVSG_OK;
   }
@@ -1007,6 +1049,29 @@ int dvsg_locnet_view_create_surface(const dvsg_locnet_t *net, int surface_format
                "%s: surface_format=%d is neither DVSG_SURFACE_NV12 (0) nor DVSG_SURFACE_P010 (1)", fn, surface_format);
   if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
   (*view)->surface_format = surface_format;
+  set_view_size(*view, net->out_h, net->out_w);
+  return DVSG_OK;
+}
+
+// a view of net's parent with net's own filter, border, shape and surface format and the given output size ("Output size")
+int dvsg_locnet_view_create_scaled(const dvsg_locnet_t *net, int out_H, int out_W, dvsg_locnet_t **view) {
+  const char *fn = "dvsg_locnet_view_create_scaled";
+  DVSG_REQUIRE(net, "%s: NULL net", fn);
+  DVSG_REQUIRE(view, "%s: NULL view", fn);
+  *view = nullptr;
+  if (!(out_H == 0 && out_W == 0)) {
+    DVSG_REQUIRE(out_H >= 1, "%s: out_H=%d (with out_W=%d) is neither >= 1 nor, together with out_W, 0", fn, out_H, out_W);
+    DVSG_REQUIRE(out_W >= 1, "%s: out_W=%d (with out_H=%d) is neither >= 1 nor, together with out_H, 0", fn, out_W, out_H);
+  }
+  if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
+  (*view)->surface_format = net->surface_format;
+  set_view_size(*view, out_H, out_W);
+  return DVSG_OK;
+}
+
+int dvsg_locnet_render_size(const dvsg_locnet_t *net, int *out_H, int *out_W) {
+  if (out_H) *out_H = net ? net->out_h : 0;
+  if (out_W) *out_W = net ? net->out_w : 0;
   return DVSG_OK;
 }
 
@@ -1381,7 +1446,7 @@ int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t
                        int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_u8: NULL net");
   return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, nullptr, net->render_filter, net->render_border, net->render_shape);
+                         u8_W, u8_x0, stream, nullptr, net->render_filter, net->render_border, net->render_shape, net->out_h, net->out_w);
 }
 
 // dvsg_tps_render_u8 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_u8 itself)
@@ -1390,7 +1455,7 @@ int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const ui
                             int u8_x0, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_zoom_u8: NULL net");
   return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, zoom, net->render_filter, net->render_border, net->render_shape);
+                         u8_W, u8_x0, stream, zoom, net->render_filter, net->render_border, net->render_shape, net->out_h, net->out_w);
 }
 
 // dvsg_tps_render_u8 for NV12 frames (nv12.hip): the same T, then both planes warped at their own sizes in one launch.
@@ -1399,16 +1464,18 @@ int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8
                          size_t frame_stride, int n, int H, int W, float *T, uint8_t *out_y, uint8_t *out_uv, size_t out_pitch,
                          size_t out_frame_stride, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_nv12: NULL net");
+  int oh = 0, ow = 0;
+  scaled_view_size(net, &oh, &ow);   // by the pointer's value: the handle itself is not read yet
   if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
-                                     "dvsg_tps_render_nv12"))
+                                     "dvsg_tps_render_nv12", oh, ow))
     return rc;
   if (net->surface_format == DVSG_SURFACE_P010)   // the first read of the handle
     if (int rc = tps_render_p010_check(y, uv, pitch, frame_stride, n, W, out_y, out_uv, out_pitch, out_frame_stride,
-                                       "dvsg_tps_render_nv12"))
+                                       "dvsg_tps_render_nv12", ow))
       return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
                               out_pitch, out_frame_stride, stream, nullptr, net->render_filter, net->render_border,
-                              net->render_shape, net->surface_format);
+                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_nv12");
 }
 
 // dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
@@ -1416,16 +1483,18 @@ int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const 
                               size_t frame_stride, int n, int H, int W, const float *zoom, float *T, uint8_t *out_y,
                               uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream) {
   DVSG_REQUIRE(net, "dvsg_tps_render_zoom_nv12: NULL net");
+  int oh = 0, ow = 0;
+  scaled_view_size(net, &oh, &ow);   // by the pointer's value: the handle itself is not read yet
   if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
-                                     "dvsg_tps_render_zoom_nv12"))
+                                     "dvsg_tps_render_zoom_nv12", oh, ow))
     return rc;
   if (net->surface_format == DVSG_SURFACE_P010)   // the first read of the handle
     if (int rc = tps_render_p010_check(y, uv, pitch, frame_stride, n, W, out_y, out_uv, out_pitch, out_frame_stride,
-                                       "dvsg_tps_render_zoom_nv12"))
+                                       "dvsg_tps_render_zoom_nv12", ow))
       return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
                               out_pitch, out_frame_stride, stream, zoom, net->render_filter, net->render_border,
-                              net->render_shape, net->surface_format);
+                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_zoom_nv12");
 }
 
 // T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)

@@ -16,6 +16,9 @@
 //                           nv12_render_kernel keeps its instructions.
 //   nv12_render_cubic_kernel  both of the above through a bicubic view (dvsg_locnet_view_create): the same tiles and map, the
 //                           4 x 4-tap filter of warp_device.h behind it, bytes rounded to nearest.
+//   nv12_render_scaled_kernel  the render through a scaled view (dvsg_locnet_view_create_scaled): output planes of another size,
+//                           each sample the float32 average of sy x sx samples of that map and filter (scaled_device.h), for
+//                           NV12 and P010, both filters, the black, replicate and mirror borders.
 //
 // Every kernel is bit-identical to a composition of pinned entry points (stated at each); this translation unit is compiled
 // with -ffp-contract=off like frames.hip and warp_kernels.hip.  The map comes from tps_stage / tps_map_rows and the blend from
@@ -23,6 +26,7 @@
 #include <cstdint>
 
 #include "frames_device.h"
+#include "scaled_device.h"
 #include "warp_device.h"
 
 namespace dvsg {
@@ -185,44 +189,8 @@ __global__ __launch_bounds__(kThreads) void ingest_nv12_resize_kernel(Nv12 s, in
 // ----------------------------------------------------------------------------------------
 // Render.
 // ----------------------------------------------------------------------------------------
-// A plane's sample as the float32 image dvsg_tps_warp_f32 would be given.  Luma: (float)((double)Y / 255.0); chroma:
-// (float)(((double)c - 128.0) / 255.0).  One correctly rounded float32 division of the exact integer gives the same value
-// for every byte (exhaustive on the host: tests/test_nv12_cpu.py; the luma case is load_pix<C>(const uint8_t *)'s).
-// S = uint16_t: a P010 plane, the 10-bit rule of warp_device.h's sample_f32.
-template <int C, typename S = uint8_t>
-__device__ __forceinline__ Pix<C> load_plane(const S *__restrict__ p) {
-  Pix<C> r;
-#pragma unroll
-  for (int c = 0; c < C; ++c) r.v[c] = load_sample<S, C == 2>(p + c);
-  return r;
-}
-
-// sample_a_load on a plane whose rows are `pitch` bytes apart: its coordinate, index and weight expressions in its order,
-// C samples of type S per pixel.  The indices are clipped into the plane, so every tap address lies inside it.
-template <int C, typename S = uint8_t>
-__device__ __forceinline__ void plane_a_load(const uint8_t *__restrict__ img, size_t pitch, int H, int W, float xs, float ys,
-                                             TapsA<C> &t) {
-  const float x = ((xs + 1.0f) * (float)W) / 2.0f;  // :48
-  const float y = ((ys + 1.0f) * (float)H) / 2.0f;  // :49
-  int x0 = f2i(floorf(x));
-  int y0 = f2i(floorf(y));
-  int x1 = x0 + 1;
-  int y1 = y0 + 1;
-  x0 = clampi(x0, 0, W - 1);  // :57-60
-  x1 = clampi(x1, 0, W - 1);
-  y0 = clampi(y0, 0, H - 1);
-  y1 = clampi(y1, 0, H - 1);
-  const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-  t.wa = (x1f - x) * (y1f - y);  // :85-88
-  t.wb = (x1f - x) * (y - y0f);
-  t.wc = (x - x0f) * (y1f - y);
-  t.wd = (x - x0f) * (y - y0f);
-  constexpr int kStep = C * kSampleBytes<S>;   // bytes from one sample to the next
-  t.a = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y0 * pitch + x0 * kStep));  // (x0,y0)
-  t.b = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y1 * pitch + x0 * kStep));  // (x0,y1)
-  t.c = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y0 * pitch + x1 * kStep));  // (x1,y0)
-  t.d = load_plane<C, S>(reinterpret_cast<const S *>(img + (size_t)y1 * pitch + x1 * kStep));  // (x1,y1)
-}
+// load_plane / plane_a_load -- a plane's samples as the float32 image dvsg_tps_warp_f32 would be given, and sample_a_load on
+// a plane whose rows are `pitch` bytes apart -- are scaled_device.h's: the scaled kernels of warp_kernels.hip use them too.
 
 // chroma back to a byte: clamp(floor((double)v * 255.0 + 128.5), 0, 255); NaN gives 0 like to_u8
 __device__ __forceinline__ uint8_t chroma_u8(float v) {
@@ -464,6 +432,76 @@ __global__ __launch_bounds__(kThreads) void p010_render_kernel(Nv12 s, const flo
                                                 out_pitch, out_frame_stride);
 }
 
+// One output pixel's C samples at d from its float32 values: render_plane's output rules (bilinear luma truncates, chroma
+// rounds at 128.5, the bicubic bytes and the P010 words round to nearest).
+template <int C, bool kCubic, typename S>
+__device__ __forceinline__ void store_sample(uint8_t *__restrict__ d, const float (&v)[C]) {
+  if constexpr (kSampleBytes<S> == 2) {
+    store_words<C>(d, v);
+  } else if constexpr (kCubic) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = cubic_u8(v[c], C == 2 ? 128.5 : 0.5);
+  } else if constexpr (C == 1) {
+    d[0] = to_u8((double)v[0]);
+  } else {
+    const uint8_t u = chroma_u8(v[0]), w = chroma_u8(v[1]);
+    if ((reinterpret_cast<uintptr_t>(d) & 1) == 0) {
+      *reinterpret_cast<uint16_t *>(d) = (uint16_t)((uint16_t)u | ((uint16_t)w << 8));
+    } else {
+      d[0] = u;
+      d[1] = w;
+    }
+  }
+}
+
+// The render through a scaled view (dvsg_locnet_view_create_scaled; include/dvsg_amd.h, "Output size"): planes of (H, W) /
+// (H / 2, W / 2) in, (oh, ow) / (oh / 2, ow / 2) out, each output sample the float32 average of sy x sx virtual samples
+// (scaled_device.h).  blockIdx.y: the frame.  blockIdx.x: the luma tiles (kThreads output columns x 4 / sy output rows,
+// row-major, gx_l per row group), then from n_l on the chroma tiles.  step_*: lin_step of the planes' VIRTUAL grids.  zoom may
+// be NULL (z = 1.0f).  Kernels of their own: a handle without the property launches the kernels above.
+template <typename S, bool kCubic, int kBorder>
+__global__ __launch_bounds__(kThreads) void nv12_render_scaled_kernel(Nv12 s, const float *__restrict__ coord,
+                                                                      const float *__restrict__ T,
+                                                                      const float *__restrict__ zoom, int H, int W, int P,
+                                                                      int oh, int ow, int sx, int sy, float sx_l, float sy_l,
+                                                                      float sx_c, float sy_c, int gx_l, int n_l, int gx_c,
+                                                                      uint8_t *__restrict__ out_y, uint8_t *__restrict__ out_uv,
+                                                                      size_t out_pitch, size_t out_frame_stride) {
+  __shared__ float4 sp[64];
+  __shared__ float4 sdy[64];
+  __shared__ float sa[6];
+  const int b = blockIdx.y, t = threadIdx.x;
+  int id = blockIdx.x;
+  const bool chroma = id >= n_l;
+  if (chroma) id -= n_l;
+  const int gx = chroma ? gx_c : gx_l;
+  const int rows = scaled_rows_per_group(sy);
+  const int io0 = (id / gx) * rows, i0v = io0 * sy;   // the first output row and its first virtual row
+  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
+  const int po = chroma ? oh / 2 : oh, qo = chroma ? ow / 2 : ow;
+  const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
+  const float z = zoom ? zoom[b] : 1.0f;
+  tps_stage<true, true>(coord, 0, T, b, P, t, i0v, step_y, sp, sdy, sa, z);
+  __syncthreads();
+  const int j = (id % gx) * kThreads + t;
+  if (j >= qo) return;
+  float xs[4][4], ys[4][4];
+  scaled_map(sp, sdy, sa, P, j, sx, step_x, step_y, i0v, z, xs, ys);
+  const int n_v = min(rows, po - io0) * sy;
+  const size_t in_off = (size_t)b * s.frame_stride, out_off = (size_t)b * out_frame_stride;
+  if (chroma) {
+    uint8_t *const d0 = out_uv + out_off + (size_t)io0 * out_pitch + (size_t)j * (2 * kSampleBytes<S>);
+    scaled_average<2, kCubic, kBorder, S>(s.uv + in_off, s.pitch, ph, pw, sx, sy, n_v, xs, ys, [&](int io, const float (&v)[2]) {
+      store_sample<2, kCubic, S>(d0 + (size_t)io * out_pitch, v);
+    });
+  } else {
+    uint8_t *const d0 = out_y + out_off + (size_t)io0 * out_pitch + (size_t)j * kSampleBytes<S>;
+    scaled_average<1, kCubic, kBorder, S>(s.y + in_off, s.pitch, ph, pw, sx, sy, n_v, xs, ys, [&](int io, const float (&v)[1]) {
+      store_sample<1, kCubic, S>(d0 + (size_t)io * out_pitch, v);
+    });
+  }
+}
+
 inline int grid_for(size_t items, int cap = 1 << 16) {
   const size_t b = (items + kThreads - 1) / kThreads;
   return (int)(b < (size_t)cap ? (b ? b : 1) : (size_t)cap);
@@ -504,23 +542,75 @@ int check_matrix(const char *fn, int matrix) {
 
 int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
                           int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
-                          size_t out_frame_stride, const char *fn) {
+                          size_t out_frame_stride, const char *fn, int out_H, int out_W) {
   DVSG_REQUIRE(F_t && T, "%s: NULL pointer", fn);
   if (int rc = check_nv12(fn, "source", y, uv, pitch, frame_stride, n, H, W)) return rc;
-  return check_nv12(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, H, W);
+  if (out_H == 0 && out_W == 0) out_H = H, out_W = W;
+  if (out_H != H || out_W != W) {   // a scaled view: the output planes are those of an (out_H, out_W) frame
+    DVSG_REQUIRE(out_H >= 4 && out_H % 2 == 0, "%s: out_H=%d of the scaled view is odd or below 4 (NV12 / P010 output)", fn, out_H);
+    DVSG_REQUIRE(out_W >= 4 && out_W % 2 == 0, "%s: out_W=%d of the scaled view is odd or below 4 (NV12 / P010 output)", fn, out_W);
+  }
+  return check_nv12(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, out_H, out_W);
 }
 
 int tps_render_p010_check(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int W,
-                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, const char *fn) {
+                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, const char *fn,
+                          int out_W) {
   if (int rc = check_p010(fn, "source", y, uv, pitch, frame_stride, n, W)) return rc;
-  return check_p010(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, W);
+  return check_p010(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, out_W ? out_W : W);
+}
+
+// What a scaled view asks of a render of (H, W) frames at (out_H, out_W) != (H, W), before any device work: at most 4 virtual
+// samples per axis, and no DVSG_BORDER_KEEP (the caller's bytes have no counterpart at another size).
+int render_scaled_check(const char *fn, int H, int W, int out_H, int out_W, int render_border) {
+  const int sy = scaled_factor(H, out_H), sx = scaled_factor(W, out_W);
+  DVSG_REQUIRE(sy <= 4, "%s: out_H=%d of the scaled view is a %dx minification of src_H=%d; more than 4x is not served", fn, out_H,
+               sy, H);
+  DVSG_REQUIRE(sx <= 4, "%s: out_W=%d of the scaled view is a %dx minification of src_W=%d; more than 4x is not served", fn, out_W,
+               sx, W);
+  DVSG_REQUIRE(render_border != DVSG_BORDER_KEEP,
+               "%s: render_border=DVSG_BORDER_KEEP on a scaled view whose size %dx%d differs from the source's %dx%d", fn, out_H,
+               out_W, H, W);
+  return DVSG_OK;
 }
 
 // the arguments have passed tps_render_nv12_check (and, for DVSG_SURFACE_P010, tps_render_p010_check)
 int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream, const float *zoom,
-                         int render_filter, int render_border, RenderShape shape, int surface_format) {
+                         int render_filter, int render_border, RenderShape shape, int surface_format, int out_H, int out_W,
+                         const char *fn) {
+  if ((out_H || out_W) && (out_H != H || out_W != W)) {   // a scaled view at another size: kernels of their own
+    if (int rc = render_scaled_check(fn, H, W, out_H, out_W, render_border)) return rc;
+    const int sy = scaled_factor(H, out_H), sx = scaled_factor(W, out_W), rows = scaled_rows_per_group(sy);
+    const int gx_l = ceil_div(out_W, kThreads), gx_c = ceil_div(out_W / 2, kThreads);
+    const long n_l = (long)gx_l * ceil_div(out_H, rows), n_c = (long)gx_c * ceil_div(out_H / 2, rows);
+    DVSG_REQUIRE(n_l + n_c < (1L << 31), "%s: frame %dx%d too large", fn, out_H, out_W);
+    if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, shape)) return rc;
+    hipStream_t s = as_stream(stream);
+    const bool p010 = surface_format == DVSG_SURFACE_P010;
+    // algorithmic bytes: the source planes once in, the output planes once out
+    ProfScope prof(kClsTpsWarp, s, 0.0, (p010 ? 3.0 : 1.5) * n * ((double)H * W + (double)out_H * out_W));
+    const dim3 grid((unsigned)(n_l + n_c), n);
+    auto launch = [&](auto kS, auto kCubic, auto kBorder) {
+      hipLaunchKernelGGL((nv12_render_scaled_kernel<decltype(kS), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
+                         Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, out_H, out_W, sx, sy, lin_step(sx * out_W),
+                         lin_step(sy * out_H), lin_step(sx * (out_W / 2)), lin_step(sy * (out_H / 2)), gx_l, (int)n_l, gx_c,
+                         out_y, out_uv, out_pitch, out_frame_stride);
+    };
+    auto with_border = [&](auto kS, auto kCubic) {
+      if (render_border == DVSG_BORDER_REPLICATE) launch(kS, kCubic, std::integral_constant<int, DVSG_BORDER_REPLICATE>());
+      else if (render_border == DVSG_BORDER_MIRROR) launch(kS, kCubic, std::integral_constant<int, DVSG_BORDER_MIRROR>());
+      else launch(kS, kCubic, std::integral_constant<int, DVSG_BORDER_BLACK>());
+    };
+    auto with_filter = [&](auto kS) {
+      if (render_filter == DVSG_RENDER_BICUBIC) with_border(kS, std::true_type());
+      else with_border(kS, std::false_type());
+    };
+    if (p010) with_filter(uint16_t());
+    else with_filter(uint8_t());
+    return check_launch("nv12_render_scaled_kernel");
+  }
   const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
   const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(H / 2, kTpsRows);
   DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);

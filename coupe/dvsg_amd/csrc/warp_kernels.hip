@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "cnn_device.h"
+#include "scaled_device.h"
 #include "warp_device.h"
 
 namespace dvsg {
@@ -356,6 +357,44 @@ __global__ __launch_bounds__(kThreads) void tps_render_border_kernel(
   constexpr int u_stride = 0, n_pool = 0;
   float *const xs_out = nullptr, *const ys_out = nullptr;
 #include "tps_warp_body.inc"
+}
+
+// The uint8 render through a scaled view (dvsg_locnet_view_create_scaled; include/dvsg_amd.h, "Output size"): frames of
+// (H, W) in, (out_h, out_w) out, each output sample the float32 average of sy x sx virtual samples (scaled_device.h), the
+// output forms of tps_warp_kernel<3, uint8_t, uint8_t>.  Grid: (output column tiles, groups of 4 / sy output rows, frames).
+// step_x / step_y: lin_step of the VIRTUAL grid (sx out_w, sy out_h).  zoom may be NULL (z = 1.0f).  Kernels of their own.
+template <bool kCubic, int kBorder>
+__global__ __launch_bounds__(kThreads) void tps_render_scaled_kernel(
+    const uint8_t *__restrict__ U, const float *__restrict__ coord, const float *__restrict__ T,
+    const float *__restrict__ zoom, int H, int W, int P, int out_h, int out_w, int sx, int sy, float step_x, float step_y,
+    uint8_t *__restrict__ out, int out_row, int out_x0, int flip, float *__restrict__ out_rgb) {
+  __shared__ float4 sp[64];
+  __shared__ float4 sdy[64];
+  __shared__ float sa[6];
+  const int b = blockIdx.z, t = threadIdx.x;
+  const int rows = scaled_rows_per_group(sy);
+  const int io0 = blockIdx.y * rows, i0v = io0 * sy;   // the first output row and its first virtual row
+  const float z = zoom ? zoom[b] : 1.0f;
+  tps_stage<true, true>(coord, 0, T, b, P, t, i0v, step_y, sp, sdy, sa, z);
+  __syncthreads();
+  const int j = blockIdx.x * kThreads + t;
+  if (j >= out_w) return;
+  float xs[4][4], ys[4][4];
+  scaled_map(sp, sdy, sa, P, j, sx, step_x, step_y, i0v, z, xs, ys);
+  const int n_v = min(rows, out_h - io0) * sy;
+  scaled_average<3, kCubic, kBorder, uint8_t>(U + (size_t)b * H * W * 3, (size_t)W * 3, H, W, sx, sy, n_v, xs, ys,
+                                              [&](int io, const float (&v)[3]) {
+    const size_t i = (size_t)b * out_h + io0 + io;
+    if (out_rgb) {
+      const float rgb[3] = {v[flip ? 2 : 0], v[1], v[flip ? 0 : 2]};
+      store_pix<3>(out_rgb, i * out_w + j, 3, rgb);
+    }
+    if (out) {
+      uint8_t *d = out + (i * out_row + out_x0 + j) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) d[c] = kCubic ? cubic_u8(v[c], 0.5) : to_u8((double)v[c]);
+    }
+  });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -894,14 +933,37 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 // and / or uint8 out_u8 [B,H,u8_W,3] in columns [u8_x0, u8_x0 + W).  Every argument is checked before the first launch.
 int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
                     int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
-                    const float *zoom, int render_filter, int render_border, RenderShape shape) {
+                    const float *zoom, int render_filter, int render_border, RenderShape shape, int out_H, int out_W) {
   DVSG_REQUIRE(winv_cols && coord && F_t && src && T, "dvsg_tps_render_u8: NULL pointer");
   DVSG_REQUIRE(out_f32 || out_u8, "dvsg_tps_render_u8: neither out_f32 nor out_u8 given");
   DVSG_REQUIRE(B >= 1 && B <= 65535, "dvsg_tps_render_u8: n=%d outside [1, 65535]", B);
-  if (int rc = check_image_args("dvsg_tps_render_u8", B, H, W, 3, H, W)) return rc;
-  DVSG_REQUIRE(!out_u8 || (u8_x0 >= 0 && (long)u8_W >= (long)u8_x0 + W),
-               "dvsg_tps_render_u8: columns [%d, %ld) do not fit a row of %d pixels", u8_x0, (long)u8_x0 + W, u8_W);
-  DVSG_REQUIRE(!out_u8 || (long)H * u8_W < (1L << 31), "dvsg_tps_render_u8: uint8 image too large");
+  if (out_H == 0 && out_W == 0) out_H = H, out_W = W;   // an unscaled handle
+  if (int rc = check_image_args("dvsg_tps_render_u8", B, H, W, 3, out_H, out_W)) return rc;
+  DVSG_REQUIRE(!out_u8 || (u8_x0 >= 0 && (long)u8_W >= (long)u8_x0 + out_W),
+               "dvsg_tps_render_u8: columns [%d, %ld) do not fit a row of %d pixels", u8_x0, (long)u8_x0 + out_W, u8_W);
+  DVSG_REQUIRE(!out_u8 || (long)out_H * u8_W < (1L << 31), "dvsg_tps_render_u8: uint8 image too large");
+  if (out_H != H || out_W != W) {   // a scaled view at another size: kernels of their own
+    if (int rc = render_scaled_check("dvsg_tps_render_u8", H, W, out_H, out_W, render_border)) return rc;
+    if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream, shape)) return rc;
+    const int sy = scaled_factor(H, out_H), sx = scaled_factor(W, out_W);
+    const dim3 grid(ceil_div(out_W, kThreads), ceil_div(out_H, scaled_rows_per_group(sy)), B);
+    hipStream_t s = as_stream(stream);
+    ProfScope prof(kClsTpsWarp, s, 0.0,
+                   (double)B * (3.0 * H * W + (double)out_H * out_W * ((out_u8 ? 3.0 : 0.0) + (out_f32 ? 12.0 : 0.0))));
+    auto launch = [&](auto kCubic, auto kBorder) {
+      hipLaunchKernelGGL((tps_render_scaled_kernel<kCubic(), kBorder()>), grid, dim3(kThreads), 0, s, src, coord, T, zoom, H, W,
+                         P, out_H, out_W, sx, sy, lin_step(sx * out_W), lin_step(sy * out_H), out_u8, u8_W, u8_x0,
+                         channel_flip ? 1 : 0, out_f32);
+    };
+    auto with_border = [&](auto kCubic) {
+      if (render_border == DVSG_BORDER_REPLICATE) launch(kCubic, std::integral_constant<int, DVSG_BORDER_REPLICATE>());
+      else if (render_border == DVSG_BORDER_MIRROR) launch(kCubic, std::integral_constant<int, DVSG_BORDER_MIRROR>());
+      else launch(kCubic, std::integral_constant<int, DVSG_BORDER_BLACK>());
+    };
+    if (render_filter == DVSG_RENDER_BICUBIC) with_border(std::true_type());
+    else with_border(std::false_type());
+    return check_launch("tps_render_scaled_kernel");
+  }
   if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream, shape)) return rc;
   dim3 grid(ceil_div(W, kThreads), ceil_div(H, kTpsRows), B);
   const float sx = lin_step(W), sy = lin_step(H);

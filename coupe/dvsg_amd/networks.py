@@ -99,6 +99,44 @@ def check_surface(surface):
     return surface
 
 
+MAX_SCALED_FACTOR = 4   # virtual samples per axis and output sample that the scaled renders serve
+
+
+def scaled_factors(source_size, out_size):
+    """(H, W), (oh, ow) -> (sy, sx), the supersampling factors of a render at a delivery size: max(1, ceil(H / oh)) and
+    max(1, ceil(W / ow)), from the two sizes alone (include/dvsg_amd.h, "Output size").  ValueError above 4: more than 4x
+    minification is not served.  Pure: no device."""
+    (H, W), (oh, ow) = source_size, out_size
+    if min(H, W, oh, ow) < 1:
+        raise ValueError("sizes must be positive, got source %r and out_size %r" % (tuple(source_size), tuple(out_size)))
+    sy, sx = max(1, -(-int(H) // int(oh))), max(1, -(-int(W) // int(ow)))
+    if sy > MAX_SCALED_FACTOR or sx > MAX_SCALED_FACTOR:
+        raise ValueError("out_size=%dx%d (H x W) is a %dx%d minification of a %dx%d source; more than %dx is not served"
+                         % (oh, ow, sy, sx, H, W, MAX_SCALED_FACTOR))
+    return sy, sx
+
+
+def check_out_size(out_size, source_size_render=True, surface=False):
+    """out_size argument -> None or (H, W) as two ints >= 1.  An out_size where no source-size render happens (RGB at the
+    model's size, float frames) is a ValueError that names source_res: only the source-size renders have an output size.
+    surface: the frames are NV12 / P010, whose planes need even sizes of at least 4."""
+    if out_size is None:
+        return None
+    try:
+        ok = len(out_size) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in out_size)
+    except TypeError:
+        ok = False
+    if not ok or min(out_size) < 1:
+        raise ValueError("out_size must be (H, W), two integers >= 1, got %r" % (out_size,))
+    if not source_size_render:
+        raise ValueError("out_size=%r sizes the source-size render only: it needs source_res=True (uint8 frames) or "
+                         "frame_format='nv12'; frames at the model's size are warped at that size" % (tuple(out_size),))
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if surface and (oh % 2 or ow % 2 or oh < 4 or ow < 4):
+        raise ValueError("out_size=%r: NV12 / P010 frames are even-sized and at least 4x4" % ((oh, ow),))
+    return oh, ow
+
+
 class LocNet(object):
     """Owns the device-side network (`dvsg_locnet_t`) and one growable workspace per stream that uses it."""
 
@@ -126,14 +164,26 @@ class LocNet(object):
         self._ws = None
         self.in_channels = _lib.load().dvsg_locnet_in_channels(self.handle)
 
-    def view(self, render_filter="bilinear", border="black", strength=1.0, rigidity=0.0, shape_model="affine", surface="nv12"):
+    def view(self, render_filter="bilinear", border="black", strength=1.0, rigidity=0.0, shape_model="affine", surface="nv12",
+             out_size=None):
         """The handle the source-size renders, the coverage scan and `dvsg_tps_coefficients_f32` take for `render_filter`,
         `border` and the warp shape: this network itself for ("bilinear", "black") unshaped, else a view of it
         (`dvsg_locnet_view_create_border`, or `dvsg_locnet_view_create_shaped` when strength != 1 or rigidity != 0: the same
         network, nothing copied, its own filter, border mode and shape), made once per set of five values and kept until the
         network goes.  An unshaped view is the same whatever its shape_model.  surface="p010": the view of that handle
         whose NV12 renders read and write P010 surfaces (`dvsg_locnet_view_create_surface`: filter, border and shape
-        inherited); no other entry point reads it."""
+        inherited); no other entry point reads it.  out_size=(H, W): the view of THAT handle whose four renders write frames
+        of this size (`dvsg_locnet_view_create_scaled`: everything else inherited); no other entry point reads it."""
+        out_size = check_out_size(out_size)
+        if out_size is not None:
+            key = (render_filter, border, strength, rigidity, shape_model, surface, out_size)
+            v = self._views.get(key)
+            if v is None:
+                inner = self.view(render_filter, border, strength, rigidity, shape_model, surface)
+                v = ctypes.c_void_p()
+                _lib.call("dvsg_locnet_view_create_scaled", inner, out_size[0], out_size[1], ctypes.byref(v))
+                self._views[key] = v
+            return v
         check_surface(surface)
         if surface != "nv12":
             key = (render_filter, border, strength, rigidity, shape_model, surface)

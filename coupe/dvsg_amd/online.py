@@ -135,12 +135,15 @@ def _surface_key(sid, t, name):
     return (H0, W0)
 
 
-def plan_step(frames, stream_of, h, w, frame_format="rgb", source_res=False, crop=False):
+def plan_step(frames, stream_of, h, w, frame_format="rgb", source_res=False, crop=False, out_size=None):
     """What a step of `frames` ({sid: frame}) will do, decided without a device: (rows, runs).  rows: one `Row` per frame in
     BATCH ORDER -- resized uint8 by source size, same-size uint8, float32, float64; surfaces by source size; equal keys in
     feed order -- and runs: the maximal ranges (i, j) of rows of one key, each one ingest and one render launch.
     stream_of(sid) -> (ring, count) of an open stream; h, w: the model's size; crop: whether the step crops.  Every frame is
-    checked here, before the first launch: a bad frame raises and leaves every stream as it was."""
+    checked here, before the first launch: a bad frame raises and leaves every stream as it was.  out_size (H, W): the
+    size every source-size render of the step writes; a frame it minifies more than 4x is a ValueError (`scaled_factors`).
+    The grouping key stays the SOURCE size: frames of one source size share their factors too."""
+    from .networks import scaled_factors
     rows = []
     for sid, fr in frames.items():
         ring, k = stream_of(sid)
@@ -150,6 +153,12 @@ def plan_step(frames, stream_of, h, w, frame_format="rgb", source_res=False, cro
         t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
         key = _surface_key(sid, t, frame_format) if frame_format in SURFACE_FORMATS else \
             _rgb_key(sid, t, h, w, source_res, crop)
+        if out_size is not None:
+            src = key if frame_format in SURFACE_FORMATS else tuple(int(v) for v in t.shape[:2])
+            try:
+                scaled_factors(src, out_size)
+            except ValueError as e:
+                raise ValueError("stream %r: %s" % (sid, e))
         rows.append(Row(key, sid, host, t, ring, k, words))
     rows.sort(key=lambda r: r.key)   # stable
     runs, i = [], 0
@@ -252,6 +261,17 @@ class OnlineStabilizer(object):
     history slots keep uncropped frames, and the pool and F_t are those of a run without crop.  The unstable half of
     side_by_side stays the uncropped source.  `crop_state(sid)` reports a stream's zoom.
 
+    out_size=(H, W): every stream's output has that size whatever its source size -- RGB [H, W, 3] (source_res=True),
+    NV12 [3 H / 2, W], P010 in the form it was given -- rendered straight at that size by the scaled view of the render's
+    handle (`LocNet.view(..., out_size=)`; include/dvsg_amd.h, "Output size"): each output sample is the float32 average of
+    sy x sx samples of the TPS map on the virtual grid (sy H, sx W), sy = max(1, ceil(H0 / H)), sx = max(1, ceil(W0 / W)),
+    so a 4K stream leaves at 1080p without a second resampling pass and without aliasing.  crop composes: a fixed zoom is
+    passed through; "auto" scans the VIRTUAL grids ((sy H, sx W) and, for surfaces, (sy H / 2, sx W / 2)), so the zoom it
+    settles on leaves no invalid virtual sample, and its default crop_margin is one pixel of the virtual (chroma) grid's
+    shorter axis.  The recurrence is untouched: the pool, F_t, the history and scene_cut are those of a run without it.
+    Without a source-size render (source_res=False with RGB), with border="keep", with side_by_side, with odd sizes for a
+    surface format, or for a pushed frame it would minify more than 4x it raises ValueError.
+
     scene_cut: a live stream cuts, and after a cut the window would mix two scenes for `span` steps (and crop="auto" would keep
     the old scene's zoom for good).  None (default) leaves the caller to close() and open(); a step launches what it
     launches without the option.  A threshold in (0, 1] makes every stream notice its own cuts on the device: per step,
@@ -271,9 +291,14 @@ class OnlineStabilizer(object):
     def __init__(self, model, max_streams=1, skip_length=SKIP_LENGTH, channel_order="rgb", side_by_side=False,
                  as_uint8=False, source_res=False, frame_format="rgb", yuv_matrix="bt709", crop=None, crop_margin=None,
                  crop_min=0.5, crop_start=1.0, crop_recover=0.0, scene_cut=None, scene_min_len=1, render_filter="bilinear",
-                 border="black", strength=1.0, rigidity=0.0, shape_model="affine"):
-        from .networks import check_border, check_render_filter, check_shape
+                 border="black", strength=1.0, rigidity=0.0, shape_model="affine", out_size=None):
+        from .networks import check_border, check_out_size, check_render_filter, check_shape
         surface = frame_format in SURFACE_FORMATS
+        out_size = check_out_size(out_size, bool(source_res) or surface, surface)
+        if out_size is not None and border == "keep":
+            raise ValueError("out_size has no border='keep': the surface a stream keeps has no counterpart at another size")
+        if out_size is not None and side_by_side:
+            raise ValueError("out_size has no side_by_side layout: the source half keeps the source's size")
         check_render_filter(render_filter, bool(source_res) or surface)
         check_border(border, bool(source_res) or surface)
         shape = check_shape(strength, rigidity, shape_model, bool(source_res) or surface)
@@ -319,7 +344,7 @@ class OnlineStabilizer(object):
         self.flip = 1 if channel_order == "bgr" else 0
         self.side_by_side, self.as_uint8, self.source_res = bool(side_by_side), bool(as_uint8), bool(source_res)
         self.frame_format, self.yuv_matrix = frame_format, YUV_MATRICES[yuv_matrix]
-        self.render_filter, self.border = render_filter, border
+        self.render_filter, self.border, self.out_size = render_filter, border, out_size
         self.strength, self.rigidity, self.shape_model = shape
         self._keep = {}           # border="keep": ring -> the stream's persistent output surface, at its source size
         self._keep_fresh = set()  # rings whose next frame is a step 0: the surface restarts from that frame's source bytes
@@ -421,7 +446,7 @@ class OnlineStabilizer(object):
         `dvsg_tps_coefficients_f32`): the view the render uses without the surface, so that scan, crop and render see one
         warp; the network itself when nothing is shaped (the scan does not read a filter or a border)."""
         if not scan:
-            return self.model.locnet.view(surface=self.frame_format, **self._render_options)
+            return self.model.locnet.view(surface=self.frame_format, out_size=self.out_size, **self._render_options)
         if self.strength == 1.0 and self.rigidity == 0.0:
             return self.model.locnet.handle
         return self.model.locnet.view(**self._render_options)
@@ -453,7 +478,8 @@ class OnlineStabilizer(object):
     def _step_zoom(self, rows, i, j, grids):
         """The zoom of batch rows [i, j) -> float32 [j - i] on the device.  crop=z: the constant.  "auto": one coverage
         scan of the rows' F_t per grid of `grids` (one (H, W), or the luma and the chroma plane's), each with the source
-        and the output of that size, then the ratchet on the rows' streams; T rows [i, j) are written."""
+        and the output of that size -- or, an entry (src_h, src_w, gh, gw), a source of one size scanned on the grid of
+        another (out_size: the virtual grid) -- then the ratchet on the rows' streams; T rows [i, j) are written."""
         n = j - i
         if not self._crop_auto:
             return self._crop_zoom[:n]
@@ -462,17 +488,18 @@ class OnlineStabilizer(object):
         if np.unique(rings).size != n:
             raise ValueError("two frames of one step share a crop state slot")
         keys = torch.empty((len(grids), 2, n), dtype=torch.int32, device=dev)   # per grid: n_border | key_min
-        for g, (gh, gw) in enumerate(grids):
+        grids = [g if len(g) == 4 else (g[0], g[1], g[0], g[1]) for g in grids]
+        for g, (sh, sw, gh, gw) in enumerate(grids):
             need = ctypes.c_size_t()
             _lib.call("dvsg_tps_coverage_workspace_bytes", n, gh, gw, ctypes.byref(need))
             ws = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=dev)
-            _lib.call("dvsg_tps_coverage_net_f32", self._view(scan=True), ptr(self._F[i:j]), None, n, gh, gw, gh, gw,
+            _lib.call("dvsg_tps_coverage_net_f32", self._view(scan=True), ptr(self._F[i:j]), None, n, sh, sw, gh, gw,
                       ptr(self._T[i:j]), ptr(keys[g, 0]), ptr(keys[g, 1]), ptr(ws), ws.numel() * 8, stream())
         slots = torch.from_numpy(rings).pin_memory().to(dev, non_blocking=True)
         zoom = torch.empty((n,), dtype=torch.float32, device=dev)
         free = torch.empty((n,), dtype=torch.float64, device=dev)
-        D = [(gh - 1) * (gw - 1) for gh, gw in grids]
-        margin = 2.0 / (min(grids[-1]) - 1) if self.crop_margin is None else self.crop_margin
+        D = [(gh - 1) * (gw - 1) for _, _, gh, gw in grids]
+        margin = 2.0 / (min(grids[-1][2:]) - 1) if self.crop_margin is None else self.crop_margin
         _lib.call("dvsg_crop_ratchet_f32", ptr(keys[0, 1]), D[0], ptr(keys[1, 1]) if len(grids) > 1 else None,
                   D[1] if len(grids) > 1 else 0, ptr(slots), n, ptr(self._crop_zoom), self.max_streams, margin, self.crop_min,
                   self.crop_recover, ptr(zoom), ptr(free), stream())
@@ -551,7 +578,8 @@ class OnlineStabilizer(object):
         the check (`_rgb_key`, `_surface_key` under `plan_step`), the ingest of a run and its render."""
         if not frames:
             return {}
-        rows, runs = plan_step(frames, self._stream, self.h, self.w, self.frame_format, self.source_res, self.crop is not None)
+        rows, runs = plan_step(frames, self._stream, self.h, self.w, self.frame_format, self.source_res, self.crop is not None,
+                               self.out_size)
         B = len(rows)
         if self.frame_format in SURFACE_FORMATS:
             ingest, render = self._ingest_surface, self._render_surface
@@ -668,11 +696,24 @@ class OnlineStabilizer(object):
                 _lib.call("dvsg_frames_u8_to_f32", ptr(src), n * H0 * W0, self.flip, ptr(first), stream())
             out, done = self._keep_surfaces(rows, i, j, first)
         else:
-            out = torch.empty((n, H0, W0, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
+            oh, ow = (H0, W0) if self.out_size is None else self.out_size
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8 if self.as_uint8 else torch.float32, device=src.device)
         side = torch.empty((n, H0, 2 * W0, 3), dtype=torch.uint8, device=src.device) if self.side_by_side else None
-        zoom = self._step_zoom(rows, i, j, [(H0, W0)]) if self.crop is not None else None
-        render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, **self._render_options)
+        zoom = self._step_zoom(rows, i, j, self._scan_grids(H0, W0, False)) if self.crop is not None else None
+        render_source_into(self.model, src, self._F[i:j], self._T[i:j], self.flip, out, side, zoom, out_size=self.out_size,
+                           **self._render_options)
         return (out if done is None else done()), side
+
+    def _scan_grids(self, H0, W0, surface):
+        """The grids crop="auto" scans for a source of (H0, W0): the output's own -- with out_size the VIRTUAL grid
+        (sy H, sx W) against the source's size, so that no virtual sample of the render is left invalid -- and for a
+        surface the chroma plane's too."""
+        if self.out_size is None:
+            return [(H0, W0), (H0 // 2, W0 // 2)] if surface else [(H0, W0)]
+        from .networks import scaled_factors
+        (oh, ow), (sy, sx) = self.out_size, scaled_factors((H0, W0), self.out_size)
+        luma = (H0, W0, sy * oh, sx * ow)
+        return [luma, (H0 // 2, W0 // 2, sy * (oh // 2), sx * (ow // 2))] if surface else [luma]
 
     def _ingest_surface(self, rows, i, j, in_slots, side):
         """Ingest of a run of NV12 or P010 surfaces of one size: one `dvsg_frames_ingest_nv12` launch; returns the frames on
@@ -694,16 +735,21 @@ class OnlineStabilizer(object):
         """Egress of a run of surfaces: one `dvsg_tps_render_nv12` (or `_zoom_nv12`) launch that warps both planes of `src`."""
         (H0, W0), net = rows[i].key, self._view()
         pitch = int(src.shape[2])   # bps W0: rows are packed; the UV plane follows the Y plane
-        out, done = self._keep_surfaces(rows, i, j, src) if self.border == "keep" else (torch.empty_like(src), None)
+        oh, ow = (H0, W0) if self.out_size is None else self.out_size
+        if self.border == "keep":
+            out, done = self._keep_surfaces(rows, i, j, src)
+        else:
+            out, done = torch.empty((j - i, 3 * oh // 2, pitch // W0 * ow), dtype=src.dtype, device=src.device), None
+        opitch = int(out.shape[2])
         if self.crop is None:
             _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * pitch, pitch,
-                      3 * H0 // 2 * pitch, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + H0 * pitch, pitch,
-                      3 * H0 // 2 * pitch, stream())
+                      3 * H0 // 2 * pitch, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + oh * opitch, opitch,
+                      3 * oh // 2 * opitch, stream())
         else:   # chroma leaves the source first: both planes are scanned, each on its own grid
-            zoom = self._step_zoom(rows, i, j, [(H0, W0), (H0 // 2, W0 // 2)])
+            zoom = self._step_zoom(rows, i, j, self._scan_grids(H0, W0, True))
             _lib.call("dvsg_tps_render_zoom_nv12", net, ptr(self._F[i:j]), ptr(src),
                       ptr(src) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]),
-                      ptr(out), ptr(out) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, stream())
+                      ptr(out), ptr(out) + oh * opitch, opitch, 3 * oh // 2 * opitch, stream())
         return (out if done is None else done()), None
 
 

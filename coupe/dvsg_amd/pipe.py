@@ -126,7 +126,7 @@ _PLANAR = {"i420": (y4m.i420_to_nv12, y4m.nv12_to_i420), "i420p10": (y4m.i420p10
 class _Lane(object):
     """One source, its sink, its slots and its two threads."""
 
-    def __init__(self, index, source, sink, depth, staging, shared):
+    def __init__(self, index, source, sink, depth, staging, shared, out_shape=None):
         self.index, self.source, self.sink, self.depth = index, source, sink, depth
         self.staging, self.shared = staging, shared
         self.frames = 0          # frames written
@@ -139,6 +139,7 @@ class _Lane(object):
         self.t0 = time.perf_counter()
         self.seconds = None
         shape = tuple(source.frame_shape)
+        out_shape = shape if out_shape is None else tuple(out_shape)   # out_size: the stabilised frames have another size
         self.free = queue.Queue(maxsize=depth)          # slots the reader may fill
         self.filled = queue.Queue(maxsize=depth + 1)    # slots with a frame, then _END or a _Failure
         self.towrite = queue.Queue(maxsize=depth + 1)   # slots with a stabilised frame on its way, then _END
@@ -146,8 +147,8 @@ class _Lane(object):
             s = _Slot()
             s.host_in, s.dev_in = staging.host(shape), staging.dev(shape)
             s.nv12_in = staging.dev(shape) if source.layout in _PLANAR else None
-            s.dev_out = staging.dev(shape) if sink.layout in _PLANAR else None
-            s.host_out = staging.host(shape)
+            s.dev_out = staging.dev(out_shape) if sink.layout in _PLANAR else None
+            s.host_out = staging.host(out_shape)
             s.e_up, s.e_step, s.e_down = staging.event(), staging.event(), staging.event()
             self.free.put(s)
         staging.fence()
@@ -286,8 +287,9 @@ def _snapshot(on, sid):
     return state
 
 
-def _check_ends(sources, sinks):
-    """Everything that can be said of the ends before a frame is read; returns the run's bit depth (8 without sources)."""
+def _check_ends(sources, sinks, out_size=None):
+    """Everything that can be said of the ends before a frame is read; returns the run's bit depth (8 without sources).
+    out_size (H, W): what every sink that states a size must state instead of its source's."""
     if len(sources) != len(sinks):
         raise ValueError("stabilize_pipes needs one sink per source, got %d sources and %d sinks" % (len(sources), len(sinks)))
     bits = None
@@ -304,8 +306,11 @@ def _check_ends(sources, sinks):
         if tuple(src.frame_shape) != (3 * int(src.height) // 2, (2 if bits == 10 else 1) * int(src.width)):
             raise ValueError("source %d: frame_shape %s is not [3 H / 2, %sW] of %d x %d"
                              % (i, tuple(src.frame_shape), "2 " if bits == 10 else "", src.width, src.height))
-        size = (getattr(snk, "width", src.width), getattr(snk, "height", src.height))
-        if size != (src.width, src.height):
+        want = (src.width, src.height) if out_size is None else (out_size[1], out_size[0])
+        size = (getattr(snk, "width", want[0]), getattr(snk, "height", want[1]))
+        if size != want and out_size is not None:
+            raise ValueError("sink %d is %d x %d but out_size is %d x %d" % ((i,) + size + want))
+        if size != want:
             raise ValueError("sink %d is %d x %d but its source is %d x %d: the output has the size of the input"
                              % ((i,) + size + (src.width, src.height)))
     return bits or 8
@@ -327,7 +332,8 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
         `OnlineStabilizer(frame_format="p010")`; an 8-bit run is what it was.
     batch: streams per step (default: all sources).  depth: frames in flight per source, >= 1.
     online_kw: OnlineStabilizer's crop, crop_*, scene_cut, scene_min_len, skip_length, render_filter, border, strength, rigidity,
-        shape_model and yuv_matrix, passed through.
+        shape_model, out_size and yuv_matrix, passed through.  out_size=(H, W): every sink receives frames of that size
+        ([3 H / 2, W], 10-bit [3 H / 2, 2 W]) whatever its source's; a sink that states a size must state that one.
         yuv_matrix defaults to "auto" here: `y4m.default_yuv_matrix` of the first source's height, resolved per call.
 
     One `OnlineStabilizer(model, max_streams=batch, frame_format="nv12")` serves all sources on `stabilize_clips`' own
@@ -346,7 +352,11 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
     Returns a list with, per source, dict(frames written, high_water: the most frames it ever had between readinto and
     write (<= depth), seconds from its opening to its last write, zoom with crop and cuts with scene_cut, else None)."""
     sources, sinks = list(sources), list(sinks)
-    bits = _check_ends(sources, sinks)
+    out_size = online_kw.get("out_size")
+    if out_size is not None:
+        from .networks import check_out_size
+        out_size = check_out_size(out_size, True, True)
+    bits = _check_ends(sources, sinks, out_size)
     K = len(sources)
     if isinstance(depth, bool) or int(depth) != depth or depth < 1:
         raise ValueError("depth must be an integer >= 1, got %r" % (depth,))
@@ -388,7 +398,8 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
                     active[sid] = (lane, slot)
             while waiting and len(active) < batch:
                 i = waiting.pop(0)
-                lane = _Lane(i, sources[i], sinks[i], depth, staging, shared)
+                lane = _Lane(i, sources[i], sinks[i], depth, staging, shared,
+                             None if out_size is None else (3 * out_size[0] // 2, (2 if bits == 10 else 1) * out_size[1]))
                 lanes.append(lane)
                 sid = on.open()
                 slot = lane.next_slot()
@@ -426,6 +437,14 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
                           zoom=float(state["zoom"].item()) if "zoom" in state else None,
                           cuts=int(state["cuts"].item()) if "cuts" in state else None))
     return stats
+
+
+def output_aspect(aspect, source_size, out_size):
+    """The `A` tag of a Y4M output of (H, W) = out_size made from a source of source_size: the source's pixel aspect where
+    the two sizes have the same shape (out_W src_H == out_H src_W: square pixels stay square), else unknown, (0, 0) ->
+    "A0:0" -- a scaled picture of another shape has pixels of another shape, which nobody stated."""
+    (sh, sw), (oh, ow) = source_size, out_size
+    return aspect if ow * sh == oh * sw else (0, 0)
 
 
 # ---- python -m coupe.dvsg_amd.pipe -----------------------------------------------------------------------------------
@@ -476,6 +495,9 @@ def _parser():
                     "1 cannot wobble)")
     ap.add_argument("--shape-model", default=None, choices=["affine", "similarity", "translation"],
                     help="the rigid motion --rigidity pulls towards (default: affine)")
+    ap.add_argument("--out-size", default=None, metavar="WxH",
+                    help="render every output at this size (even, at most 4x smaller than its input per axis) with an area "
+                         "filter, instead of at the input's size")
     ap.add_argument("--scene-cut", type=float, default=None, metavar="THR")
     ap.add_argument("--scene-min-len", type=int, default=None, metavar="N")
     ap.add_argument("--yuv-matrix", default="auto", choices=["auto", "bt709", "bt601"])
@@ -521,6 +543,15 @@ def _arguments(argv):
         args.crop = args.crop if args.crop in (None, "auto") else float(args.crop)
     except ValueError:
         raise _UsageError("--crop takes 'auto' or a zoom in (0, 1], got %r" % args.crop) from None
+    if args.out_size is not None:
+        from .networks import check_out_size
+        ow, oh = _size(args.out_size, "--out-size")
+        if args.border == "keep":
+            raise _UsageError("--border keep has no --out-size: the kept surface has no counterpart at another size")
+        try:
+            args.out_size = check_out_size((oh, ow), True, True)
+        except ValueError as e:
+            raise _UsageError("--out-size %s: %s" % (args.out_size, e)) from None
     if args.depth < 1 or (args.batch is not None and args.batch < 1):
         raise _UsageError("--depth and --batch must be at least 1")
     return args
@@ -557,7 +588,7 @@ def _run(args, note):
         model.precision = args.precision
         kw = dict(skip_length=skip, yuv_matrix=args.yuv_matrix)
         for key in ("crop", "crop_min", "crop_margin", "crop_recover", "scene_cut", "scene_min_len", "render_filter", "border",
-                    "strength", "rigidity", "shape_model"):
+                    "strength", "rigidity", "shape_model", "out_size"):
             if getattr(args, key) is not None:
                 kw[key] = getattr(args, key)
         sinks = []
@@ -568,12 +599,14 @@ def _run(args, note):
             else:
                 f = open(path, "wb")
             files.append(f)
+            out_h, out_w = args.out_size or (src.height, src.width)
             if args.output_format == "nv12":
-                sinks.append(y4m.RawNV12Writer(f, src.width, src.height))
+                sinks.append(y4m.RawNV12Writer(f, out_w, out_h))
             elif args.output_format == "p010":
-                sinks.append(y4m.RawP010Writer(f, src.width, src.height))
+                sinks.append(y4m.RawP010Writer(f, out_w, out_h))
             else:   # a Y4M header repeats the source's C tag (C420p10 for a raw P010 source) and its X tags
-                sinks.append(y4m.Y4MWriter(f, src.width, src.height, src.fps or args.fps, aspect=src.aspect,
+                sinks.append(y4m.Y4MWriter(f, out_w, out_h, src.fps or args.fps,
+                                           aspect=output_aspect(src.aspect, (src.height, src.width), (out_h, out_w)),
                                            colorspace="420p10" if src.layout == "p010" else src.colorspace, tags=src.tags,
                                            interlace=src.interlace))
         stats = stabilize_pipes(model, sources, sinks, batch=args.batch, depth=args.depth, **kw)

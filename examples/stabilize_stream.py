@@ -99,6 +99,9 @@ def main():
     ap.add_argument("--rigidity", type=float, default=0.0,
                     help="pull of the rendered warp towards its --shape-model fit, in [0, 1]: 1 renders a warp that cannot wobble")
     ap.add_argument("--shape-model", default="affine", choices=["affine", "similarity", "translation"])
+    ap.add_argument("--out-size", default=None, metavar="WxH",
+                    help="render every stream at this delivery size with an area filter (at most 4x smaller than the source "
+                    "per axis); with --format rgb it turns source_res on and drops the side-by-side frame")
     ap.add_argument("--skip-length", default=None, metavar="A,B,...",
                     help="the window's frame offsets, oldest first (default: the reference's 0,16,24,28,30,31,32)")
     args = ap.parse_args()
@@ -113,15 +116,22 @@ def main():
     nv12 = args.format in ("nv12", "p010")   # a decoder's surfaces: two planes, rendered at source size
     shape = dict(strength=args.strength, rigidity=args.rigidity, shape_model=args.shape_model)
     shaped = args.strength != 1.0 or args.rigidity != 0.0
+    out_size = None
+    if args.out_size is not None:
+        ow, oh = (int(v) for v in args.out_size.lower().split("x"))
+        out_size = (oh, ow)
     if nv12:
         stab = OnlineStabilizer(net, max_streams=args.streams, frame_format=args.format, yuv_matrix="bt709", crop=crop,
-                                render_filter=args.render_filter, border=args.border, **shape, **scene, **window)
+                                render_filter=args.render_filter, border=args.border, out_size=out_size, **shape, **scene,
+                                **window)
         make = synthetic_nv12_source if args.format == "nv12" else synthetic_p010_source
     else:
-        stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr", side_by_side=args.border != "keep",
-                                as_uint8=True, crop=crop,
-                                source_res=args.render_filter != "bilinear" or args.border != "black" or shaped,
-                                render_filter=args.render_filter, border=args.border, **shape, **scene, **window)
+        stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr",
+                                side_by_side=args.border != "keep" and out_size is None, as_uint8=True, crop=crop,
+                                source_res=args.render_filter != "bilinear" or args.border != "black" or shaped
+                                or out_size is not None,
+                                render_filter=args.render_filter, border=args.border, out_size=out_size, **shape, **scene,
+                                **window)
         make = synthetic_source
     H0, W0 = args.height * 3 // 2, args.width * 3 // 2
     if nv12:

@@ -326,6 +326,46 @@ int dvsg_locnet_render_shape(const dvsg_locnet_t *net, int *shape_model, float *
 int dvsg_locnet_view_create_surface(const dvsg_locnet_t *net, int surface_format, dvsg_locnet_t **view);
 int dvsg_locnet_render_surface(const dvsg_locnet_t *net);
 
+/* Output size: rendering at a delivery size.  The size of the frames that the four source-size renders WRITE is, like the
+ * filter, the border, the shape and the surface format, a property of the handle: no entry point is added for it.  Both
+ * functions are host-side: no stream, no device work, everything decided before anything is allocated.
+ *   dvsg_locnet_view_create_scaled  a view of `net`'s parent that carries `net`'s OWN filter, border, shape and surface format
+ *          (INHERITED, as in dvsg_locnet_view_create_surface, which now inherits the size as well) and an output size
+ *          (out_H, out_W).  out_H == 0 && out_W == 0: "the source's size", an unscaled view.  Otherwise both are >= 1; anything
+ *          else, or a NULL pointer, is DVSG_ERR_INVALID_ARG ("out_H=<n>").  The view rules are the ones above.
+ *   dvsg_locnet_render_size  the handle's size; always DVSG_OK.  (0, 0) for NULL, for every handle of dvsg_locnet_create and
+ *          for every view of dvsg_locnet_view_create, _border and _shaped.  Either pointer may be NULL.
+ * ONLY dvsg_tps_render_u8, dvsg_tps_render_zoom_u8, dvsg_tps_render_nv12 and dvsg_tps_render_zoom_nv12 read the size.  Every
+ * other entry point -- dvsg_tps_coverage_net_f32, which takes its grid as arguments, dvsg_tps_coefficients_f32 and all the
+ * rest -- behaves on a scaled view exactly as on the same view without the property, bit for bit.
+ *
+ * Given a scaled view, a render reads its source (src_H, src_W) = (H, W) as before and writes frames of (oh, ow) = (out_H, out_W):
+ *   Factors.  sy = max(1, ceil(H / oh)), sx = max(1, ceil(W / ow)), in integers, from the two sizes alone (never from zoom).
+ *   Planes.  RGB and NV12 / P010 luma (H, W) -> (oh, ow); chroma (H / 2, W / 2) -> (oh / 2, ow / 2) with the same sy, sx.
+ *          A plane (ph, pw) -> (po, qo) has the VIRTUAL grid (sy po, sx qo).
+ *   Map.   x_s, y_s of every virtual sample are the bits of the grid-only form of dvsg_tps_warp_zoom_f32 (U == NULL,
+ *          out == NULL, coord = V_src, the T this call writes, the call's zoom or none, out_h x out_w = the virtual grid).
+ *   Value. v[p][q] of a virtual sample is what the view's filter and border give at that (x_s, y_s) on the source plane: the
+ *          paragraphs above, unchanged, the float32 value before any byte rule.  An invalid virtual sample under
+ *          DVSG_BORDER_BLACK contributes what sampler A or the cubic gives there (0), so the black border fades over one
+ *          output pixel.
+ *   Average.  Output sample (i, j) averages virtual rows sy i .. sy i + sy - 1 and columns sx j .. sx j + sx - 1, row-major,
+ *          every float32 operation rounded on its own: acc = v[0][0]; acc = acc + v[p][q] for the rest;
+ *          out = acc / (float)(sx sy).
+ *   Output rule.  The plane's existing rule applied to `out`: RGB / luma bytes truncate under bilinear and round to nearest
+ *          under bicubic, chroma rounds at 128.5, P010 words round, out_f32 is stored as it is.  T is written exactly as
+ *          dvsg_tps_render_u8 writes it.
+ *   Buffers.  out_f32 [n, oh, ow, 3]; out_u8 [n, oh, u8_W, 3] in columns [u8_x0, u8_x0 + ow); out_y / out_uv planes of an
+ *          (oh, ow) frame with out_pitch >= ow (P010: 2 ow) and out_frame_stride >= oh out_pitch.  Bytes beyond that are never
+ *          written.  No load touches a byte outside the used bytes of the source row it reads.
+ *   Checks, before any device work; DVSG_ERR_INVALID_ARG, the message names the argument.  sx > 4 or sy > 4 (more than 4x
+ *          minification is not served); DVSG_BORDER_KEEP on a view whose size differs from the source's; for the NV12 / P010
+ *          renders, out_H or out_W odd or below 4.
+ *   Identity.  A scaled view whose size equals the call's (H, W), or is (0, 0), launches the kernels of the same view without
+ *          the property, and so produces their bits; the scaled kernels are kernels of their own. */
+int dvsg_locnet_view_create_scaled(const dvsg_locnet_t *net, int out_H, int out_W, dvsg_locnet_t **view);
+int dvsg_locnet_render_size(const dvsg_locnet_t *net, int *out_H, int *out_W);
+
 /* patches [B,H,W,c_in] in [0,1] -> F_t [B,25,2].  float32 storage, exact-f32 MFMA
  * (v_mfma_f32_32x32x2_f32) accumulation.  c_in != 21: conv1 is the same arithmetic in the root-conv kernel. */
 int dvsg_locnet_forward_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W,
