@@ -43,6 +43,8 @@ SIGNATURES = {
     "dvsg_locnet_render_surface": [_vp],    # returns the surface format (DVSG_SURFACE_*), not a status
     "dvsg_locnet_view_create_scaled": [_vp, _i, _i, ctypes.POINTER(_vp)],
     "dvsg_locnet_render_size": [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    "dvsg_locnet_view_create_chroma": [_vp, _i, ctypes.POINTER(_vp)],
+    "dvsg_locnet_render_chroma": [_vp],     # returns the chroma format (DVSG_CHROMA_*), not a status
     "dvsg_locnet_workspace_bytes": [_vp, _i, _i, _i, ctypes.POINTER(ctypes.c_size_t)],
     "dvsg_locnet_forward_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp],
     "dvsg_locnet_forward_tap_f32": [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t,

@@ -82,7 +82,8 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
                          const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR,
                          int render_border = DVSG_BORDER_BLACK, RenderShape shape = RenderShape(),
                          int surface_format = DVSG_SURFACE_NV12, int out_H = 0, int out_W = 0 /* a scaled view's size */,
-                         const char *fn = "dvsg_tps_render_nv12");
+                         const char *fn = "dvsg_tps_render_nv12",
+                         int chroma_format = DVSG_CHROMA_420 /* the view's: the chroma plane is (H, W / 2) for DVSG_CHROMA_422 */);
 // nv12.hip: what a scaled view (dvsg_locnet_view_create_scaled) asks of a render of (H, W) frames at another size
 // (out_H, out_W): at most 4 virtual samples per axis, no DVSG_BORDER_KEEP.  No HIP call.
 int render_scaled_check(const char *fn, int H, int W, int out_H, int out_W, int render_border);

@@ -106,6 +106,7 @@ struct dvsg_locnet {
   int render_border = DVSG_BORDER_BLACK;
   RenderShape render_shape;
   int surface_format = DVSG_SURFACE_NV12;   // read by dvsg_tps_render_nv12 / _zoom_nv12 alone
+  int chroma_format = DVSG_CHROMA_420;      // likewise: the rows of the chroma plane ("Chroma sampling")
   int out_h = 0, out_w = 0;                 // read by the four source-size renders alone; (0, 0): the source's size
   mutable std::atomic<int> n_views{0};
 };
@@ -1049,11 +1050,12 @@ int dvsg_locnet_view_create_surface(const dvsg_locnet_t *net, int surface_format
                "%s: surface_format=%d is neither DVSG_SURFACE_NV12 (0) nor DVSG_SURFACE_P010 (1)", fn, surface_format);
   if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
   (*view)->surface_format = surface_format;
+  (*view)->chroma_format = net->chroma_format;
   set_view_size(*view, net->out_h, net->out_w);
   return DVSG_OK;
 }
 
-// a view of net's parent with net's own filter, border, shape and surface format and the given output size ("Output size")
+// a view of net's parent with net's own filter, border, shape, surface and chroma format and the given output size ("Output size")
 int dvsg_locnet_view_create_scaled(const dvsg_locnet_t *net, int out_H, int out_W, dvsg_locnet_t **view) {
   const char *fn = "dvsg_locnet_view_create_scaled";
   DVSG_REQUIRE(net, "%s: NULL net", fn);
@@ -1065,7 +1067,24 @@ int dvsg_locnet_view_create_scaled(const dvsg_locnet_t *net, int out_H, int out_
   }
   if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
   (*view)->surface_format = net->surface_format;
+  (*view)->chroma_format = net->chroma_format;
   set_view_size(*view, out_H, out_W);
+  return DVSG_OK;
+}
+
+// a view of net's parent with net's own filter, border, shape, surface format and output size and the given chroma format
+// ("Chroma sampling"); the value is checked before the handle is read
+int dvsg_locnet_view_create_chroma(const dvsg_locnet_t *net, int chroma_format, dvsg_locnet_t **view) {
+  const char *fn = "dvsg_locnet_view_create_chroma";
+  DVSG_REQUIRE(net, "%s: NULL net", fn);
+  DVSG_REQUIRE(view, "%s: NULL view", fn);
+  *view = nullptr;
+  DVSG_REQUIRE(chroma_format == DVSG_CHROMA_420 || chroma_format == DVSG_CHROMA_422,
+               "%s: chroma_format=%d is neither DVSG_CHROMA_420 (0) nor DVSG_CHROMA_422 (1)", fn, chroma_format);
+  if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
+  (*view)->surface_format = net->surface_format;
+  (*view)->chroma_format = chroma_format;
+  set_view_size(*view, net->out_h, net->out_w);
   return DVSG_OK;
 }
 
@@ -1076,6 +1095,8 @@ int dvsg_locnet_render_size(const dvsg_locnet_t *net, int *out_H, int *out_W) {
 }
 
 int dvsg_locnet_render_surface(const dvsg_locnet_t *net) { return net ? net->surface_format : DVSG_SURFACE_NV12; }
+
+int dvsg_locnet_render_chroma(const dvsg_locnet_t *net) { return net ? net->chroma_format : DVSG_CHROMA_420; }
 
 int dvsg_locnet_render_shape(const dvsg_locnet_t *net, int *shape_model, float *strength, float *rigidity) {
   const RenderShape shape = net ? net->render_shape : RenderShape();
@@ -1475,7 +1496,7 @@ int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8
       return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
                               out_pitch, out_frame_stride, stream, nullptr, net->render_filter, net->render_border,
-                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_nv12");
+                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_nv12", net->chroma_format);
 }
 
 // dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
@@ -1494,7 +1515,7 @@ int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const 
       return rc;
   return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
                               out_pitch, out_frame_stride, stream, zoom, net->render_filter, net->render_border,
-                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_zoom_nv12");
+                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_zoom_nv12", net->chroma_format);
 }
 
 // T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)

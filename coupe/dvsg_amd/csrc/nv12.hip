@@ -16,6 +16,8 @@
 //                           nv12_render_kernel keeps its instructions.
 //   nv12_render_cubic_kernel  both of the above through a bicubic view (dvsg_locnet_view_create): the same tiles and map, the
 //                           4 x 4-tap filter of warp_device.h behind it, bytes rounded to nearest.
+//   Every render kernel takes the chroma plane's rows as an argument, ch (the scaled one: och for the output too), worked out
+//   on the host with the tile counts and lin_step: H / 2 for a 4:2:0 handle, H for a DVSG_CHROMA_422 view ("Chroma sampling").
 //   nv12_render_scaled_kernel  the render through a scaled view (dvsg_locnet_view_create_scaled): output planes of another size,
 //                           each sample the float32 average of sy x sx samples of that map and filter (scaled_device.h), for
 //                           NV12 and P010, both filters, the black, replicate and mirror borders.
@@ -290,7 +292,7 @@ __device__ __forceinline__ void render_plane(const uint8_t *__restrict__ src, si
 __global__ __launch_bounds__(kThreads) void nv12_render_kernel(Nv12 s, const float *__restrict__ coord,
                                                                const float *__restrict__ T, int H, int W, int P,
                                                                float sx_l, float sy_l, float sx_c, float sy_c, int gx_l,
-                                                               int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                               int n_l, int gx_c, int ch, uint8_t *__restrict__ out_y,
                                                                uint8_t *__restrict__ out_uv, size_t out_pitch,
                                                                size_t out_frame_stride) {
   __shared__ float4 sp[64];
@@ -302,7 +304,7 @@ __global__ __launch_bounds__(kThreads) void nv12_render_kernel(Nv12 s, const flo
   if (chroma) id -= n_l;
   const int gx = chroma ? gx_c : gx_l;
   const int i0 = (id / gx) * kTpsRows;
-  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
+  const int ph = chroma ? ch : H, pw = chroma ? W / 2 : W;
   const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
   tps_stage<true>(coord, 0, T, b, P, t, i0, step_y, sp, sdy, sa);
   __syncthreads();
@@ -324,7 +326,7 @@ __global__ __launch_bounds__(kThreads) void nv12_render_zoom_kernel(Nv12 s, cons
                                                                     const float *__restrict__ T,
                                                                     const float *__restrict__ zoom, int H, int W, int P,
                                                                     float sx_l, float sy_l, float sx_c, float sy_c,
-                                                                    int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                                    int gx_l, int n_l, int gx_c, int ch, uint8_t *__restrict__ out_y,
                                                                     uint8_t *__restrict__ out_uv, size_t out_pitch,
                                                                     size_t out_frame_stride) {
   __shared__ float4 sp[64];
@@ -336,7 +338,7 @@ __global__ __launch_bounds__(kThreads) void nv12_render_zoom_kernel(Nv12 s, cons
   if (chroma) id -= n_l;
   const int gx = chroma ? gx_c : gx_l;
   const int i0 = (id / gx) * kTpsRows;
-  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
+  const int ph = chroma ? ch : H, pw = chroma ? W / 2 : W;
   const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
   const float z = zoom[b];
   tps_stage<true, true>(coord, 0, T, b, P, t, i0, step_y, sp, sdy, sa, z);
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(kThreads) void nv12_render_zoom_kernel(Nv12 s, cons
 template <typename S, bool kZoom, bool kCubic, int kBorder>
 __device__ __forceinline__ void render_tile(const Nv12 &s, const float *__restrict__ coord, const float *__restrict__ T,
                                             const float *__restrict__ zoom, int H, int W, int P, float sx_l, float sy_l,
-                                            float sx_c, float sy_c, int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                            float sx_c, float sy_c, int gx_l, int n_l, int gx_c, int ch, uint8_t *__restrict__ out_y,
                                             uint8_t *__restrict__ out_uv, size_t out_pitch, size_t out_frame_stride) {
   __shared__ float4 sp[64];
   __shared__ float4 sdy[64];
@@ -369,7 +371,7 @@ __device__ __forceinline__ void render_tile(const Nv12 &s, const float *__restri
   if (chroma) id -= n_l;
   const int gx = chroma ? gx_c : gx_l;
   const int i0 = (id / gx) * kTpsRows;
-  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
+  const int ph = chroma ? ch : H, pw = chroma ? W / 2 : W;
   const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
   float z = 1.0f;
   if constexpr (kZoom) z = zoom[b];
@@ -395,10 +397,10 @@ __global__ __launch_bounds__(kThreads) void nv12_render_cubic_kernel(Nv12 s, con
                                                                      const float *__restrict__ T,
                                                                      const float *__restrict__ zoom, int H, int W, int P,
                                                                      float sx_l, float sy_l, float sx_c, float sy_c,
-                                                                     int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                                     int gx_l, int n_l, int gx_c, int ch, uint8_t *__restrict__ out_y,
                                                                      uint8_t *__restrict__ out_uv, size_t out_pitch,
                                                                      size_t out_frame_stride) {
-  render_tile<uint8_t, kZoom, true, DVSG_BORDER_BLACK>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, out_y,
+  render_tile<uint8_t, kZoom, true, DVSG_BORDER_BLACK>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, ch, out_y,
                                                        out_uv, out_pitch, out_frame_stride);
 }
 
@@ -410,11 +412,11 @@ __global__ __launch_bounds__(kThreads) void nv12_render_border_kernel(Nv12 s, co
                                                                       const float *__restrict__ T,
                                                                       const float *__restrict__ zoom, int H, int W, int P,
                                                                       float sx_l, float sy_l, float sx_c, float sy_c,
-                                                                      int gx_l, int n_l, int gx_c, uint8_t *__restrict__ out_y,
+                                                                      int gx_l, int n_l, int gx_c, int ch, uint8_t *__restrict__ out_y,
                                                                       uint8_t *__restrict__ out_uv, size_t out_pitch,
                                                                       size_t out_frame_stride) {
   static_assert(kBorder != DVSG_BORDER_BLACK, "DVSG_BORDER_BLACK is the kernels without a border parameter");
-  render_tile<uint8_t, kZoom, kCubic, kBorder>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, out_y, out_uv,
+  render_tile<uint8_t, kZoom, kCubic, kBorder>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, ch, out_y, out_uv,
                                                out_pitch, out_frame_stride);
 }
 
@@ -425,10 +427,10 @@ template <bool kZoom, bool kCubic, int kBorder>
 __global__ __launch_bounds__(kThreads) void p010_render_kernel(Nv12 s, const float *__restrict__ coord,
                                                                const float *__restrict__ T, const float *__restrict__ zoom,
                                                                int H, int W, int P, float sx_l, float sy_l, float sx_c,
-                                                               float sy_c, int gx_l, int n_l, int gx_c,
+                                                               float sy_c, int gx_l, int n_l, int gx_c, int ch,
                                                                uint8_t *__restrict__ out_y, uint8_t *__restrict__ out_uv,
                                                                size_t out_pitch, size_t out_frame_stride) {
-  render_tile<uint16_t, kZoom, kCubic, kBorder>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, out_y, out_uv,
+  render_tile<uint16_t, kZoom, kCubic, kBorder>(s, coord, T, zoom, H, W, P, sx_l, sy_l, sx_c, sy_c, gx_l, n_l, gx_c, ch, out_y, out_uv,
                                                 out_pitch, out_frame_stride);
 }
 
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(kThreads) void nv12_render_scaled_kernel(Nv12 s, co
                                                                       const float *__restrict__ T,
                                                                       const float *__restrict__ zoom, int H, int W, int P,
                                                                       int oh, int ow, int sx, int sy, float sx_l, float sy_l,
-                                                                      float sx_c, float sy_c, int gx_l, int n_l, int gx_c,
+                                                                      float sx_c, float sy_c, int gx_l, int n_l, int gx_c, int ch, int och,
                                                                       uint8_t *__restrict__ out_y, uint8_t *__restrict__ out_uv,
                                                                       size_t out_pitch, size_t out_frame_stride) {
   __shared__ float4 sp[64];
@@ -477,8 +479,8 @@ __global__ __launch_bounds__(kThreads) void nv12_render_scaled_kernel(Nv12 s, co
   const int gx = chroma ? gx_c : gx_l;
   const int rows = scaled_rows_per_group(sy);
   const int io0 = (id / gx) * rows, i0v = io0 * sy;   // the first output row and its first virtual row
-  const int ph = chroma ? H / 2 : H, pw = chroma ? W / 2 : W;
-  const int po = chroma ? oh / 2 : oh, qo = chroma ? ow / 2 : ow;
+  const int ph = chroma ? ch : H, pw = chroma ? W / 2 : W;
+  const int po = chroma ? och : oh, qo = chroma ? ow / 2 : ow;
   const float step_x = chroma ? sx_c : sx_l, step_y = chroma ? sy_c : sy_l;
   const float z = zoom ? zoom[b] : 1.0f;
   tps_stage<true, true>(coord, 0, T, b, P, t, i0v, step_y, sp, sdy, sa, z);
@@ -579,23 +581,29 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
                          size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
                          uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream, const float *zoom,
                          int render_filter, int render_border, RenderShape shape, int surface_format, int out_H, int out_W,
-                         const char *fn) {
+                         const char *fn, int chroma_format) {
+  // the chroma plane's rows ("Chroma sampling"): H / 2 of a 4:2:0 frame, H of a 4:2:2 one; its columns are W / 2 in both
+  const bool c422 = chroma_format == DVSG_CHROMA_422;
+  const int ch = c422 ? H : H / 2;
+  // the planes' samples per luma sample, 1 + the chroma share (1 / 2, or 1 for 4:2:2), times the bytes of a sample
+  const double bytes = (c422 ? 2.0 : 1.5) * (surface_format == DVSG_SURFACE_P010 ? 2.0 : 1.0);
   if ((out_H || out_W) && (out_H != H || out_W != W)) {   // a scaled view at another size: kernels of their own
     if (int rc = render_scaled_check(fn, H, W, out_H, out_W, render_border)) return rc;
     const int sy = scaled_factor(H, out_H), sx = scaled_factor(W, out_W), rows = scaled_rows_per_group(sy);
     const int gx_l = ceil_div(out_W, kThreads), gx_c = ceil_div(out_W / 2, kThreads);
-    const long n_l = (long)gx_l * ceil_div(out_H, rows), n_c = (long)gx_c * ceil_div(out_H / 2, rows);
+    const int och = c422 ? out_H : out_H / 2;
+    const long n_l = (long)gx_l * ceil_div(out_H, rows), n_c = (long)gx_c * ceil_div(och, rows);
     DVSG_REQUIRE(n_l + n_c < (1L << 31), "%s: frame %dx%d too large", fn, out_H, out_W);
     if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, shape)) return rc;
     hipStream_t s = as_stream(stream);
     const bool p010 = surface_format == DVSG_SURFACE_P010;
     // algorithmic bytes: the source planes once in, the output planes once out
-    ProfScope prof(kClsTpsWarp, s, 0.0, (p010 ? 3.0 : 1.5) * n * ((double)H * W + (double)out_H * out_W));
+    ProfScope prof(kClsTpsWarp, s, 0.0, bytes * n * ((double)H * W + (double)out_H * out_W));
     const dim3 grid((unsigned)(n_l + n_c), n);
     auto launch = [&](auto kS, auto kCubic, auto kBorder) {
       hipLaunchKernelGGL((nv12_render_scaled_kernel<decltype(kS), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
                          Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, out_H, out_W, sx, sy, lin_step(sx * out_W),
-                         lin_step(sy * out_H), lin_step(sx * (out_W / 2)), lin_step(sy * (out_H / 2)), gx_l, (int)n_l, gx_c,
+                         lin_step(sy * out_H), lin_step(sx * (out_W / 2)), lin_step(sy * och), gx_l, (int)n_l, gx_c, ch, och,
                          out_y, out_uv, out_pitch, out_frame_stride);
     };
     auto with_border = [&](auto kS, auto kCubic) {
@@ -612,18 +620,18 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
     return check_launch("nv12_render_scaled_kernel");
   }
   const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
-  const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(H / 2, kTpsRows);
+  const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(ch, kTpsRows);
   DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);
   if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, shape)) return rc;
   hipStream_t s = as_stream(stream);
-  // algorithmic bytes: both planes once in, once out (P010: two bytes per sample)
-  ProfScope prof(kClsTpsWarp, s, 0.0, (surface_format == DVSG_SURFACE_P010 ? 6.0 : 3.0) * n * H * W);
+  // algorithmic bytes: both planes once in, once out
+  ProfScope prof(kClsTpsWarp, s, 0.0, 2.0 * bytes * n * H * W);
   if (surface_format == DVSG_SURFACE_P010) {   // a P010 view: the same grid of workgroups for every filter, border and zoom
     const dim3 grid((unsigned)(n_l + n_c), n);
     auto launch = [&](auto kZoom, auto kCubic, auto kBorder) {
       hipLaunchKernelGGL((p010_render_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
                          Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
-                         lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y, out_uv, out_pitch, out_frame_stride);
+                         lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch, out_frame_stride);
     };
     const bool cubic = render_filter == DVSG_RENDER_BICUBIC;
     if (render_border != DVSG_BORDER_BLACK) {
@@ -642,7 +650,7 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
     for_render_border(zoom != nullptr, render_filter == DVSG_RENDER_BICUBIC, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {
       hipLaunchKernelGGL((nv12_render_border_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
                          Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
-                         lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y, out_uv, out_pitch, out_frame_stride);
+                         lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch, out_frame_stride);
     });
     return check_launch("nv12_render_border_kernel");
   }
@@ -650,22 +658,22 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
     const dim3 grid((unsigned)(n_l + n_c), n);
     if (zoom)
       hipLaunchKernelGGL(nv12_render_cubic_kernel<true>, grid, dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride}, coord, T,
-                         zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y,
+                         zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y,
                          out_uv, out_pitch, out_frame_stride);
     else
       hipLaunchKernelGGL(nv12_render_cubic_kernel<false>, grid, dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride}, coord, T,
-                         zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y,
+                         zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y,
                          out_uv, out_pitch, out_frame_stride);
     return check_launch("nv12_render_cubic_kernel");
   }
   if (zoom) {   // dvsg_tps_render_zoom_nv12: the same grid of workgroups on the zoomed output grid
     hipLaunchKernelGGL(nv12_render_zoom_kernel, dim3((unsigned)(n_l + n_c), n), dim3(kThreads), 0, s,
                        Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
-                       lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y, out_uv, out_pitch, out_frame_stride);
+                       lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch, out_frame_stride);
     return check_launch("nv12_render_zoom_kernel");
   }
   hipLaunchKernelGGL(nv12_render_kernel, dim3((unsigned)(n_l + n_c), n), dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride},
-                     coord, T, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(H / 2), gx_l, (int)n_l, gx_c, out_y,
+                     coord, T, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y,
                      out_uv, out_pitch, out_frame_stride);
   return check_launch("nv12_render_kernel");
 }

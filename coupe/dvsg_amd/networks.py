@@ -99,6 +99,15 @@ def check_surface(surface):
     return surface
 
 
+CHROMAS = {"420": 0, "422": 1}   # DVSG_CHROMA_420, DVSG_CHROMA_422
+
+
+def check_chroma(chroma):
+    if not isinstance(chroma, str) or chroma not in CHROMAS:
+        raise ValueError("chroma must be '420' or '422', got %r" % (chroma,))
+    return chroma
+
+
 MAX_SCALED_FACTOR = 4   # virtual samples per axis and output sample that the scaled renders serve
 
 
@@ -165,7 +174,7 @@ class LocNet(object):
         self.in_channels = _lib.load().dvsg_locnet_in_channels(self.handle)
 
     def view(self, render_filter="bilinear", border="black", strength=1.0, rigidity=0.0, shape_model="affine", surface="nv12",
-             out_size=None):
+             out_size=None, chroma="420"):
         """The handle the source-size renders, the coverage scan and `dvsg_tps_coefficients_f32` take for `render_filter`,
         `border` and the warp shape: this network itself for ("bilinear", "black") unshaped, else a view of it
         (`dvsg_locnet_view_create_border`, or `dvsg_locnet_view_create_shaped` when strength != 1 or rigidity != 0: the same
@@ -173,7 +182,20 @@ class LocNet(object):
         network goes.  An unshaped view is the same whatever its shape_model.  surface="p010": the view of that handle
         whose NV12 renders read and write P010 surfaces (`dvsg_locnet_view_create_surface`: filter, border and shape
         inherited); no other entry point reads it.  out_size=(H, W): the view of THAT handle whose four renders write frames
-        of this size (`dvsg_locnet_view_create_scaled`: everything else inherited); no other entry point reads it."""
+        of this size (`dvsg_locnet_view_create_scaled`: everything else inherited); no other entry point reads it.  chroma="422": the view of
+        THAT handle whose NV12 renders read and write 4:2:2 frames, a UV plane of H rows (`dvsg_locnet_view_create_chroma`:
+        everything else inherited; include/dvsg_amd.h, "Chroma sampling"); no other entry point reads it."""
+        check_chroma(chroma)
+        if chroma != "420":
+            out_size = check_out_size(out_size)
+            key = (render_filter, border, strength, rigidity, shape_model, surface, out_size, chroma)
+            v = self._views.get(key)
+            if v is None:
+                inner = self.view(render_filter, border, strength, rigidity, shape_model, surface, out_size)
+                v = ctypes.c_void_p()
+                _lib.call("dvsg_locnet_view_create_chroma", inner, CHROMAS[chroma], ctypes.byref(v))
+                self._views[key] = v
+            return v
         out_size = check_out_size(out_size)
         if out_size is not None:
             key = (render_filter, border, strength, rigidity, shape_model, surface, out_size)

@@ -29,7 +29,10 @@ from .clip import SKIP_LENGTH, _check_crop, _check_crop_grid, _check_window, che
 
 
 YUV_MATRICES = {"bt601": 0, "bt709": 1}   # DVSG_YUV_BT601_LIMITED, DVSG_YUV_BT709_LIMITED
-SURFACE_FORMATS = ("nv12", "p010")         # frame formats that are decoder surfaces: two planes, a source-size render
+SURFACE_FORMATS = ("nv12", "p010", "nv16", "p210")   # frame formats that are decoder surfaces: two planes, a source-size render
+# a surface format's sample type and chroma sampling, by the names `LocNet.view` gives them (surface=, chroma=)
+SURFACE_OF = {"nv12": ("nv12", "420"), "p010": ("p010", "420"), "nv16": ("nv12", "422"), "p210": ("p010", "422")}
+WORD_FORMATS = ("p010", "p210")            # surfaces of 16-bit words: uint8 [.., 2 W0] or uint16 [.., W0], returned as given
 SCENE_STATE_INTS = 68                     # DVSG_SCENE_STATE_INTS: k, cuts, S, 0, the previous histogram [64]
 
 
@@ -115,23 +118,29 @@ def _rgb_key(sid, t, h, w, source_res, crop):
     return (3,) if t.dtype == torch.float64 else (2,)
 
 
+def _surface_rows(name, H0):
+    """The rows of a packed surface of height H0: H0 of Y, then the UV plane's H0 / 2 (4:2:0) or H0 (4:2:2)."""
+    return 2 * H0 if SURFACE_OF[name][1] == "422" else 3 * H0 // 2
+
+
 def _surface_key(sid, t, name):
-    """Check an NV12 or P010 surface in the uint8 form; its sort key (H0, W0)."""
-    bps = 2 if name == "p010" else 1   # the bytes of a sample
+    """Check an NV12, P010, NV16 or P210 surface in the uint8 form; its sort key (H0, W0)."""
+    bps = 2 if name in WORD_FORMATS else 1   # the bytes of a sample
+    c422 = SURFACE_OF[name][1] == "422"      # R rows are H0 of Y and H0 / 2 (4:2:0) or H0 (4:2:2) of UV
+    layout = "[%s, %sW0]" % ("2*H0" if c422 else "3*H0/2", "2*" if bps == 2 else "")
+    article = "a" if bps == 2 else "an"
     if t.dtype.is_floating_point:
         raise ValueError("stream %r: frame_format=%r takes uint8 surfaces, not float frames (%s)" % (sid, name, t.dtype))
     if t.dtype != torch.uint8:
         raise TypeError("stream %r: %s frames must be uint8%s, got %s"
                         % (sid, name.upper(), " or uint16" if bps == 2 else "", t.dtype))
     if t.dim() != 2:
-        raise ValueError("stream %r: %s frame must be [3*H0/2, %sW0], got %s"
-                         % (sid, "an NV12" if bps == 1 else "a P010", "2*" if bps == 2 else "", tuple(t.shape)))
+        raise ValueError("stream %r: %s %s frame must be %s, got %s" % (sid, article, name.upper(), layout, tuple(t.shape)))
     R, W0 = int(t.shape[0]), int(t.shape[1]) // bps
-    H0 = 2 * R // 3
-    if R % 3 or H0 % 2 or W0 % 2 or H0 < 4 or W0 < 4 or int(t.shape[1]) % bps:
-        raise ValueError("stream %r: %s frame [3*H0/2, %sW0] needs even H0, W0 >= 4 (odd sizes have no chroma "
-                         "layout), got %s" % (sid, "an NV12" if bps == 1 else "a P010 uint8", "2*" if bps == 2 else "",
-                                              tuple(t.shape)))
+    H0 = R // 2 if c422 else 2 * R // 3
+    if R % (2 if c422 else 3) or H0 % 2 or W0 % 2 or H0 < 4 or W0 < 4 or int(t.shape[1]) % bps:
+        raise ValueError("stream %r: %s %s%s frame %s needs even H0, W0 >= 4 (odd sizes have no chroma layout), got %s"
+                         % (sid, article, name.upper(), " uint8" if bps == 2 else "", layout, tuple(t.shape)))
     return (H0, W0)
 
 
@@ -148,7 +157,7 @@ def plan_step(frames, stream_of, h, w, frame_format="rgb", source_res=False, cro
     for sid, fr in frames.items():
         ring, k = stream_of(sid)
         host, words = not isinstance(fr, torch.Tensor), False
-        if frame_format == "p010":
+        if frame_format in WORD_FORMATS:
             fr, words = _words_to_bytes(fr, "stream %r" % (sid,))
         t = torch.as_tensor(np.ascontiguousarray(fr)) if host else fr
         key = _surface_key(sid, t, frame_format) if frame_format in SURFACE_FORMATS else \
@@ -215,6 +224,17 @@ class OnlineStabilizer(object):
     bits): one strided copy per source-size group, `src[..., 1::2]`, into a buffer this object owns, then the same
     `dvsg_frames_ingest_nv12`.  The pool, F_t and the crop state are therefore those of an "nv12" run fed those bytes.  The
     render goes through `LocNet.view(..., surface="p010")` with pitch = 2 W0 and warps the 10-bit planes themselves.
+
+    frame_format="nv16" / "p210": 4:2:2 footage (camera originals, mezzanine files; include/dvsg_amd.h, "Chroma sampling"),
+    8-bit and 10-bit.  A frame is H0 rows of Y, then H0 rows of interleaved UV: uint8 [2 H0, W0] for "nv16"; for "p210"
+    uint8 [2 H0, 2 W0] or uint16 [2 H0, W0], returned in the form given, exactly as "p010".  The options, checks and results
+    are those of "nv12" / "p010".  What the network sees is DEFINED as the NV12 surface made of the Y plane and the EVEN
+    chroma rows (for "p210" the high byte of each of those words): one strided device copy per source-size run into the
+    buffer this object owns, then the unchanged `dvsg_frames_ingest_nv12`.  The pool, F_t, scene cuts and the crop's inputs
+    are therefore those of an "nv12" run fed that surface, bit for bit.  The render goes through
+    `LocNet.view(..., surface=, chroma="422", out_size=)` and warps every chroma row; crop="auto" scans the chroma grid
+    (H0, W0 / 2), with out_size the virtual grid (sy H, sx W / 2), and the default crop_margin stays one pixel of that
+    grid's shorter axis.
 
     render_filter: the filter of the source-size render (source_res=True or frame_format="nv12", with and without crop).
     "bilinear" (default) is sampler A; "bicubic" gives the render calls a view of the network with that filter
@@ -317,7 +337,8 @@ class OnlineStabilizer(object):
         if channel_order not in ("rgb", "bgr"):
             raise ValueError("channel_order must be 'rgb' or 'bgr'")
         if frame_format not in ("rgb",) + SURFACE_FORMATS:
-            raise ValueError("frame_format must be 'rgb', 'nv12' or 'p010', got %r" % (frame_format,))
+            raise ValueError("frame_format must be 'rgb', 'nv12' or 'p010', or for 4:2:2 'nv16' or 'p210', got %r"
+                             % (frame_format,))
         if yuv_matrix not in YUV_MATRICES:
             raise ValueError("yuv_matrix must be 'bt709' or 'bt601', got %r" % (yuv_matrix,))
         if surface:
@@ -348,7 +369,9 @@ class OnlineStabilizer(object):
         self.strength, self.rigidity, self.shape_model = shape
         self._keep = {}           # border="keep": ring -> the stream's persistent output surface, at its source size
         self._keep_fresh = set()  # rings whose next frame is a step 0: the surface restarts from that frame's source bytes
-        self._hi = {}             # frame_format="p010": (H0, W0) -> uint8 [max_streams, 3 H0 / 2, W0], the words' high bytes
+        # frame_format="p010", "nv16", "p210": (H0, W0) -> (uint8 [max_streams, 3 H0 / 2, W0], the NV12 surface the network sees:
+        # the words' high bytes, the even chroma rows, or both; for 4:2:2 the rows it is gathered from, else None)
+        self._hi = {}
         self._cut = None          # int32 [B] on the device: the `cut` output of this step's dvsg_scene_step_f32
         dev = device()
         self.pool = torch.empty((self.max_streams * self.frames_per_stream, self.h, self.w, 3), dtype=torch.float32,
@@ -446,7 +469,8 @@ class OnlineStabilizer(object):
         `dvsg_tps_coefficients_f32`): the view the render uses without the surface, so that scan, crop and render see one
         warp; the network itself when nothing is shaped (the scan does not read a filter or a border)."""
         if not scan:
-            return self.model.locnet.view(surface=self.frame_format, out_size=self.out_size, **self._render_options)
+            surface, chroma = SURFACE_OF[self.frame_format]
+            return self.model.locnet.view(surface=surface, out_size=self.out_size, chroma=chroma, **self._render_options)
         if self.strength == 1.0 and self.rigidity == 0.0:
             return self.model.locnet.handle
         return self.model.locnet.view(**self._render_options)
@@ -707,26 +731,38 @@ class OnlineStabilizer(object):
     def _scan_grids(self, H0, W0, surface):
         """The grids crop="auto" scans for a source of (H0, W0): the output's own -- with out_size the VIRTUAL grid
         (sy H, sx W) against the source's size, so that no virtual sample of the render is left invalid -- and for a
-        surface the chroma plane's too."""
+        surface the chroma plane's too: (H0 / 2, W0 / 2), or (H0, W0 / 2) for a 4:2:2 format."""
+        c422 = surface and SURFACE_OF[self.frame_format][1] == "422"
         if self.out_size is None:
-            return [(H0, W0), (H0 // 2, W0 // 2)] if surface else [(H0, W0)]
+            return [(H0, W0), (H0 if c422 else H0 // 2, W0 // 2)] if surface else [(H0, W0)]
         from .networks import scaled_factors
         (oh, ow), (sy, sx) = self.out_size, scaled_factors((H0, W0), self.out_size)
         luma = (H0, W0, sy * oh, sx * ow)
-        return [luma, (H0 // 2, W0 // 2, sy * (oh // 2), sx * (ow // 2))] if surface else [luma]
+        chroma = (H0, W0 // 2, sy * oh, sx * (ow // 2)) if c422 else (H0 // 2, W0 // 2, sy * (oh // 2), sx * (ow // 2))
+        return [luma, chroma] if surface else [luma]
 
     def _ingest_surface(self, rows, i, j, in_slots, side):
-        """Ingest of a run of NV12 or P010 surfaces of one size: one `dvsg_frames_ingest_nv12` launch; returns the frames on
-        the device, [j-i, 3 H0 / 2, bps W0] (bps: the bytes of a sample; a P010 frame is handled as its bytes)."""
+        """Ingest of a run of surfaces of one size: one `dvsg_frames_ingest_nv12` launch; returns the frames on the device,
+        [j-i, R, bps W0] (R: the format's rows, 3 H0 / 2 or 2 H0; bps: the bytes of a sample; words are handled as their bytes)."""
         dev, (H0, W0) = device(), rows[i].key
         src = torch.stack([r.t.to(dev) for r in rows[i:j]]).contiguous()
         seen = src
-        if self.frame_format == "p010":   # the network sees the words' high bytes: one strided copy into a buffer this object owns
-            buf = self._hi.get((H0, W0))
+        if self.frame_format != "nv12":
+            # the network sees an NV12 surface: the words' high bytes (P010, P210), the Y plane and the EVEN chroma rows
+            # (NV16, P210): one strided copy into a buffer this object owns -- for 4:2:2 one gather of the rows 0 .. H0 - 1,
+            # H0, H0 + 2, .. by an index kept beside the buffer
+            buf, picked = self._hi.get((H0, W0), (None, None))
             if buf is None:
-                buf = self._hi[(H0, W0)] = torch.empty((self.max_streams, 3 * H0 // 2, W0), dtype=torch.uint8, device=dev)
+                buf = torch.empty((self.max_streams, 3 * H0 // 2, W0), dtype=torch.uint8, device=dev)
+                if SURFACE_OF[self.frame_format][1] == "422":
+                    picked = torch.cat([torch.arange(H0), torch.arange(H0, 2 * H0, 2)]).to(dev)
+                self._hi[(H0, W0)] = (buf, picked)
             seen = buf[:j - i]
-            seen.copy_(src[..., 1::2])
+            hi = src[..., 1::2] if self.frame_format in WORD_FORMATS else src
+            if picked is not None:
+                torch.index_select(hi, 1, picked, out=seen)
+            else:
+                seen.copy_(hi)
         _lib.call("dvsg_frames_ingest_nv12", ptr(seen), ptr(seen) + H0 * W0, W0, 3 * H0 // 2 * W0, j - i, H0, W0,
                   self.yuv_matrix, ptr(self.pool), int(self.pool.shape[0]), ptr(in_slots[i:j]), self.h, self.w, stream())
         return src
@@ -736,20 +772,21 @@ class OnlineStabilizer(object):
         (H0, W0), net = rows[i].key, self._view()
         pitch = int(src.shape[2])   # bps W0: rows are packed; the UV plane follows the Y plane
         oh, ow = (H0, W0) if self.out_size is None else self.out_size
+        R0, ro = _surface_rows(self.frame_format, H0), _surface_rows(self.frame_format, oh)   # a frame's rows, in and out
         if self.border == "keep":
             out, done = self._keep_surfaces(rows, i, j, src)
         else:
-            out, done = torch.empty((j - i, 3 * oh // 2, pitch // W0 * ow), dtype=src.dtype, device=src.device), None
+            out, done = torch.empty((j - i, ro, pitch // W0 * ow), dtype=src.dtype, device=src.device), None
         opitch = int(out.shape[2])
         if self.crop is None:
             _lib.call("dvsg_tps_render_nv12", net, ptr(self._F[i:j]), ptr(src), ptr(src) + H0 * pitch, pitch,
-                      3 * H0 // 2 * pitch, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + oh * opitch, opitch,
-                      3 * oh // 2 * opitch, stream())
+                      R0 * pitch, j - i, H0, W0, ptr(self._T[i:j]), ptr(out), ptr(out) + oh * opitch, opitch,
+                      ro * opitch, stream())
         else:   # chroma leaves the source first: both planes are scanned, each on its own grid
             zoom = self._step_zoom(rows, i, j, self._scan_grids(H0, W0, True))
             _lib.call("dvsg_tps_render_zoom_nv12", net, ptr(self._F[i:j]), ptr(src),
-                      ptr(src) + H0 * pitch, pitch, 3 * H0 // 2 * pitch, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]),
-                      ptr(out), ptr(out) + oh * opitch, opitch, 3 * oh // 2 * opitch, stream())
+                      ptr(src) + H0 * pitch, pitch, R0 * pitch, j - i, H0, W0, ptr(zoom), ptr(self._T[i:j]),
+                      ptr(out), ptr(out) + oh * opitch, opitch, ro * opitch, stream())
         return (out if done is None else done()), None
 
 
@@ -761,7 +798,7 @@ def stabilize_clips(model, clips, batch=None, **kw):
     and shape_model shape every clip's source-size render alike.
     Returns a list with, per clip, what `clip.stabilize_clip` returns for it (NumPy for NumPy clips).  With
     frame_format="nv12" a clip is [N,3*H0/2,W0] uint8 and so is its result; with "p010" [N,3*H0/2,2*W0] uint8 or
-    [N,3*H0/2,W0] uint16, likewise.  crop=... is OnlineStabilizer's: frame k of a
+    [N,3*H0/2,W0] uint16, likewise; with "nv16" / "p210" the same with 2*H0 rows.  crop=... is OnlineStabilizer's: frame k of a
     clip is rendered with the zoom the ratchet has reached at frame k, NOT with `stabilize_clip`'s one clip-wide zoom
     (the two agree from the frame on that sets the clip's minimum)."""
     K = len(clips)
@@ -774,13 +811,14 @@ def stabilize_clips(model, clips, batch=None, **kw):
     for c, hst in zip(clips, host):
         fmt = kw.get("frame_format", "rgb")
         words.append(False)
-        if fmt == "p010":   # uint16 clips run in the uint8 form and come back as words
+        if fmt in WORD_FORMATS:   # uint16 clips run in the uint8 form and come back as words
             c, words[-1] = _words_to_bytes(c, "clip %d" % len(dclips))
         t = (torch.as_tensor(np.ascontiguousarray(c)) if hst else c).to(dev).contiguous()
         if fmt in SURFACE_FORMATS:
             if t.dim() != 3 or t.shape[0] < 1:
-                raise ValueError("every %s clip must be [N,3*H0/2,%sW0] with N >= 1, got %s"
-                                 % (fmt.upper(), "2*" if fmt == "p010" else "", tuple(t.shape)))
+                raise ValueError("every %s clip must be [N,%s,%sW0] with N >= 1, got %s"
+                                 % (fmt.upper(), "2*H0" if SURFACE_OF[fmt][1] == "422" else "3*H0/2",
+                                    "2*" if fmt in WORD_FORMATS else "", tuple(t.shape)))
         elif t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
             raise ValueError("every clip must be [N,h,w,3] with N >= 1, got %s" % (tuple(t.shape),))
         dclips.append(t)

@@ -25,6 +25,11 @@ Ten-bit runs (`C420p10` Y4M or raw P010 at every end) are the same loop around o
 frames are uint8 [3 H / 2, 2 W], the repacks are `y4m.i420p10_to_p010` and `y4m.p010_to_i420p10`.  All ends of one call share
 a bit depth.
 
+4:2:2 runs (`C422` / `C422p10` Y4M, raw NV16 or raw P210 at every end) are the same loop again around one
+`OnlineStabilizer(frame_format="nv16")` or `("p210")`: frames are uint8 [2 H, W] or [2 H, 2 W], the repacks are
+`y4m.i422_to_nv16` / `nv16_to_i422` and `y4m.i422p10_to_p210` / `p210_to_i422p10`.  All ends of one call share their chroma
+sampling as they share their bit depth.
+
 A slot is not refilled before its frame is written, so a source never has more than `depth` frames between `readinto` and
 `write` (back-pressure: a slow sink stalls its reader, memory does not grow), and every reuse hazard is covered by the order
 of the stations: when a slot returns to (a) its download has finished, hence the step that read its device input, hence its
@@ -120,7 +125,15 @@ class _Staging(object):
 
 
 # the planar layouts and their repacks to and from what OnlineStabilizer takes
-_PLANAR = {"i420": (y4m.i420_to_nv12, y4m.nv12_to_i420), "i420p10": (y4m.i420p10_to_p010, y4m.p010_to_i420p10)}
+_PLANAR = {"i420": (y4m.i420_to_nv12, y4m.nv12_to_i420), "i420p10": (y4m.i420p10_to_p010, y4m.p010_to_i420p10),
+           "i422": (y4m.i422_to_nv16, y4m.nv16_to_i422), "i422p10": (y4m.i422p10_to_p210, y4m.p210_to_i422p10)}
+# the OnlineStabilizer frame format of a run, by (bit depth, chroma sampling)
+_FRAME_FORMAT = {(8, "420"): "nv12", (10, "420"): "p010", (8, "422"): "nv16", (10, "422"): "p210"}
+
+
+def _frame_shape(height, width, bits, chroma):
+    """[3 H / 2, W] of a 4:2:0 frame or [2 H, W] of a 4:2:2 one; a 10-bit row is 2 W bytes."""
+    return (y4m._frame_rows(int(height), chroma), (2 if bits == 10 else 1) * int(width))
 
 
 class _Lane(object):
@@ -287,25 +300,31 @@ def _snapshot(on, sid):
     return state
 
 
-def _check_ends(sources, sinks, out_size=None):
-    """Everything that can be said of the ends before a frame is read; returns the run's bit depth (8 without sources).
-    out_size (H, W): what every sink that states a size must state instead of its source's."""
+def _ends_format(sources, sinks, out_size=None):
+    """Everything that can be said of the ends before a frame is read; returns the run's (bit depth, chroma sampling),
+    (8, "420") without sources.  out_size (H, W): what every sink that states a size must state instead of its source's."""
     if len(sources) != len(sinks):
         raise ValueError("stabilize_pipes needs one sink per source, got %d sources and %d sinks" % (len(sources), len(sinks)))
-    bits = None
+    bits = chroma = None
     for i, (src, snk) in enumerate(zip(sources, sinks)):
         for end, what in ((src, "source"), (snk, "sink")):
             layout = getattr(end, "layout", None)
             if layout not in y4m.LAYOUT_BITS:
-                raise ValueError("%s %d: layout must be 'i420' or 'nv12' (10-bit: 'i420p10' or 'p010'), got %r" % (what, i, layout))
+                raise ValueError("%s %d: layout must be 'i420' or 'nv12' (10-bit: 'i420p10' or 'p010'; 4:2:2: 'i422', 'nv16', 'i422p10' "
+                                 "or 'p210'), got %r" % (what, i, layout))
             bits = y4m.LAYOUT_BITS[layout] if bits is None else bits
             if y4m.LAYOUT_BITS[layout] != bits:
                 raise ValueError("%s %d is %d-bit (%s) in a %d-bit run: all sources and sinks of one call share a bit depth"
                                  % (what, i, y4m.LAYOUT_BITS[layout], layout, bits))
+            chroma = y4m.LAYOUT_CHROMA[layout] if chroma is None else chroma
+            if y4m.LAYOUT_CHROMA[layout] != chroma:
+                raise ValueError("%s %d is 4:2:%s (%s) in a 4:2:%s run: all sources and sinks of one call share their chroma "
+                                 "sampling" % (what, i, y4m.LAYOUT_CHROMA[layout][2], layout, chroma[2]))
         y4m.check_size(int(src.width), int(src.height))
-        if tuple(src.frame_shape) != (3 * int(src.height) // 2, (2 if bits == 10 else 1) * int(src.width)):
-            raise ValueError("source %d: frame_shape %s is not [3 H / 2, %sW] of %d x %d"
-                             % (i, tuple(src.frame_shape), "2 " if bits == 10 else "", src.width, src.height))
+        if tuple(src.frame_shape) != _frame_shape(src.height, src.width, bits, chroma):
+            raise ValueError("source %d: frame_shape %s is not [%s, %sW] of %d x %d"
+                             % (i, tuple(src.frame_shape), "2 H" if chroma == "422" else "3 H / 2", "2 " if bits == 10 else "",
+                                src.width, src.height))
         want = (src.width, src.height) if out_size is None else (out_size[1], out_size[0])
         size = (getattr(snk, "width", want[0]), getattr(snk, "height", want[1]))
         if size != want and out_size is not None:
@@ -313,7 +332,12 @@ def _check_ends(sources, sinks, out_size=None):
         if size != want:
             raise ValueError("sink %d is %d x %d but its source is %d x %d: the output has the size of the input"
                              % ((i,) + size + (src.width, src.height)))
-    return bits or 8
+    return bits or 8, chroma or "420"
+
+
+def _check_ends(sources, sinks, out_size=None):
+    """`_ends_format`'s checks; returns the run's bit depth alone."""
+    return _ends_format(sources, sinks, out_size)[0]
 
 
 def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, **online_kw):
@@ -330,6 +354,9 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
         (semi-planar, value in the high 10 bits), frames uint8 [3 H / 2, 2 W].  All sources and sinks of one call share a
         bit depth; a mix raises ValueError before any frame is read.  A 10-bit run goes through one
         `OnlineStabilizer(frame_format="p010")`; an 8-bit run is what it was.
+        4:2:2: layouts "i422" / "i422p10" (Y4M C422 / C422p10) and "nv16" / "p210", frames uint8 [2 H, W] / [2 H, 2 W].  All
+        sources and sinks of one call share their chroma sampling too; a mix raises ValueError naming the end before any
+        frame is read.  Such a run goes through `OnlineStabilizer(frame_format="nv16")` or `("p210")`.
     batch: streams per step (default: all sources).  depth: frames in flight per source, >= 1.
     online_kw: OnlineStabilizer's crop, crop_*, scene_cut, scene_min_len, skip_length, render_filter, border, strength, rigidity,
         shape_model, out_size and yuv_matrix, passed through.  out_size=(H, W): every sink receives frames of that size
@@ -356,7 +383,7 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
     if out_size is not None:
         from .networks import check_out_size
         out_size = check_out_size(out_size, True, True)
-    bits = _check_ends(sources, sinks, out_size)
+    bits, chroma = _ends_format(sources, sinks, out_size)
     K = len(sources)
     if isinstance(depth, bool) or int(depth) != depth or depth < 1:
         raise ValueError("depth must be an integer >= 1, got %r" % (depth,))
@@ -369,7 +396,7 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
         kw = dict(online_kw)
         if kw.get("yuv_matrix", "auto") == "auto":
             kw["yuv_matrix"] = y4m.default_yuv_matrix(sources[0].height)
-        on = OnlineStabilizer(model, max_streams=batch, frame_format="p010" if bits == 10 else "nv12", **kw)
+        on = OnlineStabilizer(model, max_streams=batch, frame_format=_FRAME_FORMAT[(bits, chroma)], **kw)
         step, staging = on.step, _Staging(True)
     else:
         import torch
@@ -399,7 +426,7 @@ def stabilize_pipes(model, sources, sinks, batch=None, depth=3, _step_fn=None, *
             while waiting and len(active) < batch:
                 i = waiting.pop(0)
                 lane = _Lane(i, sources[i], sinks[i], depth, staging, shared,
-                             None if out_size is None else (3 * out_size[0] // 2, (2 if bits == 10 else 1) * out_size[1]))
+                             None if out_size is None else _frame_shape(out_size[0], out_size[1], bits, chroma))
                 lanes.append(lane)
                 sid = on.open()
                 slot = lane.next_slot()
@@ -462,14 +489,14 @@ def _parser():
         def error(self, message):     # one line and status 1, not argparse's usage block and status 2
             raise _UsageError(message)
 
-    ap = Parser(prog=PROG, description="Stabilise uncompressed video from files or pipes (Y4M, raw NV12 or raw P010).")
+    ap = Parser(prog=PROG, description="Stabilise uncompressed video from files or pipes (Y4M, raw NV12, P010, NV16 or P210).")
     ap.add_argument("--input", action="append", metavar="PATH|-", help="repeatable; default: stdin")
     ap.add_argument("--output", action="append", metavar="PATH|-", help="repeatable, one per input; default: stdout")
-    ap.add_argument("--format", default="y4m", choices=["y4m", "nv12", "p010"],
-                    help="of the inputs (nv12, p010: header-less, need --size; y4m: 8-bit, or 10-bit C420p10)")
-    ap.add_argument("--output-format", default=None, choices=["y4m", "nv12", "p010"],
-                    help="of the outputs (default: --format); of the inputs' bit depth")
-    ap.add_argument("--size", default=None, metavar="WxH", help="frame size of raw NV12 / P010 inputs")
+    ap.add_argument("--format", default="y4m", choices=["y4m", "nv12", "p010", "nv16", "p210"],
+                    help="of the inputs (nv12, p010, 4:2:2 nv16, p210: header-less, need --size; y4m: C420, C420p10, C422, C422p10)")
+    ap.add_argument("--output-format", default=None, choices=["y4m", "nv12", "p010", "nv16", "p210"],
+                    help="of the outputs (default: --format); of the inputs' bit depth and chroma sampling")
+    ap.add_argument("--size", default=None, metavar="WxH", help="frame size of raw NV12 / P010 / NV16 / P210 inputs")
     ap.add_argument("--fps", default="25", metavar="N[/D]", help="frame rate written to a Y4M output of a raw NV12 input")
     w = ap.add_mutually_exclusive_group(required=True)
     w.add_argument("--ckpt", metavar="DIR", help="reference checkpoint directory (with its `checkpoints` index)")
@@ -507,6 +534,13 @@ def _parser():
     return ap
 
 
+# the header-less formats of --format / --output-format: (reader, writer)
+_RAW = {"nv12": (y4m.RawNV12Reader, y4m.RawNV12Writer), "p010": (y4m.RawP010Reader, y4m.RawP010Writer),
+        "nv16": (y4m.RawNV16Reader, y4m.RawNV16Writer), "p210": (y4m.RawP210Reader, y4m.RawP210Writer)}
+# the C tag of a Y4M output of a raw source
+_RAW_COLORSPACE = {"p010": "420p10", "nv16": "422", "p210": "422p10"}
+
+
 def _size(text, option):
     try:
         w, h = (int(v) for v in text.lower().split("x"))
@@ -528,7 +562,7 @@ def _arguments(argv):
         raise _UsageError("stdin and stdout can serve one stream each")
     args.output_format = args.output_format or args.format
     args.size = _size(args.size, "--size") if args.size is not None else None
-    if args.format in ("nv12", "p010") and args.size is None:
+    if args.format in _RAW and args.size is None:
         raise _UsageError("--format %s has no header: --size WxH is required" % args.format)
     args.model_size = _size(args.model_size, "--model-size")
     try:
@@ -568,8 +602,8 @@ def _run(args, note):
         for path in args.input:
             f = sys.stdin.buffer if path == "-" else open(path, "rb")
             files.append(f)
-            sources.append(y4m.Y4MReader(f, depths=(8, 10)) if args.format == "y4m" else
-                           y4m.RawP010Reader(f, *args.size) if args.format == "p010" else y4m.RawNV12Reader(f, *args.size))
+            sources.append(y4m.Y4MReader(f, depths=(8, 10), chromas=("420", "422")) if args.format == "y4m" else
+                           _RAW[args.format][0](f, *args.size))
         for path, src in zip(args.input, sources):
             if any(t.upper() == "XCOLORRANGE=FULL" for t in src.tags):
                 note("%s: full-range video goes through unchanged; the CNN sees it through a limited-range matrix" % path)
@@ -600,15 +634,13 @@ def _run(args, note):
                 f = open(path, "wb")
             files.append(f)
             out_h, out_w = args.out_size or (src.height, src.width)
-            if args.output_format == "nv12":
-                sinks.append(y4m.RawNV12Writer(f, out_w, out_h))
-            elif args.output_format == "p010":
-                sinks.append(y4m.RawP010Writer(f, out_w, out_h))
-            else:   # a Y4M header repeats the source's C tag (C420p10 for a raw P010 source) and its X tags
+            if args.output_format in _RAW:
+                sinks.append(_RAW[args.output_format][1](f, out_w, out_h))
+            else:   # a Y4M header repeats the source's C tag (C420p10, C422, C422p10 for a raw P010, NV16, P210 source) and its X tags
                 sinks.append(y4m.Y4MWriter(f, out_w, out_h, src.fps or args.fps,
                                            aspect=output_aspect(src.aspect, (src.height, src.width), (out_h, out_w)),
-                                           colorspace="420p10" if src.layout == "p010" else src.colorspace, tags=src.tags,
-                                           interlace=src.interlace))
+                                           colorspace=_RAW_COLORSPACE.get(src.layout, src.colorspace), tags=src.tags,
+                                           interlace=src.interlace, chromas=("420", "422")))
         stats = stabilize_pipes(model, sources, sinks, batch=args.batch, depth=args.depth, **kw)
         if args.stats:
             for path, st in zip(args.input, stats):

@@ -29,6 +29,15 @@ is the stream's bytes, uint8 [3 H / 2, 2 W] (3 W H bytes).  `Y4MWriter(colorspac
 `RawP010Writer` are header-less P010 (`-f rawvideo -pix_fmt p010le`, `layout` "p010"): Y and interleaved U V as 16-bit
 little-endian words with the value in the HIGH 10 bits -- what `OnlineStabilizer(frame_format="p010")` takes.
 `i420p10_to_p010` and `p010_to_i420p10` repack between the two on the device.  The default `depths=(8,)` refuses `C420p10`.
+
+4:2:2.  `Y4MReader(f, chromas=("420", "422"))` also takes `C422` (`ffmpeg -pix_fmt yuv422p -f yuv4mpegpipe`) and, with 10
+among `depths`, `C422p10` (`-pix_fmt yuv422p10le -strict -1`): H rows of Y, then the U plane and the V plane of H x W / 2
+each, so a frame is uint8 [2 H, W] ([2 H, 2 W] at ten bits, the value in the LOW 10 bits); `layout` is "i422" / "i422p10".
+`Y4MWriter(colorspace="422" | "422p10", chromas=("420", "422"))` writes them.  `RawNV16Reader` / `RawNV16Writer` and
+`RawP210Reader` / `RawP210Writer` are header-less NV16 and P210 (`-f rawvideo -pix_fmt nv16`, `p210le`): Y and H rows of
+interleaved U V, what `OnlineStabilizer(frame_format="nv16" | "p210")` takes.  `i422_to_nv16`, `nv16_to_i422`,
+`i422p10_to_p210` and `p210_to_i422p10` repack on the device.  The default `chromas=("420",)` refuses 4:2:2 as before; H and W
+are even and at least 4 here too.  `LAYOUT_CHROMA` names every layout's chroma sampling beside `LAYOUT_BITS`.
 """
 import numpy as np
 
@@ -36,7 +45,12 @@ MAGIC = b"YUV4MPEG2"
 FRAME_MAGIC = b"FRAME"
 CHROMA_420 = ("420", "420jpeg", "420mpeg2", "420paldv")   # 8-bit 4:2:0; they differ in chroma siting only
 CHROMA_420_P10 = ("420p10",)                               # 10-bit 4:2:0, 2 bytes per sample
-LAYOUT_BITS = {"i420": 8, "nv12": 8, "i420p10": 10, "p010": 10}   # the layouts of this module and their bit depth
+CHROMA_422 = ("422",)                                      # 8-bit 4:2:2: chroma planes of H x W / 2
+CHROMA_422_P10 = ("422p10",)                               # 10-bit 4:2:2, 2 bytes per sample
+# the layouts of this module, their bit depth and their chroma sampling
+LAYOUT_BITS = {"i420": 8, "nv12": 8, "i420p10": 10, "p010": 10, "i422": 8, "nv16": 8, "i422p10": 10, "p210": 10}
+LAYOUT_CHROMA = {"i420": "420", "nv12": "420", "i420p10": "420", "p010": "420",
+                 "i422": "422", "nv16": "422", "i422p10": "422", "p210": "422"}
 MAX_HEADER = 4096                                          # bytes of one header line, the newline included
 
 
@@ -119,6 +133,18 @@ def check_size(width, height, wtag="width", htag="height"):
             raise Y4MError("%s%d: 4:2:0 frames need an even width and height of at least 4" % (tag, v))
 
 
+def _check_chromas(chromas):
+    chromas = tuple(chromas)
+    if not chromas or any(c not in ("420", "422") for c in chromas):
+        raise ValueError("chromas must be a non-empty subset of ('420', '422'), got %r" % (chromas,))
+    return chromas
+
+
+def _frame_rows(height, chroma):
+    """The rows of a frame of `height`: Y, then the chroma of H / 2 rows' worth (4:2:0) or H rows' worth (4:2:2)."""
+    return 2 * height if chroma == "422" else 3 * height // 2
+
+
 def _frame_view(buf, nbytes):
     """`buf` (anything with the buffer protocol, a pinned tensor's .numpy() included) as a flat byte view of nbytes."""
     view = memoryview(buf)
@@ -133,9 +159,9 @@ def _frame_view(buf, nbytes):
 class _Reader(object):
     layout = None
 
-    def _init_frames(self, fileobj, width, height, sample_bytes=1):
+    def _init_frames(self, fileobj, width, height, sample_bytes=1, chroma="420"):
         self.fileobj, self.width, self.height = fileobj, int(width), int(height)
-        self.frame_shape = (3 * self.height // 2, sample_bytes * self.width)
+        self.frame_shape = (_frame_rows(self.height, chroma), sample_bytes * self.width)
         self.frame_bytes = self.frame_shape[0] * self.frame_shape[1]
         self.frames_read = 0
 
@@ -174,14 +200,25 @@ class Y4MReader(_Reader):
 
     depths: the bit depths the caller is ready for, a subset of (8, 10).  With 10 among them C420p10 is accepted as well:
     `layout` is "i420p10", `colorspace` "420p10", and a frame is uint8 [3 H / 2, 2 W], every sample 2 bytes little-endian
-    with its value in the low 10 bits.  The default (8,) refuses it like any other format."""
+    with its value in the low 10 bits.  The default (8,) refuses it like any other format.
+
+    chromas: the chroma samplings the caller is ready for, a subset of ("420", "422").  With "422" among them C422 (and, with
+    10 among depths, C422p10) is accepted as well: `layout` is "i422" / "i422p10" and a frame is uint8 [2 H, W] / [2 H, 2 W],
+    H rows of Y, then the U plane and the V plane of H x W / 2 each.  The default ("420",) refuses them like any other
+    format."""
     layout = "i420"
 
-    def __init__(self, fileobj, depths=(8,)):
+    def __init__(self, fileobj, depths=(8,), chromas=("420",)):
         depths = tuple(depths)
         if not depths or any(d not in (8, 10) for d in depths):
             raise ValueError("depths must be a non-empty subset of (8, 10), got %r" % (depths,))
-        accepted = (CHROMA_420 if 8 in depths else ()) + (CHROMA_420_P10 if 10 in depths else ())
+        chromas = _check_chromas(chromas)
+        accepted = ()
+        if "420" in chromas:
+            accepted += (CHROMA_420 if 8 in depths else ()) + (CHROMA_420_P10 if 10 in depths else ())
+        if "422" in chromas:
+            accepted += (CHROMA_422 if 8 in depths else ()) + (CHROMA_422_P10 if 10 in depths else ())
+        sampling = " and ".join("4:2:" + c[2] for c in sorted(chromas))
         sample_bytes = 1 if 8 in depths else 2   # without a C tag a stream is 8-bit 4:2:0
         line = _read_line(fileobj)
         if line is None:
@@ -212,10 +249,10 @@ class Y4MReader(_Reader):
                 self.interlace = tag[1:]
             elif key == "C":
                 if tag[1:] not in accepted:
-                    raise Y4MError("tag %s: only %s 4:2:0 is supported (%s)" % (tag, " and ".join("%d-bit" % d for d in sorted(depths)),
-                                                                                ", ".join("C" + c for c in accepted)))
+                    raise Y4MError("tag %s: only %s %s is supported (%s)" % (tag, " and ".join("%d-bit" % d for d in sorted(depths)),
+                                                                             sampling, ", ".join("C" + c for c in accepted)))
                 self.colorspace = tag[1:]
-                sample_bytes = 2 if tag[1:] in CHROMA_420_P10 else 1
+                sample_bytes = 2 if tag[1:] in CHROMA_420_P10 + CHROMA_422_P10 else 1
             elif key not in "WH":
                 tags.append(tag)
         if width is None or height is None:
@@ -223,10 +260,12 @@ class Y4MReader(_Reader):
         check_size(width, height, "W", "H")
         if self.colorspace is None and 8 not in depths:
             raise Y4MError("the Y4M header has no C tag, which means 8-bit 4:2:0, and depths=%r does not take it" % (depths,))
+        if self.colorspace is None and "420" not in chromas:
+            raise Y4MError("the Y4M header has no C tag, which means 8-bit 4:2:0, and chromas=%r does not take it" % (chromas,))
         self.tags = tuple(tags)
-        if sample_bytes == 2:
-            self.layout = "i420p10"
-        self._init_frames(fileobj, width, height, sample_bytes)
+        chroma = "422" if self.colorspace in CHROMA_422 + CHROMA_422_P10 else "420"
+        self.layout = ("i422" if chroma == "422" else "i420") + ("p10" if sample_bytes == 2 else "")
+        self._init_frames(fileobj, width, height, sample_bytes, chroma)
 
     def readinto(self, buf):
         view = _frame_view(buf, self.frame_bytes)
@@ -279,13 +318,34 @@ class RawP010Reader(RawNV12Reader):
         self._init_frames(fileobj, width, height, 2)
 
 
+class RawNV16Reader(RawNV12Reader):
+    """Header-less NV16 (`-f rawvideo -pix_fmt nv16`): frames of 2 W H bytes, [2 H, W] uint8 with H rows of Y and H rows of
+    interleaved U V.  RawNV12Reader's interface."""
+    layout = "nv16"
+
+    def __init__(self, fileobj, width, height):
+        check_size(int(width), int(height))
+        self._init_frames(fileobj, width, height, 1, "422")
+
+
+class RawP210Reader(RawNV12Reader):
+    """Header-less P210 (`-f rawvideo -pix_fmt p210le`): frames of 4 W H bytes, uint8 [2 H, 2 W] -- H rows of Y and H rows of
+    interleaved U V, every sample a 16-bit little-endian word with its value in the high 10 bits.  RawNV12Reader's
+    interface."""
+    layout = "p210"
+
+    def __init__(self, fileobj, width, height):
+        check_size(int(width), int(height))
+        self._init_frames(fileobj, width, height, 2, "422")
+
+
 class _Writer(object):
     layout = None
 
-    def _init_frames(self, fileobj, width, height, sample_bytes=1):
+    def _init_frames(self, fileobj, width, height, sample_bytes=1, chroma="420"):
         self.fileobj, self.width, self.height = fileobj, int(width), int(height)
         check_size(self.width, self.height)
-        self.frame_shape = (3 * self.height // 2, sample_bytes * self.width)
+        self.frame_shape = (_frame_rows(self.height, chroma), sample_bytes * self.width)
         self.frame_bytes = self.frame_shape[0] * self.frame_shape[1]
         self.frames_written = 0
 
@@ -307,16 +367,22 @@ class Y4MWriter(_Writer):
     """Writes the stream header once, then `FRAME\\n` and the I420 bytes per `write(frame)`.  fps and aspect are a
     Fraction, (num, den), an int or "N/D"; aspect, interlace and colorspace of None leave their tag out; `tags` are appended
     verbatim (a reader's `tags`, to carry XCOLORRANGE and the like through).  colorspace="420p10": 10-bit frames, uint8
-    [3 H / 2, 2 W] as Y4MReader hands them over; `layout` is then "i420p10"."""
+    [3 H / 2, 2 W] as Y4MReader hands them over; `layout` is then "i420p10".  chromas: with "422" among them
+    colorspace="422" and "422p10" are written too (frames [2 H, W] / [2 H, 2 W], `layout` "i422" / "i422p10"); the default
+    ("420",) refuses them."""
     layout = "i420"
 
-    def __init__(self, fileobj, width, height, fps, aspect=None, colorspace="420jpeg", tags=(), interlace="p"):
-        if colorspace is not None and colorspace not in CHROMA_420 + CHROMA_420_P10:
-            raise Y4MError("colorspace %r: only 8-bit and 10-bit 4:2:0 is written (%s)"
-                           % (colorspace, ", ".join(CHROMA_420 + CHROMA_420_P10)))
-        if colorspace in CHROMA_420_P10:
-            self.layout = "i420p10"
-        self._init_frames(fileobj, width, height, 2 if colorspace in CHROMA_420_P10 else 1)
+    def __init__(self, fileobj, width, height, fps, aspect=None, colorspace="420jpeg", tags=(), interlace="p", chromas=("420",)):
+        chromas = _check_chromas(chromas)
+        written = (CHROMA_420 + CHROMA_420_P10 if "420" in chromas else ()) + (CHROMA_422 + CHROMA_422_P10 if "422" in chromas else ())
+        if colorspace is None and "420" not in chromas:
+            raise Y4MError("colorspace None means 8-bit 4:2:0, and chromas=%r does not write it" % (chromas,))
+        if colorspace is not None and colorspace not in written:
+            raise Y4MError("colorspace %r: only 8-bit and 10-bit %s is written (%s)"
+                           % (colorspace, " and ".join("4:2:" + c[2] for c in sorted(chromas)), ", ".join(written)))
+        p10, chroma = colorspace in CHROMA_420_P10 + CHROMA_422_P10, "422" if colorspace in CHROMA_422 + CHROMA_422_P10 else "420"
+        self.layout = ("i422" if chroma == "422" else "i420") + ("p10" if p10 else "")
+        self._init_frames(fileobj, width, height, 2 if p10 else 1, chroma)
         self.fps = _as_ratio(fps, "fps")
         self.aspect = None if aspect is None else _as_ratio(aspect, "aspect")
         if interlace not in (None, "p", "?"):
@@ -365,6 +431,46 @@ class RawP010Writer(_Writer):
         self.frames_written += 1
 
 
+class RawNV16Writer(_Writer):
+    """Header-less NV16: `write(frame)` writes the 2 W H bytes of an NV16 frame [2 H, W]."""
+    layout = "nv16"
+
+    def __init__(self, fileobj, width, height):
+        self._init_frames(fileobj, width, height, 1, "422")
+
+    def write(self, frame):
+        self._write_all(_frame_view(frame, self.frame_bytes))
+        self.frames_written += 1
+
+
+class RawP210Writer(_Writer):
+    """Header-less P210: `write(frame)` writes the 4 W H bytes of a P210 frame, uint8 [2 H, 2 W]."""
+    layout = "p210"
+
+    def __init__(self, fileobj, width, height):
+        self._init_frames(fileobj, width, height, 2, "422")
+
+    def write(self, frame):
+        self._write_all(_frame_view(frame, self.frame_bytes))
+        self.frames_written += 1
+
+
+def _planes_422(t):
+    """`_planes` for 4:2:2: a frame [2 H, W] or a batch [n, 2 H, W] as views (y [n, H W], chroma [n, H W], H, W)."""
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3:
+        raise ValueError("a frame is [2 H, W] and a batch [n, 2 H, W], got %s" % (tuple(t.shape),))
+    n, R, W = (int(v) for v in t.shape)
+    H = R // 2
+    if R % 2 or H % 2 or W % 2:
+        raise ValueError("4:2:2 frames [2 H, W] need even H and W, got %s" % (tuple(t.shape),))
+    if n > 0 and (t.stride(2) != 1 or t.stride(1) != W):
+        raise ValueError("the rows of a frame must be contiguous (strides %s)" % (tuple(t.stride()),))
+    flat = t.as_strided((n, R * W), (t.stride(0), 1), t.storage_offset())
+    return flat[:, :H * W], flat[:, H * W:], H, W
+
+
 def _planes(t):
     """A frame [3 H / 2, W] or a batch [n, 3 H / 2, W] as views: (y [n, H W], chroma [n, H W / 2], H, W)."""
     if t.dim() == 2:
@@ -393,12 +499,13 @@ def _repack_out(src, out):
     return out
 
 
-def _repack(src, out, to_nv12, given=None):
-    """The two strided copies; given: the caller's own `out` (already checked) in the place of the check here."""
+def _repack(src, out, to_nv12, given=None, planes=_planes):
+    """The two strided copies; given: the caller's own `out` (already checked) in the place of the check here.  planes:
+    `_planes`, or `_planes_422` for frames whose chroma planes have H rows."""
     out = _repack_out(src, out) if given is None else out
-    sy, sc, H, W = _planes(src)
-    oy, oc, _, _ = _planes(out)
-    n, q = int(sy.shape[0]), H * W // 4
+    sy, sc, H, W = planes(src)
+    oy, oc, _, _ = planes(out)
+    n, q = int(sy.shape[0]), int(sc.shape[1]) // 2   # the samples of one chroma plane
     oy.copy_(sy)
     if to_nv12:   # U plane | V plane -> U0 V0 U1 V1 ...
         oc.view(n, q, 2).copy_(sc.view(n, 2, q).transpose(1, 2))
@@ -419,13 +526,13 @@ def nv12_to_i420(src, out=None):
     return _repack(src, out, False)
 
 
-def _words(t, what):
+def _words(t, what, layout=("4:2:0", "3 H / 2")):
     """A 10-bit frame or batch, uint8 [..., 3 H / 2, 2 W], as int16 words [..., 3 H / 2, W] over the same memory (int16: the
-    16-bit type every torch has; the bits are what matters)."""
+    16-bit type every torch has; the bits are what matters).  layout: the names its message uses."""
     import torch
     if t.dtype != torch.uint8 or t.dim() not in (2, 3) or int(t.shape[-1]) % 4:
-        raise ValueError("%s: a 10-bit 4:2:0 frame is uint8 [3 H / 2, 2 W] with even W (a batch [n, 3 H / 2, 2 W]), got %s %s"
-                         % (what, t.dtype, tuple(t.shape)))
+        raise ValueError("%s: a 10-bit %s frame is uint8 [%s, 2 W] with even W (a batch [n, %s, 2 W]), got %s %s"
+                         % (what, layout[0], layout[1], layout[1], t.dtype, tuple(t.shape)))
     if t.numel() and (t.stride(-1) != 1 or any(s % 2 for s in t.stride()[:-1]) or t.data_ptr() % 2):
         raise ValueError("%s: the rows of a frame must be contiguous and 2-byte aligned (strides %s)" % (what, tuple(t.stride())))
     return t.view(torch.int16)
@@ -449,6 +556,40 @@ def p010_to_i420p10(src, out=None):
     out = _repack_out(src, out)
     o16 = _words(out, "out")
     _repack(_words(src, "src"), o16, False, given=out)
+    o16.bitwise_right_shift_(6).bitwise_and_(0x03FF)
+    return out
+
+
+def i422_to_nv16(src, out=None):
+    """I422 (Y, the U plane, the V plane of H x W / 2 each) -> NV16 (Y, H rows of interleaved U V) for a uint8 tensor
+    [2 H, W] or a batch [n, 2 H, W]: `i420_to_nv12`'s contract at the 4:2:2 plane size."""
+    return _repack(src, out, True, planes=_planes_422)
+
+
+def nv16_to_i422(src, out=None):
+    """The inverse of `i422_to_nv16`, with the same contract."""
+    return _repack(src, out, False, planes=_planes_422)
+
+
+_L422 = ("4:2:2", "2 H")
+
+
+def i422p10_to_p210(src, out=None):
+    """C422p10 frames as Y4MReader(depths=(8, 10), chromas=("420", "422")) yields them (uint8 [2 H, 2 W] or a batch, value in
+    the low 10 bits) -> P210 (Y, interleaved U V, value in the HIGH 10 bits): `i420p10_to_p010`'s contract at the 4:2:2
+    plane size."""
+    out = _repack_out(src, out)
+    o16 = _words(out, "out", _L422)
+    _repack(_words(src, "src", _L422), o16, True, given=out, planes=_planes_422)
+    o16.bitwise_left_shift_(6)
+    return out
+
+
+def p210_to_i422p10(src, out=None):
+    """The inverse for P210 words, as `p010_to_i420p10`: an unsigned shift by 6, then U and V split into planes."""
+    out = _repack_out(src, out)
+    o16 = _words(out, "out", _L422)
+    _repack(_words(src, "src", _L422), o16, False, given=out, planes=_planes_422)
     o16.bitwise_right_shift_(6).bitwise_and_(0x03FF)
     return out
 

@@ -13,6 +13,9 @@ each step returns the stabilised surfaces at source size in the same layout, rea
 --format p010: the same for 10-bit surfaces (HEVC Main10 from a hardware decoder): uint16 [3 H0 / 2, W0], the sample in
 each word's high 10 bits; all ten bits come back warped, the network looks at the words' high bytes.
 
+--format nv16 | p210: 4:2:2 surfaces (camera originals, mezzanine files), uint8 [2 H0, W0] and uint16 [2 H0, W0]: H0 rows of Y,
+then H0 rows of interleaved U V.  Every chroma row comes back warped; the network looks at the even ones.
+
 --crop auto|Z: the frames come back without sampler A's black border.  Z in (0, 1] is a fixed zoom; "auto" keeps one zoom
 per stream on the device and only ever lowers it (OnlineStabilizer(crop="auto")); the zoom each stream has reached is
 printed at the end.
@@ -58,21 +61,25 @@ def synthetic_source(seed, n, h, w, cut_at=None):
         yield np.ascontiguousarray((_scene(bank[k % 8], k, cut_at) * 255).astype(np.uint8))
 
 
-def synthetic_nv12_source(seed, n, h, w, cut_at=None):
-    """Yields n NV12 frames [3h/2, w] uint8 (h rows of Y, h/2 rows of U0 V0 U1 V1 ...), limited range, one at a time."""
+def synthetic_nv12_source(seed, n, h, w, cut_at=None, rows_c=None):
+    """Yields n NV12 frames [3h/2, w] uint8 (h rows of Y, h/2 rows of U0 V0 U1 V1 ...), limited range, one at a time.
+    rows_c=h: NV16 frames [2h, w], h chroma rows."""
     import inputs
+    rows_c = h // 2 if rows_c is None else rows_c
     y = inputs.smooth_frames(seed, 8, h, w, C=1)[..., 0]
-    c = (16 + inputs.smooth_frames(seed + 100, 8, h // 2, w // 2, C=2) * 224).reshape(8, h // 2, w)
+    c = (16 + inputs.smooth_frames(seed + 100, 8, rows_c, w // 2, C=2) * 224).reshape(8, rows_c, w)
     for k in range(n):
         yk = 16 + _scene(y[k % 8], k, cut_at) * 219
         yield np.ascontiguousarray(np.concatenate([yk, c[k % 8]], axis=0).astype(np.uint8))
 
 
-def synthetic_p010_source(seed, n, h, w, cut_at=None):
-    """Yields n P010 frames [3h/2, w] uint16 (the sample in the high 10 bits, limited range 64 .. 940 / 960), one at a time."""
+def synthetic_p010_source(seed, n, h, w, cut_at=None, rows_c=None):
+    """Yields n P010 frames [3h/2, w] uint16 (the sample in the high 10 bits, limited range 64 .. 940 / 960), one at a time.
+    rows_c=h: P210 frames [2h, w], h chroma rows."""
     import inputs
+    rows_c = h // 2 if rows_c is None else rows_c
     y = inputs.smooth_frames(seed, 8, h, w, C=1)[..., 0]
-    c = (64 + inputs.smooth_frames(seed + 100, 8, h // 2, w // 2, C=2) * 896).reshape(8, h // 2, w)
+    c = (64 + inputs.smooth_frames(seed + 100, 8, rows_c, w // 2, C=2) * 896).reshape(8, rows_c, w)
     for k in range(n):
         yk = 64 + _scene(y[k % 8], k, cut_at) * 876
         yield np.ascontiguousarray(np.concatenate([yk, c[k % 8]], axis=0).astype(np.uint16) << 6)
@@ -85,7 +92,7 @@ def main():
     ap.add_argument("--height", type=int, default=288)    # config.py:12-13
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--precision", default="f32", choices=["f32", "f32x3", "f32s", "f16"])
-    ap.add_argument("--format", default="rgb", choices=["rgb", "nv12", "p010"])
+    ap.add_argument("--format", default="rgb", choices=["rgb", "nv12", "p010", "nv16", "p210"])
     ap.add_argument("--crop", default=None, help="'auto' or a zoom in (0, 1]")
     ap.add_argument("--scene-cut", type=float, default=None, metavar="THR", help="detect scene cuts: a threshold in (0, 1]")
     ap.add_argument("--render-filter", default="bilinear", choices=["bilinear", "bicubic"],
@@ -113,7 +120,7 @@ def main():
     net = StabNet(args.height, args.width).load_weights(make_synthetic_weights(seed=0, c_in=3 * S))
     net.get_evaluation_model(S)
     net.precision = args.precision
-    nv12 = args.format in ("nv12", "p010")   # a decoder's surfaces: two planes, rendered at source size
+    nv12 = args.format in ("nv12", "p010", "nv16", "p210")   # a decoder's surfaces: two planes, rendered at source size
     shape = dict(strength=args.strength, rigidity=args.rigidity, shape_model=args.shape_model)
     shaped = args.strength != 1.0 or args.rigidity != 0.0
     out_size = None
@@ -124,7 +131,12 @@ def main():
         stab = OnlineStabilizer(net, max_streams=args.streams, frame_format=args.format, yuv_matrix="bt709", crop=crop,
                                 render_filter=args.render_filter, border=args.border, out_size=out_size, **shape, **scene,
                                 **window)
-        make = synthetic_nv12_source if args.format == "nv12" else synthetic_p010_source
+        make = synthetic_nv12_source if args.format in ("nv12", "nv16") else synthetic_p010_source
+        if args.format in ("nv16", "p210"):   # 4:2:2: as many chroma rows as luma rows
+            frames_420 = make
+
+            def make(seed, n, h, w, cut_at):
+                return frames_420(seed, n, h, w, cut_at, rows_c=h)
     else:
         stab = OnlineStabilizer(net, max_streams=args.streams, channel_order="bgr",
                                 side_by_side=args.border != "keep" and out_size is None, as_uint8=True, crop=crop,

@@ -366,6 +366,42 @@ int dvsg_locnet_render_surface(const dvsg_locnet_t *net);
 int dvsg_locnet_view_create_scaled(const dvsg_locnet_t *net, int out_H, int out_W, dvsg_locnet_t **view);
 int dvsg_locnet_render_size(const dvsg_locnet_t *net, int *out_H, int *out_W);
 
+/* Chroma sampling: 4:2:2 frames (NV16, and P210 on a DVSG_SURFACE_P010 view).  How many ROWS the interleaved UV plane of the
+ * frames that dvsg_tps_render_nv12 and dvsg_tps_render_zoom_nv12 read and write has is, like the filter, the border, the
+ * shape, the surface format and the size, a property of the handle: no entry point is added for it.  It is orthogonal to the
+ * surface format, which stays "the sample type".  Both functions are host-side: no stream, no device work, everything
+ * decided before anything is allocated.
+ *   dvsg_locnet_view_create_chroma  a view of `net`'s parent that carries `net`'s OWN filter, border, shape, surface format
+ *          and output size (INHERITED, as in dvsg_locnet_view_create_surface and _scaled, which now inherit the chroma format
+ *          as well) and the given chroma format.  An unknown value or a NULL pointer is DVSG_ERR_INVALID_ARG
+ *          ("chroma_format=<n>"); the value is checked before the handle is read.  The view rules are the ones above.
+ *   dvsg_locnet_render_chroma  the handle's value: 0 for NULL, for every handle of dvsg_locnet_create and for every view of
+ *          dvsg_locnet_view_create, _border and _shaped.
+ * ONLY dvsg_tps_render_nv12 and dvsg_tps_render_zoom_nv12 read the property.  Every other entry point -- dvsg_tps_render_u8,
+ * dvsg_tps_render_zoom_u8, dvsg_tps_coverage_net_f32, dvsg_tps_coefficients_f32 and all the rest -- behaves on such a view
+ * exactly as on the same view without it, bit for bit.  dvsg_frames_ingest_nv12 takes no handle and is 4:2:0 only: the network
+ * sees 4:2:2 footage through the NV12 surface made of the Y plane and the EVEN chroma rows.
+ *
+ * Given a DVSG_CHROMA_422 view, the two renders take a 4:2:2 frame through their existing arguments:
+ *   Layout.  The y plane is as before.  The uv plane is interleaved U0 V0 U1 V1 .. of H ROWS (4:2:0: H / 2), each of W / 2
+ *          pairs: W samples, W bytes (P010 words: 2 W bytes), with the same pitch and frame_stride as luma.  A packed tensor is
+ *          [n, 2 H, W] (P210: [n, 2 H, 2 W] bytes) with uv = y + H * pitch and frame_stride = 2 H * pitch.
+ *   Checks.  The NV12 and P010 ones, unchanged: H and W even and >= 4, the pitch rules, 2-byte alignment for words.
+ *   Per plane.  Chroma is an image of (H, W / 2) with C = 2 under the same normalised TPS map: dvsg_tps_warp_f32 / _zoom_f32 on
+ *          a grid of that size, bit for bit, for the bilinear filter.  The filter, the border mode, shaping, zoom and the
+ *          sample and output rules are those of the view's surface format, as their paragraphs above state with (H, W / 2) in
+ *          the place of (H / 2, W / 2).  Luma is what the same view without the property gives, bit for bit.
+ *   Scaled.  On a scaled view chroma maps (H, W / 2) -> (oh, ow / 2) with the same sy, sx; the virtual grid is
+ *          (sy oh, sx ow / 2).  The scaled view's checks stay: oh, ow even and >= 4, factors <= 4, no DVSG_BORDER_KEEP.
+ *   Buffers.  Bytes beyond the used bytes of a row and between frames are never written; no load touches a byte outside the
+ *          used bytes of the source row it reads.
+ *   4:4:4 is not served: its UV row is 2 W samples, which breaks "both planes use the same pitch" for packed frames.
+ *   A handle without the property produces the bytes it produced. */
+#define DVSG_CHROMA_420 0
+#define DVSG_CHROMA_422 1
+int dvsg_locnet_view_create_chroma(const dvsg_locnet_t *net, int chroma_format, dvsg_locnet_t **view);
+int dvsg_locnet_render_chroma(const dvsg_locnet_t *net);
+
 /* patches [B,H,W,c_in] in [0,1] -> F_t [B,25,2].  float32 storage, exact-f32 MFMA
  * (v_mfma_f32_32x32x2_f32) accumulation.  c_in != 21: conv1 is the same arithmetic in the root-conv kernel. */
 int dvsg_locnet_forward_f32(const dvsg_locnet_t *net, const float *patches, int B, int H, int W,

@@ -10,7 +10,7 @@ stabilize_clip on one clip of the same frames is the K = 1 reference.  One JSON 
     python tools/online_bench.py [--steps 40] [--warmup 6] [--sizes 720x1280,288x512] [--precisions f32,f32x3] [--out FILE]
 
 --crop: the cost of OnlineStabilizer(crop=...) per step instead.  K streams of device-resident 1080p frames (--source),
-NV12 surfaces and RGB uint8 with source_res (--formats), through a 512x288 f32 model: one OnlineStabilizer per variant
+NV12 surfaces and RGB uint8 with source_res (--formats; also p010, nv16, p210), through a 512x288 f32 model: one OnlineStabilizer per variant
 (--variants none,0.9,auto: crop=None, a fixed zoom, the per-stream ratchet), all warmed up, then --rounds rounds in each of
 which every variant in turn runs --steps steps between device events, so the variants alternate inside a round.  One JSON
 line per (format, K, variant): the median, smallest and largest step over all rounds.  "none" passes no crop argument at
@@ -147,11 +147,14 @@ def crop_legs(args, weights, emit):
     variants = args.variants.split(",")
     for fmt in args.formats.split(","):
         # 8 distinct frames on the device; stream s at step k reads frame (k + 3 s) % 8
-        if fmt == "nv12":
+        if fmt in ("nv12", "p010", "nv16", "p210"):   # surfaces: 4:2:2 has H0 chroma rows; words are byte << 8
+            rows_c = H0 if fmt in ("nv16", "p210") else H0 // 2
             y = 16 + inputs.smooth_frames(11, 8, H0, W0, C=1, factor=32)[..., 0] * 219
-            c = 16 + inputs.smooth_frames(12, 8, H0 // 2, W0 // 2, C=2, factor=32) * 224
-            bank = torch.from_numpy(np.concatenate([y, c.reshape(8, H0 // 2, W0)], axis=1).astype(np.uint8)).cuda()
-            base = dict(frame_format="nv12")
+            c = 16 + inputs.smooth_frames(12, 8, rows_c, W0 // 2, C=2, factor=32) * 224
+            bank = torch.from_numpy(np.concatenate([y, c.reshape(8, rows_c, W0)], axis=1).astype(np.uint8)).cuda()
+            if fmt in ("p010", "p210"):
+                bank = torch.stack([torch.zeros_like(bank), bank], dim=-1).reshape(8, H0 + rows_c, 2 * W0).contiguous()
+            base = dict(frame_format=fmt)
         else:
             bank = torch.from_numpy((inputs.smooth_frames(11, 8, H0, W0, factor=32) * 255).astype(np.uint8)).cuda()
             base = dict(source_res=True, as_uint8=True)
