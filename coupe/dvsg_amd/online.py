@@ -755,7 +755,8 @@ class OnlineStabilizer(object):
             if buf is None:
                 buf = torch.empty((self.max_streams, 3 * H0 // 2, W0), dtype=torch.uint8, device=dev)
                 if SURFACE_OF[self.frame_format][1] == "422":
-                    picked = torch.cat([torch.arange(H0), torch.arange(H0, 2 * H0, 2)]).to(dev)
+                    # made on the device: a copy of a host index would wait for the caller's stream
+                    picked = torch.cat([torch.arange(H0, device=dev), torch.arange(H0, 2 * H0, 2, device=dev)])
                 self._hi[(H0, W0)] = (buf, picked)
             seen = buf[:j - i]
             hi = src[..., 1::2] if self.frame_format in WORD_FORMATS else src

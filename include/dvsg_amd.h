@@ -20,7 +20,9 @@
  *     Calls on distinct streams are re-entrant as long as their output / workspace buffers
  *     are distinct.  tests/test_gpu_streams.py holds every entry point with a `stream` to this:
  *     captured into a HIP graph and replayed on fresh values, and in pairs on two streams of one
- *     handle.  The exceptions say "synchronous" in their own comment (the float16 calibration:
+ *     handle.  The four source-size renders are held to it through every view constructor below (filter, border,
+ *     shape, surface format, output size, chroma format), and while another thread makes and destroys views.
+ *     The exceptions say "synchronous" in their own comment (the float16 calibration:
  *     it waits for `stream`, in every mode, before it rewrites the handle's weights).  Found
  *     with that module and fixed: dvsg_scene_step_f32 zeroed its histograms with a memset node,
  *     which did not take effect on the second and later replays of a captured step (it is a

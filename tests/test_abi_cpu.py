@@ -80,6 +80,37 @@ def test_every_stream_entry_point_is_held_to_the_stream_contract_or_exempt():
         assert re.search(r"synchronous|host|debug", reason + " " + name, flags=re.I), name
 
 
+def test_every_view_constructor_has_stream_cases():
+    """The four source-size renders are registered in tests/test_gpu_streams.py once per row of its VIEWS table, and every view
+    constructor the header declares is named by VIEW_CONSTRUCTORS with the rows built through it: a new view property fails
+    here until someone gives it a stream case.  Imported without torch, as above."""
+    import sys
+    had_torch = "torch" in sys.modules
+    import test_gpu_streams as streams
+    assert had_torch or "torch" not in sys.modules, "tests/test_gpu_streams.py imports torch at module level"
+    declared = sorted(s for s in declared_symbols() if s.startswith("dvsg_locnet_view_create"))
+    assert len(declared) >= 6 and "dvsg_locnet_view_create" in declared and "dvsg_locnet_view_create_chroma" in declared
+    missing = sorted(set(declared) - set(streams.VIEW_CONSTRUCTORS))
+    assert not missing, "no view of tests/test_gpu_streams.py is built through %s" % missing
+    stale = sorted(set(streams.VIEW_CONSTRUCTORS) - set(declared))
+    assert not stale, "named, but the header declares no such constructor: %s" % stale
+    for name, labels in streams.VIEW_CONSTRUCTORS.items():
+        assert labels, "%s: no label" % name
+        unknown = sorted(set(labels) - set(streams.VIEWS))
+        assert not unknown, "%s names labels that VIEWS does not have: %s" % (name, unknown)
+    # the mapping is what LocNet.view's chain gives for each row's arguments, and every row is a registered case
+    for label in streams.VIEWS:
+        named = sorted(n for n, labels in streams.VIEW_CONSTRUCTORS.items() if label in labels)
+        assert named == sorted(streams.constructors_of(label)) and named, (label, named, streams.constructors_of(label))
+    renders = {"dvsg_tps_render_u8": streams.RGB_VIEWS, "dvsg_tps_render_zoom_u8": streams.RGB_VIEWS,
+               "dvsg_tps_render_nv12": streams.SURFACE_VIEWS, "dvsg_tps_render_zoom_nv12": streams.SURFACE_VIEWS}
+    assert set(streams.RGB_VIEWS) | set(streams.SURFACE_VIEWS) == set(streams.VIEWS)
+    for name, labels in renders.items():
+        assert [f.label for f in streams.CASES[name]] == [""] + list(labels), name
+    for name in ("dvsg_tps_coefficients_f32", "dvsg_tps_coverage_net_f32"):
+        assert [f.label for f in streams.CASES[name]] == ["", "shaped"], name
+
+
 def test_bad_arguments_return_status_not_abort(lib):
     from coupe.dvsg_amd import DvsgError, _lib
     assert lib.dvsg_tps_solve_f32(None, None, 1, 1, 25, None, None) == -1

@@ -6,24 +6,45 @@ BIT equality of a call against the same call run alone or eagerly, and no number
 0. `CASES` maps every such entry point to one or more builders; `EXEMPT` names the ones the header itself documents as
    synchronous (tests/test_abi_cpu.py checks on the CPU that the two cover the header).  A builder allocates everything up
    front and returns a `Case`: input, output and state tensors and `issue(stream)`, which makes exactly ONE ABI call through
-   `_lib.call` and allocates nothing.
+   `_lib.call` and allocates nothing.  The four source-size renders are registered once on the plain handle and once per row
+   of `VIEWS` (label -> LocNet.view arguments), on the plain and on the _zoom_ entry point: every kernel family behind a
+   view property (bicubic, the three border modes, shaping, P010 words, a delivery size, 4:2:2 chroma rows) is launched,
+   and dvsg_tps_coefficients_f32 and dvsg_tps_coverage_net_f32 are given the shaped view.  `VIEW_CONSTRUCTORS` names, for
+   every view constructor of the header, the rows built through it (tests/test_abi_cpu.py holds it to the header and to
+   the rows' arguments on the CPU).  No row of the table is refused by render_scaled_check.  View handles are made in the
+   builder with LocNet.view (`cubic` by dvsg_locnet_view_create itself, which LocNet.view never calls).  What makes such a case able to fail is asserted on its eager references before any replay is compared
+   (`ViewCheck`): the outputs of the three seeds differ pairwise; the output differs from that of the same call through
+   the plain handle on the same inputs while T is the plain handle's bit for bit (on a shaped view T differs); and a
+   `keep` output, poisoned beforehand, has bytes inside each plane that still are the poison and bytes that are not.
 1. Capture and replay: `issue` is captured on one non-blocking stream into a HIP graph (default capture error mode: an
    allocation, a free, a synchronisation or a launch on another stream inside the call fails the capture) and replayed three
    times on fresh input values, restored state and poisoned outputs; each replay equals the eager call on those values.  The
    scene step carries its state through the three replays as three consecutive steps.
 2. Re-entrancy at the ABI: pairs of cases on two non-blocking streams of ONE handle, each with its own workspace of exactly
    dvsg_locnet_workspace_bytes between sentinels, released together by one event; once more from two Python threads, each of
-   which also makes an invalid call and reads its own dvsg_last_error_string().
+   which also makes an invalid call and reads its own dvsg_last_error_string().  Four of the pairs are views of one parent:
+   two delivery sizes on a shared F_t, a P010 beside an NV16 view, one scaled view twice, and the plain handle beside a
+   scaled view on one source buffer.
+2a. The table of scaled views (g_scaled_views, locnet.hip: the library's one process-global host table on a hot path, read
+   by every NV12 render before it touches the handle): two threads render through scaled views while a third makes and
+   destroys 64 scaled views of the same parent; the renders equal their runs alone, the sizes of the views used and of the
+   plain handle are unchanged, the parent's views are those from before, and each thread's refused call names the size of
+   its own view.
 3. The Python facade: LocNet.workspace is per stream; forward / stabilize / tap of one LocNet under two torch streams, and two
-   OnlineStabilizers that share a model, equal the serial runs.
+   OnlineStabilizers that share a model, equal the serial runs -- with default options, and as an NV12 stream (bicubic,
+   mirrored border, crop="auto", a scene cut at its third step, asserted) beside a P210 stream at half strength and size.
 4. Calibration is synchronous: a float16 forward queued on a non-blocking stream in front of dvsg_locnet_calibrate_f16(NULL)
    or dvsg_debug_calibrate_f16_weights(mode 0 / 1) on that stream still runs on the weights it was issued against.
 
 The bounded delay of 2-4 is ordinary work, a chain of torch.matmul sized once per module with events (about 20 ms).  A run is
 CONCLUSIVE when the event recorded right behind the delay has not completed at the moment the host returns from issuing the
 calls under test; an inconclusive run doubles the chain, at most four times, and then FAILS.  A condition, not a tolerance.
-Measured on one MI355X: 156 cases in 23 s, every delayed case conclusive behind one chain; the slowest cases are the three
-calibration ones (2-3 s: each re-rounds 25 M weights on the host several times).
+Measured on one MI355X: 198 cases in 34.6 s, next to 21.7 s for the 156 cases of the module before the views, on the same
+machine in the same run (26.7 s for the 198 on another machine); every delayed case conclusive behind one chain; the slowest
+cases are the three calibration ones (2-3 s: each re-rounds 25 M weights on the host several times), the two facade pairs of
+OnlineStabilizers take about 1 s each and every view case well under 0.2 s.  `keep` is visible at the default scale of
+vectors(): the poisoned `keep` outputs hold 69 to 1722 untouched samples of 17649 (RGB, float32) and 70 to 1436 untouched
+bytes per plane (NV12), the small counts under the zoom.
 
 Found with this module (the paragraph is in the header's "Conventions" block).  Against the library and facade from before
 the fixes: the captured dvsg_scene_step_f32 differed from its second replay on (a memset node zeroed the histograms and did
@@ -33,7 +54,13 @@ dvsg_debug_calibrate_f16_weights rewrote the weights under a queued float16 forw
 dvsg_locnet_calibrate_f16, which has the same defect in the code, happened to pass: the 20 ms delay ran out before redo()
 reached the layers that forward reads.  Sections 1 (every other case) and 2 passed before and after.  The parity taps'
 hipMemcpyAsync (device to device, locnet.hip) is captured as a memcpy node and replays correctly: every
-dvsg_locnet_forward_tap_* case below passes, so it needs no kernel of its own."""
+dvsg_locnet_forward_tap_* case below passes, so it needs no kernel of its own.
+With the views (sections 0 to 3 extended): every capture case, the four pairs of views and the thread test on the table of
+scaled views passed against the library as it was; the dispatch and the table needed no change.  The facade pair on the
+newer formats did not: before, the run was inconclusive behind every delay up to 16 chains of 20 ms, because the first
+step of an "nv16" / "p210" OnlineStabilizer built the index of the even chroma rows on the host and copied it to the device,
+and that copy waits for the caller's stream ("device tensors in still means nothing synchronised", online.py); after, with
+the index made on the device, it is conclusive behind one chain and equals the serial run, bit for bit."""
 import ctypes
 import gc
 import threading
@@ -54,6 +81,77 @@ SRC = (37, 53)                              # tests/test_gpu_source_res.py's odd
 NV = (38, 54)                               # tests/test_gpu_nv12.py's MODEL
 LOSS = (3, 33, 65)                          # tests/test_gpu_losses.py
 SCENE = (37, 53, 3)                         # tests/test_gpu_scene.py
+SURF = (68, 102)                            # the NV12 / P010 / 4:2:2 source of the surface renders
+
+# label -> the LocNet.view arguments of a view the four source-size renders are given.  Every row is registered on the plain
+# and on the _zoom_ entry point; what it launches is read off tps_render_impl (warp_kernels.hip) and tps_render_nv12_impl
+# (nv12.hip).  The scaled sizes give factors 2 x 2 and 3 x 3 (37 / 13 and 53 / 18 do not divide), are even and >= 4 for the
+# surfaces, and no scaled row asks for `keep` (render_scaled_check): no row is refused.
+_SHAPE = dict(strength=0.25, rigidity=0.75, shape_model="similarity")
+VIEWS = {
+    # RGB and surface rows
+    "cubic": dict(render_filter="bicubic"),                                   # tps_ / nv12_render_cubic_kernel
+    # RGB rows
+    "replicate": dict(border="replicate"),                                    # tps_render_border_kernel
+    "cubic-mirror": dict(render_filter="bicubic", border="mirror"),           # tps_render_border_kernel, cubic
+    "keep": dict(border="keep"),                                              # tps_render_border_kernel, keep
+    "shaped": dict(**_SHAPE),                                                 # tps_shape_apply_kernel forms T
+    "scaled-2x2": dict(out_size=(19, 27)),                                    # tps_render_scaled_kernel
+    "scaled-3x3-cubic-mirror": dict(render_filter="bicubic", border="mirror", out_size=(13, 18)),
+    # surface rows
+    "mirror": dict(border="mirror"),                                          # nv12_render_border_kernel
+    "cubic-keep": dict(render_filter="bicubic", border="keep"),               # nv12_render_border_kernel, cubic, keep
+    "p010": dict(surface="p010"),                                             # p010_render_kernel
+    "p010-cubic-replicate": dict(render_filter="bicubic", border="replicate", surface="p010"),
+    "scaled-3x3": dict(out_size=(24, 36)),                                    # nv12_render_scaled_kernel on bytes
+    "p010-scaled-2x2-cubic-mirror": dict(render_filter="bicubic", border="mirror", surface="p010", out_size=(34, 52)),
+    "nv16": dict(chroma="422"),                                               # the NV12 kernels, chroma rows = H
+    "p210-cubic-mirror-shaped": dict(render_filter="bicubic", border="mirror", surface="p010", chroma="422", **_SHAPE),
+    "p210-scaled-2x2": dict(surface="p010", out_size=(34, 52), chroma="422"),  # nv12_render_scaled_kernel, words, 4:2:2
+}
+RGB_VIEWS = ("cubic", "replicate", "cubic-mirror", "keep", "shaped", "scaled-2x2", "scaled-3x3-cubic-mirror")
+SURFACE_VIEWS = ("cubic", "mirror", "cubic-keep", "p010", "p010-cubic-replicate", "scaled-3x3", "p010-scaled-2x2-cubic-mirror",
+                 "nv16", "p210-cubic-mirror-shaped", "p210-scaled-2x2")
+# Every view constructor of the header -> the labels built through it (tests/test_abi_cpu.py: each declared constructor is
+# here, none is empty, every label exists, and the entries are what `constructors_of` derives from the arguments).
+# LocNet.view never calls dvsg_locnet_view_create (it is dvsg_locnet_view_create_border with a black border), so the views
+# listed for it are made by that constructor itself (`_view`) and destroyed with the module's context.
+VIEW_CONSTRUCTORS = {
+    "dvsg_locnet_view_create": ("cubic",),
+    "dvsg_locnet_view_create_border": ("replicate", "cubic-mirror", "keep", "scaled-3x3-cubic-mirror", "mirror", "cubic-keep",
+                                       "p010-cubic-replicate", "p010-scaled-2x2-cubic-mirror"),
+    "dvsg_locnet_view_create_shaped": ("shaped", "p210-cubic-mirror-shaped"),
+    "dvsg_locnet_view_create_surface": ("p010", "p010-cubic-replicate", "p010-scaled-2x2-cubic-mirror",
+                                        "p210-cubic-mirror-shaped", "p210-scaled-2x2"),
+    "dvsg_locnet_view_create_scaled": ("scaled-2x2", "scaled-3x3-cubic-mirror", "scaled-3x3", "p010-scaled-2x2-cubic-mirror",
+                                       "p210-scaled-2x2"),
+    "dvsg_locnet_view_create_chroma": ("nv16", "p210-cubic-mirror-shaped", "p210-scaled-2x2"),
+}
+
+
+def _shaped(label):
+    kw = VIEWS.get(label, {})
+    return kw.get("strength", 1.0) != 1.0 or kw.get("rigidity", 0.0) != 0.0
+
+
+def constructors_of(label):
+    """The constructors the view of `label` is built through: LocNet.view's chain (coupe/dvsg_amd/networks.py), innermost
+    first, with dvsg_locnet_view_create in the place of _border for the labels `_view` makes with it."""
+    kw, chain = VIEWS[label], []
+    if _shaped(label):
+        chain.append("dvsg_locnet_view_create_shaped")
+    elif label in VIEW_CONSTRUCTORS["dvsg_locnet_view_create"]:
+        assert kw.get("border", "black") == "black", "dvsg_locnet_view_create takes a filter only"
+        chain.append("dvsg_locnet_view_create")
+    elif kw.get("render_filter", "bilinear") != "bilinear" or kw.get("border", "black") != "black":
+        chain.append("dvsg_locnet_view_create_border")
+    if kw.get("surface", "nv12") != "nv12":
+        chain.append("dvsg_locnet_view_create_surface")
+    if kw.get("out_size") is not None:
+        chain.append("dvsg_locnet_view_create_scaled")
+    if kw.get("chroma", "420") != "420":
+        chain.append("dvsg_locnet_view_create_chroma")
+    return chain
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -112,6 +210,7 @@ class Case(object):
         self.inputs, self.outputs, self.state, self.also, self.guards, self.keep = [], [], [], [], [], []
         self.issue = None
         self.carry = False          # the scene step: state runs on through the three replays
+        self.view = None            # a case on a view handle: its `ViewCheck`
 
     def inp(self, gen):
         t = gen(0).clone()
@@ -159,6 +258,46 @@ class Case(object):
             assert g.intact(), "%s: a workspace was written outside its bytes" % what
 
 
+class ViewCheck(object):
+    """What makes a case on a view handle able to fail, asserted on its eager references before any replay is compared.
+    plain_issue(stream): the same ABI call through the plain handle on the same inputs, into plain_outputs (the first is T),
+    allocated by the builder.  pairs(w): [(tensor of the snapshot w, the same region of a plain output)], or None for the
+    entry points that write nothing but T and counts.  fresh: the outputs that must differ between any two seeds (default:
+    all).  kept(w): the planes of a `keep` output, [(what, tensor)]."""
+
+    def __init__(self, label, plain_issue, plain_outputs, pairs=None, fresh=None, kept=None):
+        self.label, self.plain_issue, self.plain_outputs = label, plain_issue, plain_outputs
+        self.pairs, self.fresh, self.kept = pairs, fresh, kept
+
+    def check(self, c, want, s, side, what):
+        """want: the eager snapshots of seeds 1, 2, 3; the inputs still hold seed 3's values."""
+        torch = _torch()
+        fresh = range(len(c.outputs)) if self.fresh is None else self.fresh
+        for a, b in ((0, 1), (0, 2), (1, 2)):
+            for i in fresh:
+                assert not torch.equal(_bits(want[a][i]), _bits(want[b][i])), \
+                    "%s: output %d is the same for seeds %d and %d: a replay on stale values would pass" % (what, i, a + 1, b + 1)
+        for t in self.plain_outputs:
+            _poison(t)
+        torch.cuda.synchronize()
+        self.plain_issue(s)
+        side.synchronize()
+        same_T = torch.equal(_bits(want[2][0]), _bits(self.plain_outputs[0]))
+        if _shaped(self.label):
+            assert not same_T, "%s: T of the shaped view is the plain handle's" % what
+        else:
+            assert same_T, "%s: T differs from the plain handle's on an unshaped view" % what
+        if self.pairs is not None:
+            assert any(not torch.equal(_bits(v), _bits(p)) for v, p in self.pairs(want[2])), \
+                "%s: the view renders what the plain handle renders: the property was not exercised" % what
+        if self.kept is not None:
+            for w in want:
+                for name, plane in self.kept(w):
+                    left = int(plane.isnan().sum()) if plane.dtype.is_floating_point else int((plane == POISON).sum())
+                    print("STREAMS %s: %s keeps %d of %d" % (what, name, left, plane.numel()))
+                    assert 0 < left < plane.numel(), "%s: %s keeps %d of %d: `keep` is not visible" % (what, name, left, plane.numel())
+
+
 class Ctx(object):
     """What the builders share: the handle, the ABI, a scratch for the stand-alone convs."""
 
@@ -171,9 +310,44 @@ class Ctx(object):
         self.h = self.net.handle
         self.lib = _lib
         self._scratch = None
+        self._own = {}              # label -> a view made by dvsg_locnet_view_create itself (LocNet.view never calls it)
 
     def call(self, name, *args):
         self.lib.call(name, *args)
+
+    def view(self, label):
+        """The handle of VIEWS[label], made on first use and kept; "": the plain handle."""
+        if not label:
+            return self.h
+        from coupe.dvsg_amd.networks import RENDER_FILTERS
+        kw = VIEWS[label]
+        if label not in VIEW_CONSTRUCTORS["dvsg_locnet_view_create"]:
+            return self.net.view(**kw)
+        v = self._own.get(label)
+        if v is None:
+            assert set(kw) == {"render_filter"}, "dvsg_locnet_view_create takes a filter only"
+            v = self._own[label] = ctypes.c_void_p()
+            self.call("dvsg_locnet_view_create", self.h, RENDER_FILTERS[kw["render_filter"]], ctypes.byref(v))
+        return v
+
+    def render_size(self, handle):
+        oh, ow = ctypes.c_int(-1), ctypes.c_int(-1)
+        self.call("dvsg_locnet_render_size", handle, ctypes.byref(oh), ctypes.byref(ow))
+        return oh.value, ow.value
+
+    def n_views(self):
+        """The live views of the parent, from the refusal of dvsg_locnet_destroy(parent) (the header: "destroying a parent
+        that still has views is DVSG_ERR_INVALID_ARG and destroys nothing"); only asked while LocNet holds a view."""
+        import re
+        assert self.net._views, "the parent has no view: dvsg_locnet_destroy would destroy it"
+        lib = self.lib.load()
+        assert lib.dvsg_locnet_destroy(self.h) == -1
+        return int(re.search(r"still has (\d+) view", lib.dvsg_last_error_string().decode()).group(1))
+
+    def close(self):
+        for v in self._own.values():
+            self.call("dvsg_locnet_destroy", v)
+        self._own = {}
 
     def ws_bytes(self, B, H, W):
         need = ctypes.c_size_t()
@@ -411,28 +585,49 @@ for _i in (1, 2):
     case("dvsg_tps_coverage_f32", "crop%d" % _i)(_coverage_builder(_i))
 
 
-@case("dvsg_tps_coverage_net_f32")
-def _coverage_net(ctx, n=3):
-    import test_gpu_crop as crop
-    c = Case()
-    oh, ow, sh, sw = 8, crop.KT + 3, 9, 300        # the grid and source of crop.CASES[2]
-    F = c.inp(vectors(n, 3, scale=0.08))
-    z = c.inp(fixed(crop.ZOOMS[:n]))
-    T = c.out((n, 2, 28))
-    nb, km = c.out((n,), _torch().int32), c.out((n,), _torch().int32)
-    ws, wb = c.work(crop.cover_bytes(n, oh, ow))
-    c.issue = lambda s: ctx.call("dvsg_tps_coverage_net_f32", ctx.h, F.data_ptr(), z.data_ptr(), n, sh, sw, oh, ow, T.data_ptr(),
-                                 nb.data_ptr(), km.data_ptr(), ws, wb, s)
-    return c
+def _coverage_net_builder(label=""):
+    def build(ctx, n=3):
+        import test_gpu_crop as crop
+        torch = _torch()
+        c = Case()
+        oh, ow, sh, sw = 8, crop.KT + 3, 9, 300        # the grid and source of crop.CASES[2]
+        F = c.inp(vectors(n, 3, scale=0.08))
+        z = c.inp(fixed(crop.ZOOMS[:n]))
+
+        def call(handle, T, nb, km, ws, wb):
+            return lambda s: ctx.call("dvsg_tps_coverage_net_f32", handle, F.data_ptr(), z.data_ptr(), n, sh, sw, oh, ow,
+                                      T.data_ptr(), nb.data_ptr(), km.data_ptr(), ws, wb, s)
+        T = c.out((n, 2, 28))
+        nb, km = c.out((n,), torch.int32), c.out((n,), torch.int32)
+        c.issue = call(ctx.view(label), T, nb, km, *c.work(crop.cover_bytes(n, oh, ow)))
+        if label:   # the counts of a coarse grid need not move with the seed or the shape: T is what is held to both
+            plain = [torch.empty_like(t) for t in (T, nb, km)]
+            c.view = ViewCheck(label, call(ctx.h, *(plain + list(c.work(crop.cover_bytes(n, oh, ow))))), plain, fresh=(0,))
+        return c
+    return build
 
 
-@case("dvsg_tps_coefficients_f32")
-def _coefficients(ctx):
-    c, n = Case(), 3
-    F = c.inp(vectors(n, 4))
-    T = c.out((n, 2, 28))
-    c.issue = lambda s: ctx.call("dvsg_tps_coefficients_f32", ctx.h, F.data_ptr(), n, T.data_ptr(), s)
-    return c
+_coverage_net = _coverage_net_builder()
+case("dvsg_tps_coverage_net_f32")(_coverage_net)
+case("dvsg_tps_coverage_net_f32", "shaped")(_coverage_net_builder("shaped"))
+
+
+def _coefficients_builder(label=""):
+    def build(ctx):
+        c, n = Case(), 3
+        F = c.inp(vectors(n, 4))
+        T, h = c.out((n, 2, 28)), ctx.view(label)
+        c.issue = lambda s: ctx.call("dvsg_tps_coefficients_f32", h, F.data_ptr(), n, T.data_ptr(), s)
+        if label:
+            pT = _torch().empty_like(T)
+            c.view = ViewCheck(label, lambda s: ctx.call("dvsg_tps_coefficients_f32", ctx.h, F.data_ptr(), n, pT.data_ptr(), s),
+                               [pT])
+        return c
+    return build
+
+
+case("dvsg_tps_coefficients_f32")(_coefficients_builder())
+case("dvsg_tps_coefficients_f32", "shaped")(_coefficients_builder("shaped"))
 
 
 @case("dvsg_crop_ratchet_f32")
@@ -766,29 +961,47 @@ case("dvsg_frames_f32_to_u8")(_to_u8_builder("dvsg_frames_f32_to_u8", np.float32
 case("dvsg_frames_f64_to_u8")(_to_u8_builder("dvsg_frames_f64_to_u8", np.float64))
 
 
-def _render_u8_builder(zoomed, F=None):
+def _render_u8_builder(zoomed, F=None, label=""):
+    """The RGB render of SRC frames through the view of `label` ("": the plain handle): out_f32 [n, oh, ow, 3] and out_u8 in
+    the right half of rows of 2 ow pixels, (oh, ow) the view's size or the source's."""
     def build(ctx):
         import test_gpu_crop as crop
         torch = _torch()
         c, n = Case(), 3
         H0, W0 = SRC
+        oh, ow = VIEWS.get(label, {}).get("out_size") or SRC
         Fd = F if F is not None else c.inp(vectors(n, 5))
         src = c.inp(_u8_frames(n, H0, W0, 1))
-        T, o32 = c.out((n, 2, 28)), c.out((n, H0, W0, 3))
-        o8 = c.out((n, H0, 2 * W0, 3), torch.uint8)
-        if zoomed:
-            z = c.inp(fixed(crop.ZOOMS[:n]))
-            c.issue = lambda s: ctx.call("dvsg_tps_render_zoom_u8", ctx.h, Fd.data_ptr(), src.data_ptr(), n, H0, W0, 1,
-                                         z.data_ptr(), T.data_ptr(), o32.data_ptr(), o8.data_ptr(), 2 * W0, W0, s)
-        else:
-            c.issue = lambda s: ctx.call("dvsg_tps_render_u8", ctx.h, Fd.data_ptr(), src.data_ptr(), n, H0, W0, 1, T.data_ptr(),
-                                         o32.data_ptr(), o8.data_ptr(), 2 * W0, W0, s)
+        z = c.inp(fixed(crop.ZOOMS[:n])) if zoomed else None
+
+        def outs(h, w, alloc):
+            return alloc((n, 2, 28), torch.float32), alloc((n, h, w, 3), torch.float32), alloc((n, h, 2 * w, 3), torch.uint8)
+
+        def call(handle, T, o32, o8):
+            w = o32.shape[2]
+            if zoomed:
+                return lambda s: ctx.call("dvsg_tps_render_zoom_u8", handle, Fd.data_ptr(), src.data_ptr(), n, H0, W0, 1,
+                                          z.data_ptr(), T.data_ptr(), o32.data_ptr(), o8.data_ptr(), 2 * w, w, s)
+            return lambda s: ctx.call("dvsg_tps_render_u8", handle, Fd.data_ptr(), src.data_ptr(), n, H0, W0, 1, T.data_ptr(),
+                                      o32.data_ptr(), o8.data_ptr(), 2 * w, w, s)
+        c.issue = call(ctx.view(label), *outs(oh, ow, c.out))
+        if label:
+            assert ctx.render_size(ctx.view(label)) == (VIEWS[label].get("out_size") or (0, 0))
+            # the plain handle writes source-size frames: a scaled view is compared with their top left (oh, ow) pixels
+            plain = outs(H0, W0, lambda shape, dtype: torch.empty(shape, dtype=dtype, device="cuda"))
+            c.view = ViewCheck(
+                label, call(ctx.h, *plain), plain,
+                pairs=lambda w: [(w[1], plain[1][:, :oh, :ow]), (w[2][:, :, ow:], plain[2][:, :oh, W0:W0 + ow])],
+                kept=(lambda w: [("out_f32", w[1]), ("out_u8", w[2][:, :, ow:])]) if VIEWS[label].get("border") == "keep" else None)
         return c
     return build
 
 
 case("dvsg_tps_render_u8")(_render_u8_builder(False))
 case("dvsg_tps_render_zoom_u8")(_render_u8_builder(True))
+for _l in RGB_VIEWS:
+    case("dvsg_tps_render_u8", _l)(_render_u8_builder(False, label=_l))
+    case("dvsg_tps_render_zoom_u8", _l)(_render_u8_builder(True, label=_l))
 
 
 def _nv12_in(c, n, H, W, pitch, uv_row, salt):
@@ -827,33 +1040,90 @@ case("dvsg_frames_ingest_nv12", "same-size")(_nv12_ingest_builder(False))
 case("dvsg_frames_ingest_nv12", "resized")(_nv12_ingest_builder(True))
 
 
-def _render_nv12_builder(zoomed, F=None):
+def _surface(label, seed, n, H, W, pitch, uv_row, fill=None):
+    """A batch of the frames the view of `label` reads and writes: nv12_ref.Batch, p010_ref.P010Batch or, for a 4:2:2 view,
+    yuv422_ref.Batch422 of bytes or words."""
+    kw = VIEWS.get(label, {})
+    words = kw.get("surface", "nv12") == "p010"
+    if kw.get("chroma", "420") == "422":
+        import yuv422_ref
+        return yuv422_ref.Batch422(seed, n, H, W, words, pitch, uv_row, fill=fill)
+    if words:
+        import p010_ref
+        return p010_ref.P010Batch(seed, n, H, W, pitch, uv_row, fill=fill)
+    import nv12_ref
+    return nv12_ref.Batch(seed, n, H, W, pitch, uv_row, fill=fill)
+
+
+def _surface_source(label, seed, n=3):
+    """SURF frames for the view of `label`: packed bytes as the plain cases read them, words with a row gap and a plane gap"""
+    H, W = SURF
+    words = VIEWS.get(label, {}).get("surface", "nv12") == "p010"
+    return _surface(label, seed, n, H, W, 2 * W + 4 if words else W, H + 2 if words else H)
+
+
+def _shared_surface(label="", n=3):
+    """one source buffer for two calls of a pair: not an input of either, so neither refills it -> (batch, device bytes)"""
+    b = _surface_source(label, 77, n)
+    return b, _t(b.buf)
+
+
+def _render_nv12_builder(zoomed, F=None, label="", src=None):
+    """The surface render of SURF frames through the view of `label` ("": the plain handle).  The label gives the sample
+    (bytes, or P010 words), the chroma rows (H / 2, or H for 4:2:2) and the size of the frames written; the output has 26
+    bytes behind every row and 4 rows between the planes, poisoned like the planes themselves."""
     def build(ctx):
-        import nv12_ref
         import test_gpu_crop as crop
         torch = _torch()
         c, n = Case(), 3
-        H, W = 68, 102
-        b, buf = _nv12_in(c, n, H, W, 102, 68, 3)
-        ob = nv12_ref.Batch(0, n, H, W, 128, 72, fill=POISON)
+        H, W = SURF
+        kw = VIEWS.get(label, {})
+        oh, ow = kw.get("out_size") or SURF
+        bps = 2 if kw.get("surface", "nv12") == "p010" else 1
+        if src is None:
+            b = _surface_source(label, 0)
+            buf = c.inp(lambda seed: _t(_surface_source(label, 31 * seed + 3).buf))
+        else:
+            b, buf = src
         Fd = F if F is not None else c.inp(vectors(n, 6))
+        z = c.inp(fixed(crop.ZOOMS[:n])) if zoomed else None
+
+        def call(handle, T, out, ob):
+            if zoomed:
+                return lambda s: ctx.call("dvsg_tps_render_zoom_nv12", handle, Fd.data_ptr(), buf.data_ptr(),
+                                          buf.data_ptr() + b.uv_offset, b.pitch, b.frame_stride, n, H, W, z.data_ptr(),
+                                          T.data_ptr(), out.data_ptr(), out.data_ptr() + ob.uv_offset, ob.pitch, ob.frame_stride, s)
+            return lambda s: ctx.call("dvsg_tps_render_nv12", handle, Fd.data_ptr(), buf.data_ptr(),
+                                      buf.data_ptr() + b.uv_offset, b.pitch, b.frame_stride, n, H, W, T.data_ptr(),
+                                      out.data_ptr(), out.data_ptr() + ob.uv_offset, ob.pitch, ob.frame_stride, s)
+        ob = _surface(label, 0, n, oh, ow, bps * ow + 26, oh + 4, fill=POISON)
         T = c.out((n, 2, 28))
         out = c.out(ob.buf.shape, torch.uint8)
-        if zoomed:
-            z = c.inp(fixed(crop.ZOOMS[:n]))
-            c.issue = lambda s: ctx.call("dvsg_tps_render_zoom_nv12", ctx.h, Fd.data_ptr(), buf.data_ptr(),
-                                         buf.data_ptr() + b.uv_offset, b.pitch, b.frame_stride, n, H, W, z.data_ptr(),
-                                         T.data_ptr(), out.data_ptr(), out.data_ptr() + ob.uv_offset, ob.pitch, ob.frame_stride, s)
-        else:
-            c.issue = lambda s: ctx.call("dvsg_tps_render_nv12", ctx.h, Fd.data_ptr(), buf.data_ptr(),
-                                         buf.data_ptr() + b.uv_offset, b.pitch, b.frame_stride, n, H, W, T.data_ptr(),
-                                         out.data_ptr(), out.data_ptr() + ob.uv_offset, ob.pitch, ob.frame_stride, s)
+        c.issue = call(ctx.view(label), T, out, ob)
+        if label:
+            import nv12_ref
+            assert ctx.render_size(ctx.view(label)) == (kw.get("out_size") or (0, 0))
+            # The plain handle on the same bytes: it reads them as NV12 (fewer bytes of every row, fewer chroma rows) and writes
+            # an NV12 frame of SURF.  At the source's size that fits the view's own output layout, so the two outputs are
+            # compared whole; of a scaled view the first ow bytes of the oh luma rows are compared with those of a source-size
+            # NV12 output.
+            scaled = (oh, ow) != SURF
+            pb = nv12_ref.Batch(0, n, H, W, W + 26, H + 4, fill=POISON) if scaled else ob
+            pT, p_out = torch.empty_like(T), torch.empty(pb.buf.shape, dtype=torch.uint8, device="cuda")
+            c.view = ViewCheck(
+                label, call(ctx.h, pT, p_out, pb), [pT, p_out],
+                pairs=(lambda w: [(w[1][:, :oh, :ow], p_out[:, :oh, :ow])]) if scaled else (lambda w: [(w[1], p_out)]),
+                kept=(lambda w: [("luma", w[1][:, :oh, :bps * ow]), ("chroma", w[1][:, ob.uv_row:, :bps * ow])])
+                if kw.get("border") == "keep" else None)
         return c
     return build
 
 
 case("dvsg_tps_render_nv12")(_render_nv12_builder(False))
 case("dvsg_tps_render_zoom_nv12")(_render_nv12_builder(True))
+for _l in SURFACE_VIEWS:
+    case("dvsg_tps_render_nv12", _l)(_render_nv12_builder(False, label=_l))
+    case("dvsg_tps_render_zoom_nv12", _l)(_render_nv12_builder(True, label=_l))
 
 
 @case("dvsg_scene_step_f32")
@@ -1000,7 +1270,9 @@ ALL_IDS = ["%s%s" % (name, "-" + CASES[name][i].label if CASES[name][i].label el
 def ctx(synthetic_weights):
     import time
     t0 = time.time()
-    yield Ctx(synthetic_weights)
+    c = Ctx(synthetic_weights)
+    yield c
+    c.close()
     print("\nSTREAMS module total: %.1f s" % (time.time() - t0))
 
 
@@ -1088,6 +1360,8 @@ def test_replays_from_a_captured_graph(ctx, name, i):
         want.append(c.snapshot())
     if c.carry:
         assert any(int(w[2][:3].sum()) > 0 for w in want), "the scene plan was meant to cut"
+    if c.view is not None:
+        c.view.check(c, want, s, side, ALL_IDS[ALL.index((name, i))])
     c.fill(0)
     c.restore()
     torch.cuda.synchronize()
@@ -1127,6 +1401,16 @@ PAIRS = {
     "ring_u8-masked": lambda: (net_case("ring_u8", "f32", 2, 64, 96), net_case("masked", "f32", 2, 64, 96), (1, 2)),
     "render_u8-render_nv12": lambda: (lambda F: (_render_u8_builder(False, F), _render_nv12_builder(False, F), (1, 2)))(_shared_F()),
     "stabilize-coverage_net": lambda: (net_case("stabilize", "f32", 2, 64, 96), _coverage_net, (1, 2)),
+    # views of ONE parent: a shared F_t at two delivery sizes; two surface views; one view twice; and the plain handle beside
+    # a scaled view on one source buffer, where the size each call writes comes from a table looked up by the handle's address
+    "views-scaled_u8-scaled_nv12": lambda: (lambda F: (_render_u8_builder(False, F, "scaled-2x2"),
+                                                       _render_nv12_builder(False, F, "scaled-3x3"), (1, 2)))(_shared_F()),
+    "views-p010-nv16": lambda: (_render_nv12_builder(False, label="p010"), _render_nv12_builder(False, label="nv16"), (1, 2)),
+    "views-one-view-twice": lambda: (_render_nv12_builder(False, label="p010-scaled-2x2-cubic-mirror"),
+                                     _render_nv12_builder(False, label="p010-scaled-2x2-cubic-mirror"), (1, 2)),
+    "views-plain-scaled-one-source": lambda: (lambda src: (_render_nv12_builder(False, src=src),
+                                                           _render_nv12_builder(False, label="scaled-3x3", src=src),
+                                                           (1, 2)))(_shared_surface()),
 }
 
 
@@ -1216,6 +1500,90 @@ def test_two_threads_of_one_handle(ctx, delay):
     assert seen["B"][0] < 0 and "workspace" in seen["B"][1] and "bad shape" not in seen["B"][1], seen["B"]
 
 
+def test_two_threads_of_views(ctx, delay):
+    """Two renders through scaled views from two Python threads while a third makes and destroys 64 scaled views of the same
+    parent: the NV12 renders look the size of their handle up, by its address, in a process-global table that the view
+    constructors and dvsg_locnet_destroy write (the invariant above g_scaled_mutex, locnet.hip).  A bounded loop of valid
+    calls.  Each worker then makes a call that is refused before any launch and reads its own message: the output pitch is
+    too short for the VIEW's row -- 34 bytes for the 36 of the byte view, the 102 bytes of a source row of bytes for the
+    2 x 52 of the word view -- so the message also shows that the size came from the right table entry."""
+    torch = _torch()
+    labels = {"A": "scaled-3x3", "B": "p210-scaled-2x2"}
+    a, b = (_render_nv12_builder(False, label=labels[t])(ctx) for t in "AB")
+    plain = _render_nv12_builder(False)(ctx)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    want_a, want_b = _alone(a, 1, s1.cuda_stream, s1), _alone(b, 2, s2.cuda_stream, s2)
+    want_plain = _alone(plain, 3, s1.cuda_stream, s1)
+    views = {t: ctx.view(labels[t]) for t in "AB"}
+    sizes = {t: ctx.render_size(views[t]) for t in "AB"}
+    assert sizes == {t: VIEWS[labels[t]]["out_size"] for t in "AB"} and ctx.render_size(ctx.h) == (0, 0)
+    n_views = ctx.n_views()
+    lib = ctx.lib.load()
+    H, W = SURF
+
+    def refused(c, tag, pitch):
+        (buf, _), (F, _), T, out = c.inputs[0], c.inputs[1], c.outputs[0], c.outputs[1]
+        src = _surface_source(labels[tag], 0)
+        return lambda: lib.dvsg_tps_render_nv12(views[tag], F.data_ptr(), buf.data_ptr(), buf.data_ptr() + src.uv_offset,
+                                                src.pitch, src.frame_stride, 3, H, W, T.data_ptr(), out.data_ptr(),
+                                                out.data_ptr() + 64, pitch, 1 << 20, 0)
+    bad = {"A": refused(a, "A", 34), "B": refused(b, "B", W)}
+    seen, churn = {}, []
+
+    def run(scale):
+        for c in (a, b):
+            c.poison()
+        del churn[:]
+        torch.cuda.synchronize()
+        ev = delay.enqueue(delay.stream, scale)
+        s1.wait_event(ev)
+        s2.wait_event(ev)
+        start, both = threading.Barrier(3), threading.Barrier(2)
+        errors = []
+
+        def worker(tag, c, s):
+            try:
+                start.wait(timeout=60)
+                c.issue(s)
+                done = ev.query()
+                rc = bad[tag]()
+                both.wait(timeout=60)               # both failures are made before either message is read
+                seen[tag] = (rc, lib.dvsg_last_error_string().decode(), done)
+            except Exception as e:                  # noqa: a worker's failure is the test's
+                errors.append(e)
+                start.abort()
+                both.abort()
+
+        def churner():
+            try:
+                start.wait(timeout=60)
+                for k in range(64):
+                    v = ctypes.c_void_p()
+                    rc = lib.dvsg_locnet_view_create_scaled(ctx.h, 8 + k, 12 + k, ctypes.byref(v))
+                    churn.append((rc, lib.dvsg_locnet_destroy(v) if rc == 0 else None))
+            except Exception as e:                  # noqa
+                errors.append(e)
+                start.abort()
+        ts = [threading.Thread(target=worker, args=("A", a, s1.cuda_stream)),
+              threading.Thread(target=worker, args=("B", b, s2.cuda_stream)), threading.Thread(target=churner)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        assert not errors, errors
+        return seen["A"][2] or seen["B"][2]
+    behind_delay(delay, run, "two threads of views")
+    assert churn == [(0, 0)] * 64, churn
+    a.same(want_a, "thread A")
+    b.same(want_b, "thread B")
+    assert {t: ctx.render_size(views[t]) for t in "AB"} == sizes and ctx.render_size(ctx.h) == (0, 0)
+    assert ctx.n_views() == n_views, "the parent's views are not those from before the test"
+    _alone(plain, 3, s1.cuda_stream, s1)            # a source-size frame into an output of exactly that size, as before
+    plain.same(want_plain, "the plain handle after the views came and went")
+    assert seen["A"][0] == -1 and "output pitch=34 < W=36" in seen["A"][1], seen["A"]
+    assert seen["B"][0] == -1 and "output pitch=102 < 2 W = 104" in seen["B"][1], seen["B"]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. the Python facade
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1281,30 +1649,54 @@ def test_facade_two_streams_one_locnet(ctx, delay, what):
             assert torch.equal(_bits(g), _bits(w)), "%s on stream %d differs from its serial run" % (what, k)
 
 
-def test_facade_two_online_stabilizers_share_a_model(ctx, delay, synthetic_weights):
-    """Two OnlineStabilizers on one model, three steps each under its own stream, against the same streams stepped one after
-    the other."""
+def _online_pair(which, H, W):
+    """(options of the two stabilisers, their frames [2][steps]).  "defaults": float frames at the model's size, three steps.
+    "views": four steps through the newer stream formats -- an NV12 stream (tests/test_gpu_scene.py's clips: two frames of
+    scene A, then two of scene B) rendered bicubic with a mirrored border, cropped and cut on the device, beside a P210
+    stream of SURF frames rendered at half strength and at half size."""
+    if which == "defaults":
+        return [dict(max_streams=1)] * 2, \
+            [[_t(inputs.smooth_frames(60 + 10 * k + j, 1, H, W)[0]) for j in range(3)] for k in (0, 1)]
+    import test_gpu_scene as scene
+    import yuv422_ref
+    A, B, kw = scene._clips("nv12", 2)
+    assert kw == dict(frame_format="nv12")
+    p210 = yuv422_ref.Batch422(91, 4, SURF[0], SURF[1], words=True).buf        # packed: [4, 2 H, 2 W] bytes
+    return [dict(frame_format="nv12", crop="auto", scene_cut=scene.THR, render_filter="bicubic", border="mirror"),
+            dict(frame_format="p210", out_size=(34, 52), strength=0.5)], \
+        [[_t(f) for f in np.concatenate([A, B])], [_t(f) for f in p210]]
+
+
+@pytest.mark.parametrize("which", ["defaults", "views"])
+def test_facade_two_online_stabilizers_share_a_model(ctx, delay, synthetic_weights, which):
+    """Two OnlineStabilizers on one model, three or four steps each under its own stream, against the same streams stepped
+    one after the other."""
     import test_gpu_scene as scene
     from coupe.dvsg_amd.online import OnlineStabilizer
     torch = _torch()
     H, W = 64, 96
     model = scene._model(synthetic_weights, H, W)
-    frames = [[_t(inputs.smooth_frames(60 + 10 * k + j, 1, H, W)[0]) for j in range(3)] for k in (0, 1)]
+    options, frames = _online_pair(which, H, W)
+    steps = len(frames[0])
     ss = [torch.cuda.Stream(), torch.cuda.Stream()]
     torch.cuda.synchronize()
 
     def opened():
-        ons = [OnlineStabilizer(model, max_streams=1) for _ in (0, 1)]
+        ons = [OnlineStabilizer(model, **kw) for kw in options]
         return ons, [on.open() for on in ons]
     ons, sids = opened()
     torch.cuda.synchronize()
     want = [[], []]
-    for j in range(3):
+    for j in range(steps):
         for k in (0, 1):
             with torch.cuda.stream(ss[k]):
                 want[k].append(ons[k].push(sids[k], frames[k][j]).clone())
             ss[k].synchronize()
     torch.cuda.synchronize()
+    if which == "views":
+        st = ons[0].scene_state(sids[0])
+        assert st["cuts"] == 1 and st["frames_since_cut"] == 2, "scene B was meant to cut at the third step: %s" % (st,)
+        assert tuple(want[1][0].shape) == (2 * 34, 2 * 52) and tuple(want[0][0].shape) == tuple(frames[0][0].shape)
     got = [[], []]
     state = {}
 
@@ -1317,7 +1709,7 @@ def test_facade_two_online_stabilizers_share_a_model(ctx, delay, synthetic_weigh
     def run(scale):
         fresh()
         late = False
-        for j in range(3):
+        for j in range(steps):
             ev = delay.enqueue(delay.stream, scale)
             for k in (0, 1):
                 ss[k].wait_event(ev)
@@ -1326,10 +1718,11 @@ def test_facade_two_online_stabilizers_share_a_model(ctx, delay, synthetic_weigh
             late = late or ev.query()
             torch.cuda.synchronize()
         return late
-    behind_delay(delay, run, "online")
+    behind_delay(delay, run, "online " + which)
     for k in (0, 1):
-        for j in range(3):
-            assert torch.equal(_bits(got[k][j]), _bits(want[k][j])), "stabilizer %d, step %d differs from its serial run" % (k, j)
+        for j in range(steps):
+            assert got[k][j].cpu().numpy().tobytes() == want[k][j].cpu().numpy().tobytes(), \
+                "stabilizer %d, step %d differs from its serial run" % (k, j)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
