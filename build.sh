@@ -33,6 +33,7 @@ SOURCES=(
   "conv_gemm_wide16.hip  |"
   "head.hip              |"
   "locnet.hip            |"
+  "views.cpp             | -x hip"
   "api_common.cpp        | -x hip"
 )
 JOBS=16   # compiles at a time

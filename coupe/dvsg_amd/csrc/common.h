@@ -35,7 +35,7 @@ inline int check_launch(const char *what) {
       return ::dvsg::fail(DVSG_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
   } while (0)
 
-// warp_kernels.hip internals shared with locnet.hip (coord_bstride in floats; 0 = broadcast)
+// warp_kernels.hip internals shared with locnet.hip and views.cpp (coord_bstride in floats; 0 = broadcast)
 int tps_solve_impl(const float *coord, long coord_bstride, const float *rhs, int rhs_is_vector, int B,
                    int P, float *T, int *n_singular, void *stream);
 // constant control points (the evaluation graph's V_src): W^-1 once, then a matrix-vector product per frame
@@ -58,32 +58,36 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
                        long coord_bstride, const float *T, int B, int H, int W, int P, float *out, float *x_s, float *y_s,
                        void *stream, const int *out_index = nullptr);
 
-// dvsg_tps_render_u8 (winv_cols / coord: the handle's W^-1 columns and V_src)
-int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
-                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
-                    const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR /* the handle's or view's */,
-                    int render_border = DVSG_BORDER_BLACK /* likewise */,
-                    RenderShape shape = RenderShape() /* likewise */,
-                    int out_H = 0, int out_W = 0 /* a scaled view's output size; (0, 0): the source's */);
+// What a handle tells the source-size renders: a plain handle's values by default, a view's own otherwise (views.cpp makes
+// them; include/dvsg_amd.h says what each one means).  filter and border are read by the four renders, shape by them, by
+// dvsg_tps_coefficients_f32 and by dvsg_tps_coverage_net_f32.
+struct RenderView {
+  int filter = DVSG_RENDER_BILINEAR;
+  int border = DVSG_BORDER_BLACK;
+  RenderShape shape;
+  int surface_format = DVSG_SURFACE_NV12;   // read by dvsg_tps_render_nv12 / _zoom_nv12 alone
+  int chroma_format = DVSG_CHROMA_420;      // likewise: the chroma plane is (H, W / 2) for DVSG_CHROMA_422 ("Chroma sampling")
+  int out_h = 0, out_w = 0;                 // read by the four renders alone; (0, 0): the source's size
+};
+// dvsg_tps_render_u8 and, with zoom [B] on the device, dvsg_tps_render_zoom_u8 (winv_cols / coord: the handle's W^-1 columns
+// and V_src)
+int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const float *zoom, const uint8_t *src, int B,
+                    int H, int W, int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0,
+                    void *stream, const RenderView &view);
 // nv12.hip: dvsg_tps_render_nv12 and, with zoom [n] on the device, dvsg_tps_render_zoom_nv12.  The check makes no HIP call
-// and reads no handle (fn: the entry point its messages name); the launch half assumes it passed.  tps_render_p010_check:
-// what a P010 view (dvsg_locnet_view_create_surface) asks on top of it, once the handle may be read -- planes of 16-bit
-// words, pitch >= 2 W, pitches, frame strides and plane pointers 2-byte aligned; no HIP call either.
-int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
-                          int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
-                          size_t out_frame_stride, const char *fn = "dvsg_tps_render_nv12",
-                          int out_H = 0, int out_W = 0 /* a scaled view's output size; (0, 0): the source's */);
-int tps_render_p010_check(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int W,
-                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, const char *fn,
-                          int out_W = 0 /* a scaled view's output width; 0: W */);
-int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
-                         size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
-                         uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream,
-                         const float *zoom = nullptr, int render_filter = DVSG_RENDER_BILINEAR,
-                         int render_border = DVSG_BORDER_BLACK, RenderShape shape = RenderShape(),
-                         int surface_format = DVSG_SURFACE_NV12, int out_H = 0, int out_W = 0 /* a scaled view's size */,
-                         const char *fn = "dvsg_tps_render_nv12",
-                         int chroma_format = DVSG_CHROMA_420 /* the view's: the chroma plane is (H, W / 2) for DVSG_CHROMA_422 */);
+// and reads no handle (fn: the entry point its messages name; out_H, out_W: a scaled view's output size, (0, 0) for the
+// source's); the launch half assumes it passed.  tps_render_p010_check: what a P010 view (dvsg_locnet_view_create_surface)
+// asks on top of it, once the handle may be read -- planes of 16-bit words, pitch >= 2 W, pitches, frame strides and plane
+// pointers 2-byte aligned (out_W: a scaled view's output width, 0 for W); no HIP call either.
+int tps_render_nv12_check(const char *fn, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride,
+                          int n, int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
+                          size_t out_frame_stride, int out_H, int out_W);
+int tps_render_p010_check(const char *fn, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int W,
+                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, int out_W);
+int tps_render_nv12_impl(const char *fn, const double *winv_cols, const float *coord, const float *F_t, const float *zoom,
+                         const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T,
+                         uint8_t *out_y, uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream,
+                         const RenderView &view);
 // nv12.hip: what a scaled view (dvsg_locnet_view_create_scaled) asks of a render of (H, W) frames at another size
 // (out_H, out_W): at most 4 virtual samples per axis, no DVSG_BORDER_KEEP.  No HIP call.
 int render_scaled_check(const char *fn, int H, int W, int out_H, int out_W, int render_border);

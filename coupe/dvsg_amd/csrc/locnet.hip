@@ -1,18 +1,16 @@
 // Host side of localizationNet (networks.py:30-46) and of the fused evaluation graph
 // (model.py:98-123): checkpoint ingestion (BatchNorm folding, weight re-layout for the MFMA
 // fragment scheme of conv_gemm.hip / the conv1_*.hip kernels, float16 copies), workspace planning and the
-// launch sequence for both storage precisions.
-#include <atomic>
+// launch sequence for both storage precisions; with them the calibration of the float16 mode, the conv and fused operator
+// entry points and the debug API.  The handle itself is locnet_internal.h's; its views, dvsg_locnet_destroy and the entry
+// points that read a handle's render properties (the source-size renders among them) are views.cpp's.
 #include <cmath>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <string>
-#include <unordered_map>
-#include <utility>
 #include <vector>
 
-#include "cnn_kernels.h"
+#include "locnet_internal.h"
 
 namespace dvsg {
 namespace {
@@ -31,91 +29,12 @@ struct HostArray {
   }
 };
 
-struct ConvLayer {
-  int ksize, cin, cout, stride;
-  bool relu;
-  float *wt = nullptr;        // device, [cout][k*k*cin] float32 (conv1: [7][64][kConv1Ld])
-  _Float16 *wt16 = nullptr;   // device, same layout in float16 (not for conv1)
-  _Float16 *wt16s = nullptr;  // device, float16 hi / lo pairs [cout/64][128][k*k*cin] (conv_gemm.hip SPLIT; not for conv1)
-  _Float16 *wt16p = nullptr;  // device, wt16s packed stage by stage for conv_gemm_wide16.hip (cin % 64 == 0 layers)
-  _Float16 *wt16pa = nullptr; // device, the same in the order of its 128-byte-activation-row kernel
-  _Float16 *wt16ph = nullptr; // device, the same in the order of its 3x3 stride-1 kernel (3x3 layers only)
-  _Float16 *wt16q = nullptr, *wt16qa = nullptr, *wt16qh = nullptr;   // device, the PLAIN copy wt16 packed the same three ways
-                              // (cin % 64 == 0, cout % 128 == 0 layers: what runs when a layer has no lo piece)
-  _Float16 *wt32s = nullptr;  // device, "f32s" pieces [cout][k*k*cin/32][32 hi | 32 lo] (conv_gemm.hip SPLIT, T = float; not for conv1)
-  unsigned short *wt3x = nullptr;  // device, "f32x3" bfloat16 pieces, packed stage by stage (launch_pack_x3; not for conv1)
-  float *bias = nullptr;      // device, [cout] float32
-  // the weight image a math multiplies by: the one place that pairs the two up
-  ConvWeights image(ConvMath math) const {
-    switch (math) {
-      case kMathF32S: return {wt32s};
-      case kMathF32X: return {wt3x};
-      case kMathF16Pairs: return {wt16s, wt16p, wt16pa, wt16ph};
-      case kMathF16Plain: return {wt16, wt16q, wt16qa, wt16qh};
-      default: return {wt};
-    }
-  }
-  Conv1Weights conv1_images() const { return {wt, wt16, wt32s, wt3x, bias}; }   // (conv1 keeps its images in the same members)
-};
-
-struct Unit {
-  int block;   // 0..3
-  int base, depth, stride;
-  bool has_shortcut;
-  ConvLayer shortcut, c1, c2, c3;
-  // units that open blocks 2-4: `shortcut` and `conv1` read the same input -- their weight rows concatenated along N
-  // ([shortcut | conv1], float32 and f32s pieces) run as ONE launch (forward(), "concat_sc")
-  ConvLayer cat;
-  bool has_cat = false;
-};
-
 struct BlockSpec {
   const char *name;
   int base, units, last_stride;
 };
 const BlockSpec kBlocks[4] = {{"block1", 64, 3, 2}, {"block2", 128, 4, 2}, {"block3", 256, 6, 2}, {"block4", 512, 3, 1}};
 const int kDenseDims[4][2] = {{2048, 2048}, {2048, 1024}, {1024, 512}, {512, 50}};
-
-}  // namespace
-}  // namespace dvsg
-
-using namespace dvsg;
-
-struct dvsg_locnet {
-  int c_in = 0;
-  ConvLayer conv1;
-  std::vector<Unit> units;
-  float *dense_w[4] = {nullptr, nullptr, nullptr, nullptr};
-  float *dense_b[4] = {nullptr, nullptr, nullptr, nullptr};
-  float *v_src = nullptr;  // [25,2] model.py:105-110
-  double *winv = nullptr;  // [25][28]: columns of the TPS system's inverse for v_src (see tps_apply_kernel)
-  // float16 mode: which layers multiply by hi / lo weight PAIRS (bit 4 * kind + block, see DebugOptions::f16_pair_mask).  All of them
-  // until dvsg_locnet_calibrate_f16 has re-rounded the plain copies of blocks 2-4 with error feedback: then block 1 only.
-  int f16_pair_mask = 0xFFFF;
-  // what the last calibrate_f16 of this handle re-rounded against (dvsg_debug_calibration_means): the channel means mu
-  // [48][2048] that redo() read and the rows summed per slot; 1.0 and 0 rows where no means were measured (a new handle,
-  // mode 0, mode 1)
-  std::vector<double> calib_mu = std::vector<double>((size_t)48 * 2048, 1.0);
-  double calib_rows[48] = {0};
-  std::vector<void *> allocs;
-  // A VIEW (dvsg_locnet_view_create) is one of these with nothing in it but `parent` and its own render filter, border and shape: every entry
-  // point reads the network and the TPS constants through base() at call time, so a later calibration of the parent is seen
-  // through its views.  n_views: the live views of a parent, which dvsg_locnet_destroy refuses to pull the network from under.
-  const dvsg_locnet *parent = nullptr;
-  int render_filter = DVSG_RENDER_BILINEAR;
-  int render_border = DVSG_BORDER_BLACK;
-  RenderShape render_shape;
-  int surface_format = DVSG_SURFACE_NV12;   // read by dvsg_tps_render_nv12 / _zoom_nv12 alone
-  int chroma_format = DVSG_CHROMA_420;      // likewise: the rows of the chroma plane ("Chroma sampling")
-  int out_h = 0, out_w = 0;                 // read by the four source-size renders alone; (0, 0): the source's size
-  mutable std::atomic<int> n_views{0};
-};
-
-// the handle that owns the network `net` shows: itself, or a view's parent
-static inline const dvsg_locnet *base(const dvsg_locnet *net) { return net && net->parent ? net->parent : net; }
-
-namespace dvsg {
-namespace {
 
 typedef std::map<std::string, HostArray> ArrayMap;
 
@@ -833,6 +752,8 @@ constexpr struct {
 }  // namespace
 }  // namespace dvsg
 
+using namespace dvsg;
+
 extern "C" {
 
 int dvsg_locnet_create(int n_arrays, const char *const *names, const float *const *host_data, const int *ndims,
@@ -943,172 +864,6 @@ int dvsg_locnet_create(int n_arrays, const char *const *names, const float *cons
   *out = net;
   return DVSG_OK;
 }
-
-// The views that carry an output size other than (0, 0), by address.  dvsg_tps_render_nv12 / _zoom_nv12 check every argument
-// before they read the handle (a caller's garbage pointer with a bad pitch is refused, not followed), and what the output
-// planes must hold depends on the view's size: looking the POINTER up here tells them without reading through it.  Any
-// other pointer has (0, 0), the source's size.
-// INVARIANT: the table and the handles' out_h / out_w always agree.  set_view_size is the one place that writes either, once
-// per view and before the constructor hands the view out; a view's fields never change afterwards; dvsg_locnet_destroy
-// erases the entry before it frees the view.  So a live view v has g_scaled_views[v] == (v->out_h, v->out_w) if that is not
-// (0, 0) and no entry otherwise, and the RGB renders (which read the fields) and the NV12 renders (which read the table) see
-// one size.  g_n_scaled counts the entries: while no scaled view exists a render takes no lock.
-static std::mutex g_scaled_mutex;
-static std::unordered_map<const dvsg_locnet *, std::pair<int, int>> g_scaled_views;
-static std::atomic<int> g_n_scaled{0};
-
-static void scaled_view_size(const dvsg_locnet *net, int *out_h, int *out_w) {
-  *out_h = *out_w = 0;
-  if (g_n_scaled.load(std::memory_order_acquire) == 0) return;
-  std::lock_guard<std::mutex> lock(g_scaled_mutex);
-  const auto it = g_scaled_views.find(net);
-  *out_h = it == g_scaled_views.end() ? 0 : it->second.first;
-  *out_w = it == g_scaled_views.end() ? 0 : it->second.second;
-}
-
-// the view's size is set once, here, before the constructor hands the view out
-static void set_view_size(dvsg_locnet *v, int out_h, int out_w) {
-  v->out_h = out_h;
-  v->out_w = out_w;
-  if (out_h || out_w) {
-    std::lock_guard<std::mutex> lock(g_scaled_mutex);
-    g_scaled_views[v] = std::make_pair(out_h, out_w);
-    g_n_scaled.store((int)g_scaled_views.size(), std::memory_order_release);
-  }
-}
-
-int dvsg_locnet_destroy(dvsg_locnet_t *net) {
-  if (!net) return DVSG_OK;
-  if (net->parent) {   // a view owns nothing
-    net->parent->n_views.fetch_sub(1);
-    if (net->out_h || net->out_w) {
-      std::lock_guard<std::mutex> lock(g_scaled_mutex);
-      g_scaled_views.erase(net);
-      g_n_scaled.store((int)g_scaled_views.size(), std::memory_order_release);
-    }
-    delete net;
-    return DVSG_OK;
-  }
-  const int views = net->n_views.load();
-  DVSG_REQUIRE(views == 0, "dvsg_locnet_destroy: the handle still has %d view(s); destroy them first", views);
-  for (void *p : net->allocs) (void)hipFree(p);
-  delete net;
-  return DVSG_OK;
-}
-
-// the view constructors; fn: the one its messages name.  Everything is decided before the handle is read or anything allocated.
-static int view_create(const char *fn, const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view,
-                       RenderShape shape = RenderShape()) {
-  DVSG_REQUIRE(net, "%s: NULL net", fn);
-  DVSG_REQUIRE(view, "%s: NULL view", fn);
-  *view = nullptr;
-  DVSG_REQUIRE(render_filter == DVSG_RENDER_BILINEAR || render_filter == DVSG_RENDER_BICUBIC,
-               "%s: render_filter=%d is neither DVSG_RENDER_BILINEAR (0) nor DVSG_RENDER_BICUBIC (1)", fn, render_filter);
-  DVSG_REQUIRE(render_border >= DVSG_BORDER_BLACK && render_border <= DVSG_BORDER_KEEP,
-               "%s: render_border=%d is none of DVSG_BORDER_BLACK (0), _REPLICATE (1), _MIRROR (2), _KEEP (3)", fn,
-               render_border);
-  DVSG_REQUIRE(shape.model >= DVSG_SHAPE_AFFINE && shape.model <= DVSG_SHAPE_TRANSLATION,
-               "%s: shape_model=%d is none of DVSG_SHAPE_AFFINE (0), _SIMILARITY (1), _TRANSLATION (2)", fn, shape.model);
-  DVSG_REQUIRE(shape.strength >= 0.0f && shape.strength <= 1.0f, "%s: strength=%g outside [0, 1]", fn, (double)shape.strength);
-  DVSG_REQUIRE(shape.rigidity >= 0.0f && shape.rigidity <= 1.0f, "%s: rigidity=%g outside [0, 1]", fn, (double)shape.rigidity);
-  dvsg_locnet *v = new dvsg_locnet();
-  v->calib_mu = std::vector<double>();   // (a view keeps no calibration record of its own)
-  v->parent = base(net);                 // a view of a view is a view of the parent: filter, border and shape are the arguments'
-  v->render_filter = render_filter;
-  v->render_border = render_border;
-  v->render_shape = shape;
-  v->parent->n_views.fetch_add(1);
-  *view = v;
-  return DVSG_OK;
-}
-
-int dvsg_locnet_view_create(const dvsg_locnet_t *net, int render_filter, dvsg_locnet_t **view) {
-  return view_create("dvsg_locnet_view_create", net, render_filter, DVSG_BORDER_BLACK, view);
-}
-
-int dvsg_locnet_view_create_border(const dvsg_locnet_t *net, int render_filter, int render_border, dvsg_locnet_t **view) {
-  return view_create("dvsg_locnet_view_create_border", net, render_filter, render_border, view);
-}
-
-int dvsg_locnet_view_create_shaped(const dvsg_locnet_t *net, int render_filter, int render_border, int shape_model,
-                                   float strength, float rigidity, dvsg_locnet_t **view) {
-  RenderShape shape;
-  shape.model = shape_model;
-  shape.strength = strength;
-  shape.rigidity = rigidity;
-  return view_create("dvsg_locnet_view_create_shaped", net, render_filter, render_border, view, shape);
-}
-
-// a view of net's parent with net's OWN filter, border and shape (inherited, unlike the three constructors above) and the
-// given surface format
-int dvsg_locnet_view_create_surface(const dvsg_locnet_t *net, int surface_format, dvsg_locnet_t **view) {
-  const char *fn = "dvsg_locnet_view_create_surface";
-  DVSG_REQUIRE(net, "%s: NULL net", fn);
-  DVSG_REQUIRE(view, "%s: NULL view", fn);
-  *view = nullptr;
-  DVSG_REQUIRE(surface_format == DVSG_SURFACE_NV12 || surface_format == DVSG_SURFACE_P010,
-               "%s: surface_format=%d is neither DVSG_SURFACE_NV12 (0) nor DVSG_SURFACE_P010 (1)", fn, surface_format);
-  if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
-  (*view)->surface_format = surface_format;
-  (*view)->chroma_format = net->chroma_format;
-  set_view_size(*view, net->out_h, net->out_w);
-  return DVSG_OK;
-}
-
-// a view of net's parent with net's own filter, border, shape, surface and chroma format and the given output size ("Output size")
-int dvsg_locnet_view_create_scaled(const dvsg_locnet_t *net, int out_H, int out_W, dvsg_locnet_t **view) {
-  const char *fn = "dvsg_locnet_view_create_scaled";
-  DVSG_REQUIRE(net, "%s: NULL net", fn);
-  DVSG_REQUIRE(view, "%s: NULL view", fn);
-  *view = nullptr;
-  if (!(out_H == 0 && out_W == 0)) {
-    DVSG_REQUIRE(out_H >= 1, "%s: out_H=%d (with out_W=%d) is neither >= 1 nor, together with out_W, 0", fn, out_H, out_W);
-    DVSG_REQUIRE(out_W >= 1, "%s: out_W=%d (with out_H=%d) is neither >= 1 nor, together with out_H, 0", fn, out_W, out_H);
-  }
-  if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
-  (*view)->surface_format = net->surface_format;
-  (*view)->chroma_format = net->chroma_format;
-  set_view_size(*view, out_H, out_W);
-  return DVSG_OK;
-}
-
-// a view of net's parent with net's own filter, border, shape, surface format and output size and the given chroma format
-// ("Chroma sampling"); the value is checked before the handle is read
-int dvsg_locnet_view_create_chroma(const dvsg_locnet_t *net, int chroma_format, dvsg_locnet_t **view) {
-  const char *fn = "dvsg_locnet_view_create_chroma";
-  DVSG_REQUIRE(net, "%s: NULL net", fn);
-  DVSG_REQUIRE(view, "%s: NULL view", fn);
-  *view = nullptr;
-  DVSG_REQUIRE(chroma_format == DVSG_CHROMA_420 || chroma_format == DVSG_CHROMA_422,
-               "%s: chroma_format=%d is neither DVSG_CHROMA_420 (0) nor DVSG_CHROMA_422 (1)", fn, chroma_format);
-  if (int rc = view_create(fn, net, net->render_filter, net->render_border, view, net->render_shape)) return rc;
-  (*view)->surface_format = net->surface_format;
-  (*view)->chroma_format = chroma_format;
-  set_view_size(*view, net->out_h, net->out_w);
-  return DVSG_OK;
-}
-
-int dvsg_locnet_render_size(const dvsg_locnet_t *net, int *out_H, int *out_W) {
-  if (out_H) *out_H = net ? net->out_h : 0;
-  if (out_W) *out_W = net ? net->out_w : 0;
-  return DVSG_OK;
-}
-
-int dvsg_locnet_render_surface(const dvsg_locnet_t *net) { return net ? net->surface_format : DVSG_SURFACE_NV12; }
-
-int dvsg_locnet_render_chroma(const dvsg_locnet_t *net) { return net ? net->chroma_format : DVSG_CHROMA_420; }
-
-int dvsg_locnet_render_shape(const dvsg_locnet_t *net, int *shape_model, float *strength, float *rigidity) {
-  const RenderShape shape = net ? net->render_shape : RenderShape();
-  if (shape_model) *shape_model = shape.model;
-  if (strength) *strength = shape.strength;
-  if (rigidity) *rigidity = shape.rigidity;
-  return DVSG_OK;
-}
-
-int dvsg_locnet_render_filter(const dvsg_locnet_t *net) { return net ? net->render_filter : DVSG_RENDER_BILINEAR; }
-
-int dvsg_locnet_render_border(const dvsg_locnet_t *net) { return net ? net->render_border : DVSG_BORDER_BLACK; }
 
 int dvsg_locnet_in_channels(const dvsg_locnet_t *net) { return net ? base(net)->c_in : 0; }
 
@@ -1459,93 +1214,6 @@ int dvsg_stabilize_ring_inplace_f32(const dvsg_locnet_t *net, int precision, flo
   DVSG_REQUIRE(out_slots, "dvsg_stabilize_ring_inplace_f32: NULL out_slots");
   return stabilize_ring(net, ring_precision(precision), pool, 0, n_pool, table, nullptr, B, H, W, pool, F_t, x_s, y_s,
                         workspace, workspace_bytes, stream, out_slots);
-}
-
-// Source-resolution render of an online step: the T of dvsg_stabilize_* for F_t (tps_apply_kernel on the handle's W^-1
-// columns and V_src, bit for bit), then the uint8 source frames warped by it at their own size.
-int dvsg_tps_render_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
-                       int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream) {
-  DVSG_REQUIRE(net, "dvsg_tps_render_u8: NULL net");
-  return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, nullptr, net->render_filter, net->render_border, net->render_shape, net->out_h, net->out_w);
-}
-
-// dvsg_tps_render_u8 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_u8 itself)
-int dvsg_tps_render_zoom_u8(const dvsg_locnet_t *net, const float *F_t, const uint8_t *src, int n, int src_H, int src_W,
-                            int channel_flip, const float *zoom, float *T, float *out_f32, uint8_t *out_u8, int u8_W,
-                            int u8_x0, void *stream) {
-  DVSG_REQUIRE(net, "dvsg_tps_render_zoom_u8: NULL net");
-  return tps_render_impl(base(net)->winv, base(net)->v_src, F_t, src, n, src_H, src_W, 25, channel_flip, T, out_f32, out_u8,
-                         u8_W, u8_x0, stream, zoom, net->render_filter, net->render_border, net->render_shape, net->out_h, net->out_w);
-}
-
-// dvsg_tps_render_u8 for NV12 frames (nv12.hip): the same T, then both planes warped at their own sizes in one launch.
-// Every argument is checked before the handle is read; a P010 view's further checks follow, before any device work.
-int dvsg_tps_render_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
-                         size_t frame_stride, int n, int H, int W, float *T, uint8_t *out_y, uint8_t *out_uv, size_t out_pitch,
-                         size_t out_frame_stride, void *stream) {
-  DVSG_REQUIRE(net, "dvsg_tps_render_nv12: NULL net");
-  int oh = 0, ow = 0;
-  scaled_view_size(net, &oh, &ow);   // by the pointer's value: the handle itself is not read yet
-  if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
-                                     "dvsg_tps_render_nv12", oh, ow))
-    return rc;
-  if (net->surface_format == DVSG_SURFACE_P010)   // the first read of the handle
-    if (int rc = tps_render_p010_check(y, uv, pitch, frame_stride, n, W, out_y, out_uv, out_pitch, out_frame_stride,
-                                       "dvsg_tps_render_nv12", ow))
-      return rc;
-  return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
-                              out_pitch, out_frame_stride, stream, nullptr, net->render_filter, net->render_border,
-                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_nv12", net->chroma_format);
-}
-
-// dvsg_tps_render_nv12 on the output grid scaled about its centre by zoom[i] (NULL: dvsg_tps_render_nv12 itself)
-int dvsg_tps_render_zoom_nv12(const dvsg_locnet_t *net, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch,
-                              size_t frame_stride, int n, int H, int W, const float *zoom, float *T, uint8_t *out_y,
-                              uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream) {
-  DVSG_REQUIRE(net, "dvsg_tps_render_zoom_nv12: NULL net");
-  int oh = 0, ow = 0;
-  scaled_view_size(net, &oh, &ow);   // by the pointer's value: the handle itself is not read yet
-  if (int rc = tps_render_nv12_check(F_t, y, uv, pitch, frame_stride, n, H, W, T, out_y, out_uv, out_pitch, out_frame_stride,
-                                     "dvsg_tps_render_zoom_nv12", oh, ow))
-    return rc;
-  if (net->surface_format == DVSG_SURFACE_P010)   // the first read of the handle
-    if (int rc = tps_render_p010_check(y, uv, pitch, frame_stride, n, W, out_y, out_uv, out_pitch, out_frame_stride,
-                                       "dvsg_tps_render_zoom_nv12", ow))
-      return rc;
-  return tps_render_nv12_impl(base(net)->winv, base(net)->v_src, F_t, y, uv, pitch, frame_stride, n, H, W, 25, T, out_y, out_uv,
-                              out_pitch, out_frame_stride, stream, zoom, net->render_filter, net->render_border,
-                              net->render_shape, net->surface_format, oh, ow, "dvsg_tps_render_zoom_nv12", net->chroma_format);
-}
-
-// T alone, as dvsg_tps_render_u8 writes it: for a zoomed warp of frames that need no scan first (a fixed crop)
-int dvsg_tps_coefficients_f32(const dvsg_locnet_t *net, const float *F_t, int n, float *T, void *stream) {
-  DVSG_REQUIRE(net && F_t && T, "dvsg_tps_coefficients_f32: NULL pointer");
-  DVSG_REQUIRE(n >= 1, "dvsg_tps_coefficients_f32: n=%d must be >= 1", n);
-  const RenderShape shape = net->render_shape;   // the handle's own; the network is the parent's
-  net = base(net);
-  return tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream, shape);
-}
-
-// The coverage scan of a clip's F_t rows: the T of dvsg_stabilize_* / dvsg_tps_render_u8 for F_t (written), then
-// dvsg_tps_coverage_f32 on it with V_src.  Shapes and workspace are checked before the first launch.
-int dvsg_tps_coverage_net_f32(const dvsg_locnet_t *net, const float *F_t, const float *zoom, int n, int src_H, int src_W,
-                              int out_h, int out_w, float *T, int32_t *n_border, int32_t *key_min, void *workspace,
-                              size_t workspace_bytes, void *stream) {
-  const char *fn = "dvsg_tps_coverage_net_f32";
-  DVSG_REQUIRE(net && F_t && T && n_border && key_min, "%s: NULL pointer", fn);
-  size_t need = 0;
-  if (int rc = dvsg_tps_coverage_workspace_bytes(n, out_h, out_w, &need)) return rc;
-  DVSG_REQUIRE(src_H >= 1 && src_W >= 1, "%s: source size %dx%d must be positive", fn, src_H, src_W);
-  DVSG_REQUIRE(workspace, "%s: NULL workspace", fn);
-  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || workspace_bytes < need)
-    return fail(DVSG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed, 8-byte aligned (dvsg_tps_coverage_workspace_bytes)",
-                fn, workspace_bytes, need);
-  const RenderShape shape = net->render_shape;   // the scan counts the border the shaped render draws
-  net = base(net);
-  if (int rc = tps_apply_impl(net->winv, net->v_src, F_t, 1, n, 25, T, stream, shape)) return rc;
-  return tps_coverage_impl(fn, net->v_src, 0, T, zoom, n, 25, src_H, src_W, out_h, out_w, n_border, key_min, workspace,
-                           workspace_bytes, stream);
 }
 
 // eval_train.py's evaluation graph (:25-51): F_t = localizationNet(patches_t * mask), the warp on the unmasked u_t.

@@ -542,9 +542,9 @@ int check_matrix(const char *fn, int matrix) {
 
 }  // namespace
 
-int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n,
-                          int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
-                          size_t out_frame_stride, const char *fn, int out_H, int out_W) {
+int tps_render_nv12_check(const char *fn, const float *F_t, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride,
+                          int n, int H, int W, const float *T, const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch,
+                          size_t out_frame_stride, int out_H, int out_W) {
   DVSG_REQUIRE(F_t && T, "%s: NULL pointer", fn);
   if (int rc = check_nv12(fn, "source", y, uv, pitch, frame_stride, n, H, W)) return rc;
   if (out_H == 0 && out_W == 0) out_H = H, out_W = W;
@@ -555,9 +555,8 @@ int tps_render_nv12_check(const float *F_t, const uint8_t *y, const uint8_t *uv,
   return check_nv12(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, out_H, out_W);
 }
 
-int tps_render_p010_check(const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int W,
-                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, const char *fn,
-                          int out_W) {
+int tps_render_p010_check(const char *fn, const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int W,
+                          const uint8_t *out_y, const uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, int out_W) {
   if (int rc = check_p010(fn, "source", y, uv, pitch, frame_stride, n, W)) return rc;
   return check_p010(fn, "output", out_y, out_uv, out_pitch, out_frame_stride, n, out_W ? out_W : W);
 }
@@ -577,16 +576,17 @@ int render_scaled_check(const char *fn, int H, int W, int out_H, int out_W, int 
 }
 
 // the arguments have passed tps_render_nv12_check (and, for DVSG_SURFACE_P010, tps_render_p010_check)
-int tps_render_nv12_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *y, const uint8_t *uv,
-                         size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T, uint8_t *out_y,
-                         uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream, const float *zoom,
-                         int render_filter, int render_border, RenderShape shape, int surface_format, int out_H, int out_W,
-                         const char *fn, int chroma_format) {
+int tps_render_nv12_impl(const char *fn, const double *winv_cols, const float *coord, const float *F_t, const float *zoom,
+                         const uint8_t *y, const uint8_t *uv, size_t pitch, size_t frame_stride, int n, int H, int W, int P, float *T,
+                         uint8_t *out_y, uint8_t *out_uv, size_t out_pitch, size_t out_frame_stride, void *stream,
+                         const RenderView &view) {
+  const int render_border = view.border, out_H = view.out_h, out_W = view.out_w;
+  const bool cubic = view.filter == DVSG_RENDER_BICUBIC, p010 = view.surface_format == DVSG_SURFACE_P010;
   // the chroma plane's rows ("Chroma sampling"): H / 2 of a 4:2:0 frame, H of a 4:2:2 one; its columns are W / 2 in both
-  const bool c422 = chroma_format == DVSG_CHROMA_422;
+  const bool c422 = view.chroma_format == DVSG_CHROMA_422;
   const int ch = c422 ? H : H / 2;
   // the planes' samples per luma sample, 1 + the chroma share (1 / 2, or 1 for 4:2:2), times the bytes of a sample
-  const double bytes = (c422 ? 2.0 : 1.5) * (surface_format == DVSG_SURFACE_P010 ? 2.0 : 1.0);
+  const double bytes = (c422 ? 2.0 : 1.5) * (p010 ? 2.0 : 1.0);
   if ((out_H || out_W) && (out_H != H || out_W != W)) {   // a scaled view at another size: kernels of their own
     if (int rc = render_scaled_check(fn, H, W, out_H, out_W, render_border)) return rc;
     const int sy = scaled_factor(H, out_H), sx = scaled_factor(W, out_W), rows = scaled_rows_per_group(sy);
@@ -594,9 +594,8 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
     const int och = c422 ? out_H : out_H / 2;
     const long n_l = (long)gx_l * ceil_div(out_H, rows), n_c = (long)gx_c * ceil_div(och, rows);
     DVSG_REQUIRE(n_l + n_c < (1L << 31), "%s: frame %dx%d too large", fn, out_H, out_W);
-    if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, shape)) return rc;
+    if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, view.shape)) return rc;
     hipStream_t s = as_stream(stream);
-    const bool p010 = surface_format == DVSG_SURFACE_P010;
     // algorithmic bytes: the source planes once in, the output planes once out
     ProfScope prof(kClsTpsWarp, s, 0.0, bytes * n * ((double)H * W + (double)out_H * out_W));
     const dim3 grid((unsigned)(n_l + n_c), n);
@@ -612,7 +611,7 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
       else launch(kS, kCubic, std::integral_constant<int, DVSG_BORDER_BLACK>());
     };
     auto with_filter = [&](auto kS) {
-      if (render_filter == DVSG_RENDER_BICUBIC) with_border(kS, std::true_type());
+      if (cubic) with_border(kS, std::true_type());
       else with_border(kS, std::false_type());
     };
     if (p010) with_filter(uint16_t());
@@ -622,59 +621,48 @@ int tps_render_nv12_impl(const double *winv_cols, const float *coord, const floa
   const int gx_l = ceil_div(W, kThreads), gx_c = ceil_div(W / 2, kThreads);
   const long n_l = (long)gx_l * ceil_div(H, kTpsRows), n_c = (long)gx_c * ceil_div(ch, kTpsRows);
   DVSG_REQUIRE(n_l + n_c < (1L << 31), "dvsg_tps_render_nv12: frame %dx%d too large", H, W);
-  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, shape)) return rc;
+  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, n, P, T, stream, view.shape)) return rc;
   hipStream_t s = as_stream(stream);
   // algorithmic bytes: both planes once in, once out
   ProfScope prof(kClsTpsWarp, s, 0.0, 2.0 * bytes * n * H * W);
-  if (surface_format == DVSG_SURFACE_P010) {   // a P010 view: the same grid of workgroups for every filter, border and zoom
-    const dim3 grid((unsigned)(n_l + n_c), n);
-    auto launch = [&](auto kZoom, auto kCubic, auto kBorder) {
-      hipLaunchKernelGGL((p010_render_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
-                         Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
-                         lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch, out_frame_stride);
-    };
-    const bool cubic = render_filter == DVSG_RENDER_BICUBIC;
+  const dim3 grid((unsigned)(n_l + n_c), n);
+  // every kernel below but the plain one: the same grid of workgroups and one argument list for every surface, filter, border and zoom
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W),
+                       lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch,
+                       out_frame_stride);
+  };
+  if (p010) {   // a P010 view
+    auto launch_p010 = [&](auto kZoom, auto kCubic, auto kBorder) { launch(p010_render_kernel<kZoom(), kCubic(), kBorder()>); };
     if (render_border != DVSG_BORDER_BLACK) {
-      for_render_border(zoom != nullptr, cubic, render_border, launch);
+      for_render_border(zoom != nullptr, cubic, render_border, launch_p010);
     } else {
       const std::integral_constant<int, DVSG_BORDER_BLACK> black;
-      if (zoom && cubic) launch(std::true_type(), std::true_type(), black);
-      else if (zoom) launch(std::true_type(), std::false_type(), black);
-      else if (cubic) launch(std::false_type(), std::true_type(), black);
-      else launch(std::false_type(), std::false_type(), black);
+      if (zoom && cubic) launch_p010(std::true_type(), std::true_type(), black);
+      else if (zoom) launch_p010(std::true_type(), std::false_type(), black);
+      else if (cubic) launch_p010(std::false_type(), std::true_type(), black);
+      else launch_p010(std::false_type(), std::false_type(), black);
     }
     return check_launch("p010_render_kernel");
   }
-  if (render_border != DVSG_BORDER_BLACK) {   // a view with a border mode: the same grid of workgroups for either filter
-    const dim3 grid((unsigned)(n_l + n_c), n);
-    for_render_border(zoom != nullptr, render_filter == DVSG_RENDER_BICUBIC, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {
-      hipLaunchKernelGGL((nv12_render_border_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s,
-                         Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
-                         lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch, out_frame_stride);
+  if (render_border != DVSG_BORDER_BLACK) {   // a view with a border mode
+    for_render_border(zoom != nullptr, cubic, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {
+      launch(nv12_render_border_kernel<kZoom(), kCubic(), kBorder()>);
     });
     return check_launch("nv12_render_border_kernel");
   }
-  if (render_filter == DVSG_RENDER_BICUBIC) {   // a bicubic view: the same grid of workgroups, 16 taps per sample
-    const dim3 grid((unsigned)(n_l + n_c), n);
-    if (zoom)
-      hipLaunchKernelGGL(nv12_render_cubic_kernel<true>, grid, dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride}, coord, T,
-                         zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y,
-                         out_uv, out_pitch, out_frame_stride);
-    else
-      hipLaunchKernelGGL(nv12_render_cubic_kernel<false>, grid, dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride}, coord, T,
-                         zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y,
-                         out_uv, out_pitch, out_frame_stride);
+  if (cubic) {   // a bicubic view: 16 taps per sample
+    if (zoom) launch(nv12_render_cubic_kernel<true>);
+    else launch(nv12_render_cubic_kernel<false>);
     return check_launch("nv12_render_cubic_kernel");
   }
-  if (zoom) {   // dvsg_tps_render_zoom_nv12: the same grid of workgroups on the zoomed output grid
-    hipLaunchKernelGGL(nv12_render_zoom_kernel, dim3((unsigned)(n_l + n_c), n), dim3(kThreads), 0, s,
-                       Nv12{y, uv, pitch, frame_stride}, coord, T, zoom, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2),
-                       lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch, out_frame_stride);
+  if (zoom) {   // dvsg_tps_render_zoom_nv12: on the zoomed output grid
+    launch(nv12_render_zoom_kernel);
     return check_launch("nv12_render_zoom_kernel");
   }
-  hipLaunchKernelGGL(nv12_render_kernel, dim3((unsigned)(n_l + n_c), n), dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride},
-                     coord, T, H, W, P, lin_step(W), lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y,
-                     out_uv, out_pitch, out_frame_stride);
+  hipLaunchKernelGGL(nv12_render_kernel, grid, dim3(kThreads), 0, s, Nv12{y, uv, pitch, frame_stride}, coord, T, H, W, P,
+                     lin_step(W), lin_step(H), lin_step(W / 2), lin_step(ch), gx_l, (int)n_l, gx_c, ch, out_y, out_uv, out_pitch,
+                     out_frame_stride);
   return check_launch("nv12_render_kernel");
 }
 

@@ -931,9 +931,12 @@ int tps_warp_ring_impl(const void *pool, int pool_is_u8, int n_pool, const int *
 // T = the TPS coefficients of dvsg_stabilize_* for F_t (tps_apply_kernel on winv_cols / coord), then frame b of the uint8
 // frames src [B,H,W,3] warped at its own size (tps_warp_kernel<3, uint8_t, uint8_t>): float32 RGB out_f32 [B,H,W,3]
 // and / or uint8 out_u8 [B,H,u8_W,3] in columns [u8_x0, u8_x0 + W).  Every argument is checked before the first launch.
-int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const uint8_t *src, int B, int H, int W,
-                    int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0, void *stream,
-                    const float *zoom, int render_filter, int render_border, RenderShape shape, int out_H, int out_W) {
+int tps_render_impl(const double *winv_cols, const float *coord, const float *F_t, const float *zoom, const uint8_t *src, int B,
+                    int H, int W, int P, int channel_flip, float *T, float *out_f32, uint8_t *out_u8, int u8_W, int u8_x0,
+                    void *stream, const RenderView &view) {
+  const int render_border = view.border;
+  const bool cubic = view.filter == DVSG_RENDER_BICUBIC;
+  int out_H = view.out_h, out_W = view.out_w;
   DVSG_REQUIRE(winv_cols && coord && F_t && src && T, "dvsg_tps_render_u8: NULL pointer");
   DVSG_REQUIRE(out_f32 || out_u8, "dvsg_tps_render_u8: neither out_f32 nor out_u8 given");
   DVSG_REQUIRE(B >= 1 && B <= 65535, "dvsg_tps_render_u8: n=%d outside [1, 65535]", B);
@@ -944,7 +947,7 @@ int tps_render_impl(const double *winv_cols, const float *coord, const float *F_
   DVSG_REQUIRE(!out_u8 || (long)out_H * u8_W < (1L << 31), "dvsg_tps_render_u8: uint8 image too large");
   if (out_H != H || out_W != W) {   // a scaled view at another size: kernels of their own
     if (int rc = render_scaled_check("dvsg_tps_render_u8", H, W, out_H, out_W, render_border)) return rc;
-    if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream, shape)) return rc;
+    if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream, view.shape)) return rc;
     const int sy = scaled_factor(H, out_H), sx = scaled_factor(W, out_W);
     const dim3 grid(ceil_div(out_W, kThreads), ceil_div(out_H, scaled_rows_per_group(sy)), B);
     hipStream_t s = as_stream(stream);
@@ -960,30 +963,30 @@ int tps_render_impl(const double *winv_cols, const float *coord, const float *F_
       else if (render_border == DVSG_BORDER_MIRROR) launch(kCubic, std::integral_constant<int, DVSG_BORDER_MIRROR>());
       else launch(kCubic, std::integral_constant<int, DVSG_BORDER_BLACK>());
     };
-    if (render_filter == DVSG_RENDER_BICUBIC) with_border(std::true_type());
+    if (cubic) with_border(std::true_type());
     else with_border(std::false_type());
     return check_launch("tps_render_scaled_kernel");
   }
-  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream, shape)) return rc;
+  if (int rc = tps_apply_impl(winv_cols, coord, F_t, 1, B, P, T, stream, view.shape)) return rc;
   dim3 grid(ceil_div(W, kThreads), ceil_div(H, kTpsRows), B);
   const float sx = lin_step(W), sy = lin_step(H);
   hipStream_t s = as_stream(stream);
   // algorithmic bytes: the uint8 frame once, then 3 B (uint8) and / or 12 B (float32) per output pixel
   ProfScope prof(kClsTpsWarp, s, 0.0, (double)B * H * W * (3.0 + (out_u8 ? 3.0 : 0.0) + (out_f32 ? 12.0 : 0.0)));
-  if (render_border != DVSG_BORDER_BLACK) {   // a view with a border mode: the same grid of workgroups for either filter
-    for_render_border(zoom != nullptr, render_filter == DVSG_RENDER_BICUBIC, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {
-      hipLaunchKernelGGL((tps_render_border_kernel<kZoom(), kCubic(), kBorder()>), grid, dim3(kThreads), 0, s, src, coord, 0L, T,
-                         zoom, H, W, P, H, W, sx, sy, out_u8, u8_W, u8_x0, channel_flip ? 1 : 0, out_f32);
+  // the border and bicubic kernels: the same grid of workgroups as the plain ones and one argument list
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, s, src, coord, 0L, T, zoom, H, W, P, H, W, sx, sy, out_u8, u8_W, u8_x0,
+                       channel_flip ? 1 : 0, out_f32);
+  };
+  if (render_border != DVSG_BORDER_BLACK) {   // a view with a border mode, either filter
+    for_render_border(zoom != nullptr, cubic, render_border, [&](auto kZoom, auto kCubic, auto kBorder) {
+      launch(tps_render_border_kernel<kZoom(), kCubic(), kBorder()>);
     });
     return check_launch("tps_render_border_kernel");
   }
-  if (render_filter == DVSG_RENDER_BICUBIC) {   // a bicubic view: the same grid of workgroups, 16 taps per pixel
-    if (zoom)
-      hipLaunchKernelGGL(tps_render_cubic_kernel<true>, grid, dim3(kThreads), 0, s, src, coord, 0L, T, zoom, H, W, P, H, W, sx,
-                         sy, out_u8, u8_W, u8_x0, channel_flip ? 1 : 0, out_f32);
-    else
-      hipLaunchKernelGGL(tps_render_cubic_kernel<false>, grid, dim3(kThreads), 0, s, src, coord, 0L, T, zoom, H, W, P, H, W, sx,
-                         sy, out_u8, u8_W, u8_x0, channel_flip ? 1 : 0, out_f32);
+  if (cubic) {   // a bicubic view: 16 taps per pixel
+    if (zoom) launch(tps_render_cubic_kernel<true>);
+    else launch(tps_render_cubic_kernel<false>);
     return check_launch("tps_render_cubic_kernel");
   }
   if (zoom) {   // dvsg_tps_render_zoom_u8: the same launch on the zoomed grid

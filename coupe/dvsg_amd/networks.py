@@ -168,7 +168,8 @@ class LocNet(object):
         _lib.call("dvsg_locnet_create", n, c_names, c_data, c_nd,
                   dims.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(handle))
         self.handle = handle
-        self._views = {}   # (render filter, border, strength, rigidity, shape model, surface) -> view handle, made on first use
+        self._views = {}   # (render filter, border, strength, rigidity, shape model, surface[, out_size[, chroma]]) -> view
+                           # handle, made on first use (view())
         self._keep = None  # the library copied everything to the device
         self._ws = None
         self.in_channels = _lib.load().dvsg_locnet_in_channels(self.handle)
@@ -186,54 +187,41 @@ class LocNet(object):
         THAT handle whose NV12 renders read and write 4:2:2 frames, a UV plane of H rows (`dvsg_locnet_view_create_chroma`:
         everything else inherited; include/dvsg_amd.h, "Chroma sampling"); no other entry point reads it."""
         check_chroma(chroma)
-        if chroma != "420":
-            out_size = check_out_size(out_size)
-            key = (render_filter, border, strength, rigidity, shape_model, surface, out_size, chroma)
-            v = self._views.get(key)
-            if v is None:
-                inner = self.view(render_filter, border, strength, rigidity, shape_model, surface, out_size)
-                v = ctypes.c_void_p()
-                _lib.call("dvsg_locnet_view_create_chroma", inner, CHROMAS[chroma], ctypes.byref(v))
-                self._views[key] = v
-            return v
         out_size = check_out_size(out_size)
-        if out_size is not None:
-            key = (render_filter, border, strength, rigidity, shape_model, surface, out_size)
-            v = self._views.get(key)
-            if v is None:
-                inner = self.view(render_filter, border, strength, rigidity, shape_model, surface)
-                v = ctypes.c_void_p()
-                _lib.call("dvsg_locnet_view_create_scaled", inner, out_size[0], out_size[1], ctypes.byref(v))
-                self._views[key] = v
-            return v
         check_surface(surface)
-        if surface != "nv12":
-            key = (render_filter, border, strength, rigidity, shape_model, surface)
-            v = self._views.get(key)
-            if v is None:
-                inner = self.view(render_filter, border, strength, rigidity, shape_model)
-                v = ctypes.c_void_p()
-                _lib.call("dvsg_locnet_view_create_surface", inner, SURFACES[surface], ctypes.byref(v))
-                self._views[key] = v
-            return v
         check_render_filter(render_filter)
         check_border(border)
+        key = (render_filter, border, strength, rigidity, shape_model)   # as given: what the layers above the base are kept by
         strength, rigidity, shape_model = check_shape(strength, rigidity, shape_model)
+        # the base: filter, border and shape by value, on the network itself
         shaped = strength != 1.0 or rigidity != 0.0
         if not shaped:
             shape_model = "affine"
-            if render_filter == "bilinear" and border == "black":
-                return self.handle
-        key = (render_filter, border, strength, rigidity, shape_model, surface)
+        base = (render_filter, border, strength, rigidity, shape_model, "nv12")   # (these five as the library receives them)
+        if shaped:
+            v = self._view(base, "dvsg_locnet_view_create_shaped", self.handle, RENDER_FILTERS[render_filter],
+                           RENDER_BORDERS[border], SHAPE_MODELS[shape_model], strength, rigidity)
+        elif render_filter != "bilinear" or border != "black":
+            v = self._view(base, "dvsg_locnet_view_create_border", self.handle, RENDER_FILTERS[render_filter],
+                           RENDER_BORDERS[border])
+        else:
+            v = self.handle
+        # then one layer per inherited property, each a view of the handle so far: (value, its default, constructor, arguments)
+        for value, default, constructor, args in (
+                (surface, "nv12", "dvsg_locnet_view_create_surface", (SURFACES[surface],)),
+                (out_size, None, "dvsg_locnet_view_create_scaled", out_size),
+                (chroma, "420", "dvsg_locnet_view_create_chroma", (CHROMAS[chroma],))):
+            key += (value,)
+            if value != default:
+                v = self._view(key, constructor, v, *args)
+        return v
+
+    def _view(self, key, constructor, *args):
+        """The view kept under `key`, made on first use by `constructor(*args, &view)`."""
         v = self._views.get(key)
         if v is None:
             v = ctypes.c_void_p()
-            if shaped:
-                _lib.call("dvsg_locnet_view_create_shaped", self.handle, RENDER_FILTERS[render_filter], RENDER_BORDERS[border],
-                          SHAPE_MODELS[shape_model], strength, rigidity, ctypes.byref(v))
-            else:
-                _lib.call("dvsg_locnet_view_create_border", self.handle, RENDER_FILTERS[render_filter],
-                          RENDER_BORDERS[border], ctypes.byref(v))
+            _lib.call(constructor, *(args + (ctypes.byref(v),)))
             self._views[key] = v
         return v
 

@@ -25,7 +25,7 @@ BIT equality of a call against the same call run alone or eagerly, and no number
    which also makes an invalid call and reads its own dvsg_last_error_string().  Four of the pairs are views of one parent:
    two delivery sizes on a shared F_t, a P010 beside an NV16 view, one scaled view twice, and the plain handle beside a
    scaled view on one source buffer.
-2a. The table of scaled views (g_scaled_views, locnet.hip: the library's one process-global host table on a hot path, read
+2a. The table of scaled views (g_scaled_views, views.cpp: the library's one process-global host table on a hot path, read
    by every NV12 render before it touches the handle): two threads render through scaled views while a third makes and
    destroys 64 scaled views of the same parent; the renders equal their runs alone, the sizes of the views used and of the
    plain handle are unchanged, the parent's views are those from before, and each thread's refused call names the size of
@@ -1503,7 +1503,7 @@ def test_two_threads_of_one_handle(ctx, delay):
 def test_two_threads_of_views(ctx, delay):
     """Two renders through scaled views from two Python threads while a third makes and destroys 64 scaled views of the same
     parent: the NV12 renders look the size of their handle up, by its address, in a process-global table that the view
-    constructors and dvsg_locnet_destroy write (the invariant above g_scaled_mutex, locnet.hip).  A bounded loop of valid
+    constructors and dvsg_locnet_destroy write (the invariant above g_scaled_mutex, views.cpp).  A bounded loop of valid
     calls.  Each worker then makes a call that is refused before any launch and reads its own message: the output pitch is
     too short for the VIEW's row -- 34 bytes for the 36 of the byte view, the 102 bytes of a source row of bytes for the
     2 x 52 of the word view -- so the message also shows that the size came from the right table entry."""
