@@ -19,6 +19,7 @@ SOURCES=(
   "loss_kernels.hip      | -ffp-contract=off"
   "crop_kernels.hip      | -ffp-contract=off"
   "scene_kernels.hip     | -ffp-contract=off"
+  "shake_kernels.hip     |"
   "conv1_f16.hip         | -ffp-contract=off"
   "conv1_f32.hip         | -ffp-contract=off"
   "conv1_x3.hip          | -ffp-contract=off"

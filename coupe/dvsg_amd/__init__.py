@@ -13,4 +13,4 @@ from . import _lib  # noqa: F401
 from ._lib import DvsgError  # noqa: F401
 
 __all__ = ["DvsgError", "model", "networks", "ThinPlateSpline", "ThinPlateSpline2",
-           "warp_with_optical_flow", "spatial_transformer", "weights", "clip", "online", "eval_train", "y4m", "pipe"]
+           "warp_with_optical_flow", "spatial_transformer", "weights", "clip", "online", "eval_train", "y4m", "pipe", "shake"]

@@ -711,6 +711,55 @@ int dvsg_scene_step_f32(const float *pool, int n_pool, int H, int W, const int32
                         int32_t *table, int32_t *out_slots, int32_t *cut, void *workspace, size_t workspace_bytes,
                         void *stream);
 /* ---------------------------------------------------------------------------------------
+ * SHAKE (coupe.dvsg_amd.shake): how much a clip moves from frame to frame, measured from its own luma planes -- no ground
+ * truth, no model.  The global motion of every pair of consecutive frames by block matching, in sixteenths of a reduced
+ * pixel.  dvsg_shake_measure_u8 is synchronous and takes no stream: its result is a small HOST array, so it has to wait for
+ * the device whatever its interface.  In order: 1. every argument is checked before any HIP call; 2. the call waits for the
+ * device (hipDeviceSynchronize: whatever stream wrote the planes has finished); 3. it launches three kernels on the legacy
+ * default stream; 4. it copies the results to the host and returns.  It allocates and frees nothing.
+ *   luma          n planes of H x W bytes ON THE DEVICE: row i of frame t at luma + t * frame_stride + i * pitch, W bytes used
+ *                 -- the Y plane of an NV12 / NV16 batch is passed as it lies.  Only those bytes are read.
+ *   vectors_host  int32 [n - 1, 4] on the HOST: row t - 1 describes frame t against frame t - 1.
+ *   blocks_host   int32 [n - 1, n_blk, 3] on the HOST, or NULL.
+ *   workspace     caller-owned device memory, 16-byte aligned, dvsg_shake_workspace_bytes(...) bytes (DVSG_ERR_WORKSPACE if
+ *                 short or misaligned, before any device work): the reduced planes, the per-block results and the device copy
+ *                 of the vectors.
+ *   The rule.  All of it is integer arithmetic; tests/shake_ref.py restates it in NumPy and the bar is bit equality.
+ *   1. Reduce.  With f = factor >= 1, h = H / f and w = W / f (integer division, trailing rows and columns dropped):
+ *      r[i][j] = (sum of the f x f bytes + f*f/2) / (f*f), in uint8.  For f = 1 this is the plane itself.
+ *   2. Blocks.  Blocks are 16 x 16 on the reduced plane.  Counts: ny = (h - 2*margin_y) / 16, nx = (w - 2*margin_x) / 16,
+ *      n_blk = ny*nx.  Block (a, c) has its top-left at (margin_y + 16a, margin_x + 16c); it is row a*nx + c of blocks_host.
+ *      Requirements: 1 <= radius <= 16, both margins >= radius, 1 <= n_blk <= 2048.  An n_blk above 2048 is
+ *      DVSG_ERR_INVALID_ARG, and the text names factor.
+ *   3. Match.  For a block of frame t at (y0, x0) and every (dy, dx) in [-R, R]^2:
+ *      S(dy,dx) = sum over the 256 pixels |cur[y0+i][x0+j] - prev[y0+i+dy][x0+j+dx]|, which is at most 65280.
+ *      The best candidate is the minimum under the order (S, dy*dy + dx*dx, dy, dx).  Equal SADs resolve to the shortest
+ *      vector, then the smallest dy, then the smallest dx.  So cur[y][x] looks like prev[y+dy][x+dx]: the vector says where
+ *      the content came from.
+ *   4. Validity and the sixteenth-pel step.  A block is invalid when its best candidate lies on the search boundary
+ *      (|dy| == R or |dx| == R).  Otherwise, with S0 the best SAD, Sxm / Sxp its left / right neighbours and Sym / Syp its
+ *      upper / lower ones: cx = Sxm - 2*S0 + Sxp, and cy likewise, both >= 0.  The block is valid iff cx >= max(texture, 1)
+ *      and cy >= max(texture, 1).  Flat blocks and blocks with edges in one direction only drop out here.
+ *      vx = 16*dx + floor((16*(Sxm - Sxp) + cx) / (2*cx)), and vy likewise.  The division is a floor with a possibly
+ *      negative numerator.  The fraction lies in [-8, 8].  Invalid blocks report (0, 0, 0); valid ones report (vx, vy, 1).
+ *   5. Global vector of a pair.  n_valid counts the valid blocks, and ok = n_valid >= min_blocks (min_blocks >= 1).
+ *      gx is the lower median of vx over the valid blocks: the element of rank (n_valid - 1) / 2 in sorted order.  gy is the
+ *      same for vy, independently.  The row is [gx, gy, n_valid, ok], with gx = gy = 0 when not ok.  Units are sixteenths
+ *      of a reduced pixel per frame.
+ *   Checked before any device work (DVSG_ERR_INVALID_ARG, the message names the argument): NULL luma / vectors_host /
+ *   workspace / bytes, 2 <= n <= 4096 (feed longer clips in chunks that overlap by one frame), 1 <= H, W <= 16384,
+ *   1 <= factor <= 16, the requirements of 2., pitch >= W, frame_stride >= (H - 1) pitch + W, texture >= 0, min_blocks >= 1.
+ *   What the figure is not: motion beyond the radius is lost, not measured; a scene cut gives one meaningless row.
+ *   Kernels (shake_kernels.hip): the reduction (16-byte loads over every whole 16-byte unit of a row, a scalar path at the
+ *   ragged ends, nothing padded), the matcher (one workgroup per block and pair; block and window staged in LDS once,
+ *   v_sad_u8 on dwords formed with v_alignbyte_b32, all SADs kept in LDS as 16-bit values, the minimum one packed key per
+ *   lane) and the medians (one workgroup per pair, rank counting).
+ * ------------------------------------------------------------------------------------- */
+int dvsg_shake_workspace_bytes(int n, int H, int W, int factor, int radius, int margin_y, int margin_x, size_t *bytes);
+int dvsg_shake_measure_u8(const uint8_t *luma, size_t pitch, size_t frame_stride, int n, int H, int W, int factor, int radius,
+                          int margin_y, int margin_x, int texture, int min_blocks, int32_t *vectors_host, int32_t *blocks_host,
+                          void *workspace, size_t workspace_bytes);
+/* ---------------------------------------------------------------------------------------
  * NV12 frames (coupe.dvsg_amd.online, frame_format="nv12"): what a hardware decoder hands over and an encoder takes.
  * Layout of a batch of n frames of H x W (H, W even, >= 4):
  *   y   uint8: row i of frame f at y + f * frame_stride + i * pitch, W bytes used;
