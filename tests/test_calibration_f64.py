@@ -164,9 +164,10 @@ _CALS = {}
 
 
 def cal_of(weights, index):
-    if index not in _CALS:
-        _CALS[index] = Cal(weights, *WINDOWS[index])
-    return _CALS[index]
+    key = (id(weights), index)                    # (the checkpoint is kept in the entry, so its id stays its own)
+    if key not in _CALS:
+        _CALS[key] = (Cal(weights, *WINDOWS[index]), weights)
+    return _CALS[key][0]
 
 
 def widths():
@@ -374,7 +375,7 @@ def test_units_on_the_known_plain_weights(synthetic_weights, opts, shape):
     assert run.net is cal.net
     try:
         for i, U, kind in layers():
-            tu.PLAIN[U.scope + NAMES[kind] + "/"] = cal.q[(i, kind)][0]
+            tu.PLAIN[(id(synthetic_weights), U.scope + NAMES[kind] + "/")] = cal.q[(i, kind)][0]
         tu._set_options(opts)
         tu._check_units(synthetic_weights, run, set(range(2, 18)), opts, " [known plain weights, %s]" % (tu._opt_id(opts) or "default"))
     finally:

@@ -6,7 +6,10 @@ is tiny amplify rounding noise, and the torch-CPU float32 oracle sits 1.7e-5 (64
 same graph.  So the yardstick is that float64 ARBITER (oracle/cnn_torch.py `TorchLocNet(dtype=float64)`): F_t of each
 precision RELATIVE to max |F_t| (the stress head predicts displacements of O(1), not O(0.05)); the exact-float32 path
 may be no further from it than 2 x the float32 oracle's own distance; the other bounds are ~3x the values measured on
-MI355X (round 4) and are what the reduced precisions cost on such a checkpoint -- more than on the friendly one."""
+MI355X (round 4) and are what the reduced precisions cost on such a checkpoint -- more than on the friendly one.
+
+The per-element float64 pins on this checkpoint -- units, conv1, pool, head, calibration and the float16-subnormal weight
+pieces, at derived bounds -- live in test_stress_f64.py; this file keeps the end-to-end figures."""
 import numpy as np
 import pytest
 

@@ -687,10 +687,11 @@ _NETS = {}
 
 def _net(weights, positive):
     from coupe.dvsg_amd.networks import LocNet
-    if positive not in _NETS:
-        _NETS[positive] = (LocNet(positive_weights(weights) if positive else weights),
-                           fold_conv1(positive_weights(weights) if positive else weights))
-    return _NETS[positive]
+    key = (id(weights), positive)                 # (the checkpoint is kept in the entry, so its id stays its own)
+    if key not in _NETS:
+        _NETS[key] = (LocNet(positive_weights(weights) if positive else weights),
+                      fold_conv1(positive_weights(weights) if positive else weights), weights)
+    return _NETS[key][:2]
 
 
 class Placed(object):

@@ -222,10 +222,15 @@ def weight_class(mode, block, kind):
     return "f16p" if f16_pairs(mask, block, kind) else "f16c"
 
 
-# The exact plain float16 copy of a layer, {scope of the conv: float16 [cout][K]}, for the "f16c" class.  Empty unless a test
-# fills it from the library's read-back (test_calibration_f64.py, which first holds that copy to the rule that chose it);
-# every case of this file runs with it empty and keeps the interval below.
+# The exact plain float16 copy of a layer, {(id of the checkpoint, scope of the conv): float16 [cout][K]}, for the "f16c"
+# class.  Empty unless a test fills it from the library's read-back (test_calibration_f64.py, which first holds that copy to
+# the rule that chose it); every case of this file runs with it empty and keeps the interval below.
 PLAIN = {}
+
+
+def plain_known(weights):
+    """does PLAIN hold the copies of this checkpoint's calibrated handle?"""
+    return any(k[0] == id(weights) for k in PLAIN)
 
 
 def held(w, cls, plain=None):
@@ -301,7 +306,7 @@ def _layer(weights, U, kind, mode, x, Ex, Qx, stride, exact, opts, extra_S=None,
     if mut:
         w, b = mut(kind, w, b)
     cls = "f32" if exact else weight_class(mode, U.block, kind)
-    known = None if mut else PLAIN.get(U.scope + name + "/")
+    known = None if mut else PLAIN.get((id(weights), U.scope + name + "/"))
     w64, wabs, rad = held(w, cls, known)
     k = 3 if kind == "c2" else 1
     K = w.shape[1]
@@ -324,7 +329,7 @@ def _layer(weights, U, kind, mode, x, Ex, Qx, stride, exact, opts, extra_S=None,
     if bool((Ex > 0).any()):
         E = own + conv64(Ex, wabs, k, stride)
         # (calibrated net, plain copy known: no shared interval is carried any more, the float16 mode's quadrature holds)
-        c = C_QUAD["f16" if mode == "f16cal" and PLAIN else mode]
+        c = C_QUAD["f16" if mode == "f16cal" and plain_known(weights) else mode]
         Q = own + (c * torch.sqrt(conv64(Qx * Qx, wabs * wabs, k, stride)) if c else conv64(Qx, wabs, k, stride))
     return pre, E, Q, S
 
@@ -497,6 +502,24 @@ def _bf16x2(t):
     return torch.from_numpy((p1 + root.bf16_rn((a - p1).astype(F32))).astype(F32))
 
 
+# A defect outside MUTANTS: the synthetic checkpoint holds no float16-subnormal piece that matters, so it cannot show it
+# (test_stress_f64.py runs it on the stress checkpoint, and asserts that it is invisible here).
+FLUSH_SUBNORMAL = "float16-subnormal weight pieces flushed to zero"
+
+
+def flushed_pieces(w, cls):
+    """the value a kernel multiplies if it reads every float16-subnormal piece (0 < |p| < 2^-14) of the "f16p" / "f32s"
+    rows as 0: float64 [cout][K]"""
+    if cls == "f16p":
+        hi, lo = unrows_hi_lo(rows_hi_lo(w))
+        scale = 1.0 / 2048.0
+    else:
+        hi, lo = unrows_f32s(rows_f32s(w))
+        scale = 1.0
+    hi, lo = (np.where(np.abs(p.astype(np.float64)) < 2.0 ** -14, 0.0, p.astype(np.float64)) for p in (hi, lo))
+    return hi + lo * scale
+
+
 def replay(weights, U, mode, x, defect=None):
     """float32 replay of unit U's launches (torch CPU float32 convs on the mode's held weights, the mode's storage rounding
     after every launch), optionally with one simulated defect.  x: float32 torch [B, h, w, cin] in the mode's format."""
@@ -521,6 +544,8 @@ def replay(weights, U, mode, x, defect=None):
         cls = weight_class(mode, U.block, kind)
         if plain:
             w64 = torch.from_numpy(w.astype(np.float16).astype(np.float64))
+        elif defect == FLUSH_SUBNORMAL and cls in ("f16p", "f32s"):
+            w64 = torch.from_numpy(flushed_pieces(w, cls))
         else:
             w64 = held(w, cls)[0]
         w32 = w64.float()
@@ -732,13 +757,13 @@ def _unit_net(weights, mode):
     calibrated on inputs.window_frames patches"""
     if mode != "f16cal":
         return _net(weights, False)[0]
-    if "net" not in _CAL:
+    if id(weights) not in _CAL:
         import inputs as tin
         from coupe.dvsg_amd.networks import LocNet
         net = LocNet(weights)
         net.calibrate_f16(tin.window_frames(31, 2, 64, 96))
-        _CAL["net"] = net
-    return _CAL["net"]
+        _CAL[id(weights)] = (net, weights)        # (the checkpoint is kept in the entry, so its id stays its own)
+    return _CAL[id(weights)][0]
 
 
 def _prec(mode):
