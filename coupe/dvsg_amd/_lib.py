@@ -111,6 +111,9 @@ SIGNATURES = {
     "dvsg_shake_workspace_bytes": [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_size_t)],
     "dvsg_shake_measure_u8": [_vp, ctypes.c_size_t, ctypes.c_size_t, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                               ctypes.c_size_t],
+    "dvsg_shake_motion_workspace_bytes": [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_size_t)],
+    "dvsg_shake_motion_u8": [_vp, ctypes.c_size_t, ctypes.c_size_t, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                             ctypes.c_size_t],
     "dvsg_loss_workspace_bytes": [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t)],
     "dvsg_loss_image_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "dvsg_loss_temporal_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],

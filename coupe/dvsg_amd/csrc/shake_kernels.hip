@@ -20,6 +20,11 @@
 //   shake_global_kernel  grid (n - 1), one workgroup per pair: the block rows into LDS (an invalid block as INT_MAX), then the
 //                        two lower medians by rank counting -- the rank of entry i is the number of entries below it plus the
 //                        equal ones in front of it, so exactly one entry has rank (n_valid - 1) / 2.
+// dvsg_shake_motion_u8 ("SHAKE MOTION", tests/shake_motion_ref.py) is the same call with another third launch:
+//   shake_motion_kernel  grid (n - 1), one workgroup per pair: the same rows and medians (pair_medians, shared with
+//                        shake_global_kernel), then every lane gates its blocks against the medians and adds up the nine sums
+//                        of the similarity fit in int64 registers; __shfl_xor inside a wave, LDS across the four waves, thread
+//                        0 writes the 13 values.  Integers only and no atomics: the order of the additions cannot matter.
 #include <climits>
 #include <cstdint>
 
@@ -45,6 +50,7 @@ struct Geometry {
   int h, w, ny, nx, n_blk;
   size_t plane_stride;   // bytes from one reduced plane to the next: h w rounded up to 16
   size_t blocks_off, vectors_off, bytes;
+  size_t motion_bytes;   // of dvsg_shake_motion_u8: int64 [n - 1, 13] at vectors_off in place of the vectors
 };
 
 __global__ __launch_bounds__(kThreads) void shake_reduce_kernel(const uint8_t *__restrict__ luma, size_t pitch,
@@ -162,12 +168,11 @@ __global__ __launch_bounds__(kThreads) void shake_match_kernel(const uint8_t *__
   row[2] = valid;
 }
 
-__global__ __launch_bounds__(kThreads) void shake_global_kernel(const int32_t *__restrict__ blocks, int n_blk, int min_blocks,
-                                                                int32_t *__restrict__ vectors) {
-  __shared__ int vx[kMaxBlocks], vy[kMaxBlocks];
-  __shared__ int median[2], counts[kWaves];
-  const int t = threadIdx.x, pair = blockIdx.x;
-  const int32_t *rows = blocks + (size_t)pair * n_blk * 3;
+// The block rows of one pair into LDS (an invalid block as INT_MAX in both) and the two lower medians into median[0..1] by
+// rank counting; returns n_valid.  Ends with the barrier that publishes the medians and the rows.
+__device__ __forceinline__ int pair_medians(const int32_t *__restrict__ rows, int n_blk, int *vx, int *vy, int *median,
+                                            int *counts) {
+  const int t = threadIdx.x;
   int mine = 0;
   for (int i = t; i < n_blk; i += kThreads) {
     const int ok = rows[3 * i + 2];
@@ -197,6 +202,15 @@ __global__ __launch_bounds__(kThreads) void shake_global_kernel(const int32_t *_
     if (rb == target) median[1] = b;
   }
   __syncthreads();
+  return valid;
+}
+
+__global__ __launch_bounds__(kThreads) void shake_global_kernel(const int32_t *__restrict__ blocks, int n_blk, int min_blocks,
+                                                                int32_t *__restrict__ vectors) {
+  __shared__ int vx[kMaxBlocks], vy[kMaxBlocks];
+  __shared__ int median[2], counts[kWaves];
+  const int t = threadIdx.x, pair = blockIdx.x;
+  const int valid = pair_medians(blocks + (size_t)pair * n_blk * 3, n_blk, vx, vy, median, counts);
   if (t == 0) {
     const int ok = valid >= min_blocks ? 1 : 0;
     int32_t *row = vectors + (size_t)pair * 4;
@@ -204,6 +218,60 @@ __global__ __launch_bounds__(kThreads) void shake_global_kernel(const int32_t *_
     row[1] = ok ? median[1] : 0;
     row[2] = valid;
     row[3] = ok;
+  }
+}
+
+constexpr int kMotionSums = 9;            // n_in, Sx, Sy, Su, Sv, Sxx, Sxu, Sxv, Suu
+constexpr int kMotionRow = 4 + kMotionSums;
+constexpr int kMaxGate = 1 << 20;
+
+__global__ __launch_bounds__(kThreads) void shake_motion_kernel(const int32_t *__restrict__ blocks, int n_blk, int nx,
+                                                                int min_blocks, int gate, long long *__restrict__ motion) {
+  __shared__ int vx[kMaxBlocks], vy[kMaxBlocks];
+  __shared__ int median[2], counts[kWaves];
+  __shared__ long long wave_sum[kWaves][kMotionSums];
+  const int t = threadIdx.x, pair = blockIdx.x;
+  const int valid = pair_medians(blocks + (size_t)pair * n_blk * 3, n_blk, vx, vy, median, counts);
+  const int ok = valid >= min_blocks ? 1 : 0;
+  const int gx = ok ? median[0] : 0, gy = ok ? median[1] : 0;
+  const int ny = n_blk / nx;
+  long long s[kMotionSums];
+#pragma unroll
+  for (int k = 0; k < kMotionSums; ++k) s[k] = 0;
+  for (int i = t; i < n_blk && ok; i += kThreads) {
+    const int u = vx[i], v = vy[i];
+    if (u == INT_MAX || abs(u - gx) > gate || abs(v - gy) > gate) continue;   // |u|, |v| <= 248: no overflow
+    const int a = i / nx, c = i - a * nx;
+    const int X = 2 * c - (nx - 1), Y = 2 * a - (ny - 1);                      // |X|, |Y| <= 2047: the products fit an int
+    s[0] += 1;
+    s[1] += X;
+    s[2] += Y;
+    s[3] += u;
+    s[4] += v;
+    s[5] += X * X + Y * Y;
+    s[6] += X * u + Y * v;
+    s[7] += X * v - Y * u;
+    s[8] += u * u + v * v;
+  }
+#pragma unroll
+  for (int k = 0; k < kMotionSums; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off);
+    if ((t & 63) == 0) wave_sum[t >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (t != 0) return;
+  long long *row = motion + (size_t)pair * kMotionRow;
+  row[0] = gx;
+  row[1] = gy;
+  row[2] = valid;
+  row[3] = ok;
+#pragma unroll
+  for (int k = 0; k < kMotionSums; ++k) {
+    long long sum = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) sum += wave_sum[w][k];
+    row[4 + k] = sum;
   }
 }
 
@@ -233,7 +301,41 @@ int shake_geometry(const char *fn, int n, int H, int W, int factor, int radius, 
   g->blocks_off = (size_t)n * g->plane_stride;
   g->vectors_off = g->blocks_off + round16((size_t)(n - 1) * g->n_blk * 3 * sizeof(int32_t));
   g->bytes = g->vectors_off + (size_t)(n - 1) * 4 * sizeof(int32_t);
+  g->motion_bytes = g->vectors_off + (size_t)(n - 1) * kMotionRow * sizeof(int64_t);
   return DVSG_OK;
+}
+
+// What both calls check after their NULL pointers, before any HIP call; `need` is g.bytes or g.motion_bytes of the geometry
+// it fills and `query` the function that reports it.
+int shake_check(const char *fn, const char *query, size_t Geometry::*need, size_t pitch, size_t frame_stride, int n, int H, int W,
+                int factor, int radius, int margin_y, int margin_x, int texture, int min_blocks, const void *workspace,
+                size_t workspace_bytes, Geometry *g) {
+  if (int rc = shake_geometry(fn, n, H, W, factor, radius, margin_y, margin_x, g)) return rc;
+  DVSG_REQUIRE(pitch >= (size_t)W, "%s: pitch=%zu below W=%d", fn, pitch, W);
+  DVSG_REQUIRE(frame_stride >= (size_t)(H - 1) * pitch + (size_t)W, "%s: frame_stride=%zu below a frame's (H - 1) pitch + W = %zu",
+               fn, frame_stride, (size_t)(H - 1) * pitch + (size_t)W);
+  DVSG_REQUIRE(texture >= 0, "%s: texture=%d must be >= 0", fn, texture);
+  DVSG_REQUIRE(min_blocks >= 1, "%s: min_blocks=%d must be >= 1", fn, min_blocks);
+  DVSG_REQUIRE(workspace, "%s: NULL workspace", fn);
+  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
+    return fail(DVSG_ERR_WORKSPACE, "%s: workspace must be 16-byte aligned", fn);
+  if (workspace_bytes < g->*need)
+    return fail(DVSG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", fn, workspace_bytes, g->*need, query);
+  return DVSG_OK;
+}
+
+// The wait for the device and the two launches that both calls share: the reduced planes and the block rows.
+int shake_blocks(const Geometry &g, const uint8_t *luma, size_t pitch, size_t frame_stride, int n, int factor, int radius,
+                 int margin_y, int margin_x, int texture, uint8_t *red, int32_t *blocks) {
+  DVSG_HIP(hipDeviceSynchronize());   // whatever stream made the planes has finished
+  const int tile_w = kSegBytes / factor;
+  const int tiles = ceil_div(g.w, tile_w);
+  hipLaunchKernelGGL(shake_reduce_kernel, dim3((unsigned)tiles * g.h, n), dim3(kThreads), (size_t)factor * kSegPitch, nullptr, luma,
+                     pitch, frame_stride, g.h, g.w, factor, tiles, red, g.plane_stride);
+  if (int rc = check_launch("shake_reduce_kernel")) return rc;
+  hipLaunchKernelGGL(shake_match_kernel, dim3(g.n_blk, n - 1), dim3(kThreads), 0, nullptr, red, g.plane_stride, g.w, g.nx, g.n_blk,
+                     radius, margin_y, margin_x, texture, blocks);
+  return check_launch("shake_match_kernel");
 }
 
 }  // namespace
@@ -258,35 +360,52 @@ int dvsg_shake_measure_u8(const uint8_t *luma, size_t pitch, size_t frame_stride
   const char *fn = "dvsg_shake_measure_u8";
   DVSG_REQUIRE(luma && vectors_host, "%s: NULL pointer", fn);
   Geometry g;
-  if (int rc = shake_geometry(fn, n, H, W, factor, radius, margin_y, margin_x, &g)) return rc;
-  DVSG_REQUIRE(pitch >= (size_t)W, "%s: pitch=%zu below W=%d", fn, pitch, W);
-  DVSG_REQUIRE(frame_stride >= (size_t)(H - 1) * pitch + (size_t)W, "%s: frame_stride=%zu below a frame's (H - 1) pitch + W = %zu",
-               fn, frame_stride, (size_t)(H - 1) * pitch + (size_t)W);
-  DVSG_REQUIRE(texture >= 0, "%s: texture=%d must be >= 0", fn, texture);
-  DVSG_REQUIRE(min_blocks >= 1, "%s: min_blocks=%d must be >= 1", fn, min_blocks);
-  DVSG_REQUIRE(workspace, "%s: NULL workspace", fn);
-  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
-    return fail(DVSG_ERR_WORKSPACE, "%s: workspace must be 16-byte aligned", fn);
-  if (workspace_bytes < g.bytes)
-    return fail(DVSG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (dvsg_shake_workspace_bytes)", fn, workspace_bytes,
-                g.bytes);
+  if (int rc = shake_check(fn, "dvsg_shake_workspace_bytes", &Geometry::bytes, pitch, frame_stride, n, H, W, factor, radius, margin_y,
+                           margin_x, texture, min_blocks, workspace, workspace_bytes, &g))
+    return rc;
   uint8_t *red = static_cast<uint8_t *>(workspace);
   int32_t *blocks = reinterpret_cast<int32_t *>(red + g.blocks_off);
   int32_t *vectors = reinterpret_cast<int32_t *>(red + g.vectors_off);
   const int pairs = n - 1;
-  DVSG_HIP(hipDeviceSynchronize());   // whatever stream made the planes has finished
-  const int tile_w = kSegBytes / factor;
-  const int tiles = ceil_div(g.w, tile_w);
-  hipLaunchKernelGGL(shake_reduce_kernel, dim3((unsigned)tiles * g.h, n), dim3(kThreads), (size_t)factor * kSegPitch, nullptr, luma,
-                     pitch, frame_stride, g.h, g.w, factor, tiles, red, g.plane_stride);
-  if (int rc = check_launch("shake_reduce_kernel")) return rc;
-  hipLaunchKernelGGL(shake_match_kernel, dim3(g.n_blk, pairs), dim3(kThreads), 0, nullptr, red, g.plane_stride, g.w, g.nx, g.n_blk,
-                     radius, margin_y, margin_x, texture, blocks);
-  if (int rc = check_launch("shake_match_kernel")) return rc;
+  if (int rc = shake_blocks(g, luma, pitch, frame_stride, n, factor, radius, margin_y, margin_x, texture, red, blocks)) return rc;
   hipLaunchKernelGGL(shake_global_kernel, dim3(pairs), dim3(kThreads), 0, nullptr, blocks, g.n_blk, min_blocks, vectors);
   if (int rc = check_launch("shake_global_kernel")) return rc;
   // hipMemcpy waits for the legacy default stream
   DVSG_HIP(hipMemcpy(vectors_host, vectors, (size_t)pairs * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (blocks_host)
+    DVSG_HIP(hipMemcpy(blocks_host, blocks, (size_t)pairs * g.n_blk * 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return DVSG_OK;
+}
+
+int dvsg_shake_motion_workspace_bytes(int n, int H, int W, int factor, int radius, int margin_y, int margin_x, size_t *bytes) {
+  const char *fn = "dvsg_shake_motion_workspace_bytes";
+  DVSG_REQUIRE(bytes, "%s: NULL bytes", fn);
+  Geometry g;
+  if (int rc = shake_geometry(fn, n, H, W, factor, radius, margin_y, margin_x, &g)) return rc;
+  *bytes = g.motion_bytes;
+  return DVSG_OK;
+}
+
+int dvsg_shake_motion_u8(const uint8_t *luma, size_t pitch, size_t frame_stride, int n, int H, int W, int factor, int radius,
+                         int margin_y, int margin_x, int texture, int min_blocks, int gate, int64_t *motion_host,
+                         int32_t *blocks_host, void *workspace, size_t workspace_bytes) {
+  const char *fn = "dvsg_shake_motion_u8";
+  DVSG_REQUIRE(luma, "%s: NULL luma", fn);
+  DVSG_REQUIRE(motion_host, "%s: NULL motion_host", fn);
+  DVSG_REQUIRE(gate >= 0 && gate <= kMaxGate, "%s: gate=%d outside [0, %d]", fn, gate, kMaxGate);
+  Geometry g;
+  if (int rc = shake_check(fn, "dvsg_shake_motion_workspace_bytes", &Geometry::motion_bytes, pitch, frame_stride, n, H, W, factor,
+                           radius, margin_y, margin_x, texture, min_blocks, workspace, workspace_bytes, &g))
+    return rc;
+  uint8_t *red = static_cast<uint8_t *>(workspace);
+  int32_t *blocks = reinterpret_cast<int32_t *>(red + g.blocks_off);
+  long long *motion = reinterpret_cast<long long *>(red + g.vectors_off);
+  const int pairs = n - 1;
+  if (int rc = shake_blocks(g, luma, pitch, frame_stride, n, factor, radius, margin_y, margin_x, texture, red, blocks)) return rc;
+  hipLaunchKernelGGL(shake_motion_kernel, dim3(pairs), dim3(kThreads), 0, nullptr, blocks, g.n_blk, g.nx, min_blocks, gate, motion);
+  if (int rc = check_launch("shake_motion_kernel")) return rc;
+  // hipMemcpy waits for the legacy default stream
+  DVSG_HIP(hipMemcpy(motion_host, motion, (size_t)pairs * kMotionRow * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (blocks_host)
     DVSG_HIP(hipMemcpy(blocks_host, blocks, (size_t)pairs * g.n_blk * 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
   return DVSG_OK;

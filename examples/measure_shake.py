@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """How much steadier is the output?  Stabilise the seeded synthetic clip (as examples/stabilize_clip.py does) and print the
 no-reference shake figures of the input and of the output, and their jitter ratio (coupe.dvsg_amd.shake: block matching
-between consecutive luma planes, on the device).  With the seeded synthetic checkpoint the ratio says nothing about a
+between consecutive luma planes, on the device), then the roll, zoom and wobble that a similarity fitted to the same block
+vectors shows (shake.measure_motion).  With the seeded synthetic checkpoint the ratio says nothing about a
 trained model: give --ckpt for that.
 
     python examples/measure_shake.py [--frames 16] [--height 288] [--width 512] [--ckpt DIR] [--precision f32|f32x3|f32s|f16]
@@ -41,12 +42,20 @@ def main():
         net.load_weights(make_synthetic_weights(seed=0))
     stabilised = stabilize_clip(net, Session(), frames, as_uint8=True)
     # the same geometry for both; the margin keeps the output's black border out of the blocks
-    before = shake.measure(shake.luma_of(frames, "rgb"))
-    after = shake.measure(shake.luma_of(np.asarray(stabilised), "rgb"))
+    motion_before = shake.measure_motion(shake.luma_of(frames, "rgb"))
+    motion_after = shake.measure_motion(shake.luma_of(np.asarray(stabilised), "rgb"))
+    # columns 0 - 3 of a motion row are the row `shake.measure` gives: one pass over the clip serves both
+    before, after = (shake.Track(m.rows[:, :4], m.factor, m.size, None) for m in (motion_before, motion_after))
     result = shake.compare(before, after)
     for name, s in (("before", result["a"]), ("after", result["b"])):
         print("%-6s %d pairs, %d lost, speed %s px/frame, jitter %s px/frame" % (name, s["pairs"], s["lost"], s["speed_rms"], s["jitter_rms"]))
     print("jitter ratio after / before:", result["jitter_ratio"])
+    motion = shake.compare_motion(motion_before, motion_after)
+    for name, s in (("before", motion["a"]), ("after", motion["b"])):
+        print("%-6s roll %s deg/frame, roll jitter %s deg/frame, zoom jitter %s %%/frame, wobble %s px, %d of %d pairs unfit" % (
+            name, s["roll_rms_deg"], s["roll_jitter_deg"], s["zoom_jitter_pct"], s["wobble_rms"], s["unfit"], s["pairs"]))
+    print("roll jitter ratio after / before:", motion["roll_jitter_ratio"])
+    print("wobble ratio after / before:", motion["wobble_ratio"])
 
 
 if __name__ == "__main__":

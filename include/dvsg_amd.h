@@ -711,6 +711,57 @@ int dvsg_scene_step_f32(const float *pool, int n_pool, int H, int W, const int32
                         int32_t *table, int32_t *out_slots, int32_t *cut, void *workspace, size_t workspace_bytes,
                         void *stream);
 /* ---------------------------------------------------------------------------------------
+ * SHAKE MOTION (coupe.dvsg_amd.shake.measure_motion): roll, zoom and wobble of a clip from the same block vectors.  The median
+ * of "SHAKE" sees translation only: under a roll the left blocks move up and the right ones down, and the median is about 0.
+ * This call fits a similarity (translation + roll + zoom) to the blocks that agree with the median and reports, per pair, the
+ * exact integer sums from which roll, zoom and the residual of the fit (wobble) follow on the host.  "SHAKE" is the next
+ * section; read it first.
+ * dvsg_shake_motion_u8 is synchronous and takes no stream: its result is a small HOST array, so it has to wait for
+ * the device whatever its interface.  In order: 1. every argument is checked before any HIP call; 2. the call waits for the
+ * device (hipDeviceSynchronize: whatever stream wrote the planes has finished); 3. it launches three kernels on the legacy
+ * default stream; 4. it copies the results to the host and returns.  It allocates and frees nothing.
+ *   luma, pitch, frame_stride, n, H, W, factor, radius, margin_y, margin_x, texture, min_blocks, blocks_host: as for
+ *                 dvsg_shake_measure_u8.
+ *   gate          in sixteenths of a reduced pixel, 0 <= gate <= 2^20: how far a block's vector may lie from the pair's median,
+ *                 per axis, and still enter the fit.
+ *   motion_host   int64 [n - 1, 13] on the HOST: row t - 1 describes frame t against frame t - 1.
+ *   workspace     caller-owned device memory, 16-byte aligned, dvsg_shake_motion_workspace_bytes(...) bytes
+ *                 (DVSG_ERR_WORKSPACE if short or misaligned, before any device work): the reduced planes, the per-block
+ *                 results and the device copy of the rows.  No state survives a call.
+ *   The rule.  Integer arithmetic throughout; tests/shake_motion_ref.py restates it in NumPy and the bar is bit equality.
+ *   1. - 5. are those of "SHAKE", unchanged: the reduce, the blocks, the match, validity and the sixteenth-pel step, and the
+ *      pair's [gx, gy, n_valid, ok].  Then, per pair:
+ *   6. Block coordinates.  Block (a, c) of the ny x nx grid has X = 2c - (nx - 1) and Y = 2a - (ny - 1): integers in units of
+ *      8 reduced pixels, with zero at the centre of the block grid.
+ *   7. Inliers.  A block is an inlier iff it is valid, the pair is ok, |vx - gx| <= gate and |vy - gy| <= gate.  The gate keeps
+ *      independently moving objects out of the fit and lets through the spread that roll and zoom cause at the edges.
+ *   8. Sums over the inliers, exact, int64:  n_in;  Sx = sum X;  Sy = sum Y;  Su = sum vx;  Sv = sum vy;
+ *      Sxx = sum (X*X + Y*Y);  Sxu = sum (X*vx + Y*vy);  Sxv = sum (X*vy - Y*vx);  Suu = sum (vx*vx + vy*vy).
+ *      A side is at most 16384, so |X|, |Y| <= 1022, and |v| <= 248: every sum stays below 2^29 at any size the call accepts.
+ *      The row is int64 all the same: the products the host makes of the sums (N * Sxx, Pn * Pn) are not.
+ *   9. The row is [gx, gy, n_valid, ok, n_in, Sx, Sy, Su, Sv, Sxx, Sxu, Sxv, Suu].  Everything from n_in on is 0 when the pair
+ *      is not ok.
+ *   10. Checked before any device work (DVSG_ERR_INVALID_ARG, the message names the argument): gate outside [0, 2^20], NULL
+ *      luma / motion_host / workspace / bytes, and everything dvsg_shake_measure_u8 checks; the workspace against
+ *      dvsg_shake_motion_workspace_bytes (DVSG_ERR_WORKSPACE).
+ *   The figures (coupe.dvsg_amd.shake.motion_figures; exact rationals, then one division and one square root each).  With
+ *   N = n_in:  Pn = N*Sxu - Sx*Su - Sy*Sv;  Rn = N*Sxv - Sx*Sv + Sy*Su;  Qn = N*Sxx - Sx*Sx - Sy*Sy;  Vn = N*Suu - Su*Su - Sv*Sv.
+ *   A pair is fit iff it is ok, N >= max(min_blocks, 3) and Qn > 0.  Then zoom = Pn / (128 Qn), the fractional size change per
+ *   frame, and roll = Rn / (128 Qn) in radians per frame (small angles: exactly scale * sin); 128 = 16 sixteenths x 8 pixels per
+ *   coordinate unit, and the signs follow the vectors' convention, cur[y][x] looks like prev[y+dy][x+dx].
+ *   rss = (Vn*Qn - Pn*Pn - Rn*Rn) / (N*Qn) in sixteenths squared, clamped at 0; the pair's wobble is (f / 16) sqrt(rss / N)
+ *   source pixels, the RMS distance of an inlier's vector from the fitted similarity.
+ *   What the figures are not: an affine or projective fit; a threshold for "steady" or "wobbly" (the matcher has a wobble
+ *   floor of its own, see DESIGN); anything about motion beyond the radius.
+ *   Kernels (shake_kernels.hip): the reduction and the matcher of "SHAKE", untouched, then shake_motion_kernel in the place
+ *   of the medians' kernel: one workgroup per pair, the same rows in LDS and the same rank counting, then every lane gates its
+ *   blocks and adds up the nine sums in int64 registers; wave shuffles, LDS across the four waves, no atomics.
+ * ------------------------------------------------------------------------------------- */
+int dvsg_shake_motion_workspace_bytes(int n, int H, int W, int factor, int radius, int margin_y, int margin_x, size_t *bytes);
+int dvsg_shake_motion_u8(const uint8_t *luma, size_t pitch, size_t frame_stride, int n, int H, int W, int factor, int radius,
+                         int margin_y, int margin_x, int texture, int min_blocks, int gate, int64_t *motion_host,
+                         int32_t *blocks_host, void *workspace, size_t workspace_bytes);
+/* ---------------------------------------------------------------------------------------
  * SHAKE (coupe.dvsg_amd.shake): how much a clip moves from frame to frame, measured from its own luma planes -- no ground
  * truth, no model.  The global motion of every pair of consecutive frames by block matching, in sixteenths of a reduced
  * pixel.  dvsg_shake_measure_u8 is synchronous and takes no stream: its result is a small HOST array, so it has to wait for

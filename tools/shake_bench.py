@@ -13,9 +13,13 @@ kernels:  the entry point is synchronous, so no event can be put between its lau
           kernel's time.
 numpy:    tests/shake_ref.py on the first pairs of the same clip on the host's cores, seconds per pair, its rows compared
           with the device's -- a statement of scale, not a requirement.
+motion:   with --motion, dvsg_shake_motion_u8 (shake.measure_motion, "Shake motion" in DESIGN section 5) beside the existing call
+          on the same planes: the two are timed in turn within every round, by the same events and clock, and their records
+          carry `call`; the kernels-only run makes three calls of each, so the trace holds shake_global_kernel and
+          shake_motion_kernel side by side.  Columns 0 - 3 of the new rows are compared with the existing call's.
 One JSON line per measurement.
 
-    python tools/shake_bench.py [--rounds 7] [--frames 64] [--numpy-pairs 2] [--out FILE]
+    python tools/shake_bench.py [--rounds 7] [--frames 64] [--numpy-pairs 2] [--motion] [--out FILE]
 """
 import argparse
 import json
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--numpy-pairs", type=int, default=2)
     ap.add_argument("--kernels-only", action="store_true", help="three calls per size and nothing else: the run rocprofv3 traces")
+    ap.add_argument("--motion", action="store_true", help="also time dvsg_shake_motion_u8 on the same planes, in turn with the other")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import numpy as np
@@ -74,28 +79,39 @@ def main():
         clip = wandering_clip(np, shake_ref, 5, n, H, W, f)
         dev = torch.from_numpy(clip).cuda()
         kw = dict(chunk=n)
+        calls = [("dvsg_shake_measure_u8", shake.measure)] + ([("dvsg_shake_motion_u8", shake.measure_motion)] if args.motion else [])
         for _ in range(3 if args.kernels_only else 2):
             track = shake.measure(dev, **kw)
+            if args.motion:
+                motion = shake.measure_motion(dev, **kw)
+        if args.motion and motion.rows[:, :4].tolist() != track.vectors.tolist():
+            raise SystemExit("%s: columns 0 - 3 of the motion rows differ from dvsg_shake_measure_u8's" % name)
         if args.kernels_only:
             continue
         h, w = H // f, W // f
         common = dict(size=name, H=H, W=W, factor=f, frames=n, pairs=n - 1, blocks=((h - 2 * my) // 16) * ((w - 2 * mx) // 16),
                       radius=12, reduce_bytes=n * (h * f * w * f + h * w), lost=int((track.vectors[:, 3] == 0).sum()))
-        event_ms, host_ms = [], []
+        event_ms, host_ms = {c: [] for c, _ in calls}, {c: [] for c, _ in calls}
         for _ in range(args.rounds):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            t0 = time.perf_counter()
-            shake.measure(dev, **kw)
-            t1 = time.perf_counter()
-            e1.record()
-            torch.cuda.synchronize()
-            event_ms.append(e0.elapsed_time(e1))
-            host_ms.append(1e3 * (t1 - t0))
-        for what, values in (("device events around the call", event_ms), ("host clock around the call", host_ms)):
-            s = stats(values)
-            emit(what=what, unit="ms", per_call=s, per_pair={k: v / (n - 1) for k, v in s.items()}, rounds=args.rounds, **common)
+            for c, fn in calls:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                t0 = time.perf_counter()
+                fn(dev, **kw)
+                t1 = time.perf_counter()
+                e1.record()
+                torch.cuda.synchronize()
+                event_ms[c].append(e0.elapsed_time(e1))
+                host_ms[c].append(1e3 * (t1 - t0))
+        for c, _ in calls:
+            extra = dict(call=c, **common) if args.motion else common
+            for what, values in (("device events around the call", event_ms[c]), ("host clock around the call", host_ms[c])):
+                s = stats(values)
+                emit(what=what, unit="ms", per_call=s, per_pair={k: v / (n - 1) for k, v in s.items()}, rounds=args.rounds, **extra)
+        if args.motion:
+            fit = [shake.motion_figures(r, f)["fit"] for r in motion.rows]
+            emit(what="motion rows", size=name, pairs=n - 1, fit=sum(fit), inliers=stats([int(v) for v in motion.rows[:, 4]]))
         seconds = []
         for t in range(1, args.numpy_pairs + 1):
             t0 = time.perf_counter()
